@@ -7,9 +7,19 @@ HilbertCoreset.  With --gpus G the N rows are sharded over G ranks (strong scali
 total N is fixed), one process per GPU, one candidate-record all-gather (RCCL) per step.
 
 A "step" = one greedy iteration of SparseNNLS.build (select + reweight + monotone guard)
-over Phi resident in HBM.  The one-off K1 projection is timed separately and reported
-as points*dims/s.  Prints ONE JSON line on rank 0 -- kept short (~5 KB) so that the driver's
-record holds all of it; the evidence sits inside the two objects that record keeps whole:
+over Phi resident in HBM.  Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: data and Theta set-up, solver construction, W untimed
+and K timed steps, then the line (metric, value, unit, higher_is_better, dtype, ms_per_step, the sweep's
+roofline from the timed steps, the coreset).  --dump-outputs DIR writes what the timed steps computed --
+the coreset a caller of HilbertCoreset.build receives after the last step -- as float64 .npy files
+(coreset_weights, coreset_indices, coreset_points, coreset_error); the inputs are seeded, so two builds
+can be compared output for output.
+
+--full adds everything else (each leg as before; --no-cpu / --no-extra / --no-host drop single legs):
+the one-off K1 projection timed separately (points*dims/s), the warm K4, the per-stage diagnostic pass,
+and the legs below -- kept short (~5 KB) so that the driver's record holds all of it; the evidence sits
+inside the two objects that record keeps whole:
   roofline            the dominant kernel of a step: the sweep.  From 2M rows per shard that is `k_sweep_i4` (two-level pre-filter:
                       a 4-bit mirror of the normalised rows streamed at half a byte per element, the rows it cannot exclude
                       re-bounded from int8 records in the same launch, the handful left rescored in fp64 -- the row returned is the
@@ -26,7 +36,7 @@ record holds all of it; the evidence sits inside the two objects that record kee
 Everything verbose (full roofline objects, phase timers, solver_init parts) goes to --detail FILE, or to one stderr
 line tagged BENCH_DETAIL.
 
-  python bench.py [--gpus 1 --steps 100 --warmup 10]
+  python bench.py [--gpus 1 --steps 100 --warmup 10] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
          --master-port 29500 bench.py --gpus 8 --steps 100 --warmup 10
 """
@@ -66,7 +76,23 @@ def parse():
     ap.add_argument('--detail', default=None, help='write the full (verbose) result object to this file instead of stderr')
     ap.add_argument('--proj-reps', type=int, default=5)
     ap.add_argument('--proj-warmup', type=int, default=3)
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='also run the legs beyond the headline: K1 / K4 timings, stage diagnostics, from-host, fp64 sweep, '
+                         'other configs, beta-Cores loops, CPU baseline and oracle parity')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the coreset after the last timed step to DIR/<name>.npy (float64)')
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
+
+
+def dump_outputs(path, wts, idcs, pts, err):
+    """What HilbertCoreset.get() / error() hand a caller after the last timed step, as float64 arrays (indices < 2^53: exact).
+    A few KB: M weights, M indices, M x (D + 1) rows (with --gpus > 1: rank 0's view, NaN for the rows other ranks own)."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in (('coreset_weights', wts), ('coreset_indices', idcs), ('coreset_points', pts), ('coreset_error', [err])):
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def spawn_ranks(args):
@@ -682,14 +708,14 @@ def main():
     t_setup = time.time() - t_setup
 
     data = bc.DeviceData.from_torch(Z, ctx=ctx, row_offset=lo)
-    ctx.enable_timing(True)
+    ctx.enable_timing(args.full)
     t0 = time.perf_counter()
     theta = posterior_samples(bc, data, D, S, comm)
     t_post = time.perf_counter() - t0
     k4_ms, k4_n = ctx.kernel_time(2)
     # ... and warm: three more launches over the same rows (the first one above pays the scratch allocation and cold caches)
     k4_warm_ms = None
-    if world == 1:
+    if world == 1 and args.full:
         ctx.kernel_time_reset()
         for _ in range(3):
             bc.weighted_gram(data, None)
@@ -700,53 +726,60 @@ def main():
     model = bc.likelihoods.LinearRegression(1.0)
     prj = bc.DeviceProjector(lambda n, w, p: theta, S, model, ctx=ctx)
 
-    # ---------------- K1: projection, points*dims/s
+    # ---------------- K1: projection, points*dims/s (--full)
     import gc
     gc.collect()
     gc.disable()          # a gen-2 collection (tens of ms with torch loaded) must not land in a timed region
-    ctx.enable_timing(True)
-    for _ in range(max(1, args.proj_warmup)):
-        prj.project(data)                  # warm-up (also allocates Phi): the first launches after the set-up kernels run
-    barrier()                              # 5-15 % slower than the steady state (7.0, 7.0, 6.3, 6.1, 6.0 ms in one trace)
-    ctx.kernel_time_reset()
-    barrier()
-    t0 = time.perf_counter()
-    phi = None
-    for i in range(args.proj_reps):
-        ta = time.perf_counter()
-        phi = None                         # hand the previous result's buffers back first: every rep writes the same Phi
-        phi = prj.project(data)
-        if os.environ.get('BC_BENCH_VERBOSE'):
-            sys.stderr.write('project rep %d: %.3f ms (host call incl. sync)\n' % (i, 1e3 * (time.perf_counter() - ta)))
-    barrier()
-    t_proj = (time.perf_counter() - t0) / args.proj_reps
-    if world > 1:
-        tt = torch.tensor([t_proj], dtype=torch.float64, device=dev if backend == 'nccl' else 'cpu')
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        t_proj = float(tt.item())
-    k1_ms, k1_n = ctx.kernel_time(1)
-    k1_ms_per = k1_ms / max(k1_n, 1)
-    k1_bytes = 8.0 * n_local * (D + 1) + 8.0 * n_local * S
-    k1_flops = 2.0 * n_local * D * S
+    if args.full:
+        ctx.enable_timing(True)
+        for _ in range(max(1, args.proj_warmup)):
+            prj.project(data)                  # warm-up (also allocates Phi): the first launches after the set-up kernels run
+        barrier()                              # 5-15 % slower than the steady state (7.0, 7.0, 6.3, 6.1, 6.0 ms in one trace)
+        ctx.kernel_time_reset()
+        barrier()
+        t0 = time.perf_counter()
+        phi = None
+        for i in range(args.proj_reps):
+            ta = time.perf_counter()
+            phi = None                         # hand the previous result's buffers back first: every rep writes the same Phi
+            phi = prj.project(data)
+            if os.environ.get('BC_BENCH_VERBOSE'):
+                sys.stderr.write('project rep %d: %.3f ms (host call incl. sync)\n' % (i, 1e3 * (time.perf_counter() - ta)))
+        barrier()
+        t_proj = (time.perf_counter() - t0) / args.proj_reps
+        if world > 1:
+            tt = torch.tensor([t_proj], dtype=torch.float64, device=dev if backend == 'nccl' else 'cpu')
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            t_proj = float(tt.item())
+        k1_ms, k1_n = ctx.kernel_time(1)
+        k1_ms_per = k1_ms / max(k1_n, 1)
+        k1_bytes = 8.0 * n_local * (D + 1) + 8.0 * n_local * S
+        k1_flops = 2.0 * n_local * D * S
 
     # ---------------- solver construction (b, norms already fused into K1)
     cls = bc.snnls.GIGA if args.alg == 'giga' else bc.snnls.FrankWolfe
     phi = None                             # hand the 8 GB Phi of the projection runs back to the projector's pool: the coreset's
     barrier()                              # own projection reuses it instead of hipMalloc'ing a second one inside the timed init
-    ctx.enable_timing(True)
+    ctx.enable_timing(args.full)
     ctx.kernel_time_reset()
-    with NativeCallTimer(bc) as nct:
+    if args.full:
+        with NativeCallTimer(bc) as nct:
+            t0 = time.perf_counter()
+            alg = bc.HilbertCoreset(data, prj, snnls=cls, comm=comm)
+            barrier()
+            t_init = time.perf_counter() - t0
+        k1i_ms, k1i_n = ctx.kernel_time(1)
+        init_parts = {'phi_alloc (bc_phi_create)': nct.ms('bc_phi_create'),
+                      'K1 kernel (HIP events)': k1i_ms,
+                      'bc_project host side + column-sum / norm statistics (two small kernels, one sync)': max(0.0, nct.ms('bc_project') - k1i_ms),
+                      'solver create: mirror allocation + k_build_i8 + state (bc_snnls_create)': nct.ms('bc_snnls_create'),
+                      'other native calls': nct.other_ms(('bc_phi_create', 'bc_project', 'bc_snnls_create')),
+                      'python / collectives': max(0.0, 1e3 * t_init - nct.total_ms())}
+    else:
         t0 = time.perf_counter()
         alg = bc.HilbertCoreset(data, prj, snnls=cls, comm=comm)
         barrier()
         t_init = time.perf_counter() - t0
-    k1i_ms, k1i_n = ctx.kernel_time(1)
-    init_parts = {'phi_alloc (bc_phi_create)': nct.ms('bc_phi_create'),
-                  'K1 kernel (HIP events)': k1i_ms,
-                  'bc_project host side + column-sum / norm statistics (two small kernels, one sync)': max(0.0, nct.ms('bc_project') - k1i_ms),
-                  'solver create: mirror allocation + k_build_i8 + state (bc_snnls_create)': nct.ms('bc_snnls_create'),
-                  'other native calls': nct.other_ms(('bc_phi_create', 'bc_project', 'bc_snnls_create')),
-                  'python / collectives': max(0.0, 1e3 * t_init - nct.total_ms())}
     total = args.warmup + args.steps
 
     # ---------------- greedy iterations: W untimed, then exactly K timed
@@ -766,6 +799,12 @@ def main():
         t_steps = float(tt.item())
     k3_ms, k3_n = ctx.kernel_time(0)
     k3_ms_per = k3_ms / max(k3_n, 1)
+    # ---------------- what the timed steps computed: the coreset after the last one (all ranks pull; rank 0 writes)
+    alg._pull()
+    wts, pts, idcs = alg.get()
+    err = alg.error()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, wts, idcs, pts, err)
     eng_ = alg.snnls._eng
     exchange_kind = ('rccl all-gather issued by the C library (native loop)' if eng_.native_exchange else
                      'torch.distributed all-gather per step (%s)' % backend if eng_.exchange else 'none (single rank)')
@@ -791,38 +830,39 @@ def main():
             k3_bytes = 4.0 * n_local * S + 8.0 * n_local + 4.0 * n_local
     else:
         k3_bytes = 8.0 * n_local * S + 8.0 * n_local      # one streaming read of Phi + the norms
-    # ---------------- diagnostic pass (untimed): HIP events around every stage of every step -- sweep, rescoring / local
+    # ---------------- diagnostic pass (untimed, --full): HIP events around every stage of every step -- sweep, rescoring / local
     # winner, candidate all-gather, finish -- so that a multi-GPU run shows where its step time goes.  The event pairs cost
     # stream time (~11 us each), which is why this is a pass of its own and not part of `value`.
-    diag_steps = 30
-    ctx.timing_classes(0x3f)
-    ctx.enable_timing(1)
-    ctx.kernel_time_reset()
-    t0 = time.perf_counter()
-    alg.snnls.build(diag_steps)
-    barrier()
-    t_diag = time.perf_counter() - t0
-    stage_ms = {}
-    for nm, cl in (('sweep', 0), ('rescoring_or_local_winner', 3), ('all_gather', 4), ('finish', 5)):
-        ms_, n_ = ctx.kernel_time(cl)
-        stage_ms[nm] = ms_ / n_ if n_ else None
-    ctx.enable_timing(0)
-    ctx.timing_classes(0x7)
-    rccl_ranks = None
-    if eng_.native_exchange:
-        import ctypes as _C
-        from beta_cores_amd import _native as _N
-        rr, ww = _C.c_int32(), _C.c_int32()
-        _N.call('bc_comm_info', comm.native_comm(ctx), _C.byref(rr), _C.byref(ww))
-        rccl_ranks = int(ww.value)
-    step_diag = {'stage_ms (HIP events, every step of a separate %d-step pass)' % diag_steps: stage_ms,
-                 'instrumented_ms_per_step': 1e3 * t_diag / diag_steps, 'rccl_ranks': rccl_ranks,
-                 'transport': exchange_kind,
-                 'note': 'single rank with the pre-filter: rescoring runs inside the finish launch; '
-                         'multi-rank: sweep -> rescoring -> ncclAllGather of one (S+4)-double record per rank -> replicated finish'}
-    alg._pull()
-    wts, pts, idcs = alg.get()
-    err = alg.error()
+    if args.full:
+        diag_steps = 30
+        ctx.timing_classes(0x3f)
+        ctx.enable_timing(1)
+        ctx.kernel_time_reset()
+        t0 = time.perf_counter()
+        alg.snnls.build(diag_steps)
+        barrier()
+        t_diag = time.perf_counter() - t0
+        stage_ms = {}
+        for nm, cl in (('sweep', 0), ('rescoring_or_local_winner', 3), ('all_gather', 4), ('finish', 5)):
+            ms_, n_ = ctx.kernel_time(cl)
+            stage_ms[nm] = ms_ / n_ if n_ else None
+        ctx.enable_timing(0)
+        ctx.timing_classes(0x7)
+        rccl_ranks = None
+        if eng_.native_exchange:
+            import ctypes as _C
+            from beta_cores_amd import _native as _N
+            rr, ww = _C.c_int32(), _C.c_int32()
+            _N.call('bc_comm_info', comm.native_comm(ctx), _C.byref(rr), _C.byref(ww))
+            rccl_ranks = int(ww.value)
+        step_diag = {'stage_ms (HIP events, every step of a separate %d-step pass)' % diag_steps: stage_ms,
+                     'instrumented_ms_per_step': 1e3 * t_diag / diag_steps, 'rccl_ranks': rccl_ranks,
+                     'transport': exchange_kind,
+                     'note': 'single rank with the pre-filter: rescoring runs inside the finish launch; '
+                             'multi-rank: sweep -> rescoring -> ncclAllGather of one (S+4)-double record per rank -> replicated finish'}
+        alg._pull()                        # the line's `coreset` (and the legs below) see the solver after this pass, as before
+        wts, pts, idcs = alg.get()
+        err = alg.error()
     f_tr, st_tr, _ = alg.snnls._eng.trace()
 
     two_level = pref == 8 and int(alg.snnls._eng.prefilter_form) == 3
@@ -837,13 +877,14 @@ def main():
         if args.alg == 'giga':
             traffic, traffic_src = newest_traffic(N, D, S, world, (kname if pref else 'k_sweep'))
         # ---- roofline.kernels: every kernel this run timed, one short entry each (name | avg ms | GB, GF per launch | fractions)
-        kernels.append(kentry('K1 %s linreg N=%d D=%d (headline shape)' % ('k_project_r' if n_local >= 262144 else 'k_project', n_local, D),
-                              k1_ms_per, k1_bytes, k1_flops, k1_n))
-        k4e = k4_entry(n_local, D, max(k4_warm_ms or (k4_ms / max(k4_n, 1)), 1e-9))
-        kernels.append(dict(kentry('K4 k_gram+reduce N=%d D=%d w=1 %s' % (n_local, D, 'warm' if k4_warm_ms else 'cold'),
-                                   k4e['kernel_ms (gram + reduce)'], k4e['bytes_per_launch'],
-                                   k4e['executed_tflops'] * 1e9 * k4e['kernel_ms (gram + reduce)'], 3 if k4_warm_ms else k4_n),
-                            sym=sig(k4e['symmetry_factor'])))
+        if args.full:
+            kernels.append(kentry('K1 %s linreg N=%d D=%d (headline shape)' % ('k_project_r' if n_local >= 262144 else 'k_project', n_local, D),
+                                  k1_ms_per, k1_bytes, k1_flops, k1_n))
+            k4e = k4_entry(n_local, D, max(k4_warm_ms or (k4_ms / max(k4_n, 1)), 1e-9))
+            kernels.append(dict(kentry('K4 k_gram+reduce N=%d D=%d w=1 %s' % (n_local, D, 'warm' if k4_warm_ms else 'cold'),
+                                       k4e['kernel_ms (gram + reduce)'], k4e['bytes_per_launch'],
+                                       k4e['executed_tflops'] * 1e9 * k4e['kernel_ms (gram + reduce)'], 3 if k4_warm_ms else k4_n),
+                                sym=sig(k4e['symmetry_factor'])))
         out = {
             'metric': 'greedy coreset iterations/sec', 'value': args.steps / t_steps, 'unit': 'iterations/s',
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': 1e3 * t_steps / args.steps,
@@ -862,26 +903,29 @@ def main():
             'prefilter': dict(zip(('sweeps', 'candidates_rescored', 'fp64_fallbacks'), alg.snnls._eng.prefilter_stats()),
                               form=int(alg.snnls._eng.prefilter_form),
                               levels=dict(zip(('l1_sweeps', 'rows_passed_on', 'rows_refined_int8'), alg.snnls._eng.prefilter_levels()))),
-            'step_stages': {'sweep': sig(stage_ms['sweep']), 'rescore': sig(stage_ms['rescoring_or_local_winner']),
-                            'gather': sig(stage_ms['all_gather']), 'finish': sig(stage_ms['finish']),
-                            'instr_ms_per_step': sig(1e3 * t_diag / diag_steps), 'rccl_ranks': rccl_ranks,
-                            'transport': exchange_kind.split(' (')[0]},
-            'solver_init_ms': sig(1e3 * t_init),
-            'solver_init': {'phi_alloc': sig(init_parts['phi_alloc (bc_phi_create)']), 'k1': sig(init_parts['K1 kernel (HIP events)']),
-                            'stats': sig(init_parts['bc_project host side + column-sum / norm statistics (two small kernels, one sync)']),
-                            'solver_create': sig(init_parts['solver create: mirror allocation + k_build_i8 + state (bc_snnls_create)']),
-                            'other_native': sig(init_parts['other native calls']), 'python': sig(init_parts['python / collectives'])},
-            'projection': {'points_dims_per_s': sig(N * D / t_proj, 6), 'ms': sig(1e3 * t_proj), 'kernel_ms': sig(k1_ms_per)},
-            'coreset': {'size': int(len(idcs)), 'error': err, 'failed_steps': int(st_tr.sum())},
         }
-        detail.update({'solver_init': init_parts, 'step_stages': step_diag, 'setup_s': t_setup, 'posterior_gram_cold_wall_ms': 1e3 * t_post,
-                       'posterior_gram': k4e})
+        if args.full:
+            out['step_stages'] = {'sweep': sig(stage_ms['sweep']), 'rescore': sig(stage_ms['rescoring_or_local_winner']),
+                                  'gather': sig(stage_ms['all_gather']), 'finish': sig(stage_ms['finish']),
+                                  'instr_ms_per_step': sig(1e3 * t_diag / diag_steps), 'rccl_ranks': rccl_ranks,
+                                  'transport': exchange_kind.split(' (')[0]}
+        out['solver_init_ms'] = sig(1e3 * t_init)
+        if args.full:
+            out['solver_init'] = {'phi_alloc': sig(init_parts['phi_alloc (bc_phi_create)']), 'k1': sig(init_parts['K1 kernel (HIP events)']),
+                                  'stats': sig(init_parts['bc_project host side + column-sum / norm statistics (two small kernels, one sync)']),
+                                  'solver_create': sig(init_parts['solver create: mirror allocation + k_build_i8 + state (bc_snnls_create)']),
+                                  'other_native': sig(init_parts['other native calls']), 'python': sig(init_parts['python / collectives'])}
+            out['projection'] = {'points_dims_per_s': sig(N * D / t_proj, 6), 'ms': sig(1e3 * t_proj), 'kernel_ms': sig(k1_ms_per)}
+        out['coreset'] = {'size': int(len(idcs)), 'error': err, 'failed_steps': int(st_tr.sum())}
+        detail.update({'setup_s': t_setup, 'posterior_gram_cold_wall_ms': 1e3 * t_post})
+        if args.full:
+            detail.update({'solver_init': init_parts, 'step_stages': step_diag, 'posterior_gram': k4e})
 
     # ---------------- the host path (hilbert.py:11 takes an ndarray): upload + K1 pipelined, wall time to the first iteration.
     # (Before the legs that run NumPy / BLAS on the host: after them the runtime's pinning of the pageable 10 GB source takes
     # 0.5-1 s longer on some boxes -- 1 026 against 191 ms for the same construction, profiles/r05_notes.md.)
     Z_host = None
-    if rank == 0 and world == 1 and not args.no_host:
+    if rank == 0 and world == 1 and args.full and not args.no_host:
         Z_host = Z.cpu().numpy()
         fh = from_host_leg(bc, ctx, barrier, Z_host, theta, S, model, cls, f_tr, args)
         out['roofline']['from_host'] = fh
@@ -889,7 +933,7 @@ def main():
         out['ms_per_step_M100'] = sig((fh['M100_ms'] - fh['first_iter_ms']) / 99.0)
 
     # ---------------- the SURVEY 8(d) formulation, driver-timed too: the exact fp64 sweep (8*N*S + 8*N bytes per step)
-    if rank == 0 and world == 1 and not args.no_extra:
+    if rank == 0 and world == 1 and args.full and not args.no_extra:
         f64 = fp64_sweep_leg(bc, ctx, alg, cls, barrier, n_local, S, args)
         kernels.append(dict(kentry('K3 k_sweep<%s> fp64 Phi streamed once per step N=%d (SURVEY 8d formulation)' % (algn, n_local),
                                    f64['avg_launch_ms'], f64['bytes_per_launch'], 0, f64['steps']),
@@ -931,7 +975,7 @@ def main():
         detail['cpu_loops'] = cpu_loops
 
     # ---------------- CPU baseline (rank 0, N=1 launch only): the NumPy oracle
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         from oracle import RefGIGA, RefFrankWolfe, models_ref, coreset_ref
         Ref = RefGIGA if args.alg == 'giga' else RefFrankWolfe
         ll = lambda z, t: models_ref.linreg_loglik(z, t, 1.0)

@@ -1,10 +1,11 @@
-"""bench.py keeps its contract: one JSON line with the driver's keys, the roofline and cpu_baseline objects,
-and a CPU-parity verdict -- on a small workload so that it runs in seconds."""
+"""bench.py keeps its contract: one JSON line with the driver's keys; with --full also the roofline and cpu_baseline objects
+and a CPU-parity verdict; --dump-outputs writes the same coreset in either mode -- on a small workload so that it runs in seconds."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -24,7 +25,7 @@ def run_bench(*extra, env=None):
 
 
 def test_bench_line_contract():
-    d = run_bench()
+    d = run_bench('--full')
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
               'vs_baseline', 'dtype', 'data', 'config', 'roofline', 'cpu_baseline'):
         assert k in d, k
@@ -77,19 +78,19 @@ def test_bench_line_contract():
 
 def test_bench_detail_goes_to_a_file_or_stderr(tmp_path):
     path = str(tmp_path / 'detail.json')
-    d = run_bench('--no-cpu', '--no-extra', '--no-host', '--detail', path)
+    d = run_bench('--full', '--no-cpu', '--no-extra', '--no-host', '--detail', path)
     full = json.load(open(path))
     assert full['line']['value'] == d['value'] and 'solver_init' in full['detail']
 
 
 def test_bench_sweep_modes_agree():
-    a = run_bench('--no-cpu', env={'BC_PREFILTER': '0'})
-    b = run_bench('--no-cpu', env={'BC_PREFILTER': '8'})
+    a = run_bench('--full', '--no-cpu', env={'BC_PREFILTER': '0'})
+    b = run_bench('--full', '--no-cpu', env={'BC_PREFILTER': '8'})
     assert a['coreset'] == b['coreset']            # same size, same error, same number of failed steps
     assert a['config']['sweep'] == 'fp64' and b['config']['sweep'].startswith('int8')
     # the two-level form (a 4-bit first level; csrc/bc_prefilter_i4.h: the default from 2M rows, forced here), named in the line
     # with its bytes: S = 40 -> five dwords of eight nibbles + a 16-bit code per row
-    c = run_bench('--no-cpu', '--no-extra', '--no-host', env={'BC_PREFILTER': '4'})
+    c = run_bench('--full', '--no-cpu', '--no-extra', '--no-host', env={'BC_PREFILTER': '4'})
     assert c['coreset'] == a['coreset'] and c['config']['sweep'].startswith('4-bit') and c['prefilter']['form'] == 3
     lv = c['prefilter']['levels']
     assert lv['l1_sweeps'] >= c['steps'] and 0 < lv['rows_passed_on'] == lv['rows_refined_int8']
@@ -101,7 +102,7 @@ def test_bench_spawns_its_own_ranks():
     processes through torch.distributed.run and relays rank 0's line.  Rehearsed here with both ranks on the one
     GPU this box has and gloo carrying the records (RCCL refuses two ranks per device)."""
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '10', '--warmup', '2',
-           '--rows', '400000', '--dim', '24', '--samples', '40', '--no-cpu', '--no-extra']
+           '--rows', '400000', '--dim', '24', '--samples', '40', '--full', '--no-cpu', '--no-extra']
     e = dict(os.environ, BC_BENCH_DEVICE='0', BC_BENCH_BACKEND='gloo')
     e.pop('WORLD_SIZE', None)
     e.pop('RANK', None)
@@ -111,6 +112,41 @@ def test_bench_spawns_its_own_ranks():
     assert len(lines) == 1, out.stdout[-2000:]
     d = json.loads(lines[0])
     assert d['n_gpus'] == 2 and d['steps'] == 10 and d['config']['rows_per_gpu'] == 200064 and d['value'] > 0
-    one = run_bench('--no-cpu', '--no-extra', '--rows', '400000', '--steps', '10', '--warmup', '2')
+    one = run_bench('--full', '--no-cpu', '--no-extra', '--rows', '400000', '--steps', '10', '--warmup', '2')
     assert one['coreset']['size'] == d['coreset']['size']
     assert abs(one['coreset']['error'] - d['coreset']['error']) <= 1e-9 * one['coreset']['error']
+
+
+DUMPED = ('coreset_weights', 'coreset_indices', 'coreset_points', 'coreset_error')
+
+
+def load_dump(path):
+    return {n: np.load(os.path.join(path, n + '.npy')) for n in DUMPED}
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) prints the headline line and nothing from the other legs; --dump-outputs writes the coreset after
+    the last timed step, the same in two plain runs and in a --full run (whose extra passes come after the dump)."""
+    paths = [str(tmp_path / n) for n in ('a', 'b', 'full')]
+    d = run_bench('--dump-outputs', paths[0])
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert k in d, k
+    assert d['metric'] == 'greedy coreset iterations/sec' and d['unit'] == 'iterations/s' and d['higher_is_better'] is True
+    assert d['dtype'] == 'f64' and d['steps'] == 12 and d['warmup'] == 3
+    assert abs(d['value'] - 1e3 / d['ms_per_step']) < 1e-6 * d['value']
+    for k in ('cpu_baseline', 'step_stages', 'projection', 'solver_init', 'ms_per_step_M100'):
+        assert k not in d, k
+    assert d['roofline']['kernels'] == [] and 'from_host' not in d['roofline'] and 'fp64_formulation' not in d['roofline']
+    a = load_dump(paths[0])
+    m = d['coreset']['size']
+    assert 0 < m <= 15                                               # warmup + steps greedy iterations
+    assert a['coreset_weights'].shape == (m,) and a['coreset_indices'].shape == (m,) and a['coreset_points'].shape == (m, 25)
+    assert all(v.dtype == np.float64 for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert float(a['coreset_error'][0]) == d['coreset']['error'] and (a['coreset_weights'] > 0).all()
+    assert np.array_equal(np.sort(a['coreset_indices']), a['coreset_indices']) and (a['coreset_indices'] < 300000).all()
+    run_bench('--dump-outputs', paths[1])
+    run_bench('--full', '--no-cpu', '--no-extra', '--no-host', '--dump-outputs', paths[2])
+    for p in paths[1:]:
+        b = load_dump(p)
+        for n in DUMPED:
+            assert np.array_equal(a[n], b[n]), (p, n)

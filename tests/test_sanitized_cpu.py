@@ -135,7 +135,8 @@ def test_model_catches_the_round3_fault(tmp_path):
 
 def test_c_abi_validation_paths_under_asan_ubsan(tmp_path):
     """The whole library's HOST code built with -fsanitize=address,undefined (hipcc --offload-host-only: no device code is
-    generated, zero-filled stand-ins take the place of the eight code-object symbols; ~6 s) and every entry point of
+    generated, zero-filled stand-ins take the place of the eight code-object symbols; -fno-gpu-sanitize on every hipcc line: the
+    sanitizers are for host code only; ~6 s) and every entry point of
     include/beta_cores.h called with NULL / zero arguments through the same ctypes table the product uses
     (tests/abi_null_sweep.py): a status comes back from each, nothing is dereferenced, no sanitizer report."""
     import glob
@@ -150,7 +151,7 @@ def test_c_abi_validation_paths_under_asan_ubsan(tmp_path):
     for src in srcs:
         obj = str(tmp_path / (os.path.basename(src)[:-4] + '.o'))
         procs.append((obj, subprocess.Popen([hipcc, '-O1', '-g', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '--offload-host-only',
-                                             '-ffp-contract=off', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined',
+                                             '-ffp-contract=off', '-fsanitize=address,undefined', '-fno-gpu-sanitize', '-fno-sanitize-recover=undefined',
                                              '-I', csrc, '-c', src, '-o', obj], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
     objs = []
     for obj, p in procs:
@@ -158,7 +159,7 @@ def test_c_abi_validation_paths_under_asan_ubsan(tmp_path):
         assert p.returncode == 0, out[-3000:]
         objs.append(obj)
     lib0 = str(tmp_path / 'libbc_san0.so')
-    out = subprocess.run([hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-fsanitize=address,undefined', '-shared-libsan', '-o', lib0] + objs +
+    out = subprocess.run([hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-fsanitize=address,undefined', '-fno-gpu-sanitize', '-shared-libsan', '-o', lib0] + objs +
                          ['-ldl', '-lpthread'], capture_output=True, text=True)
     assert out.returncode == 0, out.stderr[-3000:]
     syms = sorted(set(l.split()[-1] for l in subprocess.run(['nm', '-u', lib0], capture_output=True, text=True).stdout.splitlines()
@@ -170,7 +171,7 @@ def test_c_abi_validation_paths_under_asan_ubsan(tmp_path):
     stub_o = str(tmp_path / 'fatbin_stubs.o')
     assert subprocess.run(['gcc', '-fPIC', '-c', stub_c, '-o', stub_o]).returncode == 0
     lib = str(tmp_path / 'libbc_san.so')
-    out = subprocess.run([hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-fsanitize=address,undefined', '-shared-libsan', '-o', lib] + objs +
+    out = subprocess.run([hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-fsanitize=address,undefined', '-fno-gpu-sanitize', '-shared-libsan', '-o', lib] + objs +
                          [stub_o, '-ldl', '-lpthread'], capture_output=True, text=True)
     assert out.returncode == 0, out.stderr[-3000:]
     env = dict(os.environ, LD_PRELOAD=asan[0], ASAN_OPTIONS='detect_leaks=0', UBSAN_OPTIONS='print_stacktrace=1', BETA_CORES_LIB=lib)

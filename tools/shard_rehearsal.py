@@ -28,7 +28,7 @@ def run(rows, one_level, steps=300, warmup=120):
         env['BC_PREFILTER'] = '8'
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--rows', str(rows), '--steps', str(steps),
-           '--warmup', str(warmup), '--no-cpu', '--no-extra', '--no-host', '--detail', '/dev/null']
+           '--warmup', str(warmup), '--full', '--no-cpu', '--no-extra', '--no-host', '--detail', '/dev/null']
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     if out.returncode != 0:
         raise SystemExit('bench failed: ' + out.stderr[-2000:])
