@@ -6,7 +6,8 @@ Drop-in for the `bayesiancoresets` names on this path (bayesiancoresets/__init__
     bc.BlackBoxProjector, bc.BetaBlackBoxProjector,
     bc.Projector, bc.snnls.{GIGA, FrankWolfe, OrthoPursuit, ImportanceSampling, UniformSampling},
     bc.util.{nn_opt, set_verbosity, TOL, set_tolerance}
-plus the device-resident projector bc.DeviceProjector / bc.DeviceBetaProjector (K1 on the GPU).
+plus the device-resident projector bc.DeviceProjector / bc.DeviceBetaProjector (K1 on the GPU) and the full-data logistic
+Laplace fit (bc.samplers.logistic_laplace on a DeviceData, bc.samplers.LaplaceFullDataSampler; K5 + K4).
 Importing the package does not touch the GPU; constructing a solver/projector does and
 raises if libbeta_cores.so or a gfx950 device is missing (there is no CPU fallback).
 """
@@ -19,7 +20,7 @@ from .coreset import (Coreset, HilbertCoreset, BetaCoreset, SparseVICoreset, Bat
                       BetaBlackBoxProjector, DeviceProjector, DeviceBetaProjector)
 from . import likelihoods
 from . import samplers
-from .posterior import weighted_gram, weighted_post, weighted_post_corrected, gaussian_weighted_post
+from .posterior import weighted_gram, weighted_post, weighted_post_corrected, gaussian_weighted_post, logistic_newton_pass
 from .dist import ShardComm, shard_bounds
 
 __all__ = ['util', 'snnls', 'likelihoods', 'samplers', 'NumericalPrecisionError', 'Context', 'DeviceData', 'DevicePhi',
@@ -27,4 +28,4 @@ __all__ = ['util', 'snnls', 'likelihoods', 'samplers', 'NumericalPrecisionError'
            'BatchPSVICoreset', 'UniformSamplingCoreset',
            'Projector', 'BlackBoxProjector', 'BetaBlackBoxProjector', 'DeviceProjector', 'DeviceBetaProjector',
            'ShardComm', 'shard_bounds', 'weighted_gram', 'weighted_post', 'weighted_post_corrected',
-           'gaussian_weighted_post']
+           'gaussian_weighted_post', 'logistic_newton_pass']

@@ -108,6 +108,12 @@ _SIGNATURES = {
 }
 EXPORTS = sorted(list(_SIGNATURES) + ['bc_version', 'bc_last_error'])
 
+# entry points of the extension header include/beta_cores_laplace.h (same library, same status conventions)
+_EXT_SIGNATURES = {
+    'bc_logistic_newton_pass': [vp, vp, vp, vp, vp, vp, vp, vp],
+}
+EXT_EXPORTS = sorted(_EXT_SIGNATURES)
+
 _lib = None
 
 
@@ -139,7 +145,7 @@ def load():
             'or `make -C beta_cores_amd/csrc`. There is no CPU fallback.' % LIB_PATH)
     _preload_torch_hip_runtime()
     lib = C.CDLL(LIB_PATH)
-    for name, argtypes in _SIGNATURES.items():
+    for name, argtypes in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int

@@ -95,7 +95,8 @@ extern "C" int bc_ctx_destroy(bc_ctx* ctx) {
   if (ctx->colsum_phi) bc_phi_destroy(ctx->colsum_phi);
   if (ctx->core_phi) bc_phi_destroy(ctx->core_phi);
   bc_scratch* all[] = {&ctx->proj_theta, &ctx->proj_rowaux, &ctx->proj_rowaux2, &ctx->gradx, &ctx->vi_buf, &ctx->const_rows,
-                       &ctx->gram[0], &ctx->gram[1], &ctx->gram[2], &ctx->gram[3], &ctx->gram[4]};
+                       &ctx->gram[0], &ctx->gram[1], &ctx->gram[2], &ctx->gram[3], &ctx->gram[4],
+                       &ctx->lap[0], &ctx->lap[1], &ctx->lap[2]};
   for (bc_scratch* sc : all)
     if (sc->p) (void)hipFree(sc->p);
   if (ctx->proj_pinned) (void)hipHostFree(ctx->proj_pinned);
@@ -124,7 +125,7 @@ extern "C" int bc_ctx_enable_timing(bc_ctx* ctx, int on) {
 
 extern "C" int bc_ctx_timing_classes(bc_ctx* ctx, uint32_t mask) {
   if (!ctx) return BC_INVALID_ARGUMENT;
-  ctx->timing_mask = mask & 0x3f;
+  ctx->timing_mask = mask & 0x7f;
   return BC_OK;
 }
 
@@ -167,7 +168,7 @@ static int timer_collect(bc_ctx* ctx, bc_timer& t) {
 }
 
 extern "C" int bc_ctx_kernel_time(bc_ctx* ctx, int which, double* total_ms, int64_t* launches) {
-  if (!ctx || which < 0 || which > 5) { bc_set_error("bc_ctx_kernel_time: bad argument"); return BC_INVALID_ARGUMENT; }
+  if (!ctx || which < 0 || which > 6) { bc_set_error("bc_ctx_kernel_time: bad argument"); return BC_INVALID_ARGUMENT; }
   int rc = timer_collect(ctx, ctx->timers[which]);
   if (rc) return rc;
   if (total_ms) *total_ms = ctx->timers[which].acc_ms;

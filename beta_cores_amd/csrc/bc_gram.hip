@@ -531,15 +531,18 @@ static int gram_buf(bc_ctx* ctx, int which, size_t doubles, double** out) {
   return BC_OK;
 }
 
+// y_col = false: the rows have no y column (d = dz; the logistic Hessian, bc_laplace.hip).  The kernels are the same: the y
+// loads of k_gram then read the next row's first value (or, past the slab, nothing: the range check), and the X^T (w*y)
+// they accumulate is written to outy_dev and not used.  k_gram_dma reads y without a range check: never on this path.
 template <int BT>
-static int run_gram(bc_ctx* ctx, const bc_data* data, const double* w_dev, double* out_dev, double* outy_dev) {
-  const int dz = data->dz, d = dz - 1;
+static int run_gram(bc_ctx* ctx, const bc_data* data, const double* w_dev, double* out_dev, double* outy_dev, bool y_col = true) {
+  const int dz = data->dz, d = y_col ? dz - 1 : dz;
   const int nt = (d + BT - 1) / BT;
   const int ntri = nt * (nt + 1) / 2;
   // one unweighted diagonal tile whose rows hold at least 128 doubles: the LDS-DMA kernel (k_gram_dma); BC_GRAM_DMA=0: the
   // register-staged k_gram (A/B)
   const int dma_env = getenv("BC_GRAM_DMA") ? atoi(getenv("BC_GRAM_DMA")) : 1;      // (read per call: tests flip it)
-  const bool use_dma = BT == 128 && ntri == 1 && w_dev == nullptr && dz >= 128 && dma_env != 0 && data->n_rows >= 4096;
+  const bool use_dma = BT == 128 && ntri == 1 && w_dev == nullptr && y_col && dz >= 128 && dma_env != 0 && data->n_rows >= 4096;
   const int KR = use_dma ? BC_GD_KR : (BT == 64 ? 32 : 16);
   // Row splits, in units of the 2 * n_cu resident block slots (BC_GRAM_WAVES overrides), at least 2 slabs per split.
   // One tile (D <= 128): exactly one block per slot -- every further split writes, and the reduction reads back, another
@@ -693,4 +696,15 @@ extern "C" int bc_weighted_gram(bc_ctx* ctx, const bc_data* data, const double* 
   BC_HIP(hipMemcpyAsync(out_xtwy, outy_dev, (size_t)d * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   BC_HIP(hipStreamSynchronize(ctx->stream));
   return BC_OK;
+}
+
+// Z^T diag(w) Z of rows WITHOUT a y column (d = dz), w on the device: the Hessian of bc_logistic_newton_pass.  The d x d
+// result is left in the context's K4 output buffer (*out_dev), valid until the next K4 call.
+int bc_gram_no_y(bc_ctx* ctx, const bc_data* data, const double* w_dev, double** out_dev) {
+  const int d = data->dz;
+  double* outy_dev = nullptr;
+  int rc = gram_buf(ctx, 2, (size_t)d * d, out_dev);
+  if (!rc) rc = gram_buf(ctx, 3, (size_t)d, &outy_dev);
+  if (rc) return rc;
+  return d > 64 ? run_gram<128>(ctx, data, w_dev, *out_dev, outy_dev, false) : run_gram<64>(ctx, data, w_dev, *out_dev, outy_dev, false);
 }

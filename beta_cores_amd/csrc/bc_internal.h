@@ -46,8 +46,8 @@ struct bc_ctx {
   bool own_stream = false;
   int timing = 0;                // 0 = off, n >= 1: every n-th launch of each kernel class is timed
   unsigned timing_mask = 0x7;    // which classes (bit = class): the step stages 3-5 only on request (bc_ctx_timing_classes)
-  bc_timer timers[6];            // 0 K3 sweep | 1 K1 projection | 2 K4 Gram + reduce | 3 rescoring / local winner |
-                                 // 4 candidate all-gather (RCCL) | 5 step finish
+  bc_timer timers[7];            // 0 K3 sweep | 1 K1 projection | 2 K4 Gram + reduce | 3 rescoring / local winner |
+                                 // 4 candidate all-gather (RCCL) | 5 step finish | 6 logistic rows pass + reduce (K5)
   int n_cu = 256;
   int max_lds = 64 * 1024;       // hipDeviceAttributeMaxSharedMemoryPerBlock (160 KiB on gfx950)
   double* pinned = nullptr;      // small pinned staging area (host)
@@ -58,6 +58,7 @@ struct bc_ctx {
   size_t proj_pinned_cap = 0;
   bc_scratch gradx;              // bc_project_grad_x
   bc_scratch gram[5];            // K4: partial, partial_y, out, out_y, w
+  bc_scratch lap[3];             // K5 (bc_laplace.hip): theta | reduced terms, per-block partials, curvature weights
   bc_phi* colsum_phi = nullptr;  // store-free K1: a Phi with the per-tile column partials but no tiles / norms
   bc_phi* core_phi = nullptr;    // bc_vi_gradient: the projection of the <= M coreset rows
   bc_scratch vi_buf;             // bc_vi_gradient: grad | resid
@@ -90,6 +91,7 @@ void bc_uploader_free(bc_ctx* ctx);
 int bc_scratch_grow(bc_ctx* ctx, bc_scratch* s, size_t doubles);   // contents are NOT kept when it grows
 
 int bc_timer_begin(bc_ctx* ctx, int which);
+int bc_gram_no_y(bc_ctx* ctx, const bc_data* data, const double* w_dev, double** out_dev);   // bc_gram.hip
 int bc_timer_end(bc_ctx* ctx, int which);
 
 struct bc_data {

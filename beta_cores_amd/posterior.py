@@ -122,3 +122,48 @@ def gaussian_weighted_post(th0, Sig0inv, Siginv, x, w, ctx=None, comm=None):
         LSigp = sl.solve_triangular(LSigpInv, np.eye(LSigpInv.shape[0]), lower=True, overwrite_b=True, check_finite=False)
         mup = np.dot(LSigp.dot(LSigp.T), np.dot(Sig0inv, th0) + np.dot(Siginv, xw))
     return mup, LSigp, LSigpInv
+
+
+def logistic_newton_pass(dz, theta, w=None, hessian=True, diag=False, comm=None, ctx=None):
+    """The logistic log-likelihood sum_n w_n ll_n of resident rows z = y*x (no y column, model_lr.py:29) at `theta`, and its
+    derivatives, from one streaming pass over the rows (K5) plus, for the Hessian, one weighted Gram (K4):
+    (value, grad, H or None, diag or None) with H = sum_n w_n c_n z_n z_n^T and diag its diagonal -- MINUS the likelihood's
+    Hessian, c = p (1 - p).  The N(0, I) prior is not included.  `dz`: a DeviceData (an ndarray is uploaded first); `w`: n_rows
+    host weights, a DeviceData of n_rows x 1 (upload once, pass many times), or None = all ones.  With `comm` the rows are this
+    rank's shard and the four parts are summed over ranks in rank order (the same bits on every rank)."""
+    if not isinstance(dz, DeviceData):
+        dz = DeviceData(np.atleast_2d(np.asarray(dz, dtype=np.float64)), ctx=ctx)
+    n, d = dz.shape
+    th = np.ascontiguousarray(theta, dtype=np.float64)
+    if th.shape != (d,):
+        raise ValueError('theta must have %d entries (one per column of the rows), got shape %r' % (d, th.shape))
+    wd = _weights_on_device(w, n, dz.ctx)
+    val = C.c_double()
+    g = np.empty(d)
+    dg = np.empty(d) if diag else None
+    H = np.empty((d, d)) if hessian else None
+    N.call('bc_logistic_newton_pass', dz.ctx.h, dz.h, wd.h if wd is not None else None, _ptr(th), C.byref(val), _ptr(g),
+           _ptr(dg), _ptr(H))
+    value = val.value
+    if comm is not None and comm.world > 1:
+        parts = [np.array([value]), g] + ([dg] if diag else []) + ([H.ravel()] if hessian else [])
+        tot = comm.sum_in_rank_order(np.concatenate(parts))
+        value, g = float(tot[0]), tot[1:1 + d]
+        o = 1 + d
+        if diag:
+            dg, o = tot[o:o + d], o + d
+        if hessian:
+            H = tot[o:o + d * d].reshape(d, d)
+    return value, g, H, dg
+
+
+def _weights_on_device(w, n, ctx):
+    """n host weights -> a DeviceData of n x 1 (None stays None: all ones)."""
+    if w is None or isinstance(w, DeviceData):
+        if w is not None and w.shape != (n, 1):
+            raise ValueError('w must be a DeviceData of %d x 1, got %r' % (n, w.shape))
+        return w
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    if w.shape != (n,):
+        raise ValueError('w must have one weight per row (%d), got shape %r' % (n, w.shape))
+    return DeviceData(w.reshape(n, 1), ctx=ctx)

@@ -18,7 +18,8 @@ import numpy as np
 import scipy.linalg as sl
 from scipy.optimize import minimize
 
-from .posterior import gaussian_weighted_post, small_lapack_scope, weighted_post
+from .device import DeviceData
+from .posterior import gaussian_weighted_post, logistic_newton_pass, small_lapack_scope, weighted_post, _weights_on_device
 
 
 class _PosteriorSampler:
@@ -170,14 +171,100 @@ def _lr_mode_newton(Zw, ww, mu0, max_iter=200):
     return mu
 
 
-def logistic_laplace(wts, Z, mu0, diag=False, rng=None, solver='bfgs', newton_start=None):
+def _newton_mode(lik, mu0, max_iter=200):
+    """_lr_mode_newton's iteration -- same start, backtracking constants and stopping rule, same expressions -- with the
+    likelihood parts supplied by a pass `lik(th, hessian) -> (value, grad, H or None)` of sum_n w_n ll_n (value), its gradient and
+    minus its Hessian (the device's logistic_newton_pass, or any stand-in).  Each iteration is one pass with the Hessian, each
+    backtracking trial one value-only pass."""
+    d = mu0.shape[0]
+    mu = np.array(mu0, dtype=np.float64)
+
+    def value(th):
+        return lik(th, False)[0] - 0.5 * d * np.log(2. * np.pi) - 0.5 * th.dot(th)
+    f = value(mu)
+    eye = np.eye(d)
+    for _ in range(max_iter):
+        _, gl, Hl = lik(mu, True)
+        g = -mu + gl
+        H = eye + Hl
+        step = sl.cho_solve(sl.cho_factor(H, lower=True, check_finite=False), g, check_finite=False)
+        t, dec = 1., g.dot(step)
+        while True:
+            cand = mu + t * step
+            fc = value(cand)
+            if fc >= f + 1e-4 * t * dec or t < 1e-10:
+                break
+            t *= 0.5
+        mu, f = cand, fc
+        if (t == 1. and dec <= 64. * np.finfo(np.float64).eps * (1. + abs(f))) or np.fabs(t * step).max() <= 1e-13 * (1. + np.fabs(mu).max()):
+            break
+    return mu
+
+
+def _device_laplace(wts, Z, mu0, diag, rng, solver, newton_start, ctx, comm):
+    """logistic_laplace over rows resident on the device: every pass over Z is K5 (+ K4 for the Hessian), the D x D algebra
+    stays on the host.  With `comm` each rank holds a shard of the rows (and of wts); the passes are summed in rank order, so
+    every rank walks the same iterates."""
+    n, d = Z.shape
+    mu0 = np.asarray(mu0, dtype=np.float64)
+    if mu0.shape != (d,):
+        raise ValueError('mu0 must have %d entries (one per column of Z), got shape %r' % (d, mu0.shape))
+    if wts is not None:
+        wts = np.asarray(wts, dtype=np.float64)
+        if wts.shape != (n,):
+            raise ValueError('wts must have one weight per row of Z (%d), got shape %r' % (n, wts.shape))
+    if solver not in ('bfgs', 'newton'):
+        raise ValueError("solver must be 'bfgs' (the reference's scipy.optimize.minimize call) or 'newton'")
+    if ctx is not None and ctx is not Z.ctx:
+        raise ValueError('ctx must be the context the rows Z live on')
+    # the reference keeps the rows with wts > 0 (Z[wts > 0]): the others get weight 0, which contributes exactly nothing
+    wd = None if wts is None else _weights_on_device(np.where(wts > 0, wts, 0.), n, Z.ctx)
+
+    def lik(th, hessian):
+        return logistic_newton_pass(Z, th, wd, hessian=hessian, comm=comm)[:3]
+    half_log_2pi = 0.5 * d * np.log(2. * np.pi)
+    if solver == 'newton':
+        mu = _newton_mode(lik, mu0 if newton_start is None else np.asarray(newton_start, dtype=np.float64))
+    trials = 10
+    while solver == 'bfgs':
+        def neg(th):
+            v, g, _ = lik(th, False)
+            return -(v - half_log_2pi - 0.5 * th.dot(th)), -(-th + g)
+        try:
+            res = minimize(neg, mu0, jac=True)
+        except (RuntimeError, ValueError):
+            raise                       # a failed (or misused) device pass: no restarts on a GPU that may have faulted
+        except Exception:
+            mu0 = mu0.copy()
+            mu0 += np.sqrt((mu0 ** 2).sum()) * 0.1 * (np.random.randn(mu0.shape[0]) if rng is None else rng.randn(mu0.shape[0]))
+            trials -= 1
+            if trials <= 0:
+                raise RuntimeError('logistic_laplace: the mode search failed ten times')
+            continue
+        mu = res.x
+        break
+    if diag:
+        sq = np.sqrt(1. + logistic_newton_pass(Z, mu, wd, hessian=False, diag=True, comm=comm)[3])
+        return mu, np.diag(1. / sq), np.diag(sq)
+    LSigInv = np.linalg.cholesky(np.eye(d) + lik(mu, True)[2])
+    LSig = sl.solve_triangular(LSigInv, np.eye(d), lower=True, overwrite_b=True, check_finite=False)
+    return mu, LSig, LSigInv
+
+
+def logistic_laplace(wts, Z, mu0, diag=False, rng=None, solver='bfgs', newton_start=None, ctx=None, comm=None):
     """`get_laplace` (examples/zellner_logreg/main.py:86-111 == bayesiancoresets/util/opt.py:9-33): (mu, LSig, LSigInv) of
     the Laplace approximation N(mu, LSig LSig^T) to the posterior of the rows Z with weights wts; the mode comes from
     scipy.optimize.minimize's default method started at mu0 (third-party arithmetic, shared with the reference, not
     restated), a failing optimisation restarts from a perturbed mu0 up to ten times.  diag=True returns the driver's
     diagonal MATRICES (main.py:105-108; util/opt.py:27-29 has vectors, which its own caller cannot multiply with).
     solver='newton' (not the reference's call, same unique mode): see _lr_mode_newton; BFGS stops at a gradient norm of
-    1e-5, i.e. ~1e-6 from the mode in theta, which is how far the two answers are apart."""
+    1e-5, i.e. ~1e-6 from the mode in theta, which is how far the two answers are apart.
+
+    Z a DeviceData (rows resident on the GPU, e.g. the full data set): the same fit with every pass over the rows on the device
+    (_device_laplace; wts: n_rows host weights, zeros allowed, or None = all ones; comm: Z and wts are this rank's shard).  The
+    device route has no CPU fallback."""
+    if isinstance(Z, DeviceData):
+        return _device_laplace(wts, Z, mu0, diag, rng, solver, newton_start, ctx, comm)
     trials = 10
     Zw = Z[wts > 0, :]
     ww = wts[wts > 0]
@@ -247,3 +334,22 @@ class LogisticLaplaceSampler(_PosteriorSampler):
             if self.solver == 'newton' and np.all(np.isfinite(muw)):
                 self._mode = muw.copy()
             return muw + self._normals(n, d).dot(LSigw.T)
+
+
+class LaplaceFullDataSampler(_PosteriorSampler):
+    """theta ~ the Laplace approximation of the logistic posterior of ALL the resident rows (the `sampler_optimal` /
+    `sampler_realistic` pattern of zellner_gaussian/main.py:71,83, for logistic data): fitted once, on the device, at
+    construction (logistic_laplace with Z = dz, a DeviceData of rows z = y*x); every call returns mu + randn(n, D).LSig^T and
+    ignores (wts, pts).  wts: per-row weights of dz (e.g. N/m on a sub-sample, zeros elsewhere), None = all ones."""
+
+    def __init__(self, dz, mu0, wts=None, diag=False, solver='newton', rng=None, comm=None):
+        super().__init__(rng)
+        self._shape = None
+        self.mu, self.LSig, self.LSigInv = logistic_laplace(wts, dz, np.asarray(mu0, dtype=np.float64), diag=diag, rng=rng,
+                                                            solver=solver, comm=comm)
+
+    def _dim(self):
+        return self.mu.shape[0]
+
+    def __call__(self, n, wts=None, pts=None):
+        return self.mu + self._normals(n, self.mu.shape[0]).dot(self.LSig.T)

@@ -84,7 +84,8 @@ int bc_ctx_sync(bc_ctx* ctx);
 /* time (ms) spent inside the dominant kernels since the last reset, measured
  * with HIP events on the launch stream; which: 0 = K3 score/argmax sweep,
  * 1 = K1 projection, 2 = K4 XtWX (Gram kernel + its split-order reduction), and the other stages of a greedy step:
- * 3 = rescoring / local winner, 4 = candidate all-gather (RCCL), 5 = step finish.  launches returns the number of
+ * 3 = rescoring / local winner, 4 = candidate all-gather (RCCL), 5 = step finish, 6 = the logistic rows pass of
+ * bc_logistic_newton_pass (K5 and its block-order reduction; its Hessian is class 2).  launches returns the number of
  * TIMED launches.
  * bc_ctx_enable_timing(ctx, n): 0 = off (default), n >= 1 = time every n-th launch of each class
  * (an event pair costs ~11 us of stream time on MI355X, which matters next to a 50 us sweep). */
