@@ -114,6 +114,15 @@ _EXT_SIGNATURES = {
 }
 EXT_EXPORTS = sorted(_EXT_SIGNATURES)
 
+# entry points of the extension header include/beta_cores_f32.h (float32 data rows; same library, same status conventions)
+_F32_SIGNATURES = {
+    'bc_data_from_host_f32': [vp, vp, C.c_int64, C.c_int32, vpp],
+    'bc_data_from_device_f32': [vp, vp, C.c_int64, C.c_int32, vpp],
+    'bc_project_from_host_f32': [vp, vp, C.c_int64, C.c_int32, C.c_int, vp, C.c_int32, vp, C.c_int32, C.c_int64, vpp, vpp],
+    'bc_data_elem_bytes': [vp, vp],
+}
+F32_EXPORTS = sorted(_F32_SIGNATURES)
+
 _lib = None
 
 
@@ -145,7 +154,7 @@ def load():
             'or `make -C beta_cores_amd/csrc`. There is no CPU fallback.' % LIB_PATH)
     _preload_torch_hip_runtime()
     lib = C.CDLL(LIB_PATH)
-    for name, argtypes in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()):
+    for name, argtypes in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_F32_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int

@@ -16,7 +16,7 @@ import weakref
 import numpy as np
 
 from .. import _native as N
-from ..device import DeviceData, DevicePhi, _as_f64, _ptr, default_context
+from ..device import DeviceData, DevicePhi, _as_rows, _ptr, default_context
 from ..util import numpy_bits
 
 
@@ -193,6 +193,14 @@ def _guard_release(ent):
                 _pin_guard.pop(id(arr), None)
 
 
+def _resident_dtype(arr):
+    """Storage dtype of the device copy of a host array: a float32 ndarray of _SMALL_ROWS rows or more stays float32 (results
+    are bit-identical to the widened rows', only the upload time and the memory change); everything else is float64 (None)."""
+    if isinstance(arr, np.ndarray) and arr.dtype == np.float32 and arr.ndim == 2 and arr.shape[0] >= _SMALL_ROWS:
+        return np.float32
+    return None
+
+
 class _DeviceProjectorBase(Projector):
     def __init__(self, sampler, projection_dimension, model, ctx=None):
         self.projection_dimension = projection_dimension
@@ -230,7 +238,7 @@ class _DeviceProjectorBase(Projector):
             # the view itself), so views are not pinned -- they are uploaded per call like any live array
             raise ValueError('pin(): the array is a view of another array; pin the base array or pass a copy')
         arr = np.atleast_2d(pts)
-        dd = DeviceData(arr, ctx=self.ctx)
+        dd = DeviceData(arr, ctx=self.ctx, dtype=_resident_dtype(arr))      # a float32 array keeps a float32 device copy
         ent = _guard_acquire(pts)
         fin = weakref.finalize(self, _guard_release, ent)      # a dying projector lets go of its pins
         try:
@@ -274,7 +282,7 @@ class _DeviceProjectorBase(Projector):
             if slot is None:
                 slot = self._slots[pts.shape[1]] = DeviceData.slot(pts.shape[1], cap_rows=256, ctx=self.ctx)
             return slot.update(pts), True
-        return DeviceData(pts, ctx=self.ctx), False            # live array, uploaded for this call
+        return DeviceData(pts, ctx=self.ctx, dtype=_resident_dtype(pts)), False      # live array, uploaded for this call
 
     def _zero_feature_keys(self, pts, d):
         """Sorted unique y of the rows of `pts` whose d features are all zero (host array: NumPy; resident rows: one device scan)."""
@@ -294,13 +302,15 @@ class _DeviceProjectorBase(Projector):
             except TypeError:
                 pass
             return keys
-        arr = np.atleast_2d(np.asarray(pts, dtype=np.float64))
+        arr = np.atleast_2d(np.asarray(pts))
+        if arr.dtype != np.float32 or arr.shape[0] < _SMALL_ROWS:      # (a large float32 array is scanned as it is: the zero test
+            arr = np.atleast_2d(np.asarray(pts, dtype=np.float64))     # is exact in either type, the few keys are widened below)
         big = arr.shape[0] >= _SMALL_ROWS and isinstance(pts, np.ndarray)
         if big:
             hit = self._key_cache.get(id(pts))
             if hit is not None and hit[0]() is pts:
                 return hit[1]
-        keys = np.unique(arr[~arr[:, :d].any(axis=1), d])
+        keys = np.unique(arr[~arr[:, :d].any(axis=1), d].astype(np.float64))
         if big:
             try:
                 self._key_cache[id(pts)] = (weakref.ref(pts, lambda _, k=id(pts), c=self._key_cache: c.pop(k, None)), keys)
@@ -329,7 +339,8 @@ class _DeviceProjectorBase(Projector):
         Phi, norms and column sums are the resident path's bit for bit).  Returns (DevicePhi, DeviceData of the uploaded
         rows); the latter is dropped by the caller unless it wants the rows to stay in HBM."""
         self._stage_host_constants(pts, model_id, params)
-        pts = _as_f64(np.atleast_2d(pts), 'data')
+        f32 = _resident_dtype(pts) is not None       # a float32 array goes up as it is: no float64 host copy, half the bytes
+        pts = _as_rows(np.atleast_2d(pts), np.dtype(np.float32 if f32 else np.float64), 'data')
         theta = self.model.theta_for_device(self.samples)
         if pts.shape[1] != self.model.data_width(theta.shape[1]):
             raise ValueError('data rows have %d columns, model expects %d for %d-dimensional samples'
@@ -339,7 +350,7 @@ class _DeviceProjectorBase(Projector):
         cap, h = self._pool.acquire(pts.shape[0], S)
         dh = C.c_void_p()
         try:
-            N.call('bc_project_from_host', self.ctx.h, _ptr(pts), int(pts.shape[0]), int(pts.shape[1]), int(model_id), _ptr(theta), S,
+            N.call('bc_project_from_host_f32' if f32 else 'bc_project_from_host', self.ctx.h, _ptr(pts), int(pts.shape[0]), int(pts.shape[1]), int(model_id), _ptr(theta), S,
                    _ptr(params), int(params.shape[0]), 0, C.byref(dh), C.byref(h))
         except Exception:
             self._pool.releaser(cap, S)(h)

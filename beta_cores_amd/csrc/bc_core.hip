@@ -2,6 +2,7 @@
 // sums / norms) and K3 (fused score + argmax sweep).  gfx950 only.
 #include "bc_internal.h"
 #include "bc_layout.h"
+#include "../../include/beta_cores_f32.h"
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -189,16 +190,25 @@ extern "C" int bc_ctx_kernel_time_reset(bc_ctx* ctx) {
 }
 
 // ------------------------------------------------------------------ data rows
-extern "C" int bc_data_from_host(bc_ctx* ctx, const double* z, int64_t n_rows, int32_t dz, bc_data** out) {
+int bc_refuse_f32(const bc_data* d, const char* who) {
+  if (!d || d->elem == 8) return BC_OK;
+  bc_set_error("%s: the rows are stored as float32; this entry point serves float64 rows only", who);
+  return BC_INVALID_ARGUMENT;
+}
+
+// elem: bytes per element of `z` and of the resident copy (8 = float64, 4 = float32: uploaded as it is, never converted)
+static int data_from_host(bc_ctx* ctx, const void* z, int64_t n_rows, int32_t dz, int elem, bc_data** out, const char* who) {
   if (!ctx || !out || n_rows < 0 || dz <= 0 || (n_rows > 0 && !z)) {
-    bc_set_error("bc_data_from_host: bad argument");
+    bc_set_error("%s: bad argument", who);
     return BC_INVALID_ARGUMENT;
   }
   bc_data* d = new bc_data();
   d->ctx = ctx;
   d->n_rows = n_rows;
   d->dz = dz;
-  size_t bytes = (size_t)n_rows * dz * sizeof(double);
+  d->elem = elem;
+  const size_t row_bytes = (size_t)dz * elem;
+  size_t bytes = (size_t)n_rows * row_bytes;
   if (bytes) {
     hipError_t e = hipMalloc((void**)&d->z, bytes);
     if (e != hipSuccess) { delete d; return bc_hip_fail(e, "hipMalloc(data)", __FILE__, __LINE__); }
@@ -207,10 +217,24 @@ extern "C" int bc_data_from_host(bc_ctx* ctx, const double* z, int64_t n_rows, i
     // moves pageable memory at the link rate here); BC_UPLOAD_THREADS = T >= 1 opts into T host threads copying through
     // pinned staging on copy streams of their own, with ctx->stream waiting for every chunk.  Either way the host buffer is
     // only borrowed for the call (every byte has left it when bc_upload_rows returns)
-    int rc = bc_upload_rows(ctx, z, d->z, n_rows, dz, bc_upload_default_chunk_rows(n_rows, dz), nullptr);
+    int rc = bc_upload_rows(ctx, z, d->z, n_rows, row_bytes, bc_upload_default_chunk_rows(n_rows, row_bytes), nullptr);
     if (rc) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(d->z); delete d; return rc; }
   }
   *out = d;
+  return BC_OK;
+}
+
+extern "C" int bc_data_from_host(bc_ctx* ctx, const double* z, int64_t n_rows, int32_t dz, bc_data** out) {
+  return data_from_host(ctx, z, n_rows, dz, 8, out, "bc_data_from_host");
+}
+
+extern "C" int bc_data_from_host_f32(bc_ctx* ctx, const float* z, int64_t n_rows, int32_t dz, bc_data** out) {
+  return data_from_host(ctx, z, n_rows, dz, 4, out, "bc_data_from_host_f32");
+}
+
+extern "C" int bc_data_elem_bytes(const bc_data* d, int32_t* out_bytes) {
+  if (!d || !out_bytes) { bc_set_error("bc_data_elem_bytes: bad argument"); return BC_INVALID_ARGUMENT; }
+  *out_bytes = d->elem;
   return BC_OK;
 }
 
@@ -230,6 +254,7 @@ extern "C" int bc_data_create(bc_ctx* ctx, int64_t cap_rows, int32_t dz, bc_data
 
 extern "C" int bc_data_upload(bc_data* d, const double* z, int64_t n_rows) {
   if (!d || n_rows < 0 || (n_rows > 0 && !z) || !d->owned) { bc_set_error("bc_data_upload: bad argument"); return BC_INVALID_ARGUMENT; }
+  if (bc_refuse_f32(d, "bc_data_upload")) return BC_INVALID_ARGUMENT;      // `z` holds doubles: nothing here rounds them
   bc_ctx* ctx = d->ctx;
   if (n_rows > d->cap_rows) {
     BC_HIP(hipStreamSynchronize(ctx->stream));
@@ -241,33 +266,45 @@ extern "C" int bc_data_upload(bc_data* d, const double* z, int64_t n_rows) {
   }
   d->n_rows = n_rows;
   if (n_rows > 0) {
-    int rc = bc_upload_rows(ctx, z, d->z, n_rows, d->dz, bc_upload_default_chunk_rows(n_rows, d->dz), nullptr);
+    const size_t row_bytes = (size_t)d->dz * sizeof(double);
+    int rc = bc_upload_rows(ctx, z, d->z, n_rows, row_bytes, bc_upload_default_chunk_rows(n_rows, row_bytes), nullptr);
     if (rc) return rc;                             // (the host buffer is only borrowed for the call: it has been read when this returns)
   }
   return BC_OK;
 }
 
-extern "C" int bc_data_from_device(bc_ctx* ctx, const void* z_dev, int64_t n_rows, int32_t dz, bc_data** out) {
+static int data_from_device(bc_ctx* ctx, const void* z_dev, int64_t n_rows, int32_t dz, int elem, bc_data** out, const char* who) {
   if (!ctx || !out || n_rows < 0 || dz <= 0 || (n_rows > 0 && !z_dev)) {
-    bc_set_error("bc_data_from_device: bad argument");
+    bc_set_error("%s: bad argument", who);
     return BC_INVALID_ARGUMENT;
   }
   bc_data* d = new bc_data();
   d->ctx = ctx;
   d->n_rows = n_rows;
   d->dz = dz;
+  d->elem = elem;
   d->z = (double*)z_dev;
   d->owned = false;
   *out = d;
   return BC_OK;
 }
 
-__global__ void k_gather_data_rows(const double* __restrict__ z, int dz, const long long* __restrict__ idx, long long m,
+extern "C" int bc_data_from_device(bc_ctx* ctx, const void* z_dev, int64_t n_rows, int32_t dz, bc_data** out) {
+  return data_from_device(ctx, z_dev, n_rows, dz, 8, out, "bc_data_from_device");
+}
+
+extern "C" int bc_data_from_device_f32(bc_ctx* ctx, const float* z_dev, int64_t n_rows, int32_t dz, bc_data** out) {
+  return data_from_device(ctx, z_dev, n_rows, dz, 4, out, "bc_data_from_device_f32");
+}
+
+// (ZT: the rows' storage type; the gathered rows are doubles either way)
+template <typename ZT>
+__global__ void k_gather_data_rows(const ZT* __restrict__ z, int dz, const long long* __restrict__ idx, long long m,
                                    double* __restrict__ out) {
   const long long j = blockIdx.x;
   if (j >= m) return;
   const long long r = idx[j];
-  for (int k = threadIdx.x; k < dz; k += blockDim.x) out[(size_t)j * dz + k] = z[(size_t)r * dz + k];
+  for (int k = threadIdx.x; k < dz; k += blockDim.x) out[(size_t)j * dz + k] = (double)z[(size_t)r * dz + k];
 }
 
 extern "C" int bc_data_gather_rows(bc_data* d, const int64_t* local_idx, int64_t m, double* out) {
@@ -285,7 +322,8 @@ extern "C" int bc_data_gather_rows(bc_data* d, const int64_t* local_idx, int64_t
   hipError_t e = hipMalloc((void**)&dout, (size_t)m * d->dz * sizeof(double));
   if (e == hipSuccess) e = hipMemcpyAsync(didx, local_idx, (size_t)m * sizeof(long long), hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_gather_data_rows, dim3((unsigned)m), dim3(128), 0, ctx->stream, d->z, d->dz, didx, (long long)m, dout);
+    if (d->elem == 4) hipLaunchKernelGGL(k_gather_data_rows<float>, dim3((unsigned)m), dim3(128), 0, ctx->stream, bc_rows<float>(d), d->dz, didx, (long long)m, dout);
+    else hipLaunchKernelGGL(k_gather_data_rows<double>, dim3((unsigned)m), dim3(128), 0, ctx->stream, bc_rows<double>(d), d->dz, didx, (long long)m, dout);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpyAsync(out, dout, (size_t)m * d->dz * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);

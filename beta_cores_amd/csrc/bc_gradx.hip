@@ -83,6 +83,7 @@ extern "C" int bc_project_grad_x(bc_ctx* ctx, const bc_data* data, int model, co
     return BC_INVALID_ARGUMENT;
   }
   if (data->ctx != ctx) { bc_set_error("bc_project_grad_x: data belongs to another context"); return BC_INVALID_ARGUMENT; }
+  if (bc_refuse_f32(data, "bc_project_grad_x")) return BC_INVALID_ARGUMENT;      // (the pseudo-points live in float64 slots)
   const int dz = data->dz;
   int d = dz, w = dz;
   double c0 = 0.;

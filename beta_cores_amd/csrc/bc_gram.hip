@@ -20,7 +20,7 @@
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
 struct GramArgs {
-  const double* z;        // [n_rows][dz]
+  const void* z;          // [n_rows][dz] of the kernel's ZT (double or float)
   const double* w;        // [n_rows] or null (all ones)
   double* partial;        // [splits][ntri][BT][BT]
   double* partial_y;      // [splits][nt*BT]   X^T (w*y), accumulated by the diagonal-tile blocks
@@ -84,7 +84,8 @@ __device__ const double g_gram_ones[16] = {1., 1., 1., 1., 1., 1., 1., 1., 1., 1
 // One (split, tile) of the Gram matrix.  V = -1: off-diagonal tile, every wave a square BT/2 x BT/2 wave tile; V = 0..3: diagonal
 // tile, wave V's share of its upper triangle (GramDiag).  The variant is block- (V < 0) or wave-uniform, chosen by a scalar
 // branch in k_gram; every variant passes the same barriers.
-template <int BT, int V>
+// ZT: the rows' storage type.  float rows are fetched with 4-byte loads and widened (exactly) when the slab is parked in LDS.
+template <int BT, int V, typename ZT>
 __device__ __forceinline__ void gram_tile(const GramArgs& a, int ta, int tb, long long split, int tri, double* __restrict__ Al,
                                           double* __restrict__ Bl, double* __restrict__ Yl) {
   constexpr int KR = BT == 64 ? 32 : 16; // rows per LDS slab (BT = 64: three MFMAs per wave and k-step at most -- twice the rows per barrier pair)
@@ -93,6 +94,8 @@ __device__ __forceinline__ void gram_tile(const GramArgs& a, int ta, int tb, lon
   constexpr int LP = (KR * BT) / 256;    // 8-byte loads per thread per panel per slab
   constexpr bool diag = V >= 0;          // the diagonal block of a column panel also owns its X^T (w*y) slice
   constexpr int NA = diag ? GramDiag<BT, diag ? V : 0>::n : MT * MT;
+  constexpr int ZB = (int)sizeof(ZT);
+  const ZT* __restrict__ zrows = reinterpret_cast<const ZT*>(a.z);
   const int tid = threadIdx.x, lane = tid & 63;
   const int j = lane & 15, g = lane >> 4;
   const int wa = V < 0 ? (tid >> 7) : 0, wb = V < 0 ? ((tid >> 6) & 1) : 0;   // wave position inside an off-diagonal block tile
@@ -113,32 +116,37 @@ __device__ __forceinline__ void gram_tile(const GramArgs& a, int ta, int tb, lon
   // tile) are read through an offset the descriptor's range check rejects, rows past the end likewise (z AND w: both
   // descriptors end at the last row), and a rejected load returns 0.
   constexpr int OOB = 0x40000000;
-  const int oa = a0 + lc < a.d ? (lr0 * a.dz + a0 + lc) * 8 : OOB;
-  const int ob = b0 + lc < a.d ? (lr0 * a.dz + b0 + lc) * 8 : OOB;
-  const int oy = (lr0 * a.dz + a.d) * 8;
+  const int oa = a0 + lc < a.d ? (lr0 * a.dz + a0 + lc) * ZB : OOB;
+  const int ob = b0 + lc < a.d ? (lr0 * a.dz + b0 + lc) * ZB : OOB;
+  const int oy = (lr0 * a.dz + a.d) * ZB;
   const bool weighted = a.w != nullptr;
   double vy = 0.0;
   // raw values of the slab in flight; the weighting and the X^T (w*y) term are applied when the slab is parked in LDS,
   // so that the loads can be requested in slices spread over the previous slab's k-steps (requested in one go after the
   // barrier they held the wave in the issue stage before its first MFMA of the slab -- see K1, profiles/r02_notes.md)
-  double va[LP], vb[LP], vw[LP], vyv[LP];
+  ZT va[LP], vb[LP], vyv[LP];
+  double vw[LP];
+  auto zload = [&](auto rs, int voff, int soff) __attribute__((always_inline)) -> ZT {
+    if constexpr (ZB == 8) return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, 0));
+    else return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, soff, 0));
+  };
   constexpr int NSL = KR / 4;            // one slice per k-step
   static_assert(LP % NSL == 0 || LP < NSL, "slices");
   auto load_part = [&](long long r0, int part) {
     const long long left = r_end - r0;
     const int rows_here = left < KR ? (left > 0 ? (int)left : 0) : KR;
-    const auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)(a.z + (size_t)r0 * a.dz), 0, rows_here * a.dz * 8, 0x00020000);
+    const auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)(zrows + (size_t)r0 * a.dz), 0, rows_here * a.dz * ZB, 0x00020000);
     // (no weights: sixteen ones stand in for them -- a base pointer chosen by the scalar unit, no branch and no constant moves)
     const auto rw = __builtin_amdgcn_make_buffer_rsrc((void*)(weighted ? a.w + r0 : g_gram_ones), 0, rows_here * 8, 0x00020000);
 #pragma unroll
     for (int q = part * LP / NSL; q < (part + 1) * LP / NSL; ++q) {
       vw[q] = 1.0;    // (BT = 64 is bound by its loads, not by the matrix pipe: no stand-in loads there)
       if ((BT == 128 && !(diag && !weighted)) || weighted) vw[q] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rw, (lr0 + q * RPP) * 8, 0, 0));
-      va[q] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, oa + q * RPP * a.dz * 8, 0, 0));
+      va[q] = zload(rs, oa + q * RPP * a.dz * ZB, 0);
       if (diag) {                          // both panels are the same columns: one load
-        vyv[q] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, oy + q * RPP * a.dz * 8, 0, 0));
+        vyv[q] = zload(rs, oy + q * RPP * a.dz * ZB, 0);
       } else {
-        vb[q] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, ob + q * RPP * a.dz * 8, 0, 0));
+        vb[q] = zload(rs, ob + q * RPP * a.dz * ZB, 0);
       }
     }
   };
@@ -150,18 +158,18 @@ __device__ __forceinline__ void gram_tile(const GramArgs& a, int ta, int tb, lon
     if (one_panel) {
 #pragma unroll
       for (int q = 0; q < LP; ++q) {
-        Al[(lr0 + q * RPP) * LDX + lc] = va[q];
-        vy = fma(va[q], vyv[q], vy);
+        Al[(lr0 + q * RPP) * LDX + lc] = (double)va[q];
+        vy = fma((double)va[q], (double)vyv[q], vy);
       }
       return;
     }
 #pragma unroll
     for (int q = 0; q < LP; ++q) {
       const int lr = lr0 + q * RPP;
-      const double raq = vw[q] * va[q];                  // A panel carries the weights: (w[:,None]*X)
+      const double raq = vw[q] * (double)va[q];          // A panel carries the weights: (w[:,None]*X)
       Al[lr * LDX + lc] = raq;
-      Bl[lr * LDX + lc] = diag ? va[q] : vb[q];
-      if (diag) vy = fma(raq, vyv[q], vy);               // (w[:,None]*Y[:,None]*X).sum(axis=0), model_linreg.py:31
+      Bl[lr * LDX + lc] = (double)(diag ? va[q] : vb[q]);
+      if (diag) vy = fma(raq, (double)vyv[q], vy);               // (w[:,None]*Y[:,None]*X).sum(axis=0), model_linreg.py:31
     }
   };
 
@@ -234,7 +242,7 @@ __device__ __forceinline__ void gram_tile(const GramArgs& a, int ta, int tb, lon
   }
 }
 
-template <int BT>
+template <int BT, typename ZT = double>
 __global__ __launch_bounds__(256, BT == 64 ? 3 : 2) void k_gram(GramArgs a) {
   __shared__ double Al[(BT == 64 ? 32 : 16) * (BT + 16)];
   __shared__ double Bl[(BT == 64 ? 32 : 16) * (BT + 16)];
@@ -251,12 +259,12 @@ __global__ __launch_bounds__(256, BT == 64 ? 3 : 2) void k_gram(GramArgs a) {
   int ta = 0, rem = tri;                 // tri -> (ta <= tb)
   while (rem >= a.nt - ta) { rem -= a.nt - ta; ++ta; }
   const int tb = ta + rem;
-  if (ta != tb) { gram_tile<BT, -1>(a, ta, tb, split, tri, Al, Bl, Yl); return; }
+  if (ta != tb) { gram_tile<BT, -1, ZT>(a, ta, tb, split, tri, Al, Bl, Yl); return; }
   switch (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) {     // (scalar branch: one variant per wave)
-    case 0: gram_tile<BT, 0>(a, ta, tb, split, tri, Al, Bl, Yl); break;
-    case 1: gram_tile<BT, 1>(a, ta, tb, split, tri, Al, Bl, Yl); break;
-    case 2: gram_tile<BT, 2>(a, ta, tb, split, tri, Al, Bl, Yl); break;
-    default: gram_tile<BT, 3>(a, ta, tb, split, tri, Al, Bl, Yl); break;
+    case 0: gram_tile<BT, 0, ZT>(a, ta, tb, split, tri, Al, Bl, Yl); break;
+    case 1: gram_tile<BT, 1, ZT>(a, ta, tb, split, tri, Al, Bl, Yl); break;
+    case 2: gram_tile<BT, 2, ZT>(a, ta, tb, split, tri, Al, Bl, Yl); break;
+    default: gram_tile<BT, 3, ZT>(a, ta, tb, split, tri, Al, Bl, Yl); break;
   }
 }
 
@@ -286,6 +294,7 @@ __device__ __forceinline__ void gram_dma_tile(const GramArgs& a, long long split
   // the two strips of X^T y this wave accumulates: both are in the fragment set it loads for its MFMAs
   constexpr int YS0 = V == 0 ? 0 : (V == 1 ? 4 : (V == 2 ? 2 : 6)), YS1 = YS0 + 1;
   constexpr bool ys_in_a = V == 2;          // (wave 2 holds strips 2, 3 as A fragments; the others hold theirs as B fragments)
+  const double* __restrict__ zd = reinterpret_cast<const double*>(a.z);      // float64 rows only: the DMA moves raw bytes and cannot widen
   const int tid = threadIdx.x, lane = tid & 63;
   const int j = lane & 15, g = lane >> 4;
   const long long r_begin = split * a.rows_per_split;
@@ -306,7 +315,7 @@ __device__ __forceinline__ void gram_dma_tile(const GramArgs& a, long long split
       const long long r = r0 + lr;
       double* dst = pb + lr * LDX;
       if (r < r_end) {
-        __builtin_amdgcn_global_load_lds((const void*)(a.z + (size_t)r * a.dz + 2 * lane),
+        __builtin_amdgcn_global_load_lds((const void*)(zd + (size_t)r * a.dz + 2 * lane),
                                          (void __attribute__((address_space(3)))*)dst, 16, 0, 0);
       } else {
         dst[2 * lane] = 0.;
@@ -320,7 +329,7 @@ __device__ __forceinline__ void gram_dma_tile(const GramArgs& a, long long split
         const long long r = r0 + h + (lane >> 1);
         const long long rc = r < r_end ? r : r_begin;               // (clamped: zeroed below)
         if (h + (lane >> 1) < KR)
-          __builtin_amdgcn_global_load_lds((const void*)(reinterpret_cast<const int*>(a.z + (size_t)rc * a.dz + a.d) + (lane & 1)),
+          __builtin_amdgcn_global_load_lds((const void*)(reinterpret_cast<const int*>(zd + (size_t)rc * a.dz + a.d) + (lane & 1)),
                                            (void __attribute__((address_space(3)))*)yb, 4, 0, 0);
       }
     }
@@ -542,7 +551,9 @@ static int run_gram(bc_ctx* ctx, const bc_data* data, const double* w_dev, doubl
   // one unweighted diagonal tile whose rows hold at least 128 doubles: the LDS-DMA kernel (k_gram_dma); BC_GRAM_DMA=0: the
   // register-staged k_gram (A/B)
   const int dma_env = getenv("BC_GRAM_DMA") ? atoi(getenv("BC_GRAM_DMA")) : 1;      // (read per call: tests flip it)
-  const bool use_dma = BT == 128 && ntri == 1 && w_dev == nullptr && y_col && dz >= 128 && dma_env != 0 && data->n_rows >= 4096;
+  // float32 rows always take the register-staged k_gram: the LDS-DMA path moves raw doubles and has no place to widen
+  const bool use_dma = BT == 128 && ntri == 1 && w_dev == nullptr && y_col && dz >= 128 && dma_env != 0 && data->n_rows >= 4096 &&
+                       data->elem == 8;
   const int KR = use_dma ? BC_GD_KR : (BT == 64 ? 32 : 16);
   // Row splits, in units of the 2 * n_cu resident block slots (BC_GRAM_WAVES overrides), at least 2 slabs per split.
   // One tile (D <= 128): exactly one block per slot -- every further split writes, and the reduction reads back, another
@@ -597,7 +608,9 @@ static int run_gram(bc_ctx* ctx, const bc_data* data, const double* w_dev, doubl
         e = hipGetLastError();
       }
     } else {
-      hipLaunchKernelGGL(k_gram<BT>, dim3((unsigned)(((splits + 7) / 8) * 8 * ntri)), dim3(256), 0, ctx->stream, a);
+      const dim3 ggrid((unsigned)(((splits + 7) / 8) * 8 * ntri));
+      if (data->elem == 4) hipLaunchKernelGGL((k_gram<BT, float>), ggrid, dim3(256), 0, ctx->stream, a);
+      else hipLaunchKernelGGL((k_gram<BT, double>), ggrid, dim3(256), 0, ctx->stream, a);
       e = hipGetLastError();
     }
   }

@@ -83,9 +83,10 @@ struct bc_ctx {
 // bc_upload.hip: rows of a host array -> dst_dev through pinned staging and several copy threads; the hook (optional) is
 // called per chunk in row order with the event that marks the chunk's arrival (nullptr: it has already landed)
 typedef std::function<int(int64_t chunk, int64_t row0, int64_t rows, hipEvent_t landed)> bc_chunk_hook;
-int bc_upload_rows(bc_ctx* ctx, const double* src, double* dst_dev, int64_t n_rows, int32_t dz, int64_t chunk_rows,
+// row_bytes: the size of one row (dz elements of the rows' storage type: the uploader moves bytes)
+int bc_upload_rows(bc_ctx* ctx, const void* src, void* dst_dev, int64_t n_rows, size_t row_bytes, int64_t chunk_rows,
                    const bc_chunk_hook* on_chunk);
-int64_t bc_upload_default_chunk_rows(int64_t n_rows, int32_t dz);
+int64_t bc_upload_default_chunk_rows(int64_t n_rows, size_t row_bytes);
 void bc_uploader_free(bc_ctx* ctx);
 
 int bc_scratch_grow(bc_ctx* ctx, bc_scratch* s, size_t doubles);   // contents are NOT kept when it grows
@@ -98,10 +99,18 @@ struct bc_data {
   bc_ctx* ctx = nullptr;
   int64_t n_rows = 0;
   int32_t dz = 0;
-  double* z = nullptr;           // row-major n_rows x dz
+  double* z = nullptr;           // row-major n_rows x dz; elem == 4: the allocation holds FLOATS (read it through bc_rows<float>)
   bool owned = true;
   int64_t cap_rows = 0;          // allocation size in rows (owned buffers)
+  int elem = 8;                  // bytes per stored element: 8 = float64, 4 = float32 (include/beta_cores_f32.h).  float32 rows
+                                 // are widened in registers by the kernels that read them; nothing else in the library is float32
 };
+
+// the rows of a handle as their storage type (the caller has dispatched on data->elem)
+template <typename T>
+static inline const T* bc_rows(const bc_data* d) { return reinterpret_cast<const T*>(d->z); }
+// entry points that only serve float64 rows: BC_INVALID_ARGUMENT and a message that names the dtype
+int bc_refuse_f32(const bc_data* d, const char* who);
 
 struct bc_phi {
   bc_ctx* ctx = nullptr;

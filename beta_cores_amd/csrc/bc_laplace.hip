@@ -24,7 +24,7 @@
 #define BC_LR_RED_PARTS 16        // k_lr_reduce: 16 runs of consecutive blocks per element, summed in run order
 
 struct LrArgs {
-  const double* z;        // [n_rows][d]
+  const void* z;          // [n_rows][d] of the kernel's ZT (double or float)
   const double* w;        // [n_rows] or null (all ones)
   const double* theta;    // [d]
   double* wc;             // [n_rows]: w_n c_n (the Hessian's weights), or null
@@ -48,9 +48,10 @@ __device__ __forceinline__ void lr_terms(double m, double& ll, double& p, double
   }
 }
 
-template <int NC, int R, bool DIAG>   // R: a power of two <= 64
+template <int NC, int R, bool DIAG, typename ZT = double>   // R: a power of two <= 64; ZT: the rows' storage type (float: widened as read)
 __global__ __launch_bounds__(256) void k_lr_rows(LrArgs a) {
   __shared__ double red[2 * NC * 64 + 1];
+  const ZT* __restrict__ zrows = reinterpret_cast<const ZT*>(a.z);
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int d = a.d;
   const long long start = (long long)blockIdx.x * a.rows_per_block;
@@ -72,11 +73,11 @@ __global__ __launch_bounds__(256) void k_lr_rows(LrArgs a) {
     for (int i = 0; i < R; ++i) {
       const long long row = r0 + i;
       const bool ok = row < end;
-      const double* zr = a.z + (size_t)(ok ? row : start) * d;
+      const ZT* zr = zrows + (size_t)(ok ? row : start) * d;
 #pragma unroll
       for (int c = 0; c < NC; ++c) {
         const int col = c * 64 + lane;
-        x[i][c] = ok && col < d ? zr[col] : 0.;
+        x[i][c] = ok && col < d ? (double)zr[col] : 0.;
       }
       wr[i] = ok ? (a.w ? a.w[row] : 1.) : 0.;     // (rows past the end: z = 0 and weight 0 -- finite terms times zero)
     }
@@ -165,7 +166,12 @@ __global__ __launch_bounds__(256) void k_lr_reduce(const double* __restrict__ pa
 }
 
 template <int NC, int R>
-static void launch_rows(bool diag, dim3 grid, hipStream_t s, const LrArgs& a) {
+static void launch_rows(bool diag, bool f32, dim3 grid, hipStream_t s, const LrArgs& a) {
+  if (f32) {
+    if (diag) hipLaunchKernelGGL((k_lr_rows<NC, R, true, float>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_lr_rows<NC, R, false, float>), grid, dim3(256), 0, s, a);
+    return;
+  }
   if (diag) hipLaunchKernelGGL((k_lr_rows<NC, R, true>), grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL((k_lr_rows<NC, R, false>), grid, dim3(256), 0, s, a);
 }
@@ -192,6 +198,8 @@ extern "C" int bc_logistic_newton_pass(bc_ctx* ctx, const bc_data* data, const b
     bc_set_error("bc_logistic_newton_pass: weights must be %lld x 1, got %lld x %d", (long long)data->n_rows, (long long)w->n_rows, w->dz);
     return BC_INVALID_ARGUMENT;
   }
+  if (w && bc_refuse_f32(w, "bc_logistic_newton_pass (weights)")) return BC_INVALID_ARGUMENT;
+  const bool f32 = data->elem == 4;
   const long long n = data->n_rows;
   const int elems = 1 + 2 * d;
   if (n == 0) {
@@ -233,11 +241,11 @@ extern "C" int bc_logistic_newton_pass(bc_ctx* ctx, const bc_data* data, const b
   const dim3 grid((unsigned)blocks);
   const bool diag = out_diag != nullptr;
   switch (nc) {
-    case 1: launch_rows<1, 8>(diag, grid, ctx->stream, a); break;
-    case 2: launch_rows<2, 8>(diag, grid, ctx->stream, a); break;
-    case 4: launch_rows<4, 4>(diag, grid, ctx->stream, a); break;
-    case 8: launch_rows<8, 4>(diag, grid, ctx->stream, a); break;
-    default: launch_rows<16, 2>(diag, grid, ctx->stream, a); break;
+    case 1: launch_rows<1, 8>(diag, f32, grid, ctx->stream, a); break;
+    case 2: launch_rows<2, 8>(diag, f32, grid, ctx->stream, a); break;
+    case 4: launch_rows<4, 4>(diag, f32, grid, ctx->stream, a); break;
+    case 8: launch_rows<8, 4>(diag, f32, grid, ctx->stream, a); break;
+    default: launch_rows<16, 2>(diag, f32, grid, ctx->stream, a); break;
   }
   BC_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_lr_reduce, dim3((unsigned)((elems + 15) / 16)), dim3(256), 0, ctx->stream, (const double*)a.part, blocks, elems,

@@ -77,10 +77,12 @@ BC_LAY size_t bc_lay_i4_word(long long ptile, int g, int row_in_tile, int sp8) {
 BC_LAY int bc_lay_r8_bytes(int S) { return (4 * ((S + 3) / 4) + 4 + 127) / 128 * 128; }
 
 BC_LAY long long bc_lay_chunk_unit(int rgrid) { return rgrid > 0 ? (long long)rgrid * 8 * 32 : (long long)BC_LAY_TILE * 512; }
-BC_LAY long long bc_lay_chunk_rows(int dz, long long unit, long long forced) {
-  long long rows = (((long long)128 << 20) / ((long long)dz * 8) + unit - 1) / unit * unit;
+// (row_bytes: dz elements of the rows' storage type; the chunk is a size in BYTES, its alignment a count of ROWS)
+BC_LAY long long bc_lay_chunk_rows_bytes(long long row_bytes, long long unit, long long forced) {
+  long long rows = (((long long)128 << 20) / row_bytes + unit - 1) / unit * unit;
   if (forced > 0) rows = (forced + unit - 1) / unit * unit;
   return rows;
 }
+BC_LAY long long bc_lay_chunk_rows(int dz, long long unit, long long forced) { return bc_lay_chunk_rows_bytes((long long)dz * 8, unit, forced); }
 
 #endif  // BC_LAYOUT_H

@@ -46,8 +46,7 @@ static int uploader_threads() {
 }
 
 // chunking of a plain upload (no per-chunk consumer): enough chunks to keep every copy thread busy, none below 4 MiB
-int64_t bc_upload_default_chunk_rows(int64_t n_rows, int32_t dz) {
-  const size_t row_bytes = (size_t)dz * sizeof(double);
+int64_t bc_upload_default_chunk_rows(int64_t n_rows, size_t row_bytes) {
   const size_t total = (size_t)n_rows * row_bytes;
   int t = uploader_threads();
   if (t < 1) t = 1;
@@ -123,13 +122,12 @@ static int uploader_get(bc_ctx* ctx, int nthreads, size_t nchunks, bc_uploader**
   return BC_OK;
 }
 
-// rows [0, n_rows) of `src` (row-major, dz doubles per row) -> dst_dev, in chunks of chunk_rows rows.
+// rows [0, n_rows) of `src` (row-major, row_bytes bytes per row) -> dst_dev, in chunks of chunk_rows rows.
 // on_chunk(c, row0, rows, landed): called in chunk order on the calling thread; `landed` is recorded on a copy stream
 // behind the chunk's last DMA.  Without a hook ctx->stream is made to wait for every chunk.
-int bc_upload_rows(bc_ctx* ctx, const double* src, double* dst_dev, int64_t n_rows, int32_t dz, int64_t chunk_rows,
+int bc_upload_rows(bc_ctx* ctx, const void* src, void* dst_dev, int64_t n_rows, size_t row_bytes, int64_t chunk_rows,
                    const bc_chunk_hook* on_chunk) {
   if (n_rows <= 0) return BC_OK;
-  const size_t row_bytes = (size_t)dz * sizeof(double);
   const size_t total = (size_t)n_rows * row_bytes;
   int nthreads = uploader_threads();
   if (!on_chunk && (nthreads == 0 || total < ((size_t)32 << 20))) {

@@ -23,6 +23,33 @@ def _as_f64(a, what):
     return a
 
 
+def _storage_dtype(z, dtype):
+    """The dtype a DeviceData of host rows `z` is STORED in.  dtype=None: float64, whatever `z` holds (a float32 array is
+    widened on the host, as it always was).  dtype=np.float32: `z` must already BE float32 -- the library never rounds the
+    caller's data -- and is uploaded as it is.  Needs no GPU."""
+    if dtype is None:
+        return np.dtype(np.float64)
+    dt = np.dtype(dtype)
+    if dt == np.float64:
+        return dt
+    if dt != np.float32:
+        raise ValueError('DeviceData stores float64 or float32 rows, not %s' % dt)
+    if getattr(z, 'dtype', None) != np.float32:
+        raise ValueError('dtype=float32 takes a float32 array (got %s): the library never rounds the caller\'s data; '
+                         'pass z.astype(np.float32) if that rounding is intended' % getattr(z, 'dtype', type(z).__name__))
+    return dt
+
+
+def _as_rows(a, dt, what):
+    """C-contiguous 2-D rows of storage dtype `dt` (float32 input stays float32 when dt is float32: no float64 copy)."""
+    if dt == np.float32:
+        a = np.ascontiguousarray(a)
+        if a.dtype != np.float32:
+            raise ValueError(what + ' must be a float32 array')
+        return a
+    return _as_f64(a, what)
+
+
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
 
@@ -88,24 +115,42 @@ def set_default_context(ctx):
 
 
 class DeviceData:
-    """Data rows Z (n x dz, row-major float64) resident in HBM."""
+    """Data rows Z (n x dz, row-major) resident in HBM, stored as float64 (default) or float32.
 
-    def __init__(self, z=None, ctx=None, device_ptr=None, shape=None, keepalive=None, row_offset=0):
+    dtype=np.float32 keeps a float32 array as it is: half the bytes on the host link and half the HBM.  Only the storage is
+    float32 -- every kernel widens the rows in registers (exact) and computes in float64, so all results have the bits the
+    float64 path gives on `z.astype(np.float64)`.  rows() / [] return float64 host rows either way."""
+
+    def __init__(self, z=None, ctx=None, device_ptr=None, shape=None, keepalive=None, row_offset=0, dtype=None):
+        if device_ptr is None:
+            z = np.atleast_2d(z)
+            dt = _storage_dtype(z, dtype)            # (before any context exists: a wrong dtype needs no GPU to be refused)
+        else:
+            dt = np.dtype(np.float64 if dtype is None else dtype)
+            if dt not in (np.float64, np.float32):
+                raise ValueError('DeviceData stores float64 or float32 rows, not %s' % dt)
+        f32 = dt == np.float32
         self.ctx = ctx or default_context()
         self.row_offset = int(row_offset)     # global index of row 0 when the rows are one shard of a larger set
         h = C.c_void_p()
         if device_ptr is not None:
             n, dz = shape
-            N.call('bc_data_from_device', self.ctx.h, C.c_void_p(device_ptr), int(n), int(dz), C.byref(h))
+            N.call('bc_data_from_device_f32' if f32 else 'bc_data_from_device', self.ctx.h, C.c_void_p(device_ptr), int(n), int(dz),
+                   C.byref(h))
             self._keep = keepalive
         else:
-            z = np.atleast_2d(z)
-            z = _as_f64(z, 'data')
+            z = _as_rows(z, dt, 'data')
             n, dz = z.shape
-            N.call('bc_data_from_host', self.ctx.h, _ptr(z), int(n), int(dz), C.byref(h))
+            N.call('bc_data_from_host_f32' if f32 else 'bc_data_from_host', self.ctx.h, _ptr(z), int(n), int(dz), C.byref(h))
         self.h = h
         self.shape = (int(n), int(dz))
+        self.dtype = dt
         self._fin = weakref.finalize(self, N.load().bc_data_destroy, h)
+
+    @property
+    def nbytes(self):
+        """Bytes of HBM the rows take."""
+        return self.shape[0] * self.shape[1] * self.dtype.itemsize
 
     @classmethod
     def _adopt(cls, handle, shape, ctx):
@@ -115,6 +160,9 @@ class DeviceData:
         self.row_offset = 0
         self.h = handle
         self.shape = (int(shape[0]), int(shape[1]))
+        nb = C.c_int32()
+        N.call('bc_data_elem_bytes', handle, C.byref(nb))
+        self.dtype = np.dtype(np.float32 if nb.value == 4 else np.float64)
         self._fin = weakref.finalize(self, N.load().bc_data_destroy, handle)
         return self
 
@@ -129,6 +177,7 @@ class DeviceData:
         N.call('bc_data_create', self.ctx.h, int(cap_rows), int(dz), C.byref(h))
         self.h = h
         self.shape = (0, int(dz))
+        self.dtype = np.dtype(np.float64)       # slots hold the small transient row sets: always float64
         self._fin = weakref.finalize(self, N.load().bc_data_destroy, h)
         return self
 
@@ -141,7 +190,7 @@ class DeviceData:
         return self
 
     def rows(self, local_idx):
-        """Rows by LOCAL index, on the host (m x dz)."""
+        """Rows by LOCAL index, on the host (m x dz float64, whatever the storage dtype)."""
         idx = np.ascontiguousarray(local_idx, dtype=np.int64).ravel()
         out = np.empty((idx.shape[0], self.shape[1]))
         N.call('bc_data_gather_rows', self.h, _ptr(idx), int(idx.shape[0]), _ptr(out))
@@ -157,18 +206,20 @@ class DeviceData:
 
     @classmethod
     def from_torch(cls, t, ctx=None, row_offset=0):
-        """Borrow a contiguous float64 CUDA tensor (kept alive by this object).
+        """Borrow a contiguous float64 or float32 CUDA tensor (kept alive by this object; a float32 tensor is borrowed as
+        float32 rows, see DeviceData).
 
         The tensor's producer kernels run on torch's current stream; unless this library launches on
         that same stream (Context(stream=...)), wait for them here -- otherwise our first kernel could
         read rows torch has not finished writing."""
-        assert t.is_cuda and t.is_contiguous() and str(t.dtype) == 'torch.float64' and t.dim() == 2
+        assert t.is_cuda and t.is_contiguous() and str(t.dtype) in ('torch.float64', 'torch.float32') and t.dim() == 2
+        dt = np.float32 if str(t.dtype) == 'torch.float32' else np.float64
         import torch
         cur = torch.cuda.current_stream(t.device)
         c = ctx or default_context()
         if c.stream_handle is None or c.stream_handle != cur.cuda_stream:
             cur.synchronize()
-        return cls(ctx=ctx, device_ptr=t.data_ptr(), shape=tuple(t.shape), keepalive=t, row_offset=row_offset)
+        return cls(ctx=ctx, device_ptr=t.data_ptr(), shape=tuple(t.shape), keepalive=t, row_offset=row_offset, dtype=dt)
 
 
 class _PhiT:

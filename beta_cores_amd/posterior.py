@@ -61,6 +61,8 @@ def weighted_gram(z, w=None, ctx=None, comm=None):
     ctx = ctx or default_context()
     if w is not None:
         w = np.ascontiguousarray(w, dtype=np.float64)
+    if isinstance(z, np.ndarray) and z.dtype == np.float32 and z.ndim == 2 and z.shape[0] * (z.shape[1] + 1) > 60000:
+        z = DeviceData(z, ctx=ctx, dtype=np.float32)      # a large float32 array is uploaded as it is (the same bits, half the bytes)
     if not isinstance(z, DeviceData):
         z = np.ascontiguousarray(np.atleast_2d(z), dtype=np.float64)
         if w is not None and w.shape != (z.shape[0],):
@@ -132,7 +134,10 @@ def logistic_newton_pass(dz, theta, w=None, hessian=True, diag=False, comm=None,
     host weights, a DeviceData of n_rows x 1 (upload once, pass many times), or None = all ones.  With `comm` the rows are this
     rank's shard and the four parts are summed over ranks in rank order (the same bits on every rank)."""
     if not isinstance(dz, DeviceData):
-        dz = DeviceData(np.atleast_2d(np.asarray(dz, dtype=np.float64)), ctx=ctx)
+        if isinstance(dz, np.ndarray) and dz.dtype == np.float32 and dz.ndim == 2:
+            dz = DeviceData(dz, ctx=ctx, dtype=np.float32)      # float32 rows are uploaded as they are (the same bits, half the bytes)
+        else:
+            dz = DeviceData(np.atleast_2d(np.asarray(dz, dtype=np.float64)), ctx=ctx)
     n, d = dz.shape
     th = np.ascontiguousarray(theta, dtype=np.float64)
     if th.shape != (d,):
