@@ -396,7 +396,7 @@ def test_k4_weighted_gram(bc, d):
 
 
 # ------------------------------------------------------------------ K5
-@pytest.mark.parametrize('n,d', [(5000, 7), (30011, 64), (20000, 128), (9000, 200)])
+@pytest.mark.parametrize('n,d', [(5000, 7), (30011, 64), (20000, 128), (9000, 200), (3001, 300), (2000, 512), (1500, 513), (1000, 1024)])
 def test_k5_newton_pass(bc, n, d):
     rng = np.random.RandomState(n + d)
     Z32 = rows32(rng, n, d, d, special=False)

@@ -43,7 +43,8 @@ def rows(n, d, seed):
 
 
 SHAPES = [(n, d) for n in (1, 15, 16, 17, 4097) for d in (1, 6, 11, 64, 127, 128, 129, 512)] + \
-         [(100_003, d) for d in (6, 128, 129, 512)]
+         [(100_003, d) for d in (6, 128, 129, 512)] + \
+         [(n, d) for n in (1, 9, 4097) for d in (256, 257, 513, 777, 1024)]      # (past 512 columns: k_lr_rows<16, 2>)
 
 
 @pytest.mark.parametrize('n,d', SHAPES)
@@ -69,6 +70,18 @@ def test_pass_matches_numpy(n, d):
         # value-only pass: the same value and gradient
         v3, g3, H3, dg3 = bc.logistic_newton_pass(dz, th, w=w, hessian=False)
         assert H3 is None and dg3 is None and v3 == v and np.array_equal(g3, g)
+
+
+@pytest.mark.parametrize('dtype', [np.float64, np.float32])
+def test_more_than_1024_columns_are_refused(dtype):
+    """The rows pass holds a row in 16 column slots of 64 lanes: 1025 columns are refused before anything is launched."""
+    import beta_cores_amd as bc
+    dz = bc.DeviceData(np.ones((3, 1025), dtype=dtype), dtype=dtype)
+    for hessian in (True, False):
+        with pytest.raises(ValueError, match=r'1 \.\. 1024 columns, got 1025'):
+            bc.logistic_newton_pass(dz, np.zeros(1025), hessian=hessian)
+    v, g, H, dg = bc.logistic_newton_pass(bc.DeviceData(np.ones((3, 1024), dtype=dtype), dtype=dtype), np.zeros(1024), hessian=False)
+    assert abs(v + 3. * np.log(2.)) <= 1e-14 and np.array_equal(g, np.full(1024, 1.5))      # (the context is as usable as before)
 
 
 def test_weighted_gram_unchanged_beside_the_pass():
