@@ -123,6 +123,15 @@ _F32_SIGNATURES = {
 }
 F32_EXPORTS = sorted(_F32_SIGNATURES)
 
+# entry points of the extension header include/beta_cores_nnls.h (device NNLS refit: OrthoPursuit in the fused loop, optimize())
+_NNLS_SIGNATURES = {
+    'bc_snnls_device_refit': [vp, C.c_int],
+    'bc_snnls_refit': [vp, C.c_int64],
+    'bc_snnls_optimize': [vp, c_ip],
+    'bc_snnls_refit_stats': [vp, c_i64p, c_i64p, c_i64p],
+}
+NNLS_EXPORTS = sorted(_NNLS_SIGNATURES)
+
 _lib = None
 
 
@@ -154,7 +163,7 @@ def load():
             'or `make -C beta_cores_amd/csrc`. There is no CPU fallback.' % LIB_PATH)
     _preload_torch_hip_runtime()
     lib = C.CDLL(LIB_PATH)
-    for name, argtypes in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_F32_SIGNATURES.items()):
+    for name, argtypes in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_F32_SIGNATURES.items()) + list(_NNLS_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int

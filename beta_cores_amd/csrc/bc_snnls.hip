@@ -19,6 +19,7 @@ extern "C" int bc_debug_fin_stamps(unsigned long long* out) {
 }
 #endif
 #include "bc_rescore_dev.h"
+#include "../../include/beta_cores_nnls.h"
 #include "bc_layout.h"
 #include "bc_i8_quant.h"
 #include "bc_i4_quant.h"
@@ -106,6 +107,13 @@ struct SnnlsDev {
   const long long* blk_idx;
   int nblk;
   int fuse_winner;
+  // device NNLS refit (bc_nnls_dev.h): Gram matrix of the list's cached columns [BC_NNLS_MAXP][BC_NNLS_MAXP], its right-hand
+  // side cols . b, and {refits, solves, rejected, covered}: the refit counters and the number of leading list entries the Gram
+  // state covers -- written by the kernels that extend it, lowered by every kernel that puts another column into a covered
+  // slot (dev_gram_touch).  nullptr until a refit entry point is first used
+  double* gram;
+  double* gram_c;
+  long long* nnls_stats;
 };
 
 struct bc_snnls {
@@ -135,6 +143,8 @@ struct bc_snnls {
   bool exact_step = false;        // the step in flight uses the exact fp64 sweep (redo after a pre-filter overflow)
   bool pref_suspended = false;    // repeated overflows: the rest of this build call sweeps in fp64
   int consec_overflow = 0;
+  bool dev_refit = false;         // bc_snnls_device_refit: an OrthoPursuit handle runs the fused loop with the device NNLS refit
+  void* nnls_slab = nullptr;      // gram | gram_c | nnls_stats
 };
 
 // ------------------------------------------------------------------ device building blocks (single block)
@@ -566,6 +576,12 @@ __device__ int dev_step_sizes(const SnnlsDev& P, const SnnlsState& S, double* re
   return ab_fail;
 }
 
+// list slot `at` is about to hold another column (thread 0): the Gram state of the device NNLS refit, if this solver has one,
+// no longer covers it
+__device__ __forceinline__ void dev_gram_touch(const SnnlsDev& P, long long at) {
+  if (P.nnls_stats != nullptr && P.nnls_stats[3] > at) P.nnls_stats[3] = at;
+}
+
 // w = alpha*w ; w[f] = max(0, w[f] + beta)   (giga.py:63-64, frankwolfe.py:39-40)
 __device__ void dev_apply(const SnnlsDev& P, SnnlsState& S, double alpha, double beta) {
   __shared__ int slot;
@@ -594,6 +610,7 @@ __device__ void dev_apply(const SnnlsDev& P, SnnlsState& S, double alpha, double
           P.idx[at] = f;
           P.val[at] = nv;
           P.colnorm[at] = S.sel_norm;
+          dev_gram_touch(P, at);
         }
         __syncthreads();
         if (threadIdx.x == 0) S.nnz = at + 1;
@@ -944,15 +961,12 @@ __global__ __launch_bounds__(BC_FIN_THREADS) void k_pick(SnnlsDev P) {
   }
 }
 
-// step-wise _reweight(f): no guard here, the host loop owns it (snnls.py:53-61)
-template <int ALG>
-__global__ __launch_bounds__(BC_FIN_THREADS) void k_reweight(SnnlsDev P, long long f) {
-  __shared__ SnnlsState S;
-  __shared__ double red[64];
+// column f -> P.xf (and its norm -> S.sel_norm) for a step-wise reweight: it is the last pick, or sits in a gathered
+// record, or in the local shard.  Returns 0 (block-uniform) when this rank cannot supply it.
+__device__ int dev_fetch_column(const SnnlsDev& P, SnnlsState& S, long long f) {
   __shared__ int found;
   const int s = P.s;
   if (threadIdx.x == 0) {
-    S = *P.st;
     int fd = 0;   // 0: not found, 1: xf already holds it, 2+r: record r, -1: local shard
     if (S.sel_valid && S.sel_f == f) fd = 1;
     if (!fd)
@@ -964,10 +978,7 @@ __global__ __launch_bounds__(BC_FIN_THREADS) void k_reweight(SnnlsDev P, long lo
     found = fd;
   }
   __syncthreads();
-  if (found == 0) {
-    if (threadIdx.x == 0) { S.last_status = BC_INVALID_ARGUMENT; *P.st = S; }
-    return;
-  }
+  if (found == 0) return 0;
   if (found >= 2) {
     const double* rec = P.cand_all + (size_t)(found - 2) * P.rec_len;
     for (int k = threadIdx.x; k < s; k += blockDim.x) P.xf[k] = rec[BC_REC_HDR + k];
@@ -979,6 +990,20 @@ __global__ __launch_bounds__(BC_FIN_THREADS) void k_reweight(SnnlsDev P, long lo
   }
   if (threadIdx.x == 0) { S.sel_f = f; S.sel_valid = 1; }
   __syncthreads();
+  return 1;
+}
+
+// step-wise _reweight(f): no guard here, the host loop owns it (snnls.py:53-61)
+template <int ALG>
+__global__ __launch_bounds__(BC_FIN_THREADS) void k_reweight(SnnlsDev P, long long f) {
+  __shared__ SnnlsState S;
+  __shared__ double red[64];
+  if (threadIdx.x == 0) S = *P.st;
+  __syncthreads();
+  if (!dev_fetch_column(P, S, f)) {
+    if (threadIdx.x == 0) { S.last_status = BC_INVALID_ARGUMENT; *P.st = S; }
+    return;
+  }
   double alpha = 0., beta = 0.;
   const int fail = dev_step_sizes<ALG>(P, S, red, alpha, beta);
   if (!fail) {
@@ -1053,7 +1078,7 @@ __global__ __launch_bounds__(BC_FIN_THREADS) void k_set_weights(SnnlsDev P, long
   Q.val = val2;
   Q.cols = cols2;
   Q.colnorm = colnorm2;
-  if (threadIdx.x == 0) { S.nnz = n; S.sel_valid = 0; }
+  if (threadIdx.x == 0) { S.nnz = n; S.sel_valid = 0; dev_gram_touch(P, 0); }
   __syncthreads();
   dev_xw_err(Q, S, red);
   if (threadIdx.x == 0) *P.st = S;
@@ -1065,10 +1090,224 @@ __global__ __launch_bounds__(BC_FIN_THREADS) void k_reset(SnnlsDev P) {
   if (threadIdx.x == 0) {
     memset(&S, 0, sizeof(S));
     S.sel_f = -1;
+    dev_gram_touch(P, 0);
   }
   __syncthreads();
   dev_xw_err(P, S, red);   // nnz = 0 -> xw = 0, err = ||b||
   if (threadIdx.x == 0) *P.st = S;
+}
+
+// ------------------------------------------------------------------ device NNLS refit (OrthoPursuit, optimize())
+#include "bc_nnls_dev.h"
+#define BC_ST_LIST_LIMIT 100      // last_status of k_refit: the list would outgrow BC_NNLS_MAXP (the host words the error)
+
+// would column f find a slot (dev_omp_place below): it is listed, or a slot has weight 0, or the list may grow
+__device__ bool dev_omp_room(const SnnlsDev& P, const SnnlsState& S, long long f, long long limit) {
+  __shared__ int room;
+  const long long nnz = S.nnz;
+  if (threadIdx.x == 0) room = nnz < limit ? 1 : 0;
+  __syncthreads();
+  for (long long j = threadIdx.x; j < nnz; j += blockDim.x)
+    if (P.idx[j] == f || !(P.val[j] > 0.)) room = 1;
+  __syncthreads();
+  return room != 0;
+}
+
+// orthopursuit.py:38 `w[f] = 1` on the sparse list: make sure the picked column (S.sel_f, in P.xf) has a slot -- with weight
+// 0 when it is new: the refit lets it enter.  A slot whose weight is 0 is reused before the list grows.  Returns the slot, or
+// -1 when the list is full; *fresh: the slot's column was (re)written, so its Gram row is stale (the callers go straight on to
+// dev_gram_update, which recomputes it).
+__device__ long long dev_omp_place(const SnnlsDev& P, SnnlsState& S, long long limit, int* fresh) {
+  __shared__ int hit, zero;
+  const int s = P.s;
+  const long long f = S.sel_f, nnz = S.nnz;
+  if (threadIdx.x == 0) { hit = INT_MAX; zero = INT_MAX; }
+  __syncthreads();
+  for (long long j = threadIdx.x; j < nnz; j += blockDim.x) {
+    if (P.idx[j] == f) atomicMin(&hit, (int)j);
+    else if (!(P.val[j] > 0.)) atomicMin(&zero, (int)j);
+  }
+  __syncthreads();
+  *fresh = 0;
+  if (hit != INT_MAX) return hit;
+  const long long at = zero != INT_MAX ? (long long)zero : nnz;
+  if (at == nnz && at >= limit) return -1;
+  for (int k = threadIdx.x; k < s; k += blockDim.x) P.cols[(size_t)at * s + k] = P.xf[k];
+  if (threadIdx.x == 0) {
+    P.idx[at] = f;
+    P.val[at] = 0.;
+    P.colnorm[at] = S.sel_norm;
+    if (at == nnz) S.nnz = at + 1;
+  }
+  __syncthreads();
+  *fresh = 1;
+  return at;
+}
+
+// bring the Gram state up to the list: entries [covered, n) are new to it (covered = P.nnls_stats[3], never trusted beyond
+// the list as it was when this kernel started), and so is a slot below them that was reused in this kernel
+__device__ void dev_gram_update(const SnnlsDev& P, long long nnz0, long long n, long long at, int fresh) {
+  const long long covered = P.nnls_stats[3];
+  const long long from = covered < nnz0 ? covered : nnz0;
+  __syncthreads();                 // every thread has read the mark before thread 0 moves it
+  if (from < n) bc_nnls_gram_rows(P.cols, P.s, P.b, P.gram, P.gram_c, (int)n, (int)from, (int)n);
+  if (fresh && at < from) bc_nnls_gram_rows(P.cols, P.s, P.b, P.gram, P.gram_c, (int)n, (int)at, (int)at + 1);
+  if (threadIdx.x == 0) P.nnls_stats[3] = n;
+}
+
+// one guarded OrthoPursuit iteration (snnls.py:41-74 with orthopursuit.py:17-41): k_step_finish with the closed-form step
+// replaced by "give the picked column a slot, extend the Gram state, NNLS refit".  Dynamic LDS: the refit's workspace, then
+// the five S-vectors (lds_vecs != 0).  The winner comes from the gathered candidate record(s).
+__global__ __launch_bounds__(BC_FIN_THREADS) void k_step_finish_omp(SnnlsDev P0, int lds_vecs) {
+  extern __shared__ double omp_lds[];
+  __shared__ SnnlsState S;
+  __shared__ double red[64];
+  __shared__ int sh_fail;
+  if (threadIdx.x == 0) S = *P0.st;
+  SnnlsDev P = P0;
+  const int s = P.s;
+  double* vec_lds = omp_lds + BC_NNLS_WS_DOUBLES;
+  if (lds_vecs) {
+    P.b = vec_lds;
+    P.bn = vec_lds + s;
+    P.xw = vec_lds + 2 * s;
+    P.xf = vec_lds + 3 * s;
+    P.xw_prev = vec_lds + 4 * s;
+    for (int k = threadIdx.x; k < s; k += blockDim.x) {
+      P.b[k] = P0.b[k];
+      P.bn[k] = P0.bn[k];
+      P.xw[k] = P0.xw[k];
+    }
+  }
+  __syncthreads();
+  if (S.reached_limit || S.pf_overflow) return;      // snnls.py:32-34 / :73-74; a pending exact redo consumes nothing
+  if (!S.select_fail && dev_records_overflow(P0.cand_all, P.world, P.rec_len)) {
+    if (threadIdx.x == 0) { S.pf_overflow = 1; S.skip = 1; *P0.st = S; }
+    return;
+  }
+  const bool guard = S.npos > 0;                     // snnls.py:44-45
+  int fail = S.select_fail;
+  long long f = -1;
+  if (!fail) {
+    dev_pick<BC_ALG_OMP>(P, S, red);
+    if (!S.sel_valid) fail = 1;
+    f = S.sel_f;
+  }
+  if (!fail) {
+    const long long nnz0 = S.nnz, npos0 = S.npos;
+    const double err0 = S.err_cur, xwsq0 = S.xw_sq;
+    const long long limit = P.cap < BC_NNLS_MAXP ? P.cap : BC_NNLS_MAXP;
+    int fresh = 0;
+    const long long at = nnz0 <= BC_NNLS_MAXP ? dev_omp_place(P, S, limit, &fresh) : -1;
+    if (at < 0) {                                    // the host's bound on the list length was wrong: refuse
+      if (threadIdx.x == 0) { S.overflow = 1; *P0.st = S; }
+      return;
+    }
+    for (long long j = threadIdx.x; j < nnz0; j += blockDim.x) P.prev_val[j] = P.val[j];
+    for (int k = threadIdx.x; k < s; k += blockDim.x) P.xw_prev[k] = P.xw[k];
+    dev_gram_update(P, nnz0, S.nnz, at, fresh);
+    fail = bc_nnls_solve(P.gram, P.gram_c, (int)S.nnz, P.val, (int)at, 0, P.bnorm, bc_nnls_ws(omp_lds), P.nnls_stats);
+    if (fail) {                                      // like a NumericalPrecisionError out of _reweight: w was not touched
+      if (threadIdx.x == 0) S.nnz = nnz0;
+      __syncthreads();
+    } else {
+      dev_xw_err(P, S, red);
+      if (guard) {
+        if (S.err_cur > err0) {                      // snnls.py:58-61
+          for (long long j = threadIdx.x; j < nnz0; j += blockDim.x) P.val[j] = P.prev_val[j];
+          for (int k = threadIdx.x; k < s; k += blockDim.x) P.xw[k] = P.xw_prev[k];
+          __syncthreads();
+          if (threadIdx.x == 0) {
+            S.nnz = nnz0;
+            S.npos = npos0;
+            S.err_cur = err0;
+            S.xw_sq = xwsq0;
+          }
+          fail = 1;
+        } else if (threadIdx.x == 0) {
+          S.retried = 0;                             // snnls.py:62
+        }
+        __syncthreads();
+      }
+    }
+  }
+  if (threadIdx.x == 0) {
+    if (fail) {                                      // snnls.py:63-72
+      if (S.retried) S.reached_limit = 1;
+      else S.retried = 1;
+    }
+    sh_fail = fail;
+  }
+  __syncthreads();
+  dev_trace(P, S, f, sh_fail);
+  __syncthreads();
+  dev_prep<BC_ALG_OMP>(P, S, red);
+  if (lds_vecs)
+    for (int k = threadIdx.x; k < s; k += blockDim.x) P0.xw[k] = P.xw[k];
+  if (threadIdx.x == 0) {
+    S.sel_valid = 0;      // the picked column lived in LDS: a later step-wise refit must fetch it again
+    *P0.st = S;
+  }
+}
+
+// The same refit behind a single launch, for the step-wise protocol and optimize():
+//   mode 0  orthopursuit.py:37-41 for column f (no guard here, the host loop owns it)
+//   mode 1  NNLS over every cached column of the list, zero-weight slots included
+//   mode 2  snnls.py:82-97: refit the entries with a positive weight; keep the result unless the error grew beyond
+//           (1 + tol) times the previous one (or the refit failed), else restore the weights and set reached_limit
+__global__ __launch_bounds__(BC_FIN_THREADS) void k_refit(SnnlsDev P, long long f, int mode) {
+  extern __shared__ double refit_lds[];
+  __shared__ SnnlsState S;
+  __shared__ double red[64];
+  if (threadIdx.x == 0) S = *P.st;
+  __syncthreads();
+  const long long nnz0 = S.nnz;
+  const double err0 = S.err_cur;
+  const long long limit = P.cap < BC_NNLS_MAXP ? P.cap : BC_NNLS_MAXP;
+  // refusals come first: nothing but last_status has changed when one is reported
+  if (nnz0 > BC_NNLS_MAXP || (mode == 0 && !dev_omp_room(P, S, f, limit))) {
+    if (threadIdx.x == 0) { P.st->last_status = BC_ST_LIST_LIMIT; }
+    return;
+  }
+  if (mode == 0 && !dev_fetch_column(P, S, f)) {
+    if (threadIdx.x == 0) { P.st->last_status = BC_INVALID_ARGUMENT; }
+    return;
+  }
+  int fresh = 0;
+  long long at = -1;
+  if (mode == 0) {
+    at = dev_omp_place(P, S, limit, &fresh);
+    if (at < 0) {                    // (dev_omp_room said otherwise: cannot happen)
+      if (threadIdx.x == 0) { P.st->last_status = BC_ST_LIST_LIMIT; }
+      return;
+    }
+  }
+  for (long long j = threadIdx.x; j < nnz0; j += blockDim.x) P.prev_val[j] = P.val[j];
+  dev_gram_update(P, nnz0, S.nnz, at, fresh);
+  const int fail = bc_nnls_solve(P.gram, P.gram_c, (int)S.nnz, P.val, (int)at, mode == 1, P.bnorm, bc_nnls_ws(refit_lds), P.nnls_stats);
+  int status = fail ? BC_NUMERICAL_PRECISION : BC_OK;
+  if (fail) {
+    if (threadIdx.x == 0) S.nnz = nnz0;
+    __syncthreads();
+  } else {
+    dev_xw_err(P, S, red);
+  }
+  if (mode == 2) {
+    if (!fail && S.err_cur > err0 * (1. + P.tol)) {
+      for (long long j = threadIdx.x; j < nnz0; j += blockDim.x) P.val[j] = P.prev_val[j];
+      __syncthreads();
+      dev_xw_err(P, S, red);
+      status = BC_NUMERICAL_PRECISION;
+    }
+    if (status != BC_OK && threadIdx.x == 0) {
+      S.reached_limit = 1;
+      S.skip = 1;
+    }
+  }
+  if (threadIdx.x == 0) {
+    S.last_status = status;
+    *P.st = S;
+  }
 }
 
 // ------------------------------------------------------------------ host side
@@ -1157,7 +1396,7 @@ extern "C" int bc_snnls_destroy(bc_snnls* h) {
   bc_pref_destroy(h->pref);
   h->pref = nullptr;
   free_lists(h);
-  void* ptrs[] = {h->state_slab, h->cand_all_owned, h->d.tr_f, h->d.tr_status, h->d.tr_err};
+  void* ptrs[] = {h->state_slab, h->cand_all_owned, h->d.tr_f, h->d.tr_status, h->d.tr_err, h->nnls_slab};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   delete h;
@@ -1457,11 +1696,116 @@ __global__ void k_clear_pf_overflow(SnnlsState* st) {
   st->skip = st->select_fail | st->reached_limit;
 }
 
+// ---- device NNLS refit: state and LDS budget
+static size_t nnls_lds_bytes(int s_vecs) { return ((size_t)BC_NNLS_WS_DOUBLES + (size_t)5 * s_vecs) * sizeof(double); }
+
+// Gram state of the list and the refit counters (allocated on first use), and the kernels' dynamic-LDS allowance: the packed
+// factor alone is 66 KB, above the 64 KB a kernel gets without asking
+static int ensure_nnls(bc_snnls* h, const char* who) {
+  if (h->d.world != 1 || h->comm || !h->cand_send_owned) {
+    bc_set_error("%s: the device NNLS refit serves single-rank solvers only (world != 1: sharded solvers keep the host refit)", who);
+    return BC_INVALID_ARGUMENT;
+  }
+  const size_t need = nnls_lds_bytes(h->d.s <= 1024 ? h->d.s : 0) + 16 * 1024;      // + the step kernel's static LDS
+  if (need > (size_t)h->ctx->max_lds) {
+    bc_set_error("%s: the device NNLS refit needs %zu bytes of LDS per block, the device offers %d", who, need, h->ctx->max_lds);
+    return BC_INVALID_ARGUMENT;
+  }
+  static unsigned attr_done_mask = 0;      // per device
+  if (!((attr_done_mask >> (h->ctx->device & 31)) & 1u)) {
+    BC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_step_finish_omp), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)nnls_lds_bytes(1024)));
+    BC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_refit), hipFuncAttributeMaxDynamicSharedMemorySize, (int)nnls_lds_bytes(0)));
+    attr_done_mask |= 1u << (h->ctx->device & 31);
+  }
+  if (h->nnls_slab) return BC_OK;
+  const size_t gram_doubles = (size_t)BC_NNLS_MAXP * BC_NNLS_MAXP + BC_NNLS_MAXP;
+  const size_t bytes = gram_doubles * sizeof(double) + 4 * sizeof(long long);
+  char* slab = nullptr;
+  BC_HIP(hipMalloc((void**)&slab, bytes));
+  hipError_t e = hipMemsetAsync(slab, 0, bytes, h->ctx->stream);
+  if (e != hipSuccess) { (void)hipFree(slab); return bc_hip_fail(e, "hipMemsetAsync(nnls)", __FILE__, __LINE__); }
+  h->nnls_slab = slab;
+  h->d.gram = (double*)slab;
+  h->d.gram_c = h->d.gram + (size_t)BC_NNLS_MAXP * BC_NNLS_MAXP;
+  h->d.nnls_stats = (long long*)(slab + gram_doubles * sizeof(double));
+  return BC_OK;
+}
+
+extern "C" int bc_snnls_device_refit(bc_snnls* h, int on) {
+  if (!h) { bc_set_error("bc_snnls_device_refit: bad argument"); return BC_INVALID_ARGUMENT; }
+  if (on) {
+    const int rc = ensure_nnls(h, "bc_snnls_device_refit");
+    if (rc) return rc;
+  }
+  h->dev_refit = on != 0;
+  return BC_OK;
+}
+
+// one launch of k_refit and the status it left
+static int run_refit(bc_snnls* h, long long f, int mode, const char* who, SnnlsState* st) {
+  int rc = ensure_nnls(h, who);
+  if (rc) return rc;
+  if (h->nnz_upper > BC_NNLS_MAXP) {
+    bc_set_error("%s: the device NNLS refit holds at most %d list entries (BC_NNLS_MAXP), the list has %lld", who, BC_NNLS_MAXP, h->nnz_upper);
+    return BC_INVALID_ARGUMENT;
+  }
+  rc = ensure_capacity(h, h->nnz_upper + 1);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_refit, dim3(1), dim3(BC_FIN_THREADS), nnls_lds_bytes(0), h->ctx->stream, h->d, f, mode);
+  BC_HIP(hipGetLastError());
+  rc = fetch_state(h, st);
+  if (rc) return rc;
+  h->nnz_upper = st->nnz;
+  if (st->last_status == BC_ST_LIST_LIMIT) {
+    bc_set_error("%s: the device NNLS refit holds at most %d list entries (BC_NNLS_MAXP); column %lld would be one more", who, BC_NNLS_MAXP, f);
+    return BC_INVALID_ARGUMENT;
+  }
+  return BC_OK;
+}
+
+extern "C" int bc_snnls_refit(bc_snnls* h, int64_t f) {
+  if (!h) { bc_set_error("bc_snnls_refit: bad argument"); return BC_INVALID_ARGUMENT; }
+  SnnlsState st;
+  const int rc = run_refit(h, f < 0 ? -1 : (long long)f, f < 0 ? 1 : 0, "bc_snnls_refit", &st);
+  if (rc) return rc;
+  if (st.last_status == BC_NUMERICAL_PRECISION) bc_set_error("bc_snnls_refit: the NNLS refit did not converge (numerically rank-deficient active set)");
+  if (st.last_status == BC_INVALID_ARGUMENT) bc_set_error("bc_snnls_refit: column %lld is not available on this rank", (long long)f);
+  return st.last_status;
+}
+
+extern "C" int bc_snnls_optimize(bc_snnls* h, int* accepted) {
+  if (!h || !accepted) { bc_set_error("bc_snnls_optimize: bad argument"); return BC_INVALID_ARGUMENT; }
+  SnnlsState st;
+  const int rc = run_refit(h, -1, 2, "bc_snnls_optimize", &st);
+  if (rc) return rc;
+  *accepted = st.last_status == BC_OK ? 1 : 0;
+  return BC_OK;
+}
+
+extern "C" int bc_snnls_refit_stats(const bc_snnls* h, int64_t* refits, int64_t* solves, int64_t* rejected) {
+  if (!h) { bc_set_error("bc_snnls_refit_stats: bad argument"); return BC_INVALID_ARGUMENT; }
+  long long v[3] = {0, 0, 0};
+  if (h->d.nnls_stats) {
+    BC_HIP(hipMemcpyAsync(v, h->d.nnls_stats, sizeof(v), hipMemcpyDeviceToHost, h->ctx->stream));
+    BC_HIP(hipStreamSynchronize(h->ctx->stream));
+  }
+  if (refits) *refits = v[0];
+  if (solves) *solves = v[1];
+  if (rejected) *rejected = v[2];
+  return BC_OK;
+}
+
 // ---- fused loop
 extern "C" int bc_snnls_build_begin(bc_snnls* h, int itrs) {
   if (!h || itrs < 0) { bc_set_error("bc_snnls_build_begin: bad argument"); return BC_INVALID_ARGUMENT; }
-  if (h->alg == BC_ALG_OMP) {
+  if (h->alg == BC_ALG_OMP && !h->dev_refit) {
     bc_set_error("bc_snnls_build*: OrthoPursuit refits with a host NNLS every step; use the step-wise protocol");
+    return BC_INVALID_ARGUMENT;
+  }
+  if (h->alg == BC_ALG_OMP && h->nnz_upper + itrs > BC_NNLS_MAXP) {
+    bc_set_error("bc_snnls_build*: the device NNLS refit holds at most %d list entries (BC_NNLS_MAXP); %lld are listed and %d steps "
+                 "may add as many", BC_NNLS_MAXP, h->nnz_upper, itrs);
     return BC_INVALID_ARGUMENT;
   }
   int rc = ensure_capacity(h, h->nnz_upper + itrs);
@@ -1476,6 +1820,7 @@ extern "C" int bc_snnls_build_begin(bc_snnls* h, int itrs) {
 extern "C" int bc_snnls_step_local(bc_snnls* h) {
   if (!h) return BC_INVALID_ARGUMENT;
   h->exact_step = false;
+  if (h->alg == BC_ALG_OMP) return launch_sweep(h, true, false);      // k_step_finish_omp consumes the candidate record
   return launch_sweep(h, !fuse_winner(h), true);
 }
 
@@ -1499,8 +1844,22 @@ extern "C" int bc_snnls_step_finish(bc_snnls* h) {
   h->rs_pending = false;
   h->exact_step = false;
   const long long nrec = fused ? d.rec_len : (d.fuse_winner ? 0 : (long long)d.world * d.rec_len);
+  if (h->alg == BC_ALG_OMP && (!h->dev_refit || !d.gram)) {
+    bc_set_error("bc_snnls_step_finish: OrthoPursuit without bc_snnls_device_refit");
+    return BC_INVALID_ARGUMENT;
+  }
   int rct = bc_timer_begin(h->ctx, 5);
   if (rct) return rct;
+  if (h->alg == BC_ALG_OMP) {
+    d.fuse_winner = 0;
+    const int lds_vecs = d.s <= 1024 ? 1 : 0;
+    const size_t lds = nnls_lds_bytes(lds_vecs ? d.s : 0);
+    hipLaunchKernelGGL(k_step_finish_omp, dim3(1), dim3(BC_FIN_THREADS), lds, h->ctx->stream, d, lds_vecs);
+    BC_HIP(hipGetLastError());
+    h->nnz_upper += 1;
+    h->iter_upper += 1;
+    return bc_timer_end(h->ctx, 5);
+  }
   if (fused || finish_pf_ok(h, nrec)) {
     const int hint = (int)h->nnz_upper;
     const size_t lds = ((size_t)5 * d.s + nrec + 2 * (size_t)(hint + 1)) * sizeof(double);

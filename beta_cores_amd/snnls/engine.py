@@ -14,7 +14,7 @@ from .. import _native as N
 from .. import util
 from ..device import DevicePhi, _PhiT, _ptr, default_context
 
-ALG_IDS = {'giga': N.ALG_GIGA, 'fw': N.ALG_FW, 'omp': N.ALG_OMP}
+ALG_IDS = {'giga': N.ALG_GIGA, 'fw': N.ALG_FW, 'omp': N.ALG_OMP, 'omp_dev': N.ALG_OMP}
 
 
 def phi_from_A(A, ctx=None, row_offset=0):
@@ -145,6 +145,29 @@ class HipEngine:
     def reweight(self, f):
         self._live_tol()
         N.call('bc_snnls_reweight', self.h, int(f))
+
+    # ---- device NNLS refit (include/beta_cores_nnls.h)
+    def enable_device_refit(self, on=True):
+        """Opt in: an OrthoPursuit engine's build_fused() runs the guarded loop with the NNLS refit on the device."""
+        N.call('bc_snnls_device_refit', self.h, 1 if on else 0)
+
+    def refit(self, f):
+        """orthopursuit.py:37-41 on the device for column f; f < 0: NNLS over every cached column of the list."""
+        self._live_tol()
+        N.call('bc_snnls_refit', self.h, int(f))
+
+    def optimize_device(self):
+        """snnls.py:82-97 on the device.  False: the refit was not kept (weights restored, numeric limit set)."""
+        self._live_tol()
+        ok = C.c_int()
+        N.call('bc_snnls_optimize', self.h, C.byref(ok))
+        return bool(ok.value)
+
+    def refit_stats(self):
+        """(refits, factor-and-solve rounds, columns rejected on entry) since this solver was created."""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        N.call('bc_snnls_refit_stats', self.h, C.byref(a), C.byref(b), C.byref(c))
+        return int(a.value), int(b.value), int(c.value)
 
     def error(self):
         e = C.c_double()

@@ -20,7 +20,7 @@ from .engine import HipEngine, phi_from_A
 
 
 class SparseNNLS(object):
-    _alg = None          # 'giga' | 'fw' | 'omp' for device-backed subclasses
+    _alg = None          # 'giga' | 'fw' | 'omp' | 'omp_dev' for device-backed subclasses
     _fusable = False     # True when build() may run the fused device loop
 
     def __init__(self, A, b, check_error_monotone=True, comm=None, ctx=None, row_offset=None,
@@ -143,7 +143,15 @@ class SparseNNLS(object):
                 self._stabilize()
 
     # ---- snnls.py:82-97 (host NNLS on the <= M active columns; scipy is shared with the reference)
-    def optimize(self):
+    def optimize(self, device=False):
+        """device=True: the same refit by the library's NNLS on the device (engine.optimize_device(): no host round trip;
+        the NNLS minimiser, not SciPy's bits).  The default is the SciPy path."""
+        if device:
+            if not self._eng.optimize_device():
+                self.log.warning('self.optimize() returned a solution with increasing error, or the refit did not converge. '
+                                 'Numeric limit possibly reached.')
+                self.reached_numeric_limit = True
+            return
         try:
             cost0 = self.error()
             saved = self._eng.sparse_weights()
