@@ -132,6 +132,12 @@ _NNLS_SIGNATURES = {
 }
 NNLS_EXPORTS = sorted(_NNLS_SIGNATURES)
 
+# entry points of the extension header include/beta_cores_take.h (resident rows sub-sampled on the device)
+_TAKE_SIGNATURES = {
+    'bc_data_take_rows': [vp, vp, C.c_int64, vpp],
+}
+TAKE_EXPORTS = sorted(_TAKE_SIGNATURES)
+
 _lib = None
 
 
@@ -163,7 +169,8 @@ def load():
             'or `make -C beta_cores_amd/csrc`. There is no CPU fallback.' % LIB_PATH)
     _preload_torch_hip_runtime()
     lib = C.CDLL(LIB_PATH)
-    for name, argtypes in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_F32_SIGNATURES.items()) + list(_NNLS_SIGNATURES.items()):
+    for name, argtypes in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_F32_SIGNATURES.items()) + list(_NNLS_SIGNATURES.items()) \
+            + list(_TAKE_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int

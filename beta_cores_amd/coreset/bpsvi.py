@@ -13,9 +13,10 @@ import weakref
 
 import numpy as np
 
-from ..device import DevicePhi
+from ..device import DeviceData, DevicePhi
 from ..util.opt import partial_nn_opt
 from .coreset import Coreset
+from .projector import is_device_projector
 
 
 class BatchPSVICoreset(Coreset):
@@ -30,6 +31,7 @@ class BatchPSVICoreset(Coreset):
         n = data.shape[0]
         self.n_subsample_opt = n_subsample_opt if n_subsample_opt is None else min(n, n_subsample_opt)   # bpsvi.py:11
         self._resident = None
+        self._sub_buf = None         # sub-samples of resident rows are taken into this one device buffer
         wants_pin = pin_data and self.n_subsample_opt is None and hasattr(ll_projector, 'pin')
         if wants_pin and isinstance(data, np.ndarray) and data.base is None and data.ndim == 2 and n >= 4096:
             # every gradient re-projects ALL rows: keep them in HBM (read-only on the host while pinned)
@@ -55,7 +57,11 @@ class BatchPSVICoreset(Coreset):
         if m is None:
             rows, scale = (self._resident if self._resident is not None else self.data), 1.
         else:
-            rows, scale = self.data[np.random.randint(self.data.shape[0], size=m)], self.data.shape[0] / m
+            sub_idcs, scale = np.random.randint(self.data.shape[0], size=m), self.data.shape[0] / m
+            if isinstance(self.data, DeviceData) and is_device_projector(self.ll_projector):
+                rows = self._sub_buf = self.data.take(sub_idcs, out=self._sub_buf, transient=True)      # stays in HBM
+            else:
+                rows = self.data[sub_idcs]
         if hasattr(self.ll_projector, 'colsum'):        # device projector: store-free K1, the bits of project().sum(axis=0)
             b = self.ll_projector.colsum(rows)
             if b is not None:

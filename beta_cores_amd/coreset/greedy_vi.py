@@ -81,6 +81,12 @@ class GreedyVICoreset(Coreset):
         elif pin_data and hasattr(ll_projector, 'pin') and isinstance(data, np.ndarray) and data.base is not None and data.ndim == 2 \
                 and data.shape[0] >= 4096 and (n_subsample_select is None or n_subsample_opt is None or groups is not None):
             self._dev_data = resident_copy_of_view(data, ll_projector)
+        elif isinstance(data, np.ndarray) and getattr(ll_projector, 'pinned', lambda _: None)(data) is not None:
+            # sub-sampled everywhere, but the CALLER has pinned the array on this projector: the sub-samples are drawn from that
+            # copy on the device (uploading N rows to read a few hundred per step is the caller's decision, not ours)
+            self._dev_data = ll_projector.pin(data)      # (nests: the copy stays until this coreset lets go of it too)
+            self._unpin = weakref.finalize(self, ll_projector.unpin, data)
+        self._sub_buf = None         # the one device buffer the sub-samples of resident rows are taken into (DeviceData.take)
         super().__init__(**kw)
         self.initialized = int(initialized) * len(self.wts)
 
@@ -89,6 +95,15 @@ class GreedyVICoreset(Coreset):
         raise NotImplementedError
 
     # -- pieces shared by select / gradient
+    def _sub_rows(self, local_idcs):
+        """data[local_idcs] as the input of a projection.  Resident rows stay in HBM: they are gathered on the device into one
+        buffer this coreset keeps (same rows, same row count, hence the same K1 and the same bits as the host detour)."""
+        from .projector import is_device_projector
+        if self._dev_data is None or not is_device_projector(self.ll_projector):
+            return self.data[local_idcs]
+        self._sub_buf = self._dev_data.take(local_idcs, out=self._sub_buf, transient=True)      # (refilled in place from now on)
+        return self._sub_buf
+
     def _tangent(self, n_subsample, w, p, beta, select=False, grad=False):
         """bcores.py:37-72 / sparsevi.py:35-70: returns (vecs, sum_scaling, sub_idcs, group_idcs, corevecs)
         and, with `grad`, the row-centred beta-gradient of the coreset rows (projector.py:56-61) as a sixth item."""
@@ -108,7 +123,7 @@ class GreedyVICoreset(Coreset):
             # (every rank draws the same indices: the ranks share the seed of the global NumPy stream, as they must for
             # the sampler's draws already)
             sub_idcs = np.random.randint(self._n_total, size=n_subsample)
-            vecs = self._proj(self.data[sub_idcs], beta) if self.comm is None else self._subsample_vecs(sub_idcs, beta)
+            vecs = self._proj(self._sub_rows(sub_idcs), beta) if self.comm is None else self._subsample_vecs(sub_idcs, beta)
             sum_scaling = self._n_total / n_subsample
         else:
             group_idcs = np.random.randint(len(self.groups), size=n_subsample)
@@ -155,7 +170,7 @@ class GreedyVICoreset(Coreset):
         self._tmode, self._tpos = 'positions', pos
         if pos.size == 0:
             return None
-        return self._proj(self.data[sub_idcs[pos] - off], beta)
+        return self._proj(self._sub_rows(sub_idcs[pos] - off), beta)
 
     def _on_device(self, vecs):
         """Black-box projectors hand back a host array; its N-row reductions still run on the GPU."""
@@ -270,14 +285,25 @@ class GreedyVICoreset(Coreset):
 
     # -- bcores.py:141-150
     def _fused_gradient(self, w, beta, overlap=None):
-        """The full-data, ungrouped gradient in one native call (bc_vi_gradient): the data rows go through the
-        store-free K1 (only `vecs.sum(axis=0)` is needed of them, bcores.py:144-145), the coreset rows and the M x S
-        algebra stay on the device, one host synchronisation.  None when this mode does not apply (black-box
-        projector, sub-sampling, groups, a transport without a native communicator, no coreset rows yet)."""
+        """The ungrouped gradient in one native call (bc_vi_gradient): the data rows go through the store-free K1 (only
+        `vecs.sum(axis=0)` is needed of them, bcores.py:144-145), the coreset rows and the M x S algebra stay on the device,
+        one host synchronisation.  Sub-sampled (`n_subsample_opt`): the drawn rows of a resident data set are gathered on
+        the device first (unsharded only).  None when this mode does not apply (black-box projector, groups, a sub-sample of
+        rows that are not resident or are sharded, a transport without a native communicator, no coreset rows yet)."""
         from .projector import _DeviceProjectorBase
-        if not self.fused_gradient or self.n_subsample_opt is not None or self.groups is not None \
+        if not self.fused_gradient or self.groups is not None \
                 or self.pts.size == 0 or not isinstance(self.ll_projector, _DeviceProjectorBase):
             return None
+        if self.n_subsample_opt is not None:
+            if self._dev_data is None or self.comm is not None:
+                return None
+            self.ll_projector.update(w, self.pts)          # the reference's order: new samples first, then the draw
+            sub_idcs = np.random.randint(self._n_total, size=self.n_subsample_opt)
+            g = self.ll_projector.vi_gradient(self._sub_rows(sub_idcs), self.pts, w, self._n_total / self.n_subsample_opt,
+                                              beta=self._fused_beta(beta), overlap=overlap)
+            if g is None:
+                raise RuntimeError('fused gradient not applicable after the sampler ran')      # guarded by _fused_ok
+            return g
         nc = None
         if self.comm is not None:
             nc = self.comm.native_comm(self.ll_projector.ctx)

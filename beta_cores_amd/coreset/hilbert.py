@@ -36,7 +36,9 @@ class HilbertCoreset(Coreset):
         elif not sharded:
             n_subsample = min(data.shape[0], n_subsample)
             sub_idcs = np.random.randint(data.shape[0], size=n_subsample)
-            src = data[sub_idcs]
+            # resident rows are sub-sampled on the device (the same rows, so the same Phi); anything else on the host
+            from .projector import is_device_projector
+            src = data.take(sub_idcs) if isinstance(data, DeviceData) and is_device_projector(ll_projector) else data[sub_idcs]
         else:
             # row-sharded sub-sample (hilbert.py:12-15): every rank draws the same global indices (shared seed of the global
             # stream), the drawn rows are collected once (each rank contributes the ones it owns; n_subsample x Dz doubles),

@@ -248,6 +248,11 @@ class _DeviceProjectorBase(Projector):
         self._pins[key] = [ref, dd, fin, 1, ent]
         return dd
 
+    def pinned(self, pts):
+        """The DeviceData of an array the caller has pinned on this projector (pin()), or None."""
+        hit = self._pins.get(id(pts))
+        return hit[1] if hit is not None and hit[0]() is pts else None
+
     def unpin(self, pts):
         hit = self._pins.get(id(pts))
         if hit is None or hit[0]() is not pts:
@@ -287,7 +292,8 @@ class _DeviceProjectorBase(Projector):
     def _zero_feature_keys(self, pts, d):
         """Sorted unique y of the rows of `pts` whose d features are all zero (host array: NumPy; resident rows: one device scan)."""
         if isinstance(pts, DeviceData):
-            hit = self._key_cache.get(id(pts))
+            cached = not pts._transient       # a buffer that take(out=) refills in place is scanned every time
+            hit = self._key_cache.get(id(pts)) if cached else None
             if hit is not None and hit[0]() is pts:
                 return hit[1]
             cap = 65536
@@ -297,6 +303,8 @@ class _DeviceProjectorBase(Projector):
                 raise ValueError('%d data rows have all-zero features: more than the %d the host route for constant rows handles'
                                  % (n.value, cap))
             keys = np.unique(out[:n.value])
+            if not cached:
+                return keys
             try:
                 self._key_cache[id(pts)] = (weakref.ref(pts, lambda _, k=id(pts), c=self._key_cache: c.pop(k, None)), keys)
             except TypeError:
@@ -442,6 +450,12 @@ class _DeviceProjectorBase(Projector):
         finally:
             N.call('bc_vi_gradient_end', self.ctx.h, _ptr(grad), _ptr(resid) if want_resid else None)
         return (grad, resid) if want_resid else grad
+
+
+def is_device_projector(prj):
+    """True for the projectors whose input may be a DeviceData (K1 on the GPU): what decides whether a coreset sub-samples
+    resident rows on the device (DeviceData.take) or hands host rows to a black-box callable."""
+    return isinstance(prj, _DeviceProjectorBase)
 
 
 class DeviceProjector(_DeviceProjectorBase):

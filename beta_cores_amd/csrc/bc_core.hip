@@ -97,7 +97,7 @@ extern "C" int bc_ctx_destroy(bc_ctx* ctx) {
   if (ctx->core_phi) bc_phi_destroy(ctx->core_phi);
   bc_scratch* all[] = {&ctx->proj_theta, &ctx->proj_rowaux, &ctx->proj_rowaux2, &ctx->gradx, &ctx->vi_buf, &ctx->const_rows,
                        &ctx->gram[0], &ctx->gram[1], &ctx->gram[2], &ctx->gram[3], &ctx->gram[4],
-                       &ctx->lap[0], &ctx->lap[1], &ctx->lap[2]};
+                       &ctx->lap[0], &ctx->lap[1], &ctx->lap[2], &ctx->take_idx};
   for (bc_scratch* sc : all)
     if (sc->p) (void)hipFree(sc->p);
   if (ctx->proj_pinned) (void)hipHostFree(ctx->proj_pinned);
@@ -107,6 +107,7 @@ extern "C" int bc_ctx_destroy(bc_ctx* ctx) {
   if (ctx->vi_ev_core) (void)hipEventDestroy(ctx->vi_ev_core);
   if (ctx->pinned) (void)hipHostFree(ctx->pinned);
   bc_uploader_free(ctx);
+  bc_take_free(ctx);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
   return BC_OK;

@@ -78,6 +78,13 @@ struct bc_ctx {
   int const_model = -1;
   double const_params[4] = {0., 0., 0., 0.};
   int const_n_params = 0;
+  // bc_data_take_rows (bc_take.hip): the indices on the device; two pinned staging areas used in turn, each with the event
+  // of the last copy out of it (a call waits for the copy of the call before the previous one, not for the previous one)
+  bc_scratch take_idx;
+  long long* take_pinned[2] = {nullptr, nullptr};
+  size_t take_pinned_cap[2] = {0, 0};      // indices
+  hipEvent_t take_ev[2] = {nullptr, nullptr};
+  int take_turn = 0;
 };
 
 // bc_upload.hip: rows of a host array -> dst_dev through pinned staging and several copy threads; the hook (optional) is
@@ -88,6 +95,7 @@ int bc_upload_rows(bc_ctx* ctx, const void* src, void* dst_dev, int64_t n_rows, 
                    const bc_chunk_hook* on_chunk);
 int64_t bc_upload_default_chunk_rows(int64_t n_rows, size_t row_bytes);
 void bc_uploader_free(bc_ctx* ctx);
+void bc_take_free(bc_ctx* ctx);      // bc_take.hip: the two pinned index staging areas and their events
 
 int bc_scratch_grow(bc_ctx* ctx, bc_scratch* s, size_t doubles);   // contents are NOT kept when it grows
 

@@ -119,7 +119,10 @@ class DeviceData:
 
     dtype=np.float32 keeps a float32 array as it is: half the bytes on the host link and half the HBM.  Only the storage is
     float32 -- every kernel widens the rows in registers (exact) and computes in float64, so all results have the bits the
-    float64 path gives on `z.astype(np.float64)`.  rows() / [] return float64 host rows either way."""
+    float64 path gives on `z.astype(np.float64)`.  rows() / [] return float64 host rows either way; take() keeps the chosen
+    rows on the device."""
+
+    _transient = False      # True once take(out=this) has refilled the rows in place: nothing about them may be cached
 
     def __init__(self, z=None, ctx=None, device_ptr=None, shape=None, keepalive=None, row_offset=0, dtype=None):
         if device_ptr is None:
@@ -194,6 +197,34 @@ class DeviceData:
         idx = np.ascontiguousarray(local_idx, dtype=np.int64).ravel()
         out = np.empty((idx.shape[0], self.shape[1]))
         N.call('bc_data_gather_rows', self.h, _ptr(idx), int(idx.shape[0]), _ptr(out))
+        return out
+
+    def take(self, local_idx, out=None, transient=False):
+        """Rows by LOCAL index, kept on the device: a DeviceData of shape (m, dz), the same dtype and row_offset 0
+        (bc_data_take_rows: words are copied, never converted; repeats allowed; any integer array).  `out`: a DeviceData an
+        earlier take() returned (or a slot) of the same context, column count and dtype -- it is refilled, resized and
+        returned, and marked transient: nothing may be cached about its rows, the next take(out=) replaces them.
+        `transient=True` marks a fresh result the same way (the first fill of a buffer that will be refilled)."""
+        out_given = out is not None
+        idx = np.asarray(local_idx)
+        if idx.size and not np.issubdtype(idx.dtype, np.integer):
+            raise TypeError('take() wants integer row numbers, got %s' % idx.dtype)
+        idx = np.ascontiguousarray(idx, dtype=np.int64).ravel()
+        if out is not None and not isinstance(out, DeviceData):
+            raise TypeError('take(out=...) wants a DeviceData')
+        h = C.c_void_p(out.h.value) if out is not None else C.c_void_p()
+        try:
+            N.call('bc_data_take_rows', self.h, _ptr(idx), int(idx.shape[0]), C.byref(h))
+        except RuntimeError:                # a HIP failure (not a refusal, which leaves `out` as it was): `out` holds 0 rows now
+            if out is not None:
+                out.shape = (0, out.shape[1])
+            raise
+        if out is None:
+            out = DeviceData._adopt(h, (idx.shape[0], self.shape[1]), self.ctx)
+        else:
+            out.shape = (int(idx.shape[0]), self.shape[1])
+            out.row_offset = 0
+        out._transient = transient or out_given
         return out
 
     def __getitem__(self, idx):
