@@ -138,6 +138,15 @@ _TAKE_SIGNATURES = {
 }
 TAKE_EXPORTS = sorted(_TAKE_SIGNATURES)
 
+# entry points of the extension header include/beta_cores_betagrad.h (beta-gradients of the regression models, the fused (w, beta) gradient)
+_BETAGRAD_SIGNATURES = {
+    'bc_model_beta_grad': [C.c_int],      # returns a model id (or -1), not a status
+    'bc_vi_beta_gradient': [vp, vp, vp, C.c_int64, C.c_int, vp, C.c_int32, vp, C.c_int32, vp, C.c_double, vp, vp, vp, vp],
+    'bc_vi_beta_gradient_begin': [vp, vp, vp, C.c_int64, C.c_int, vp, C.c_int32, vp, C.c_int32, vp, C.c_double, vp],
+    'bc_vi_beta_gradient_end': [vp, vp, vp, vp],
+}
+BETAGRAD_EXPORTS = sorted(_BETAGRAD_SIGNATURES)
+
 _lib = None
 
 
@@ -170,7 +179,7 @@ def load():
     _preload_torch_hip_runtime()
     lib = C.CDLL(LIB_PATH)
     for name, argtypes in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_F32_SIGNATURES.items()) + list(_NNLS_SIGNATURES.items()) \
-            + list(_TAKE_SIGNATURES.items()):
+            + list(_TAKE_SIGNATURES.items()) + list(_BETAGRAD_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int

@@ -284,12 +284,14 @@ class GreedyVICoreset(Coreset):
                 self._append(self.groups[f], self._rows(self.groups[f]) if self.comm is not None else self.data[self.groups[f], :])
 
     # -- bcores.py:141-150
-    def _fused_gradient(self, w, beta, overlap=None):
+    def _fused_gradient(self, w, beta, overlap=None, want_beta_grad=False):
         """The ungrouped gradient in one native call (bc_vi_gradient): the data rows go through the store-free K1 (only
         `vecs.sum(axis=0)` is needed of them, bcores.py:144-145), the coreset rows and the M x S algebra stay on the device,
         one host synchronisation.  Sub-sampled (`n_subsample_opt`): the drawn rows of a resident data set are gathered on
         the device first (unsharded only).  None when this mode does not apply (black-box projector, groups, a sub-sample of
-        rows that are not resident or are sharded, a transport without a native communicator, no coreset rows yet)."""
+        rows that are not resident or are sharded, a transport without a native communicator, no coreset rows yet).
+        `want_beta_grad` (BetaCoreset, learn_beta): (grad, beta_dots) from bc_vi_beta_gradient instead, see vi_gradient."""
+        kw = {'want_beta_grad': True} if want_beta_grad else {}
         from .projector import _DeviceProjectorBase
         if not self.fused_gradient or self.groups is not None \
                 or self.pts.size == 0 or not isinstance(self.ll_projector, _DeviceProjectorBase):
@@ -300,7 +302,7 @@ class GreedyVICoreset(Coreset):
             self.ll_projector.update(w, self.pts)          # the reference's order: new samples first, then the draw
             sub_idcs = np.random.randint(self._n_total, size=self.n_subsample_opt)
             g = self.ll_projector.vi_gradient(self._sub_rows(sub_idcs), self.pts, w, self._n_total / self.n_subsample_opt,
-                                              beta=self._fused_beta(beta), overlap=overlap)
+                                              beta=self._fused_beta(beta), overlap=overlap, **kw)
             if g is None:
                 raise RuntimeError('fused gradient not applicable after the sampler ran')      # guarded by _fused_ok
             return g
@@ -311,7 +313,7 @@ class GreedyVICoreset(Coreset):
                 return None
         self.ll_projector.update(w, self.pts)
         g = self.ll_projector.vi_gradient(self._dev_data if self._dev_data is not None else self.data, self.pts, w, 1.,
-                                          beta=self._fused_beta(beta), comm=nc, overlap=overlap)
+                                          beta=self._fused_beta(beta), comm=nc, overlap=overlap, **kw)
         if g is None:
             raise RuntimeError('fused gradient not applicable after the sampler ran')      # guarded by the checks above
         return g

@@ -418,19 +418,25 @@ class _DeviceProjectorBase(Projector):
                comm, _ptr(out))
         return out
 
-    def vi_gradient(self, data, core_pts, w, sum_scaling=1., beta=None, comm=None, want_resid=False, overlap=None):
+    def vi_gradient(self, data, core_pts, w, sum_scaling=1., beta=None, comm=None, want_resid=False, overlap=None,
+                    want_beta_grad=False):
         """One gradient of the greedy-VI weight optimisation in one native call (bc_vi_gradient): with the current
         samples, -corevecs.dot(sum_scaling * vecs.sum(axis=0) - w.dot(corevecs)) / S for vecs = projection of `data`
         (resident DeviceData, pinned array, or a live array that is uploaded for this call like project() does) and
         corevecs = projection of `core_pts`.  None if not covered (S > 256, no coreset rows, or a coreset too large
         for the staging area).  `overlap`: a callable run on the host between the enqueue and the wait (bc_vi_gradient_begin /
-        _end), i.e. beside the GPU -- the samplers' `prefetch` (drawing the next sample matrix's normals) goes there."""
+        _end), i.e. beside the GPU -- the samplers' `prefetch` (drawing the next sample matrix's normals) goes there.
+        `want_beta_grad` (learn_beta, needs `beta` and a model with a beta-gradient): the same call through
+        bc_vi_beta_gradient -- the same bits in grad and resid -- which also projects the coreset rows' row-centred beta-gradient
+        G and returns (grad, beta_dots[, resid]) with beta_dots = G.dot(resid) (bcores.py:134-137)."""
+        if want_beta_grad and (beta is None or self.model.beta_grad_model_id is None):
+            raise ValueError('beta-gradient was requested but this model has none')
         dd, _ = self.device_data(data)
         core = np.ascontiguousarray(np.atleast_2d(core_pts), dtype=np.float64)
         m = int(core.shape[0])
         theta = self._theta_checked(dd)
         S = int(theta.shape[0])
-        if S > 256 or m == 0 or m * (core.shape[1] + 1) > 60000:
+        if S > 256 or m == 0 or m * (core.shape[1] + 1) > 60000:      # (also keeps 2 m + S within the native staging area)
             return None
         if core.shape[1] != dd.shape[1]:
             raise ValueError('coreset rows have %d columns, data rows %d' % (core.shape[1], dd.shape[1]))
@@ -442,6 +448,18 @@ class _DeviceProjectorBase(Projector):
         self._stage_host_constants(data, model_id, params, more=core)
         grad = np.empty(m)
         resid = np.empty(S) if want_resid else None
+        if want_beta_grad:
+            if N.load().bc_model_beta_grad(int(model_id)) != int(self.model.beta_grad_model_id):
+                raise ValueError('model %d is not the beta-gradient of model %d' % (self.model.beta_grad_model_id, model_id))
+            dots = np.empty(m)
+            N.call('bc_vi_beta_gradient_begin', self.ctx.h, dd.h, _ptr(core), m, int(model_id), _ptr(theta), S, _ptr(params),
+                   int(params.shape[0]), _ptr(w), float(sum_scaling), comm)
+            try:
+                if overlap is not None:
+                    overlap()
+            finally:
+                N.call('bc_vi_beta_gradient_end', self.ctx.h, _ptr(grad), _ptr(dots), _ptr(resid) if want_resid else None)
+            return (grad, dots, resid) if want_resid else (grad, dots)
         N.call('bc_vi_gradient_begin', self.ctx.h, dd.h, _ptr(core), m, int(model_id), _ptr(theta), S, _ptr(params),
                int(params.shape[0]), _ptr(w), float(sum_scaling), comm)
         try:

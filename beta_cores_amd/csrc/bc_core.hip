@@ -95,6 +95,7 @@ extern "C" int bc_ctx_destroy(bc_ctx* ctx) {
     if (ev) (void)hipEventDestroy(ev);
   if (ctx->colsum_phi) bc_phi_destroy(ctx->colsum_phi);
   if (ctx->core_phi) bc_phi_destroy(ctx->core_phi);
+  if (ctx->core_gphi) bc_phi_destroy(ctx->core_gphi);
   bc_scratch* all[] = {&ctx->proj_theta, &ctx->proj_rowaux, &ctx->proj_rowaux2, &ctx->gradx, &ctx->vi_buf, &ctx->const_rows,
                        &ctx->gram[0], &ctx->gram[1], &ctx->gram[2], &ctx->gram[3], &ctx->gram[4],
                        &ctx->lap[0], &ctx->lap[1], &ctx->lap[2], &ctx->take_idx};

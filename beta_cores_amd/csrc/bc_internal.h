@@ -61,6 +61,7 @@ struct bc_ctx {
   bc_scratch lap[3];             // K5 (bc_laplace.hip): theta | reduced terms, per-block partials, curvature weights
   bc_phi* colsum_phi = nullptr;  // store-free K1: a Phi with the per-tile column partials but no tiles / norms
   bc_phi* core_phi = nullptr;    // bc_vi_gradient: the projection of the <= M coreset rows
+  bc_phi* core_gphi = nullptr;   // bc_vi_beta_gradient: their beta-gradient's projection
   bc_scratch vi_buf;             // bc_vi_gradient: grad | resid
   hipEvent_t vi_ev[BC_VI_PHASES + 1] = {};
   double vi_phase_ms[BC_VI_PHASES] = {};
@@ -68,6 +69,7 @@ struct bc_ctx {
   int64_t vi_pending_m = 0;      // bc_vi_gradient_begin enqueued a gradient of this many rows (bc_vi_gradient_end fetches it)
   int32_t vi_pending_s = 0;
   bool vi_pending_timed = false;
+  bool vi_pending_beta = false;  // the pending gradient is a bc_vi_beta_gradient (grad | resid | beta_dots in vi_pinned)
   double* vi_pinned = nullptr;   // pinned landing area of the pending gradient
   hipStream_t vi_side = nullptr;  // bc_vi_gradient: the coreset rows' K1 runs here, beside the data rows' launch on `stream`
   hipEvent_t vi_ev_staged = nullptr, vi_ev_core = nullptr;

@@ -16,6 +16,10 @@
 //
 // Measured against 80-bit arithmetic (tests/test_k1_math_cpu.py, two million arguments each): exp <= 1.0 ulp,
 // log1p(exp(-a)) <= 1.6 ulp.  Parity bar of the projections: 1e-11 * (1 + max|f|) against the reference (golden F2).
+// The two beta-gradient bodies at the end of this file, against their closed forms in 80-bit arithmetic (tests/betagrad_harness.c:
+// m in [-1500, 1500], q in [0, 1e4], beta in {0.01 .. 32}, sigsq in {0.3, 1, 2.5}): absolute error <= 2.9e-16 (1 + max|g|) for the
+// logistic one and <= 4.5e-16 (1 + max|g|) for the linear-regression one, max|g| taken over the grid (1e4 at beta = 0.01); their
+// bar is 1e-13 (1 + max|g|), a hundredth of the projections'.
 //
 // `tab` points at BC_K1_TAB_DOUBLES doubles laid out as bc_k1_tables.h says (in LDS inside K1).
 // Plain C99 / C++: compiled by hipcc for the device and by gcc for the host-side accuracy test.
@@ -191,6 +195,56 @@ BC_KM double bc_logistic_beta_value_pt(double m, double c0, double k1, double k2
   const double e1 = (m > BC_EXP_OVERFLOW_ARG) ? 0. : e1s;          // (1 + inf)^-b == 0 in the reference (model_lr.py:85)
   const double e23 = fma(u * ub, fpf, fpf);           // (1 + e^m)^(-beta-1) + (1 + e^-m)^(-beta-1)
   const double v = -((c0 * e1) - e23);
+  return (m != m) ? m : v;
+}
+
+// ---- d/dbeta of the two regression beta-likelihoods (include/beta_cores_betagrad.h; the reference has neither).  The constants
+// are formed on the host once per launch (the two *_consts below: model_constants() and the host harness share them).
+//
+// Linear regression, f = C (-(b+1)/b E + (1+b)^-1/2) with C = (2 pi s2)^(-b/2), E = exp(-b q / (2 s2)), L = log(2 pi s2):
+//   df/db = -(L/2) f + C (E/b^2 + (b+1)/b q/(2 s2) E - 1/2 (1+b)^-3/2)  =  (k0 + k1 q) E - k3,
+//   k0 = C ((L/2)(b+1)/b + 1/b^2),  k1 = C (b+1)/(2 s2 b),  k2 = -b/(2 s2) (E = exp(k2 q)),  k3 = C ((L/2)(1+b)^-1/2 + 1/2 (1+b)^-3/2)
+// i.e. one exp, one fma, one multiply and one subtraction behind the q the value model forms.
+BC_KM void bc_linreg_beta_grad_consts(double sigsq, double beta, double* k) {
+  const double L = log(2. * 3.141592653589793 * sigsq);
+  const double C = exp(-.5 * beta * L);
+  const double r = (beta + 1.) / beta, s1 = 1. / sqrt(1. + beta);
+  k[0] = C * (.5 * L * r + 1. / (beta * beta));
+  k[1] = C * r / (2. * sigsq);
+  k[2] = -beta / (2. * sigsq);
+  k[3] = C * (.5 * L * s1 + .5 * s1 / (1. + beta));
+}
+BC_KM double bc_linreg_beta_grad_value(double q, double k0, double k1, double k2, double k3, const double* tab) {
+  const double e = bc_exp_tab_nonpos(k2 * q, tab);
+  return fma(k1, q, k0) * e - k3;
+}
+
+// Logistic regression, m = -z.theta, a = softplus(m) = log(1+e^m), b = softplus(-m) = a - m:
+//   df/db = e^(-beta a)/beta^2 + (beta+1)/beta a e^(-beta a) - a e^(-(beta+1) a) - b e^(-(beta+1) b)
+// With Ls = log1p(e^-|m|) the two softplus values are Ls and Ls + |m| (no cancellation); e^(-(beta+1) a) = e^(-beta a) e^-a and
+// e^-a = 1/(1+e^m) is (1 or e^-|m|) / (1 + e^-|m|), as in the value model: e^-|m|, one log1p, two more exp and one reciprocal
+// of f in [1, 2].  Every exp argument is <= 0.  |m| is bounded for the log1p only (past 800 it is 0 either way); the softplus
+// values keep the whole of |m|: at beta = 0.01 the term (beta+1)/beta a e^(-beta a) is still 0.05 at m = 1500.
+// The derivative of the mathematical function, NOT of the reference's value past np.exp's overflow (m > 709.78, where
+// bc_logistic_beta_value follows the reference's jump of (1 + inf)^-beta to 0): finite for every finite m, exactly c0 = 1/beta^2
+// once m << 0 has saturated, 0 for m >> 0.  NaN in, NaN out.
+// k: c0 = 1/beta^2, c1 = (beta+1)/beta, c2 = -beta, c3 = -beta-1
+BC_KM void bc_logistic_beta_grad_consts(double beta, double* k) {
+  k[0] = 1. / (beta * beta);
+  k[1] = (beta + 1.) / beta;
+  k[2] = -beta;
+  k[3] = -beta - 1.;
+}
+BC_KM double bc_logistic_beta_grad_value(double m, double c0, double c1, double c2, double c3, const double* tab) {
+  const double am = fabs(m);
+  double u, f;
+  const double Ls = bc_log1p_exp_neg_tab_uf(fmin(am, 800.), tab, &u, &f);      // (fmin drops a NaN: restored below)
+  const int pos = m > 0.;
+  const double a = pos ? am + Ls : Ls, b = pos ? Ls : am + Ls;
+  const double e1 = bc_exp_tab_nonpos(c2 * a, tab);                // e^(-beta a)
+  const double e3 = bc_exp_tab_nonpos(c3 * b, tab);                // e^(-(beta+1) b)
+  const double e2 = e1 * ((pos ? u : 1.) * bc_rcp_1_2(f));         // e^(-(beta+1) a)
+  const double v = fma(c1, a, c0) * e1 - fma(a, e2, b * e3);
   return (m != m) ? m : v;
 }
 

@@ -20,6 +20,7 @@
 #include "bc_layout.h"
 #include "bc_k1_math.h"
 #include "../../include/beta_cores_f32.h"
+#include "../../include/beta_cores_betagrad.h"
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -194,6 +195,21 @@ static int model_constants(int model, const double* p, int np, int d, double* c,
       *siginv = p + 2;
       return BC_OK;
     }
+    case BC_MODEL_LINREG_BETA_GRAD: {      // (k0 + k1 q) exp(k2 q) - k3: bc_k1_math.h
+      if (np != 2) return BC_INVALID_ARGUMENT;
+      bc_linreg_beta_grad_consts(p[0], p[1], c);
+      return BC_OK;
+    }
+    case BC_MODEL_LOGISTIC_BETA_GRAD: {    // params as LOGISTIC_BETA takes them: [beta] or [beta, its constant at m = 0 (ignored)]
+      if (np != 1 && np != 2) return BC_INVALID_ARGUMENT;
+      const double beta = p[0];
+      if (!(beta <= BC_K1_POWTAB_MAX_BETA)) {      // the value model's range, kept
+        bc_set_error("bc_project: the logistic beta-gradient takes 0 < beta <= %g on the device (got %g)", BC_K1_POWTAB_MAX_BETA, beta);
+        return BC_INVALID_ARGUMENT;
+      }
+      bc_logistic_beta_grad_consts(beta, c);
+      return BC_OK;
+    }
   }
   return BC_INVALID_ARGUMENT;
 }
@@ -234,7 +250,9 @@ struct ProjPlan {
   const double* siginv_dev = nullptr;      // Gaussian models: Siginv [d][d] on the device
 };
 
-static bool model_has_y(int model) { return model == BC_MODEL_LINREG_LL || model == BC_MODEL_LINREG_BETA; }
+static bool model_has_y(int model) { return model == BC_MODEL_LINREG_LL || model == BC_MODEL_LINREG_BETA || model == BC_MODEL_LINREG_BETA_GRAD; }
+// the beta-gradients of the regression models: materialising projections only (include/beta_cores_betagrad.h)
+static bool model_store_only(int model) { return model == BC_MODEL_LINREG_BETA_GRAD || model == BC_MODEL_LOGISTIC_BETA_GRAD; }
 
 // `extra` (optional): further host arrays shipped in the same transfer (bc_vi_gradient: the coreset rows and their
 // weights); extra_dev[i] receives the device address of extra_src[i].  ONE pinned staging area, ONE device buffer, ONE
@@ -334,7 +352,8 @@ static int project_r_grid(const bc_ctx* ctx, const ProjPlan& pl, const bc_phi* p
   if (pl.ntsel != 4 && pl.ntsel != 6 && pl.ntsel != 7) return 0;
   // S in 101..112 with an exp in the epilogue: those three instantiations need 4-6 VGPRs more than the 256 a wave of a
   // 512-thread block may hold (they would spill): the staged kernel serves them
-  if (pl.ntsel == 7 && bc_model_has_np_exp_rt(pl.model)) return 0;
+  // (the two regression beta-gradients have no resident instantiation there either: launch_project_r_nt)
+  if (pl.ntsel == 7 && (bc_model_has_np_exp_rt(pl.model) || model_store_only(pl.model))) return 0;
   if (pl.model == BC_MODEL_LOGISTIC_BETA && !(env && atoi(env) < 0)) return 0;      // measured slower there (0.80 vs 0.74 ms at N = 1M, D = 128): four
                                                                                        // transcendental bodies per element; BC_K1_STAGED=-1 forces the resident kernel
   const int nr = pl.ntsel * 16 + (pl.ntsel == 6 ? 4 : 0);
@@ -390,7 +409,7 @@ static int project_check(bc_ctx* ctx, const bc_data* data, int model, const doub
                          const double* params, int32_t n_params, const char* who) {
   if (!ctx || !data || !theta || s <= 0 || (n_params > 0 && !params)) { bc_set_error("%s: bad argument", who); return BC_INVALID_ARGUMENT; }
   if (data->ctx != ctx) { bc_set_error("%s: data belongs to another context", who); return BC_INVALID_ARGUMENT; }
-  if (model < 0 || model > BC_MODEL_GAUSS_BETA_GRAD) { bc_set_error("%s: unknown model %d", who, model); return BC_INVALID_ARGUMENT; }
+  if (model < 0 || model > BC_MODEL_LOGISTIC_BETA_GRAD) { bc_set_error("%s: unknown model %d", who, model); return BC_INVALID_ARGUMENT; }
   return BC_OK;
 }
 
@@ -586,7 +605,7 @@ static int project_from_host(bc_ctx* ctx, const void* z_host, int elem, const ch
     bc_set_error("%s: bad argument", who);
     return BC_INVALID_ARGUMENT;
   }
-  if (model < 0 || model > BC_MODEL_GAUSS_BETA_GRAD) { bc_set_error("%s: unknown model %d", who, model); return BC_INVALID_ARGUMENT; }
+  if (model < 0 || model > BC_MODEL_LOGISTIC_BETA_GRAD) { bc_set_error("%s: unknown model %d", who, model); return BC_INVALID_ARGUMENT; }
   BC_HIP(hipSetDevice(ctx->device));
   bc_data* data = new bc_data();
   data->ctx = ctx;
@@ -697,6 +716,10 @@ extern "C" int bc_project_colsum(bc_ctx* ctx, const bc_data* data, int model, co
   int rc = project_check(ctx, data, model, theta, s, params, n_params, "bc_project_colsum");
   if (rc) return rc;
   if (!out_s) { bc_set_error("bc_project_colsum: bad argument"); return BC_INVALID_ARGUMENT; }
+  if (model_store_only(model)) {
+    bc_set_error("bc_project_colsum: model %d (a beta-gradient) has no store-free form: project and take bc_phi_colsum", model);
+    return BC_INVALID_ARGUMENT;
+  }
   if (comm && bc_comm_ctx(comm) != ctx) { bc_set_error("bc_project_colsum: the communicator belongs to another context"); return BC_INVALID_ARGUMENT; }
   if (s > 256) { bc_set_error("bc_project_colsum: at most 256 samples (S = %d): project and take bc_phi_colsum", s); return BC_INVALID_ARGUMENT; }
   BC_HIP(hipSetDevice(ctx->device));
@@ -758,17 +781,80 @@ __global__ __launch_bounds__(256) void k_vi_gradient(const double* __restrict__ 
   }
 }
 
-extern "C" int bc_vi_gradient_begin(bc_ctx* ctx, const bc_data* data, const double* core_rows, int64_t m, int model,
-                                    const double* theta, int32_t s, const double* params, int32_t n_params, const double* w,
-                                    double sum_scaling, bc_comm* comm) {
-  int rc = project_check(ctx, data, model, theta, s, params, n_params, "bc_vi_gradient");
+// learn_beta (bcores.py:134-137): beta_dots[i] = sum_k G[i, k] * resid[k] for G = the projected beta-gradient of the coreset
+// rows (tiled like C above) and the residual k_vi_gradient has just written.  A kernel of its own behind k_vi_gradient, so that
+// the latter -- and with it the bits of grad and resid -- is the same code with and without the beta part.
+__global__ __launch_bounds__(256) void k_vi_beta_dots(const double* __restrict__ bgrad, const double* __restrict__ resid, int m, int s,
+                                                     double* __restrict__ dots_out) {
+  extern __shared__ double rs[];      // [s]
+  for (int k = threadIdx.x; k < s; k += blockDim.x) rs[k] = resid[k];
+  __syncthreads();
+  for (int i = threadIdx.x; i < m; i += blockDim.x) {
+    double acc = 0.;
+    int k = 0;
+    for (; k + 8 <= s; k += 8) {
+      double c[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) c[u] = bgrad[bc_tile_off(i, k + u, s)];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) acc = fma(c[u], rs[k + u], acc);
+    }
+    for (; k < s; ++k) acc = fma(bgrad[bc_tile_off(i, k, s)], rs[k], acc);
+    dots_out[i] = acc;
+  }
+}
+
+extern "C" int bc_model_beta_grad(int beta_model) {
+  switch (beta_model) {
+    case BC_MODEL_LINREG_BETA: return BC_MODEL_LINREG_BETA_GRAD;
+    case BC_MODEL_LOGISTIC_BETA: return BC_MODEL_LOGISTIC_BETA_GRAD;
+    case BC_MODEL_GAUSS_BETA: return BC_MODEL_GAUSS_BETA_GRAD;
+    default: return -1;
+  }
+}
+
+// the Phi of the <= M coreset rows the gradient keeps in the context (*slot: core_phi, or core_gphi for the beta-gradient)
+static int core_phi_for(bc_ctx* ctx, bc_phi** slot, int64_t m, int32_t s, bc_phi** out) {
+  bc_phi* cphi = *slot;
+  if (cphi && (cphi->s != s || bc_phi_set_rows(cphi, m) != 0)) {
+    BC_HIP(hipStreamSynchronize(ctx->stream));
+    bc_phi_destroy(cphi);
+    *slot = cphi = nullptr;
+  }
+  if (!cphi) {
+    int64_t cap = 256;
+    while (cap < m) cap *= 2;
+    int rc = bc_phi_alloc(ctx, m, s, 0, &cphi, cap);
+    if (rc) return rc;
+    *slot = cphi;
+  }
+  cphi->stats_valid = false;
+  *out = cphi;
+  return BC_OK;
+}
+
+// both kinds of gradient.  grad_model < 0: bc_vi_gradient.  Otherwise (bc_vi_beta_gradient) the coreset rows are projected a
+// second time, with grad_model, and the algebra also leaves beta_dots behind grad and resid.
+static int vi_gradient_begin(bc_ctx* ctx, const bc_data* data, const double* core_rows, int64_t m, int model, int grad_model,
+                             const double* theta, int32_t s, const double* params, int32_t n_params, const double* w,
+                             double sum_scaling, bc_comm* comm) {
+  const bool with_beta = grad_model >= 0;
+  int rc = project_check(ctx, data, model, theta, s, params, n_params, with_beta ? "bc_vi_beta_gradient" : "bc_vi_gradient");
   if (rc) return rc;
+  if (model_store_only(model)) {
+    bc_set_error("bc_vi_gradient: model %d (a beta-gradient) has no store-free form for the data rows", model);
+    return BC_INVALID_ARGUMENT;
+  }
   if (m <= 0 || !core_rows || !w) { bc_set_error("bc_vi_gradient: needs a non-empty coreset (m = %lld)", (long long)m); return BC_INVALID_ARGUMENT; }
   if (s > 256) { bc_set_error("bc_vi_gradient: at most 256 samples (S = %d)", s); return BC_INVALID_ARGUMENT; }
   if (comm && bc_comm_ctx(comm) != ctx) { bc_set_error("bc_vi_gradient: the communicator belongs to another context"); return BC_INVALID_ARGUMENT; }
   const int dz = data->dz;
-  const size_t n_core = (size_t)m * dz, n_down = (size_t)m + (size_t)s;
-  if (ctx->vi_pending_m > 0) { bc_set_error("bc_vi_gradient_begin: a gradient is already pending on this context (call bc_vi_gradient_end first)"); return BC_INVALID_ARGUMENT; }
+  const size_t n_core = (size_t)m * dz, n_down = (with_beta ? 2 : 1) * (size_t)m + (size_t)s;      // grad | resid [| beta_dots]
+  if (ctx->vi_pending_m > 0) {
+    bc_set_error("bc_vi_gradient_begin: a gradient is already pending on this context (call %s first)",
+                 ctx->vi_pending_beta ? "bc_vi_beta_gradient_end" : "bc_vi_gradient_end");
+    return BC_INVALID_ARGUMENT;
+  }
   if (n_down > ctx->pinned_doubles) {
     bc_set_error("bc_vi_gradient: coreset of %lld rows x %d exceeds the staging area", (long long)m, dz);
     return BC_INVALID_ARGUMENT;
@@ -799,27 +885,30 @@ extern "C" int bc_vi_gradient_begin(bc_ctx* ctx, const bc_data* data, const doub
   core_view.owned = false;
   bc_data* cd = &core_view;
   const double* d_w = edev[1];
-  rc = bc_scratch_grow(ctx, &ctx->vi_buf, (size_t)m + (size_t)s);
+  rc = bc_scratch_grow(ctx, &ctx->vi_buf, n_down);
   if (rc) return rc;
   double* d_grad = ctx->vi_buf.p;
   double* d_resid = d_grad + m;
+  double* d_bdots = d_resid + s;           // (with_beta)
+  // the beta-gradient's plan: the value model's staged Theta, saux and Siginv (nothing is uploaded twice), its own constants
+  ProjPlan gpl = pl;
+  if (with_beta) {
+    const double* unused = nullptr;
+    if (model_constants(grad_model, params, n_params, pl.d, gpl.a.c, &unused) != BC_OK) {
+      bc_set_error("bc_vi_beta_gradient: model %d expects a different number of parameters than %d (d = %d)", grad_model, n_params, pl.d);
+      return BC_INVALID_ARGUMENT;
+    }
+    gpl.a.model = gpl.model = grad_model;
+    gpl.a.ck = gpl.a.cv = nullptr;         // host-evaluated constants belong to the value model
+    gpl.a.nck = 0;
+  }
   rc = mark(1);
   if (rc) return rc;
   // --- the <= M coreset rows (materialised: the M x S algebra below reads them), then the data rows (store-free)
-  bc_phi* cphi = ctx->core_phi;
-  if (cphi && (cphi->s != s || bc_phi_set_rows(cphi, m) != 0)) {
-    BC_HIP(hipStreamSynchronize(ctx->stream));
-    bc_phi_destroy(cphi);
-    ctx->core_phi = cphi = nullptr;
-  }
-  if (!cphi) {
-    int64_t cap = 256;
-    while (cap < m) cap *= 2;
-    rc = bc_phi_alloc(ctx, m, s, 0, &cphi, cap);
-    if (rc) return rc;
-    ctx->core_phi = cphi;
-  }
-  cphi->stats_valid = false;
+  bc_phi *cphi = nullptr, *gphi = nullptr;
+  rc = core_phi_for(ctx, &ctx->core_phi, m, s, &cphi);
+  if (!rc && with_beta) rc = core_phi_for(ctx, &ctx->core_gphi, m, s, &gphi);
+  if (rc) return rc;
   // The coreset rows' launch (one tile or a few: ~20 us of dependent latency, no work to speak of) runs on a side stream
   // BESIDE the data rows' launch instead of in front of it; the algebra kernel waits for both (0.441 -> 0.427 ms per native
   // call at N = 1M, D = 64).  The instrumented pass (timing on) keeps everything on one stream, so that its five phases stay a
@@ -838,6 +927,7 @@ extern "C" int bc_vi_gradient_begin(bc_ctx* ctx, const bc_data* data, const doub
     hipStream_t main_stream = ctx->stream;
     ctx->stream = ctx->vi_side;
     rc = plan_launch(ctx, pl, cd, cphi, PROJ_FULL, s, 0, &ctx->proj_rowaux);
+    if (!rc && with_beta) rc = plan_launch(ctx, gpl, cd, gphi, PROJ_FULL, s, 0, &ctx->proj_rowaux);      // behind it, same stream
     ctx->stream = main_stream;
     if (!rc) {
       const hipError_t e = hipEventRecord(ctx->vi_ev_core, ctx->vi_side);
@@ -845,6 +935,7 @@ extern "C" int bc_vi_gradient_begin(bc_ctx* ctx, const bc_data* data, const doub
     }
   } else {
     rc = plan_launch(ctx, pl, cd, cphi, PROJ_FULL, s, 0, &ctx->proj_rowaux);
+    if (!rc && with_beta) rc = plan_launch(ctx, gpl, cd, gphi, PROJ_FULL, s, 0, &ctx->proj_rowaux);
   }
   ctx->timing = saved_timing;
   // Everything after the side launch runs inside `rest`: on ANY failure in it the side stream is joined before the error
@@ -870,6 +961,10 @@ extern "C" int bc_vi_gradient_begin(bc_ctx* ctx, const bc_data* data, const doub
     hipLaunchKernelGGL(k_vi_gradient, dim3(1), dim3(256), (size_t)s * sizeof(double), ctx->stream, colsum, cphi->tiles, d_w,
                        (int)m, s, sum_scaling, d_resid, d_grad);
     BC_HIP(hipGetLastError());
+    if (with_beta) {
+      hipLaunchKernelGGL(k_vi_beta_dots, dim3(1), dim3(256), (size_t)s * sizeof(double), ctx->stream, gphi->tiles, d_resid, (int)m, s, d_bdots);
+      BC_HIP(hipGetLastError());
+    }
     // the result lands in a pinned area of its own: whatever the host does between _begin and _end (it may well call into this
     // library, whose other entry points stage through ctx->pinned) cannot overwrite it
     if (!ctx->vi_pinned) BC_HIP(hipHostMalloc((void**)&ctx->vi_pinned, ctx->pinned_doubles * sizeof(double), hipHostMallocDefault));
@@ -884,14 +979,37 @@ extern "C" int bc_vi_gradient_begin(bc_ctx* ctx, const bc_data* data, const doub
   ctx->vi_pending_m = m;
   ctx->vi_pending_s = s;
   ctx->vi_pending_timed = timed;
+  ctx->vi_pending_beta = with_beta;
   return BC_OK;
+}
+
+extern "C" int bc_vi_gradient_begin(bc_ctx* ctx, const bc_data* data, const double* core_rows, int64_t m, int model,
+                                    const double* theta, int32_t s, const double* params, int32_t n_params, const double* w,
+                                    double sum_scaling, bc_comm* comm) {
+  return vi_gradient_begin(ctx, data, core_rows, m, model, -1, theta, s, params, n_params, w, sum_scaling, comm);
+}
+
+extern "C" int bc_vi_beta_gradient_begin(bc_ctx* ctx, const bc_data* data, const double* core_rows, int64_t m, int beta_model,
+                                         const double* theta, int32_t s, const double* params, int32_t n_params, const double* w,
+                                         double sum_scaling, bc_comm* comm) {
+  const int grad_model = bc_model_beta_grad(beta_model);
+  if (grad_model < 0) {
+    bc_set_error("bc_vi_beta_gradient: model %d is not a beta-likelihood with a beta-gradient", beta_model);
+    return BC_INVALID_ARGUMENT;
+  }
+  return vi_gradient_begin(ctx, data, core_rows, m, beta_model, grad_model, theta, s, params, n_params, w, sum_scaling, comm);
 }
 
 // second half: wait for the enqueued gradient and hand it out (whatever the host did meanwhile -- e.g. drawing the next
 // sample matrix's normals -- ran beside the GPU)
-extern "C" int bc_vi_gradient_end(bc_ctx* ctx, double* out_grad, double* out_resid) {
-  if (!ctx || !out_grad) { bc_set_error("bc_vi_gradient_end: bad argument"); return BC_INVALID_ARGUMENT; }
-  if (ctx->vi_pending_m <= 0) { bc_set_error("bc_vi_gradient_end: no gradient is pending on this context"); return BC_INVALID_ARGUMENT; }
+static int vi_gradient_end(bc_ctx* ctx, double* out_grad, double* out_beta_dots, double* out_resid, bool beta_kind) {
+  const char* who = beta_kind ? "bc_vi_beta_gradient_end" : "bc_vi_gradient_end";
+  if (!ctx || !out_grad || (beta_kind && !out_beta_dots)) { bc_set_error("%s: bad argument", who); return BC_INVALID_ARGUMENT; }
+  if (ctx->vi_pending_m <= 0) { bc_set_error("%s: no gradient is pending on this context", who); return BC_INVALID_ARGUMENT; }
+  if (ctx->vi_pending_beta != beta_kind) {       // the pending gradient stays pending
+    bc_set_error("%s: the pending gradient was begun by %s", who, ctx->vi_pending_beta ? "bc_vi_beta_gradient_begin" : "bc_vi_gradient_begin");
+    return BC_INVALID_ARGUMENT;
+  }
   const int64_t m = ctx->vi_pending_m;
   const int32_t s = ctx->vi_pending_s;
   const bool timed = ctx->vi_pending_timed;
@@ -900,6 +1018,7 @@ extern "C" int bc_vi_gradient_end(bc_ctx* ctx, double* out_grad, double* out_res
   BC_HIP(hipStreamSynchronize(ctx->stream));
   memcpy(out_grad, ctx->vi_pinned, (size_t)m * sizeof(double));
   if (out_resid) memcpy(out_resid, ctx->vi_pinned + m, (size_t)s * sizeof(double));
+  if (beta_kind) memcpy(out_beta_dots, ctx->vi_pinned + m + s, (size_t)m * sizeof(double));
   if (timed) {
     for (int i = 0; i < BC_VI_PHASES; ++i) {
       float ms = 0.f;
@@ -909,6 +1028,23 @@ extern "C" int bc_vi_gradient_end(bc_ctx* ctx, double* out_grad, double* out_res
     ctx->vi_calls_timed++;
   }
   return BC_OK;
+}
+
+extern "C" int bc_vi_gradient_end(bc_ctx* ctx, double* out_grad, double* out_resid) {
+  return vi_gradient_end(ctx, out_grad, nullptr, out_resid, false);
+}
+
+extern "C" int bc_vi_beta_gradient_end(bc_ctx* ctx, double* out_grad, double* out_beta_dots, double* out_resid) {
+  return vi_gradient_end(ctx, out_grad, out_beta_dots, out_resid, true);
+}
+
+extern "C" int bc_vi_beta_gradient(bc_ctx* ctx, const bc_data* data, const double* core_rows, int64_t m, int beta_model,
+                                   const double* theta, int32_t s, const double* params, int32_t n_params, const double* w,
+                                   double sum_scaling, bc_comm* comm, double* out_grad, double* out_beta_dots, double* out_resid) {
+  if (!out_grad || !out_beta_dots) { bc_set_error("bc_vi_beta_gradient: bad argument"); return BC_INVALID_ARGUMENT; }
+  int rc = bc_vi_beta_gradient_begin(ctx, data, core_rows, m, beta_model, theta, s, params, n_params, w, sum_scaling, comm);
+  if (rc) return rc;
+  return bc_vi_beta_gradient_end(ctx, out_grad, out_beta_dots, out_resid);
 }
 
 extern "C" int bc_vi_gradient(bc_ctx* ctx, const bc_data* data, const double* core_rows, int64_t m, int model,

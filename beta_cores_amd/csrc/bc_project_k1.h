@@ -7,6 +7,7 @@
 #include "bc_np_pow2.h"
 #include "bc_layout.h"
 #include "bc_k1_math.h"
+#include "../../include/beta_cores_betagrad.h"
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -75,8 +76,18 @@ constexpr int bc_model_tab_doubles() { return !bc_model_uses_tables<MODEL>() ? 0
 template <int MODEL>
 constexpr bool bc_model_uses_tables() {
   return MODEL == BC_MODEL_LINREG_BETA || MODEL == BC_MODEL_LOGISTIC_LL || MODEL == BC_MODEL_LOGISTIC_BETA ||
-         MODEL == BC_MODEL_GAUSS_BETA || MODEL == BC_MODEL_GAUSS_BETA_GRAD;
+         MODEL == BC_MODEL_GAUSS_BETA || MODEL == BC_MODEL_GAUSS_BETA_GRAD || MODEL == BC_MODEL_LINREG_BETA_GRAD ||
+         MODEL == BC_MODEL_LOGISTIC_BETA_GRAD;
 }
+// which extras a model's formula takes: the row's y (the column behind the D features), or the Gaussian models' per-row and
+// per-sample quadratic forms (the beta-gradients of the regression models, ids 7 and 8, come after the Gaussian block)
+template <int MODEL>
+constexpr bool bc_model_has_y() { return MODEL == BC_MODEL_LINREG_LL || MODEL == BC_MODEL_LINREG_BETA || MODEL == BC_MODEL_LINREG_BETA_GRAD; }
+template <int MODEL>
+constexpr bool bc_model_is_gauss() { return MODEL == BC_MODEL_GAUSS_LL || MODEL == BC_MODEL_GAUSS_BETA || MODEL == BC_MODEL_GAUSS_BETA_GRAD; }
+// the beta-gradients of the regression models exist as materialising projections only (include/beta_cores_betagrad.h)
+template <int MODEL>
+constexpr bool bc_model_store_only() { return MODEL == BC_MODEL_LINREG_BETA_GRAD || MODEL == BC_MODEL_LOGISTIC_BETA_GRAD; }
 
 // (the logistic beta-likelihood's body, bc_logistic_beta_value, lives in bc_k1_math.h: compiled for the host too, where
 // tests/k1_math_harness.c measures it against 80-bit arithmetic)
@@ -87,6 +98,8 @@ constexpr bool bc_model_uses_tables() {
 #endif
 template <int MODEL>
 __device__ __forceinline__ double bc_model_value(double p, double ra, double sa, const double* c, const double* tab) {
+  // every model id has a case of its own: an id without one must not compile (it would compute another model's formula)
+  static_assert(MODEL >= BC_MODEL_LINREG_LL && MODEL <= BC_MODEL_LOGISTIC_BETA_GRAD, "bc_model_value: unknown model id");
   switch (MODEL) {
     // (2p)*y is evaluated as p*(2y): doubling is exact, so the product rounds to the same double, and 2y -- like y*y --
     // is a per-row value that stays out of the per-sample code
@@ -114,7 +127,7 @@ __device__ __forceinline__ double bc_model_value(double p, double ra, double sa,
       const double q = (ra + sa) - 2. * p;
       return c[0] * bc_exp_tab_nonpos(c[1] * q, tab) - c[2];
     }
-    default: {                            // BC_MODEL_GAUSS_BETA_GRAD, gaussian.py:46-62
+    case BC_MODEL_GAUSS_BETA_GRAD: {      // gaussian.py:46-62
       const double q = (ra + sa) - 2. * p;
       const double gq = bc_exp_tab_nonpos(c[1] * q, tab);
       const double t1 = c[3] * (c[0] * gq - c[2]);
@@ -122,6 +135,14 @@ __device__ __forceinline__ double bc_model_value(double p, double ra, double sa,
       const double t3 = c[5] * q * gq;
       return ((t1 - t2) - t3) - c[6];
     }
+    case BC_MODEL_LINREG_BETA_GRAD: {     // (k0 + k1*q)*exp(k2*q) - k3: bc_k1_math.h; q in LINREG_BETA's expression order
+      const double q = (ra * ra - p * (2. * ra)) + p * p;
+      return bc_linreg_beta_grad_value(q, c[0], c[1], c[2], c[3], tab);
+    }
+    case BC_MODEL_LOGISTIC_BETA_GRAD:     // bc_k1_math.h; static tables only (no per-launch power table)
+      return bc_logistic_beta_grad_value(-p, c[0], c[1], c[2], c[3], tab);
+    default:
+      return 0.;                          // (unreachable: see the static_assert)
   }
 }
 
@@ -220,7 +241,7 @@ __device__ __forceinline__ void k1_row_stats(double4_t (&acc)[JT][NT], double (&
       for (int st = 0; st < NT; ++st) {
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
-          const double v = bc_model_value<MODEL>(acc[jt][st][reg], ra, (MODEL >= BC_MODEL_GAUSS_LL) ? a.saux[16 * st + g + 4 * reg] : 0., a.c, tabl);
+          const double v = bc_model_value<MODEL>(acc[jt][st][reg], ra, bc_model_is_gauss<MODEL>() ? a.saux[16 * st + g + 4 * reg] : 0., a.c, tabl);
           acc[jt][st][reg] = v;
           sum += v;
           // Pin every BC_K1_GROUP elements: left to itself the compiler splits the table-driven bodies in two stages -- index
@@ -231,7 +252,7 @@ __device__ __forceinline__ void k1_row_stats(double4_t (&acc)[JT][NT], double (&
         }
       }
       {
-        const double v = (s_tail < S) ? bc_model_value<MODEL>(tv[jt], ra, (MODEL >= BC_MODEL_GAUSS_LL) ? a.saux[s_tail] : 0., a.c, tabl) : 0.;
+        const double v = (s_tail < S) ? bc_model_value<MODEL>(tv[jt], ra, bc_model_is_gauss<MODEL>() ? a.saux[s_tail] : 0., a.c, tabl) : 0.;
         tv[jt] = v;
         sum += v;
       }
@@ -279,7 +300,7 @@ __device__ __forceinline__ void k1_row_stats(double4_t (&acc)[JT][NT], double (&
         ok &= (d0 == __shfl_xor(d0, 32, BC_WAVE)) ? 1 : 0;
         ok &= __shfl_xor(ok, 32, BC_WAVE);
         if (ok) {                                    // the four lanes of a constant row take this together
-          const double cval = bc_const_row_value<MODEL>(mean + d0, p00, ra, (MODEL >= BC_MODEL_GAUSS_LL) ? a.saux[g] : 0., a.c, lane, tabl, a.ck, a.cv, a.nck);
+          const double cval = bc_const_row_value<MODEL>(mean + d0, p00, ra, bc_model_is_gauss<MODEL>() ? a.saux[g] : 0., a.c, lane, tabl, a.ck, a.cv, a.nck);
           mean = bc_np_sum_const_256(cval, S) / (double)S;
           const double v = cval - mean;
           sq = 0.;
@@ -330,11 +351,11 @@ __device__ __forceinline__ void k1_row_stats(double4_t (&acc)[JT][NT], double (&
         const int s = 16 * st + g + 4 * reg;
         double v = 0.;
         if (TL > 0) {
-          if (live) v = bc_model_value<MODEL>(acc[jt][st][reg], ra, (MODEL >= BC_MODEL_GAUSS_LL) ? a.saux[s] : 0., a.c, tabl);
+          if (live) v = bc_model_value<MODEL>(acc[jt][st][reg], ra, bc_model_is_gauss<MODEL>() ? a.saux[s] : 0., a.c, tabl);
           if (st == 0 && reg == 0) vref = v;
           differs |= (v != vref);
         } else if (s < S && live) {
-          v = bc_model_value<MODEL>(acc[jt][st][reg], ra, (MODEL >= BC_MODEL_GAUSS_LL) ? a.saux[s] : 0., a.c, tabl);
+          v = bc_model_value<MODEL>(acc[jt][st][reg], ra, bc_model_is_gauss<MODEL>() ? a.saux[s] : 0., a.c, tabl);
           vmin = fmin(vmin, v);
           vmax = fmax(vmax, v);
         }
@@ -346,7 +367,7 @@ __device__ __forceinline__ void k1_row_stats(double4_t (&acc)[JT][NT], double (&
     if (TL > 0) {
       double v = 0.;
       if (s_tail < S && live) {
-        v = bc_model_value<MODEL>(tv[jt], ra, (MODEL >= BC_MODEL_GAUSS_LL) ? a.saux[s_tail] : 0., a.c, tabl);
+        v = bc_model_value<MODEL>(tv[jt], ra, bc_model_is_gauss<MODEL>() ? a.saux[s_tail] : 0., a.c, tabl);
         differs |= (v != vref);
       }
       tv[jt] = v;
@@ -377,7 +398,7 @@ __device__ __forceinline__ void k1_row_stats(double4_t (&acc)[JT][NT], double (&
     // residue, a non-zero norm, and is NOT one of the "all-zero rows" dropped at hilbert.py:16.  The tree-order sum
     // above would round differently and flip that zero / non-zero status, so such rows use NumPy's order.
     if (bc_model_const_fixup<MODEL>() && __builtin_amdgcn_ballot_w64(constant_row && live) != 0ull) {
-      const double cnp = bc_const_row_value<MODEL>(cval, p00, ra, (MODEL >= BC_MODEL_GAUSS_LL) ? a.saux[g] : 0., a.c, lane, tabl, a.ck, a.cv, a.nck);
+      const double cnp = bc_const_row_value<MODEL>(cval, p00, ra, bc_model_is_gauss<MODEL>() ? a.saux[g] : 0., a.c, lane, tabl, a.ck, a.cv, a.nck);
       if (constant_row && live) {                // the reference's bits for the constant: every element of the row IS it
         cval = cnp;
 #pragma unroll
@@ -515,8 +536,8 @@ __global__ __launch_bounds__(128 / (16 * JT) * 64, (JT == 1 && NT <= 8) ? 4 : 2)
     const long long gr = r0 + row_base + jt;
     ra_pf[jt] = 0.;
     if (gr < a.n_rows) {
-      if (MODEL == BC_MODEL_LINREG_LL || MODEL == BC_MODEL_LINREG_BETA) ra_pf[jt] = (double)zrows[(size_t)gr * a.dz + a.d];
-      else if (MODEL >= BC_MODEL_GAUSS_LL) ra_pf[jt] = a.rowaux[gr];
+      if (bc_model_has_y<MODEL>()) ra_pf[jt] = (double)zrows[(size_t)gr * a.dz + a.d];
+      else if (bc_model_is_gauss<MODEL>())ra_pf[jt] = a.rowaux[gr];
     }
   }
   const double4_t zero4 = {0., 0., 0., 0.};
@@ -588,7 +609,7 @@ __global__ __launch_bounds__(128 / (16 * JT) * 64, (JT == 1 && NT <= 8) ? 4 : 2)
         for (int reg = 0; reg < 4; ++reg) {
           const int s = 16 * st + g + 4 * reg;
           if (s < S) {
-            const double v = live ? bc_model_value_np<MODEL>(acc[jt][st][reg], ra, (MODEL >= BC_MODEL_GAUSS_LL) ? a.saux[s] : 0., a.c, tabl) : 0.;
+            const double v = live ? bc_model_value_np<MODEL>(acc[jt][st][reg], ra, bc_model_is_gauss<MODEL>() ? a.saux[s] : 0., a.c, tabl) : 0.;
             rbase[(size_t)(a.s_off + s) * BC_TILE + jt] = v;
           }
         }
@@ -770,8 +791,8 @@ __global__ __launch_bounds__(512, 2) void k_project_r(ProjArgs a) {
       const long long gr = grp * 32 + 2 * j + jt;
       ra[jt] = 0.;
       if (gr < a.n_rows) {
-        if (MODEL == BC_MODEL_LINREG_LL || MODEL == BC_MODEL_LINREG_BETA) ra[jt] = (double)zrows[(size_t)gr * a.dz + a.d];
-        else if (MODEL >= BC_MODEL_GAUSS_LL) ra[jt] = a.rowaux[gr];
+        if (bc_model_has_y<MODEL>()) ra[jt] = (double)zrows[(size_t)gr * a.dz + a.d];
+        else if (bc_model_is_gauss<MODEL>())ra[jt] = a.rowaux[gr];
       }
     }
   };
@@ -928,8 +949,20 @@ static int launch_project(bc_ctx* ctx, const ProjArgs& a, long long ntiles) {
   return BC_OK;
 }
 
+// the launch tables below name every model id: one without a case is an error, never another model's formula
+static int bc_k1_unknown_model(int model) {
+  bc_set_error("bc_project: internal: no kernel for model %d", model);
+  return BC_INVALID_ARGUMENT;
+}
+static int bc_k1_no_store_free(int model) {
+  bc_set_error("bc_project_colsum: model %d (a beta-gradient) has no store-free form: project and take bc_phi_colsum", model);
+  return BC_INVALID_ARGUMENT;
+}
+
 template <int MODEL, bool STORE, typename ZT>
 static int launch_project_nt(bc_ctx* ctx, const ProjArgs& a, long long ntiles, int ntsel) {
+  if constexpr (!STORE && bc_model_store_only<MODEL>()) return bc_k1_no_store_free(MODEL);      // not instantiated
+  else
   switch (ntsel) {
     case 4: return launch_project<MODEL, 4, 32, 2, false, 0, STORE, ZT>(ctx, a, ntiles);
     case 6: return launch_project<MODEL, 6, 32, 2, false, 4, STORE, ZT>(ctx, a, ntiles);      // 96 < S <= 100: 6 tiles + 1 sample quad
@@ -948,7 +981,10 @@ static int launch_project_model(bc_ctx* ctx, const ProjArgs& a, long long ntiles
     case BC_MODEL_LOGISTIC_BETA: return launch_project_nt<BC_MODEL_LOGISTIC_BETA, STORE, ZT>(ctx, a, ntiles, ntsel);
     case BC_MODEL_GAUSS_LL: return launch_project_nt<BC_MODEL_GAUSS_LL, STORE, ZT>(ctx, a, ntiles, ntsel);
     case BC_MODEL_GAUSS_BETA: return launch_project_nt<BC_MODEL_GAUSS_BETA, STORE, ZT>(ctx, a, ntiles, ntsel);
-    default: return launch_project_nt<BC_MODEL_GAUSS_BETA_GRAD, STORE, ZT>(ctx, a, ntiles, ntsel);
+    case BC_MODEL_GAUSS_BETA_GRAD: return launch_project_nt<BC_MODEL_GAUSS_BETA_GRAD, STORE, ZT>(ctx, a, ntiles, ntsel);
+    case BC_MODEL_LINREG_BETA_GRAD: return launch_project_nt<BC_MODEL_LINREG_BETA_GRAD, STORE, ZT>(ctx, a, ntiles, ntsel);
+    case BC_MODEL_LOGISTIC_BETA_GRAD: return launch_project_nt<BC_MODEL_LOGISTIC_BETA_GRAD, STORE, ZT>(ctx, a, ntiles, ntsel);
+    default: return bc_k1_unknown_model(model);
   }
 }
 
@@ -974,11 +1010,13 @@ static int launch_project_r(bc_ctx* ctx, const ProjArgs& a, int grid) {
 
 template <int MODEL, bool STORE, typename ZT>
 static int launch_project_r_nt(bc_ctx* ctx, const ProjArgs& a, int grid, int ntsel) {
+  if constexpr (!STORE && bc_model_store_only<MODEL>()) return bc_k1_no_store_free(MODEL);      // not instantiated
+  else
   switch (ntsel) {
     case 4: return launch_project_r<MODEL, 4, 0, STORE, ZT>(ctx, a, grid);
     case 6: return launch_project_r<MODEL, 6, 4, STORE, ZT>(ctx, a, grid);
     default:
-      if constexpr (bc_model_has_np_exp<MODEL>()) {      // not instantiated (would spill), never selected (project_r_grid)
+      if constexpr (bc_model_has_np_exp<MODEL>() || bc_model_store_only<MODEL>()) {      // not instantiated (would spill), never selected (project_r_grid)
         bc_set_error("bc_project: internal: no resident kernel for this model at S in 101..112");
         return BC_INVALID_ARGUMENT;
       } else {
@@ -996,7 +1034,10 @@ static int launch_project_r_model(bc_ctx* ctx, const ProjArgs& a, int grid, int 
     case BC_MODEL_LOGISTIC_BETA: return launch_project_r_nt<BC_MODEL_LOGISTIC_BETA, STORE, ZT>(ctx, a, grid, ntsel);
     case BC_MODEL_GAUSS_LL: return launch_project_r_nt<BC_MODEL_GAUSS_LL, STORE, ZT>(ctx, a, grid, ntsel);
     case BC_MODEL_GAUSS_BETA: return launch_project_r_nt<BC_MODEL_GAUSS_BETA, STORE, ZT>(ctx, a, grid, ntsel);
-    default: return launch_project_r_nt<BC_MODEL_GAUSS_BETA_GRAD, STORE, ZT>(ctx, a, grid, ntsel);
+    case BC_MODEL_GAUSS_BETA_GRAD: return launch_project_r_nt<BC_MODEL_GAUSS_BETA_GRAD, STORE, ZT>(ctx, a, grid, ntsel);
+    case BC_MODEL_LINREG_BETA_GRAD: return launch_project_r_nt<BC_MODEL_LINREG_BETA_GRAD, STORE, ZT>(ctx, a, grid, ntsel);
+    case BC_MODEL_LOGISTIC_BETA_GRAD: return launch_project_r_nt<BC_MODEL_LOGISTIC_BETA_GRAD, STORE, ZT>(ctx, a, grid, ntsel);
+    default: return bc_k1_unknown_model(model);
   }
 }
 
@@ -1009,7 +1050,10 @@ static int launch_project_raw(bc_ctx* ctx, const ProjArgs& a, long long ntiles, 
     case BC_MODEL_LOGISTIC_BETA: return launch_project<BC_MODEL_LOGISTIC_BETA, 16, 16, 1, true, 0, true, ZT>(ctx, a, ntiles);
     case BC_MODEL_GAUSS_LL: return launch_project<BC_MODEL_GAUSS_LL, 16, 16, 1, true, 0, true, ZT>(ctx, a, ntiles);
     case BC_MODEL_GAUSS_BETA: return launch_project<BC_MODEL_GAUSS_BETA, 16, 16, 1, true, 0, true, ZT>(ctx, a, ntiles);
-    default: return launch_project<BC_MODEL_GAUSS_BETA_GRAD, 16, 16, 1, true, 0, true, ZT>(ctx, a, ntiles);
+    case BC_MODEL_GAUSS_BETA_GRAD: return launch_project<BC_MODEL_GAUSS_BETA_GRAD, 16, 16, 1, true, 0, true, ZT>(ctx, a, ntiles);
+    case BC_MODEL_LINREG_BETA_GRAD: return launch_project<BC_MODEL_LINREG_BETA_GRAD, 16, 16, 1, true, 0, true, ZT>(ctx, a, ntiles);
+    case BC_MODEL_LOGISTIC_BETA_GRAD: return launch_project<BC_MODEL_LOGISTIC_BETA_GRAD, 16, 16, 1, true, 0, true, ZT>(ctx, a, ntiles);
+    default: return bc_k1_unknown_model(model);
   }
 }
 

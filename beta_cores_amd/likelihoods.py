@@ -9,6 +9,7 @@ x^T Siginv theta directly).
 import numpy as np
 
 LINREG_LL, LINREG_BETA, LOGISTIC_LL, LOGISTIC_BETA, GAUSS_LL, GAUSS_BETA, GAUSS_BETA_GRAD = range(7)
+LINREG_BETA_GRAD, LOGISTIC_BETA_GRAD = 7, 8      # include/beta_cores_betagrad.h: this library's extension, opt-in (beta_gradient=True)
 
 
 def _checked_beta(beta):
@@ -34,15 +35,39 @@ class _Model:
 
 class LinearRegression(_Model):
     """Rows z = [x (D), y].  log-lik: model_linreg.py:4-10 == model_neurlinr.py:90-97;
-    beta-likelihood: model_neurlinr.py:102-110; x-gradient: model_linreg.py:12-17."""
+    beta-likelihood: model_neurlinr.py:102-110; x-gradient: model_linreg.py:12-17.
+
+    `beta_gradient=True` adds d/dbeta of the beta-likelihood (K1 model LINREG_BETA_GRAD), which BetaCoreset(learn_beta=True)
+    needs.  The reference has no such derivative for this model, so the default keeps its behaviour: project_f(..., grad=True)
+    raises ValueError."""
     has_grad_x = True
     model_id = LINREG_LL
     beta_model_id = LINREG_BETA
 
     constant_has_numpy_exp = True      # the beta-likelihood of a row with x = 0 is c(y) and holds an np.exp (util/numpy_bits.py)
 
-    def __init__(self, sigsq=1.0):
+    def __init__(self, sigsq=1.0, beta_gradient=False):
         self.sigsq = float(sigsq)
+        if beta_gradient:
+            self.beta_grad_model_id = LINREG_BETA_GRAD
+
+    def beta_gradient_host(self, z, samples, beta):
+        """d/dbeta of the beta-likelihood (model_neurlinr.py:102-110) in closed form, N x S, un-centred, in NumPy: what a
+        BetaBlackBoxProjector takes as `beta_gradient`, and what the device body is tested against.  Nothing on the device
+        path calls it.  With q = (y^2 - 2py) + p^2, L = log(2 pi sigsq), C = (2 pi sigsq)^(-beta/2), E = exp(-beta q/(2 sigsq)),
+        f = C (-(beta+1)/beta E + (1+beta)^-1/2):  df/dbeta = -(L/2) f + C (E/beta^2 + (beta+1)/beta q/(2 sigsq) E - (1+beta)^-3/2 / 2)."""
+        sigsq, beta = self.sigsq, float(beta)
+        z = np.atleast_2d(np.asarray(z, dtype=np.float64))
+        th = np.atleast_2d(np.asarray(samples, dtype=np.float64))
+        p = z[:, :-1].dot(th.T)
+        yc = z[:, -1][:, np.newaxis]
+        q = (yc ** 2 - 2 * p * yc) + p ** 2
+        L = np.log(2. * np.pi * sigsq)
+        Cn = np.exp(-.5 * beta * L)
+        with np.errstate(under='ignore'):
+            E = np.exp(-beta / (2. * sigsq) * q)
+        f = Cn * (-(beta + 1.) / beta * E + 1. / np.sqrt(1. + beta))
+        return -.5 * L * f + Cn * (E / beta ** 2 + (beta + 1.) / beta * q / (2. * sigsq) * E - .5 * (1. + beta) ** -1.5)
 
     def params(self, beta=None, grad=False):
         return np.array([self.sigsq] if beta is None else [self.sigsq, _checked_beta(beta)])
@@ -64,12 +89,35 @@ class LinearRegression(_Model):
 
 
 class LogisticRegression(_Model):
-    """Rows z = y*x (D).  log-lik: model_lr.py:72-79; beta-likelihood: model_lr.py:81-86; z-gradient: :107-114."""
+    """Rows z = y*x (D).  log-lik: model_lr.py:72-79; beta-likelihood: model_lr.py:81-86; z-gradient: :107-114.
+
+    `beta_gradient=True` adds d/dbeta of the beta-likelihood (K1 model LOGISTIC_BETA_GRAD) for BetaCoreset(learn_beta=True);
+    the reference has none for this model, so without the flag project_f(..., grad=True) keeps raising ValueError."""
     has_grad_x = True
     model_id = LOGISTIC_LL
     beta_model_id = LOGISTIC_BETA
 
     MAX_BETA = 32.     # csrc/bc_k1_math.h: BC_K1_POWTAB_MAX_BETA (the power series of the device body is truncated for beta up to here)
+
+    def __init__(self, beta_gradient=False):
+        if beta_gradient:
+            self.beta_grad_model_id = LOGISTIC_BETA_GRAD
+
+    @staticmethod
+    def beta_gradient_host(z, samples, beta):
+        """d/dbeta of the beta-likelihood (model_lr.py:81-86) in closed form, N x S, un-centred, in NumPy (for a
+        BetaBlackBoxProjector's `beta_gradient`, and what the device body is tested against; nothing on the device path calls
+        it).  With m = -z.th, a = softplus(m), b = softplus(-m) = a - m:
+            df/dbeta = e^(-beta a)/beta^2 + (beta+1)/beta a e^(-beta a) - a e^(-(beta+1) a) - b e^(-(beta+1) b)
+        the derivative of the mathematical function in a form that stays finite for every finite m (1/beta^2 as m -> -inf,
+        0 as m -> +inf) -- not of NumPy's overflow artefact in the value, the jump of (1 + inf)**(-beta) to 0 at m > 709.78."""
+        beta = float(beta)
+        m = -np.atleast_2d(np.asarray(z, dtype=np.float64)).dot(np.atleast_2d(np.asarray(samples, dtype=np.float64)).T)
+        with np.errstate(under='ignore'):
+            ls = np.log1p(np.exp(-np.abs(m)))
+            a, b = np.maximum(m, 0.) + ls, np.maximum(-m, 0.) + ls
+            ea = np.exp(-beta * a)
+            return ea / beta ** 2 + (beta + 1.) / beta * a * ea - a * np.exp(-(beta + 1.) * a) - b * np.exp(-(beta + 1.) * b)
 
     def params(self, beta=None, grad=False):
         if beta is None:

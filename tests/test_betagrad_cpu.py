@@ -1,0 +1,126 @@
+"""The beta-gradients of the linear- and logistic-regression beta-likelihoods without a GPU: the NumPy closed forms
+(likelihoods.*.beta_gradient_host) against central differences of the oracle's beta-likelihoods, the logistic one's special
+values, the two device bodies (csrc/bc_k1_math.h, compiled for the host) against 80-bit arithmetic, and the ABI of the extension
+header include/beta_cores_betagrad.h."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from beta_cores_amd import _native as N
+from beta_cores_amd import likelihoods as L
+from oracle import models_ref as M
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = ['bc_model_beta_grad', 'bc_vi_beta_gradient', 'bc_vi_beta_gradient_begin', 'bc_vi_beta_gradient_end']
+
+
+@pytest.mark.parametrize('beta', [0.05, 0.3, 2., 20.])
+@pytest.mark.parametrize('sigsq', [1., 2.5])
+def test_host_closed_forms_match_central_differences(beta, sigsq):
+    """h = 1e-6 * beta; bar 1e-8 * (1 + max|g|): the truncation of the central difference is h^2/6 |f'''|, its rounding
+    eps |f| / h ~ 1e-10 / beta relative to f -- both orders below the bar on these inputs."""
+    rng = np.random.RandomState(3)
+    X = rng.randn(200, 5)
+    Zlin = np.hstack((X, (X.dot(rng.randn(5)) + rng.randn(200))[:, None]))
+    Zlog = 3. * rng.randn(200, 5)
+    th = rng.randn(7, 5)
+    h = 1e-6 * beta
+    g = L.LinearRegression(sigsq, beta_gradient=True).beta_gradient_host(Zlin, th, beta)
+    fd = (M.linreg_beta_lik(Zlin, th, beta + h, sigsq) - M.linreg_beta_lik(Zlin, th, beta - h, sigsq)) / (2 * h)
+    print('linreg   beta %g sigsq %g: max|g| %.4g, max deviation %.3g' % (beta, sigsq, np.abs(g).max(), np.abs(g - fd).max()))
+    assert g.shape == (200, 7) and np.abs(g - fd).max() <= 1e-8 * (1. + np.abs(g).max())
+    g = L.LogisticRegression(beta_gradient=True).beta_gradient_host(Zlog, th, beta)
+    fd = (M.logistic_beta_lik(Zlog, th, beta + h) - M.logistic_beta_lik(Zlog, th, beta - h)) / (2 * h)
+    print('logistic beta %g: max|g| %.4g, max deviation %.3g' % (beta, np.abs(g).max(), np.abs(g - fd).max()))
+    assert g.shape == (200, 7) and np.abs(g - fd).max() <= 1e-8 * (1. + np.abs(g).max())
+
+
+@pytest.mark.parametrize('beta', [0.01, 0.5, 32.])
+def test_logistic_special_values(beta):
+    """Margins 0, +-120, +-800, +-1500 (z = -m against theta = 1): finite everywhere; 1/beta^2 once m << 0 has saturated; towards
+    m >> 0 the value decays like (1/beta^2 + (beta+1)/beta m) e^(-beta m) -- at beta = 0.01 that is still 0.05 at m = 1500 -- and
+    is exactly 0 once that has underflowed."""
+    ms = np.array([0., 120., -120., 800., -800., 1500., -1500.])
+    g = L.LogisticRegression.beta_gradient_host(-ms[:, None], np.ones((1, 1)), beta)[:, 0]
+    assert np.isfinite(g).all()
+    assert (g[ms < 0] == 1. / beta ** 2).all()
+    pos = ms[ms > 0]
+    tail = (1. / beta ** 2 + (beta + 1.) / beta * pos) * np.exp(-beta * pos)
+    assert (np.abs(g[ms > 0] - tail) <= 1e-12 * tail + 2. * np.exp(-pos)).all()      # (the b-term adds -e^-m up to rounding)
+    far = L.LogisticRegression.beta_gradient_host(-np.array([[1e6], [1e300]]), np.ones((1, 1)), beta)[:, 0]
+    assert (far == 0.).all()
+    if beta >= 0.5:
+        assert (np.abs(g[ms > 0]) <= 1e-20).all()                 # the margins above ARE the limit for these beta (max|g| = 1/beta^2)
+    assert np.isnan(L.LogisticRegression.beta_gradient_host(np.array([[np.nan]]), np.ones((1, 1)), beta)).all()
+
+
+def test_opt_in_flag_sets_the_model_id():
+    assert L.LinearRegression(1.0).beta_grad_model_id is None and L.LogisticRegression().beta_grad_model_id is None
+    assert L.LinearRegression(1.0, beta_gradient=True).beta_grad_model_id == L.LINREG_BETA_GRAD == 7
+    assert L.LogisticRegression(beta_gradient=True).beta_grad_model_id == L.LOGISTIC_BETA_GRAD == 8
+    assert L.LinearRegression.beta_grad_model_id is None and L.LogisticRegression.beta_grad_model_id is None      # per instance
+
+
+def test_device_bodies_against_80_bit_closed_forms(tmp_path):
+    """tests/betagrad_harness.c: bar 1e-13 * (1 + max|g| over the grid) per beta (and sigsq) -- a hundredth of the projections'
+    1e-11 * (1 + max|f|), so that the contraction keeps the rest; limits exact; NaN in, NaN out."""
+    exe = str(tmp_path / 'betagrad_harness')
+    cmd = ['gcc', '-O2', '-mfma', '-ffp-contract=off', '-Wall', '-Werror', '-I', os.path.join(ROOT, 'beta_cores_amd', 'csrc'),
+           os.path.join(ROOT, 'tests', 'betagrad_harness.c'), '-o', exe, '-lm']
+    out = subprocess.run(cmd, capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr
+    res = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    print(res.stdout)
+    assert res.returncode == 0, res.stdout + res.stderr
+    m = re.search(r'betagrad: logistic worst (\S+) linreg worst (\S+) .* bar 1e-13 ok', res.stdout)
+    assert m, res.stdout
+    assert float(m.group(1)) <= 1e-13 and float(m.group(2)) <= 1e-13
+    assert len(re.findall(r'^logistic beta', res.stdout, flags=re.M)) == 5 and len(re.findall(r'^linreg beta', res.stdout, flags=re.M)) == 15
+
+
+# ---- ABI
+def header_functions():
+    src = open(os.path.join(ROOT, 'include', 'beta_cores_betagrad.h')).read()
+    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
+    return sorted(set(re.findall(r'\b(bc_[a-z0-9_]+)\s*\(', src)))
+
+
+def test_header_compiles_as_c99(tmp_path):
+    src = tmp_path / 'use_betagrad.c'
+    src.write_text('#include "beta_cores_betagrad.h"\n'
+                   'typedef int (*fn)(void);\n'
+                   'fn table[] = {%s};\n'
+                   'int ids[] = {BC_MODEL_LINREG_BETA_GRAD, BC_MODEL_LOGISTIC_BETA_GRAD};\n' % ', '.join('(fn)%s' % n for n in NAMES))
+    cmd = ['gcc', '-std=c99', '-Wall', '-Werror', '-pedantic-errors', '-I', os.path.join(ROOT, 'include'), '-c', str(src), '-o', str(tmp_path / 'use_betagrad.o')]
+    out = subprocess.run(cmd, capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr
+
+
+def test_header_and_ctypes_table_agree():
+    names = header_functions()
+    assert names == N.BETAGRAD_EXPORTS == NAMES
+    for other in (N.EXPORTS, N.EXT_EXPORTS, N.F32_EXPORTS, N.NNLS_EXPORTS, N.TAKE_EXPORTS):      # the existing tables are left as they are
+        assert not set(names) & set(other)
+    assert len(N.EXPORTS) == 82
+    lib = N.load()
+    for n in names:
+        assert hasattr(lib, n), 'libbeta_cores.so does not export %s' % n
+        assert getattr(lib, n).argtypes == N._BETAGRAD_SIGNATURES[n]      # bound by load()
+    for hdr in ('beta_cores.h', 'beta_cores_laplace.h', 'beta_cores_f32.h', 'beta_cores_nnls.h', 'beta_cores_take.h'):
+        src = open(os.path.join(ROOT, 'include', hdr)).read()
+        assert not [n for n in names if n in src], hdr
+        assert 'BETA_GRAD 7' not in src and 'BETA_GRAD 8' not in src
+
+
+def test_model_map_and_null_arguments_need_no_device():
+    lib = N.load()
+    assert [lib.bc_model_beta_grad(i) for i in range(-1, 10)] == [-1, -1, 7, -1, 8, -1, 6, -1, -1, -1, -1]
+    assert lib.bc_vi_beta_gradient_begin(None, None, None, 0, 1, None, 0, None, 0, None, 1.0, None) == N.BC_INVALID_ARGUMENT
+    assert b'bc_vi_beta_gradient' in lib.bc_last_error()
+    assert lib.bc_vi_beta_gradient_end(None, None, None, None) == N.BC_INVALID_ARGUMENT
+    assert b'bc_vi_beta_gradient_end' in lib.bc_last_error()
+    assert lib.bc_vi_beta_gradient(None, None, None, 0, 1, None, 0, None, 0, None, 1.0, None, None, None, None) == N.BC_INVALID_ARGUMENT
+    assert lib.bc_vi_beta_gradient_begin(None, None, None, 0, 2, None, 0, None, 0, None, 1.0, None) == N.BC_INVALID_ARGUMENT      # not a beta-likelihood
