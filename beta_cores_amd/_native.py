@@ -147,6 +147,15 @@ _BETAGRAD_SIGNATURES = {
 }
 BETAGRAD_EXPORTS = sorted(_BETAGRAD_SIGNATURES)
 
+# entry points of the extension header include/beta_cores_encode.h (the device feature encoder of the neural-linear model)
+_ENCODE_SIGNATURES = {
+    'bc_encoder_create': [vp, C.c_int32, vp, vpp],
+    'bc_encoder_set_layer': [vp, C.c_int32, vp, vp, vp, vp, C.c_int32],
+    'bc_encoder_destroy': [vp],
+    'bc_data_encode': [vp, vp, C.c_int32, C.c_int32, vpp],
+}
+ENCODE_EXPORTS = sorted(_ENCODE_SIGNATURES)
+
 _lib = None
 
 
@@ -179,7 +188,7 @@ def load():
     _preload_torch_hip_runtime()
     lib = C.CDLL(LIB_PATH)
     for name, argtypes in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_F32_SIGNATURES.items()) + list(_NNLS_SIGNATURES.items()) \
-            + list(_TAKE_SIGNATURES.items()) + list(_BETAGRAD_SIGNATURES.items()):
+            + list(_TAKE_SIGNATURES.items()) + list(_BETAGRAD_SIGNATURES.items()) + list(_ENCODE_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int

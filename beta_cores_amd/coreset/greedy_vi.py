@@ -326,6 +326,9 @@ class GreedyVICoreset(Coreset):
         if self.pts.size == 0:
             return False
         m, dz = np.atleast_2d(self.pts).shape
+        enc = getattr(self.ll_projector, 'encoder', None)
+        if enc is not None:                  # the gradient stages the ENCODED coreset rows
+            dz = max(dz, enc.out_width(self.ll_projector.pass_cols))
         return self.ll_projector.projection_dimension <= 256 and m * (dz + 1) <= 60000
 
     def _optimize(self):

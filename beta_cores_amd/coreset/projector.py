@@ -202,11 +202,21 @@ def _resident_dtype(arr):
 
 
 class _DeviceProjectorBase(Projector):
-    def __init__(self, sampler, projection_dimension, model, ctx=None):
+    def __init__(self, sampler, projection_dimension, model, ctx=None, encoder=None, pass_cols=1, encoded_dtype=np.float32):
         self.projection_dimension = projection_dimension
         self.sampler = sampler
         self.model = model
         self.ctx = ctx or default_context()
+        # optional device feature encoder (encoders.MLPEncoder; the `nl` of the black-box classes): every route that turns
+        # `pts` into device rows encodes them first, so callers keep speaking RAW rows [x, pass-through]
+        self.encoder = encoder
+        self.pass_cols = int(pass_cols)
+        self.encoded_dtype = np.dtype(encoded_dtype)
+        self._enc_cache = {}       # id(resident rows) -> (weakref, encoder version, encoded DeviceData)
+        self._enc_out = None       # the one re-used output buffer for transient rows
+        self.encode_launches = 0   # bulk encodes this projector has issued (a cache hit issues none)
+        if encoder is not None and encoder.ctx is not self.ctx:
+            raise ValueError('the encoder lives on another context than the projector')
         self._pins = {}            # id(ndarray) -> (weakref, DeviceData): arrays the caller pinned (see pin())
         self._slots = {}           # dz -> DeviceData slot for small transient inputs
         self._pool = _PhiPool(self.ctx)
@@ -260,6 +270,7 @@ class _DeviceProjectorBase(Projector):
         hit[3] -= 1
         if hit[3] <= 0:
             self._pins.pop(id(pts), None)
+            self._enc_cache.pop(id(hit[1]), None)      # the encoded copy of the pinned rows goes with them
             hit[2].detach()
             _guard_release(hit[4])
 
@@ -272,9 +283,37 @@ class _DeviceProjectorBase(Projector):
             hit = self._pins.pop(key)
             hit[2].detach()
             _guard_release(hit[4])
+        self._enc_cache.clear()
         self._pool.clear()
 
     def device_data(self, pts):
+        """(DeviceData, transient) of what K1 reads: with an encoder the ENCODED rows of `pts`, otherwise its rows."""
+        dd, transient = self._raw_device_data(pts)
+        if self.encoder is None:
+            return dd, transient
+        return self._encoded(dd, transient or dd._transient), transient
+
+    def _encoded(self, dd, transient):
+        """Raw device rows -> encoded device rows.  Resident rows: cached per (rows, encoder version), re-encoded when the
+        version has moved.  Transient rows (a slot, a take(out=) buffer): into the projector's one re-used output buffer."""
+        enc = self.encoder
+        if dd.shape[1] != enc.widths[0] + self.pass_cols:
+            raise ValueError('data rows have %d columns, the encoder takes %d + %d pass-through'
+                             % (dd.shape[1], enc.widths[0], self.pass_cols))
+        if transient:
+            self.encode_launches += 1
+            self._enc_out = dd.encode(enc, pass_cols=self.pass_cols, dtype=self.encoded_dtype, out=self._enc_out, transient=True)
+            return self._enc_out
+        key = id(dd)
+        hit = self._enc_cache.get(key)
+        if hit is not None and hit[0]() is dd and hit[1] == enc.version:
+            return hit[2]
+        self.encode_launches += 1
+        out = dd.encode(enc, pass_cols=self.pass_cols, dtype=self.encoded_dtype)
+        self._enc_cache[key] = (weakref.ref(dd, lambda _, k=key, c=self._enc_cache: c.pop(k, None)), enc.version, out)
+        return out
+
+    def _raw_device_data(self, pts):
         """(DeviceData, transient): transient inputs live in a re-used upload slot that the next call overwrites."""
         if isinstance(pts, DeviceData):
             return pts, False
@@ -289,8 +328,19 @@ class _DeviceProjectorBase(Projector):
             return slot.update(pts), True
         return DeviceData(pts, ctx=self.ctx, dtype=_resident_dtype(pts)), False      # live array, uploaded for this call
 
-    def _zero_feature_keys(self, pts, d):
-        """Sorted unique y of the rows of `pts` whose d features are all zero (host array: NumPy; resident rows: one device scan)."""
+    def _zero_feature_keys(self, pts, d, encoded=False):
+        """Sorted unique y of the rows of `pts` whose d features are all zero (host array: NumPy; resident rows: one device scan).
+        With an encoder the ENCODED features are what counts (ReLU features are all zero for whole regions of x): host rows
+        go through enc(pts) -- the device's bits --, device rows are encoded first; `encoded`: `pts` already holds features."""
+        if self.encoder is not None and not encoded:
+            if isinstance(pts, DeviceData):
+                pts = self._encoded(pts, pts._transient)
+            else:
+                hit = self._pins.get(id(pts))
+                if hit is not None and hit[0]() is pts:
+                    pts = self._encoded(hit[1], False)
+                else:
+                    pts = self.encoder(np.atleast_2d(pts), pass_cols=self.pass_cols, dtype=self.encoded_dtype)
         if isinstance(pts, DeviceData):
             cached = not pts._transient       # a buffer that take(out=) refills in place is scanned every time
             hit = self._key_cache.get(id(pts)) if cached else None
@@ -336,7 +386,7 @@ class _DeviceProjectorBase(Projector):
         d = self.model.data_width(np.atleast_2d(self.samples).shape[1]) - 1
         keys = self._zero_feature_keys(pts, d)
         if more is not None:
-            keys = np.union1d(keys, self._zero_feature_keys(more, d))
+            keys = np.union1d(keys, self._zero_feature_keys(more, d, encoded=True))      # (vi_gradient has encoded them)
         vals = np.ascontiguousarray(self.model.host_constants(keys, params[1]), dtype=np.float64) if keys.size else np.zeros(0)
         self.constant_rows_from_host = int(keys.size)
         N.call('bc_ctx_set_constant_row_values', self.ctx.h, int(model_id), _ptr(params), int(params.shape[0]),
@@ -367,8 +417,9 @@ class _DeviceProjectorBase(Projector):
         return DevicePhi(h, self.ctx, release=self._pool.releaser(cap, S)), dd
 
     def _run(self, pts, model_id, params):
-        if isinstance(pts, np.ndarray) and pts.ndim == 2 and pts.shape[0] >= _PIPE_ROWS and self._pins.get(id(pts)) is None:
-            return self._run_from_host(pts, model_id, params)[0]
+        if (self.encoder is None and isinstance(pts, np.ndarray) and pts.ndim == 2 and pts.shape[0] >= _PIPE_ROWS
+                and self._pins.get(id(pts)) is None):
+            return self._run_from_host(pts, model_id, params)[0]      # (with an encoder: upload, encode, bc_project -- below)
         self._stage_host_constants(pts, model_id, params)
         dd, transient = self.device_data(pts)
         theta = self.model.theta_for_device(self.samples)
@@ -433,6 +484,8 @@ class _DeviceProjectorBase(Projector):
             raise ValueError('beta-gradient was requested but this model has none')
         dd, _ = self.device_data(data)
         core = np.ascontiguousarray(np.atleast_2d(core_pts), dtype=np.float64)
+        if self.encoder is not None and core.size:      # the coreset rows arrive raw: the device's own features of them
+            core = np.ascontiguousarray(self.encoder(core, pass_cols=self.pass_cols, dtype=self.encoded_dtype))
         m = int(core.shape[0])
         theta = self._theta_checked(dd)
         S = int(theta.shape[0])
@@ -491,6 +544,8 @@ class DeviceProjector(_DeviceProjectorBase):
     def _grad_x(self, pts):
         if not self.model.has_grad_x:
             raise ValueError('grad_loglikelihood was requested but this model has none')
+        if self.encoder is not None:
+            raise ValueError('grad_loglikelihood was requested but there is no x-gradient through a feature encoder')
         dd, _ = self.device_data(pts)
         theta = self.model.theta_for_device(self.samples)
         params = np.ascontiguousarray(self.model.params(), dtype=np.float64)

@@ -190,6 +190,7 @@ class DeviceData:
             raise ValueError('slot holds rows of %d columns, got %d' % (self.shape[1], z.shape[1]))
         N.call('bc_data_upload', self.h, _ptr(z), int(z.shape[0]))
         self.shape = (int(z.shape[0]), self.shape[1])
+        self._transient = True      # refilled in place: nothing about these rows may be cached
         return self
 
     def rows(self, local_idx):
@@ -227,7 +228,38 @@ class DeviceData:
         out._transient = transient or out_given
         return out
 
+    def encode(self, enc, pass_cols=1, dtype=np.float32, out=None, transient=False):
+        """These rows `[x, pass-through]` through a device feature encoder (encoders.MLPEncoder), kept on the device: a
+        DeviceData of shape (n, enc.widths[-1] + pass_cols) and storage `dtype` (bc_data_encode: float64 arithmetic; float32
+        storage rounds each feature once; the last `pass_cols` columns -- the neural-linear model's y -- are carried over).
+        The row_offset is kept.  `out` / `transient`: as in take() -- an earlier result (or a slot) of the same context, width
+        and dtype is refilled, resized, returned and marked transient."""
+        dt = np.dtype(dtype)
+        if dt not in (np.float64, np.float32):
+            raise ValueError('DeviceData stores float64 or float32 rows, not %s' % dt)
+        if out is not None and not isinstance(out, DeviceData):
+            raise TypeError('encode(out=...) wants a DeviceData')
+        out_given = out is not None
+        h = C.c_void_p(out.h.value) if out is not None else C.c_void_p()
+        try:
+            N.call('bc_data_encode', enc.h, self.h, int(pass_cols), int(dt.itemsize), C.byref(h))
+        except RuntimeError:                # a HIP failure (not a refusal, which leaves `out` as it was): `out` holds 0 rows now
+            if out is not None:
+                out.shape = (0, out.shape[1])
+            raise
+        enc.launches += 1
+        shape = (self.shape[0], enc.widths[-1] + int(pass_cols))
+        if out is None:
+            out = DeviceData._adopt(h, shape, self.ctx)
+        else:
+            out.shape = shape
+        out.row_offset = self.row_offset
+        out._transient = transient or out_given
+        return out
+
     def __getitem__(self, idx):
+        if isinstance(idx, tuple) and len(idx) == 2 and idx[1] == slice(None):      # data[rows, :], as the grouped selection writes it
+            idx = idx[0]
         if isinstance(idx, (int, np.integer)):
             return self.rows([idx])[0]
         return self.rows(idx)
