@@ -314,11 +314,7 @@ extern "C" int bc_data_encode(const bc_encoder* enc, const bc_data* src, int32_t
     a.out_w = out_w;
     a.pass = pass_cols;
     const long long ntiles = ((long long)n + enc->rows - 1) / enc->rows;
-    long long per_cu = (long long)(BC_ENC_LDS_DEVICE / (enc->lds ? enc->lds : 1));
-    if (per_cu > 4) per_cu = 4;
-    if (per_cu < 1) per_cu = 1;
-    long long blocks = (long long)ctx->n_cu * per_cu;
-    if (blocks > ntiles) blocks = ntiles;
+    const long long blocks = (long long)bc_enc_grid_blocks((int64_t)enc->lds, ctx->n_cu, (int64_t)ntiles);
     hipError_t e;
     if (src->elem == 4)
       e = out_elem_bytes == 4 ? launch_encode<float, float>(enc, a, src->z, d->z, (unsigned)blocks)

@@ -1,6 +1,7 @@
 // bc_encode_tile.h -- the shape arithmetic of k_encode_mlp (bc_encode.hip): how many rows a block owns, where its two LDS
-// panels lie and which slot of a panel holds activation (row r, column k).  Plain C, shared by the kernel, its launch code and
-// a host harness (tests/encode_tile_harness.c) that walks every width 1..512 and every depth 1..4 without a GPU.
+// panels lie, which slot of a panel holds activation (row r, column k) and how many blocks are launched.  Plain C, shared by
+// the kernel, its launch code and two host harnesses: tests/encode_tile_harness.c walks every width 1..512 and every depth 1..4
+// without a GPU, tests/encode_shapes_harness.c prints the launch shapes that the long-walk GPU tests are sized by.
 //
 // A block runs all layers on a tile of R rows.  Layer l reads its input (width d[l]) from panel l & 1 and, unless it is the
 // last one, writes its output into panel (l + 1) & 1; the last layer's features go to HBM from registers.  So panel 0 holds the
@@ -60,6 +61,19 @@ BC_ENC int bc_enc_tile_rows(const int32_t* widths, int n_layers) {
   for (r = BC_ENC_MAX_ROWS; r > 16; r >>= 1)
     if (bc_enc_lds_bytes(widths, n_layers, r) <= BC_ENC_LDS_BUDGET) return r;
   return bc_enc_lds_bytes(widths, n_layers, 16) <= BC_ENC_LDS_DEVICE ? 16 : 0;
+}
+
+/* The grid of k_encode_mlp (a persistent kernel: block b walks the tiles b, b + blocks, ...): as many blocks per CU as their LDS
+ * lets be resident, 1 .. 4, and never more blocks than tiles. */
+BC_ENC int64_t bc_enc_per_cu(int64_t lds) {
+  int64_t per_cu = BC_ENC_LDS_DEVICE / (lds > 0 ? lds : 1);
+  if (per_cu > 4) per_cu = 4;
+  if (per_cu < 1) per_cu = 1;
+  return per_cu;
+}
+BC_ENC int64_t bc_enc_grid_blocks(int64_t lds, int n_cu, int64_t ntiles) {
+  const int64_t blocks = (int64_t)n_cu * bc_enc_per_cu(lds);
+  return blocks > ntiles ? ntiles : blocks;
 }
 
 /* offset (doubles, from the start of the dynamic LDS) of panel p of a tile of `rows` rows */

@@ -25,6 +25,29 @@ def linreg_problem(n=5000, d=12, s=48, seed=23):
     return Z, th
 
 
+def encoder_layers(d=12, hidden=(20, 16), seed=29):
+    """A fixed network d -> 20 -> 16 (W, b, scale, shift, relu) for the modes that put a device feature encoder in front of K1."""
+    rng = np.random.RandomState(seed)
+    layers, din = [], d
+    for dout in hidden:
+        layers.append((rng.randn(dout, din) / np.sqrt(din), rng.randn(dout) * 0.3, rng.rand(dout) + 0.5, rng.randn(dout) * 0.2, True))
+        din = dout
+    return layers
+
+
+def encoded_sampler(enc, dl, E, M):
+    """The weighted-posterior sampler of the beta-Cores modes on the FEATURES of the coreset rows: `enc` None -- the rows arrive
+    encoded; otherwise they arrive raw and get the device's own features first (MLPEncoder.__call__)."""
+    def sampler(sz, wts, pts):
+        if pts.shape[0] == 0:
+            wts, pts = np.zeros(1), np.zeros((1, dl + 1))
+        elif enc is not None:
+            pts = enc(pts)
+        mu, L, _ = M.linreg_weighted_post(np.zeros(dl), np.eye(dl), 1.0, pts, wts)
+        return mu + E.dot(L.T)
+    return sampler
+
+
 def overflow_problem(n=6000, s=32, seed=4):
     rng = np.random.RandomState(seed)
     phi = rng.randn(n, 12).dot(rng.randn(12, s)) + 0.3 * rng.randn(n, s)
@@ -37,7 +60,7 @@ def main():
     mode, out = sys.argv[1], sys.argv[2]
     import torch.distributed as dist
     rank, world = int(os.environ['RANK']), int(os.environ['WORLD_SIZE'])
-    if mode in ('gpu_nccl1', 'gpu_nccl1_torch', 'gpu_nccl1_overflow', 'gpu_nccl1_overflow4', 'gpu_nccl1_bcores'):
+    if mode in ('gpu_nccl1', 'gpu_nccl1_torch', 'gpu_nccl1_overflow', 'gpu_nccl1_overflow4', 'gpu_nccl1_bcores', 'gpu_nccl1_bcores_enc'):
         import torch
         torch.cuda.set_device(0)
         dist.init_process_group('nccl', rank=rank, world_size=world, device_id=torch.device('cuda', 0))
@@ -107,9 +130,10 @@ def main():
             res[nm + '_trace_f'] = s._eng.trace()[0]
             res[nm + '_fallbacks'] = np.array(s._eng.prefilter_fallbacks())
             res[nm + '_next'] = np.array(s._select())            # step-wise protocol through the same situation
-    elif mode in ('gpu_nccl1_bcores', 'gpu_ncclN_bcores'):
+    elif mode in ('gpu_nccl1_bcores', 'gpu_ncclN_bcores', 'gpu_nccl1_bcores_enc'):
         # BetaCoreset over the library's own RCCL communicator: every gradient is ONE bc_vi_gradient call whose column sums
-        # are all-gathered and added in rank order inside the library (1 rank: rehearsal on one GPU; N ranks: one GPU each)
+        # are all-gathered and added in rank order inside the library (1 rank: rehearsal on one GPU; N ranks: one GPU each).
+        # _enc: the same with the RAW rows and a device feature encoder between them and K1 (encoder= on the projector)
         import torch
         os.environ['BC_FORCE_EXCHANGE'] = '1'
         dev_id = rank if mode == 'gpu_ncclN_bcores' else 0
@@ -128,7 +152,13 @@ def main():
                 wts, pts = np.zeros(1), np.zeros((1, Z.shape[1]))
             mu, L, _ = M.linreg_weighted_post(np.zeros(Z.shape[1] - 1), np.eye(Z.shape[1] - 1), 1.0, pts, wts)
             return mu + E.dot(L.T)
-        prj = bc.DeviceBetaProjector(sampler, th.shape[0], bc.likelihoods.LinearRegression(1.0), ctx=ctx)
+        if mode.endswith('_enc'):
+            enc = bc.encoders.MLPEncoder(encoder_layers(Z.shape[1] - 1), ctx=ctx)
+            dl = enc.widths[-1]
+            sampler = encoded_sampler(enc, dl, np.random.RandomState(3).randn(th.shape[0], dl), M)
+            prj = bc.DeviceBetaProjector(sampler, th.shape[0], bc.likelihoods.LinearRegression(1.0), ctx=ctx, encoder=enc)
+        else:
+            prj = bc.DeviceBetaProjector(sampler, th.shape[0], bc.likelihoods.LinearRegression(1.0), ctx=ctx)
         calls = {'n': 0}
         orig = prj.vi_gradient
 
@@ -142,6 +172,8 @@ def main():
             alg.build(1, m + 1)
         res['idx'], res['val'], res['pts'] = alg.idcs, alg.wts, alg.pts
         res['fused_calls'] = np.array(calls['n'])
+        if mode.endswith('_enc'):
+            res['resident_encodes'] = np.array(len(prj._enc_cache))      # encoded copies of resident rows the projector keeps
     elif mode in ('gpu_ncclN_hilbert', 'gpu_ncclN_overflow'):
         import torch
         stream = torch.cuda.Stream(device=rank)
@@ -209,14 +241,28 @@ def main():
             phi = h.snnls._eng.phi
             res['colsum_native'] = comm.colsum(phi)
             res['colsum_local'] = phi.colsum()
-    elif mode in ('gpu_hilbert', 'gpu_fw', 'gpu_bcores'):
+    elif mode in ('gpu_hilbert', 'gpu_fw', 'gpu_bcores', 'gpu_bcores_enc'):
         Z, th = linreg_problem()
         bounds = bc.shard_bounds(Z.shape[0], world)
         lo, hi = bounds[rank], bounds[rank + 1]
         ctx = bc.Context(device=0)                    # every rank shares GPU 0; records travel over gloo
         bc.set_default_context(ctx)
         model = bc.likelihoods.LinearRegression(1.0)
-        if mode == 'gpu_bcores':
+        if mode == 'gpu_bcores_enc':
+            # gpu_bcores with the RAW rows and a device feature encoder between them and K1: every rank encodes its shard
+            from oracle import models_ref as M
+            enc = bc.encoders.MLPEncoder(encoder_layers(Z.shape[1] - 1), ctx=ctx)
+            dl = enc.widths[-1]
+            sampler = encoded_sampler(enc, dl, np.random.RandomState(3).randn(th.shape[0], dl), M)
+            prj = bc.DeviceBetaProjector(sampler, th.shape[0], model, ctx=ctx, encoder=enc)
+            alg = bc.BetaCoreset(Z[lo:hi], prj, opt_itrs=5, step_sched=lambda i: 0.1 / (1. + i), beta=0.1,
+                                 learn_beta=False, comm=comm)
+            for m in range(6):
+                alg.build(1, m + 1)
+            res['idx'], res['val'] = alg.idcs, alg.wts
+            res['pts'] = alg.pts
+            res['resident_encodes'] = np.array(len(prj._enc_cache))      # encoded copies of resident rows the projector keeps
+        elif mode == 'gpu_bcores':
             E = np.random.RandomState(3).randn(th.shape[0], Z.shape[1] - 1)
             from oracle import models_ref as M
 

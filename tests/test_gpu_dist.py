@@ -10,7 +10,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 from test_dist_cpu import launch                    # noqa: E402
-from dist_worker import linreg_problem              # noqa: E402
+from dist_worker import linreg_problem, encoder_layers, encoded_sampler              # noqa: E402
 from oracle import models_ref as M                  # noqa: E402
 from oracle import coreset_ref as C                 # noqa: E402
 from oracle import RefGIGA, RefFrankWolfe           # noqa: E402
@@ -253,6 +253,58 @@ def test_fused_gradient_over_the_native_communicator_single_rank(tmp_path):
     np.testing.assert_allclose(r0['val'], ref.wts, rtol=1e-5, atol=1e-12)
     assert np.array_equal(r0['pts'], ref.pts)
     assert int(r0['fused_calls']) == 6 * 5
+
+
+def _encoded_single_process_run(n):
+    """The schedule of the beta-Cores worker modes in this process, without a communicator, on PRE-ENCODED resident rows and a
+    projector without an encoder: what the _enc modes (raw rows, encoder= on the projector, comm= on the coreset) must select."""
+    import beta_cores_amd as bc
+    Z, th = linreg_problem(n=n)
+    S = th.shape[0]
+    enc = bc.encoders.MLPEncoder(encoder_layers(Z.shape[1] - 1))
+    dl = enc.widths[-1]
+    ZE = bc.DeviceData(Z).encode(enc)
+    prj = bc.DeviceBetaProjector(encoded_sampler(None, dl, np.random.RandomState(3).randn(S, dl), M), S, bc.likelihoods.LinearRegression(1.0))
+    alg = bc.BetaCoreset(ZE, prj, opt_itrs=5, step_sched=lambda i: 0.1 / (1. + i), beta=0.1, learn_beta=False)
+    for m in range(6):
+        alg.build(1, m + 1)
+    # ... which is what the oracle selects on the device's own features
+    rows = ZE.rows(np.arange(n))
+    samp = encoded_sampler(None, dl, np.random.RandomState(3).randn(S, dl), M)
+    ref = C.RefGreedyVI(rows, lambda pts, t: C.project_f(lambda z, tt, b: M.linreg_beta_lik(z, tt, b, 1.0), pts, t, 0.1),
+                        lambda w, p: samp(0, w, p), 5, lambda i: 0.1 / (1. + i))
+    ref.build(6)
+    assert len(alg.idcs) >= 3
+    np.testing.assert_array_equal(alg.idcs, ref.idcs)
+    np.testing.assert_allclose(alg.wts, ref.wts, rtol=1e-5, atol=1e-12)
+    return Z, rows[alg.idcs], alg
+
+
+def test_encoder_over_the_native_communicator_single_rank(tmp_path):
+    """gpu_nccl1_bcores with a feature encoder: raw rows, encoder= on the projector, comm= on the coreset, a 1-rank NCCL group.
+    Same kernels in the same order as the single-process run on pre-encoded rows: the same bits; every gradient one
+    vi_gradient(comm=) call; one encoded copy of the shard is kept."""
+    Z, feats, single = _encoded_single_process_run(9000)
+    (r0,) = launch('gpu_nccl1_bcores_enc', tmp_path, world=1)
+    np.testing.assert_array_equal(r0['idx'], single.idcs)
+    assert np.array_equal(r0['val'], single.wts)
+    assert np.array_equal(r0['pts'], Z[single.idcs])                    # the coreset speaks RAW rows ...
+    assert np.array_equal(single.pts, feats)                            # ... whose device features are the pre-encoded run's points
+    assert int(r0['fused_calls']) == 6 * 5
+    assert int(r0['resident_encodes']) == 1
+
+
+def test_two_ranks_one_gpu_beta_coreset_with_an_encoder(tmp_path):
+    """gpu_bcores with a feature encoder: two ranks share GPU 0, each encodes its own shard of the raw rows (row_offset kept
+    through the encoder), sums travel over gloo."""
+    Z, feats, single = _encoded_single_process_run(5000)
+    r0, r1 = launch('gpu_bcores_enc', tmp_path)
+    for r in (r0, r1):
+        np.testing.assert_array_equal(r['idx'], single.idcs)
+        np.testing.assert_allclose(r['val'], single.wts, rtol=1e-5, atol=1e-12)
+        assert np.array_equal(r['pts'], Z[single.idcs])                 # exactly the RAW rows, broadcast from their owners
+        assert int(r['resident_encodes']) == 1
+    assert np.array_equal(r0['idx'], r1['idx']) and np.array_equal(r0['val'], r1['val']) and np.array_equal(r0['pts'], r1['pts'])
 
 
 @pytest.mark.skipif(_gpus() < 2, reason='needs two GPUs: world > 1 over RCCL (one process per GPU)')

@@ -8,10 +8,15 @@ error bound e through the layers (u = 2^-53, gamma_k = k u / (1 - k u)):
 hence the factor 2 and the +1 of slack; the epilogue is three roundings on each side).  A float64 device result must lie within
 e of the restatement, a float32 one within e + ulp32/2 + 2^-150.  Everything else is bit equality."""
 import ctypes as C
+import functools
 import os
+import sys
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import encode_shapes as ES            # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -175,6 +180,149 @@ def test_nan_and_inf_rows(bc):
         np.testing.assert_allclose(got[r, :20][fin], h[r][fin], rtol=1e-12, atol=1e-300)
     # a clean encode right after sees nothing of the infinities (no slot of the LDS panels is inherited)
     assert np.array_equal(encode_host(bc, enc, Z, 1, np.float64, np.float64), clean)
+
+
+# ------------------------------------------------------------------ 2b. long walks: a block's second and third tile
+# k_encode_mlp is persistent: block b walks the tiles b, b + B, b + 2 B, .. through the same two LDS panels.  At the sizes above
+# every block sees one tile.  Here n = ES.long_walk_n: half of the B = n_cu * per_cu blocks make three trips, the rest two, and
+# the short last tile is the third of its block.  One network per launch class (rows per tile, blocks per CU):
+# tests/test_encode_shapes_cpu.py holds the list against the header.
+CHUNK = 16384
+PAIRS = [(np.float32, np.float64), (np.float64, np.float32), (np.float32, np.float32), (np.float64, np.float64)]      # (source, output)
+
+
+def n_cu():
+    import torch
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def chunks(n, step=CHUNK):
+    for a in range(0, n, step):
+        yield np.arange(a, min(n, a + step))
+
+
+@functools.lru_cache(maxsize=2)
+def long_case(k):
+    """Network k of ES.LONG_NETS at its long-walk n: the encoder and the raw rows (float32 values, one pass-through column), on
+    the host and resident as float32."""
+    import beta_cores_amd as bc
+    widths = ES.LONG_NETS[k]
+    cu = n_cu()
+    n = ES.long_walk_n(widths, cu)
+    assert ES.trips(n, widths, cu) == 3 and ES.blocks(n, widths, cu) == cu * ES.per_cu(widths)
+    rng = np.random.RandomState(2000 + k)
+    enc = bc.encoders.MLPEncoder(make_layers(rng, widths))
+    Z = rng.randn(n, widths[0] + 1).astype(np.float32)
+    return dict(widths=widths, n=n, R=ES.tile_rows(widths), B=cu * ES.per_cu(widths), enc=enc, Z=Z, dd=bc.DeviceData(Z, dtype=np.float32))
+
+
+def same_rows(a, b, n, skip=None, what=''):
+    """Two resident row sets hold the same bits (NaNs included: compared as words), chunk by chunk; `skip`: rows left out."""
+    for idx in chunks(n):
+        if skip is not None:
+            idx = idx[~skip[idx]]
+        ra, rb = a.rows(idx), b.rows(idx)
+        bad = np.flatnonzero((ra.view(np.int64) != rb.view(np.int64)).any(axis=1))
+        assert bad.size == 0, (what, 'first differing row', int(idx[bad[0]]), 'of', int(bad.size))
+
+
+def test_long_pairs_cover_every_dtype_pair():
+    assert {PAIRS[k % 4] for k in range(len(ES.LONG_NETS))} == {(s, o) for s in DTYPES for o in DTYPES}
+
+
+@pytest.mark.parametrize('k', range(len(ES.LONG_NETS)))
+def test_long_walk_against_the_host_restatement(bc, k):
+    """Every row of a three-trip launch within the bound e of the float64 restatement (one source / output pair per network, the
+    pairs cycled over the list), pass-through columns bit-exact; the other pairs by the relations that hold at any n: a float32
+    output is the float64 output rounded, and the source's storage type does not matter."""
+    c = long_case(k)
+    widths, n, enc, Z = c['widths'], c['n'], c['enc'], c['Z']
+    d0, dl = widths[0], widths[-1]
+    src_dtype, out_dtype = PAIRS[k % 4]
+    srcs = {np.float32: c['dd'], np.float64: bc.DeviceData(Z.astype(np.float64))}
+    outs = {(s, o): srcs[s].encode(enc, pass_cols=1, dtype=o) for s in DTYPES for o in DTYPES}
+    for out in outs.values():
+        assert out.shape == (n, dl + 1)
+    worst, worst_allow = 0., 0.
+    for idx in chunks(n):
+        got = {key: out.rows(idx) for key, out in outs.items()}
+        a = got[(np.float32, np.float64)]
+        assert np.array_equal(got[(np.float64, np.float64)], a), int(idx[0])
+        for s in DTYPES:
+            assert np.array_equal(got[(s, np.float32)], a.astype(np.float32).astype(np.float64)), (s, int(idx[0]))
+        h, e = enc.host(Z[idx, :d0].astype(np.float64), dtype=np.float64, bound=True)
+        g = got[(src_dtype, out_dtype)]
+        check_features(g[:, :dl], h, e, out_dtype, 'widths=%s rows %d..%d' % (widths, idx[0], idx[-1]))
+        assert np.array_equal(g[:, dl:], Z[idx, d0:].astype(np.float64))
+        worst = max(worst, np.abs(g[:, :dl] - h).max())
+        worst_allow = max(worst_allow, e.max())
+    print('long walk widths=%s n=%d R=%d B=%d %s->%s: max |device - restatement| %.3e, max e %.3e'
+          % (widths, n, c['R'], c['B'], np.dtype(src_dtype).name, np.dtype(out_dtype).name, worst, worst_allow))
+
+
+@pytest.mark.parametrize('k', range(len(ES.LONG_NETS)))
+def test_long_walk_bits_do_not_depend_on_the_trip(bc, k):
+    """The rows on both sides of every trip boundary, the 17 rows past the last full trip tile and 200 random rows: the bits of
+    the three-trip launch are those of a launch that encodes just these rows, each block one tile."""
+    c = long_case(k)
+    n, R, B, enc, dd = c['n'], c['R'], c['B'], c['enc'], c['dd']
+    rng = np.random.RandomState(3000 + k)
+    idx = np.concatenate(([0, R * B - 1, R * B, 2 * R * B - 1, 2 * R * B, n - 1], np.arange(n - 17, n), rng.randint(n, size=200)))
+    assert ES.trips(idx.size, c['widths'], n_cu()) == 1
+    for out_dtype in DTYPES:
+        whole = dd.encode(enc, dtype=out_dtype)
+        alone = dd.take(idx).encode(enc, dtype=out_dtype)
+        assert np.array_equal(alone.rows(np.arange(idx.size)).view(np.int64), whole.rows(idx).view(np.int64)), out_dtype
+
+
+@pytest.mark.parametrize('k', range(len(ES.LONG_NETS)))
+def test_long_walk_inherits_nothing_across_tiles(bc, k):
+    """What test_nan_and_inf_rows cannot see in two one-tile launches: block t0 = 5 fills its panels with a tile of +inf rows,
+    then with tile t0 + B (one all-NaN row), then with the clean tile t0 + 2 B.  Every row but the poisoned ones keeps the bits
+    of the clean run -- no slot of a panel, padded or not, is read before this tile's own stage has written it."""
+    c = long_case(k)
+    widths, n, R, B, enc, Z = c['widths'], c['n'], c['R'], c['B'], c['enc'], c['Z']
+    d0, dl = widths[0], widths[-1]
+    src_dtype, out_dtype = PAIRS[k % 4]
+    t0 = 5
+    assert t0 + 2 * B < ES.ntiles(n, widths) and (t0 + 2 * B + 1) * R <= n      # the clean third tile exists and is full
+    bad = Z.copy()
+    bad[t0 * R:(t0 + 1) * R, :d0] = np.inf
+    nan_row = (t0 + B) * R + 7
+    bad[nan_row, :d0] = np.nan
+    poisoned = np.zeros(n, dtype=bool)
+    poisoned[t0 * R:(t0 + 1) * R] = True
+    poisoned[nan_row] = True
+    clean = bc.DeviceData(Z.astype(src_dtype), dtype=src_dtype).encode(enc, dtype=out_dtype)
+    got = bc.DeviceData(bad.astype(src_dtype), dtype=src_dtype).encode(enc, dtype=out_dtype)
+    same_rows(got, clean, n, skip=poisoned, what=widths)
+    # the poisoned rows: the restatement's pattern of NaN and inf, its values where it is finite, the pass-through untouched
+    pidx = np.flatnonzero(poisoned)
+    rows = got.rows(pidx)
+    with np.errstate(invalid='ignore', over='ignore'):
+        h = enc.host(bad[pidx, :d0].astype(np.float64), dtype=np.float64)
+    assert np.array_equal(np.isnan(rows[:, :dl]), np.isnan(h)) and np.array_equal(np.isinf(rows[:, :dl]), np.isinf(h))
+    assert np.array_equal(np.signbit(rows[:, :dl])[np.isinf(h)], np.signbit(h)[np.isinf(h)])
+    fin = np.isfinite(h)
+    np.testing.assert_allclose(rows[:, :dl][fin], h[fin], rtol=1e-12 if out_dtype == np.float64 else 2.0 ** -23, atol=1e-300)
+    assert np.isnan(rows[pidx == nan_row, :dl]).all()
+    assert np.array_equal(rows[:, dl:], Z[pidx, d0:].astype(np.float64))
+
+
+@pytest.mark.parametrize('k', range(len(ES.LONG_NETS)))
+def test_long_walk_refills_a_buffer_across_sizes(bc, k):
+    """encode(out=buf) at n = 40 -> long -> 40: the buffer grows and the grid goes from one block to B blocks and back; every
+    result has the bits of a fresh encode."""
+    c = long_case(k)
+    widths, n, enc, Z = c['widths'], c['n'], c['enc'], c['Z']
+    out_dtype = PAIRS[k % 4][1]
+    w = widths[-1] + 1
+    buf = bc.DeviceData(np.full((100, w), np.nan, dtype=out_dtype), dtype=out_dtype)
+    for m, lo in ((40, 0), (n, 0), (40, 1000)):
+        dd = c['dd'] if m == n else bc.DeviceData(Z[lo:lo + m], dtype=np.float32)
+        got = dd.encode(enc, dtype=out_dtype, out=buf)
+        assert got is buf and buf.shape == (m, w) and buf._transient
+        same_rows(buf, dd.encode(enc, dtype=out_dtype), m, what=(widths, m))
 
 
 def test_all_negative_preactivations_give_exact_zeros(bc):
@@ -429,6 +577,159 @@ def test_projector_with_encoder_equals_projector_on_encoded_rows(bc, problem):
             tol = 1.5 * n * 1e-11 * (1. + np.abs(raw).max())
             np.testing.assert_allclose(ra, resid, rtol=0., atol=tol)
             np.testing.assert_allclose(ga, -phi[core_idx].dot(resid) / S, rtol=0., atol=tol * np.abs(phi[core_idx]).sum(axis=1).max() / S + 1e-9)
+
+
+# ------------------------------------------------------------------ 4b. projector routes at 4096 rows or more and at 65 536 or more
+@pytest.fixture(scope='module')
+def big_problem(bc):
+    """The driver's network at its long-walk n (above projector._PIPE_ROWS): float32 rows, so a live array and a pinned one keep a
+    float32 device copy."""
+    from beta_cores_amd.coreset import projector as P
+    rng = np.random.RandomState(16)
+    widths = (13, 20, 20)
+    n, S = ES.long_walk_n(widths, n_cu()), 32
+    assert n >= P._PIPE_ROWS and P._SMALL_ROWS <= 5000 < P._PIPE_ROWS
+    X = rng.randn(n, 13)
+    y = np.tanh(X[:, 0]) + 0.5 * X[:, 1] + 0.3 * rng.randn(n)
+    Z = np.hstack((X, y[:, None])).astype(np.float32)
+    assert Z.base is None
+    return dict(n=n, S=S, Z=Z, layers=make_layers(rng, widths), retrained=make_layers(rng, widths), th=rng.randn(S, 20) * 0.3)
+
+
+def _same_phi(a, b, n, S):
+    assert a.shape == (n, S) and b.shape == (n, S)
+    assert np.array_equal(a.to_host(), b.to_host()) and np.array_equal(a.norms(), b.norms()) and np.array_equal(a.colsum(), b.colsum())
+
+
+@pytest.mark.parametrize('cls_name', ['DeviceProjector', 'DeviceBetaProjector'])
+def test_projector_routes_with_an_encoder_on_many_rows(bc, big_problem, cls_name):
+    """encoder= on (a) the live host array (>= _PIPE_ROWS: upload, encode, bc_project -- not bc_project_from_host), (b) a live
+    5000-row slice (between _SMALL_ROWS and _PIPE_ROWS), (c) the resident raw rows and (d) pinned rows, against the plain
+    projector on the pre-encoded rows: the same bits everywhere, and encode_launches counts what the docstrings promise."""
+    from oracle import models_ref as M
+    Z, th, S, n = big_problem['Z'], big_problem['th'], big_problem['S'], big_problem['n']
+    cls = getattr(bc, cls_name)
+    sig, beta, m5 = 1.3, 0.2, 5000
+    betas = (None,) if cls is bc.DeviceProjector else (None, beta)
+    lik = bc.likelihoods.LinearRegression(sig)
+    enc = bc.encoders.MLPEncoder(big_problem['layers'])
+    dd = bc.DeviceData(Z, dtype=np.float32)
+    ZE, ZE5 = dd.encode(enc), bc.DeviceData(Z[:m5], dtype=np.float32).encode(enc)
+    rng = np.random.RandomState(17)
+    core_idx = rng.randint(m5, size=12)
+    w = rng.rand(12)
+    core_raw = Z[core_idx].astype(np.float64)
+    core_enc = ZE.rows(core_idx)
+    p0 = cls(fixed(th), S, lik)
+
+    def reference(data):
+        out = {'project': p0.project(data)}
+        for bt in betas:
+            if bt is not None:
+                out['project_f'] = p0.project_f(data, bt)
+            out['colsum', bt] = p0.colsum(data, beta=bt)
+            out['grad', bt] = p0.vi_gradient(data, core_enc, w, 1.5, beta=bt, want_resid=True)
+        return out
+    ref, ref5 = reference(ZE), reference(ZE5)
+
+    def calls(pe, pts, want, rows):
+        """Every entry point once; returns how many there were."""
+        _same_phi(pe.project(pts), want['project'], rows, S)
+        k = 1
+        for bt in betas:
+            if bt is not None:
+                _same_phi(pe.project_f(pts, bt), want['project_f'], rows, S)
+                k += 1
+            assert np.array_equal(pe.colsum(pts, beta=bt), want['colsum', bt])
+            g, r = pe.vi_gradient(pts, core_raw, w, 1.5, beta=bt, want_resid=True)
+            assert np.array_equal(g, want['grad', bt][0]) and np.array_equal(r, want['grad', bt][1])
+            k += 2
+        return k
+
+    # (a), (b): live arrays are uploaded and encoded for every call, and the encoded copy goes with the temporary rows
+    for pts, want, rows in ((Z, ref, n), (Z[:m5], ref5, m5)):
+        pe = cls(fixed(th), S, lik, encoder=enc)
+        k = calls(pe, pts, want, rows)
+        assert pe.encode_launches == k and len(pe._enc_cache) == 0
+        assert calls(pe, pts, want, rows) == k and pe.encode_launches == 2 * k and len(pe._enc_cache) == 0
+        assert pts.flags.writeable
+    # (c), (d): one encode per version of the encoder, whatever is called and how often
+    pe = cls(fixed(th), S, lik, encoder=enc)
+    calls(pe, dd, ref, n)
+    assert pe.encode_launches == 1 and len(pe._enc_cache) == 1
+    pinned = pe.pin(Z)
+    assert pinned.dtype == np.float32 and pe.pinned(Z) is pinned and not Z.flags.writeable
+    try:
+        calls(pe, Z, ref, n)
+        calls(pe, Z, ref, n)
+        calls(pe, dd, ref, n)
+        assert pe.encode_launches == 2 and len(pe._enc_cache) == 2
+        # a live array beside the resident entries: encoded per call, nothing of it stays
+        before = pe.encode_launches
+        k = calls(pe, Z[:m5], ref5, m5)
+        assert pe.encode_launches == before + k and len(pe._enc_cache) == 2
+        # retrained parameters: each resident row set is encoded once more, at its next use
+        v = enc.version
+        enc.update(big_problem['retrained'])
+        assert enc.version == v + 1
+        ZE2 = dd.encode(enc)
+        core_enc = ZE2.rows(core_idx)
+        ref2 = reference(ZE2)
+        assert not np.array_equal(ref2['colsum', None], ref['colsum', None])
+        calls(pe, dd, ref2, n)
+        assert pe.encode_launches == before + k + 1
+        calls(pe, dd, ref2, n)
+        calls(pe, Z, ref2, n)
+        calls(pe, Z, ref2, n)
+        assert pe.encode_launches == before + k + 2 and len(pe._enc_cache) == 2
+    finally:
+        pe.unpin(Z)
+    assert len(pe._enc_cache) == 1 and Z.flags.writeable
+    # ... and the oracle on the device's own features, once per class (after the update: the retrained network's)
+    rows = ZE2.rows(np.arange(n))
+
+    def close(dev, raw):
+        np.testing.assert_allclose(dev, raw - raw.mean(axis=1)[:, None], rtol=0., atol=1e-11 * (1. + np.abs(raw).max()))
+    raw_ll = M.linreg_loglik(rows, th, sig)
+    close(ref2['project'].to_host(), raw_ll)
+    for bt in betas:
+        raw = raw_ll
+        if bt is not None:
+            raw = M.linreg_beta_lik(rows, th, bt, sig)
+            close(ref2['project_f'].to_host(), raw)
+        phi = raw - raw.mean(axis=1)[:, None]
+        np.testing.assert_allclose(ref2['colsum', bt], phi.sum(axis=0), rtol=0., atol=n * 1e-11 * (1. + np.abs(raw).max()))
+        ga, ra = ref2['grad', bt]
+        resid = 1.5 * phi.sum(axis=0) - w.dot(phi[core_idx])
+        tol = 1.5 * n * 1e-11 * (1. + np.abs(raw).max())
+        np.testing.assert_allclose(ra, resid, rtol=0., atol=tol)
+        np.testing.assert_allclose(ga, -phi[core_idx].dot(resid) / S, rtol=0., atol=tol * np.abs(phi[core_idx]).sum(axis=1).max() / S + 1e-9)
+
+
+def test_a_shard_keeps_its_row_offset_through_the_encoder(bc, big_problem):
+    """Rows a:b of a larger set: the encoded rows and the Phi projected from them through encoder= carry row_offset a and the
+    bits of rows a:b of the unsharded projection."""
+    Z, th, S, n = big_problem['Z'], big_problem['th'], big_problem['S'], big_problem['n']
+    a, b = 128 * 517, 128 * 517 + 9001
+    assert b < n
+    lik = bc.likelihoods.LinearRegression(1.0)
+    enc = bc.encoders.MLPEncoder(big_problem['layers'])
+    shard = bc.DeviceData(Z[a:b], dtype=np.float32, row_offset=a)
+    se = shard.encode(enc)
+    assert se.row_offset == a and shard.encode(enc, dtype=np.float64, out=bc.DeviceData(np.zeros((1, 21)))).row_offset == a
+    whole = bc.DeviceData(Z, dtype=np.float32)
+    assert np.array_equal(se.rows(np.arange(b - a)), whole.encode(enc).rows(np.arange(a, b)))
+    for cls in (bc.DeviceProjector, bc.DeviceBetaProjector):
+        pe = cls(fixed(th), S, lik, encoder=enc)
+        full = pe.project(whole)
+        part = pe.project(shard)
+        assert full.row_offset == 0 and part.row_offset == a and part.shape == (b - a, S)
+        assert np.array_equal(part.to_host(), full.to_host()[a:b]) and np.array_equal(part.norms(), full.norms()[a:b])
+        assert np.array_equal(part.to_host(), cls(fixed(th), S, lik).project(se).to_host())
+        # the arg-max speaks global row numbers
+        resid = np.random.RandomState(18).randn(S)
+        best, _ = part.argmax(resid, mode=1, post_div=float(S))
+        assert a <= best < b
 
 
 # ------------------------------------------------------------------ 5. coresets on raw resident rows
