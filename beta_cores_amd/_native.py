@@ -156,6 +156,20 @@ _ENCODE_SIGNATURES = {
 }
 ENCODE_EXPORTS = sorted(_ENCODE_SIGNATURES)
 
+# entry points of the extension header include/beta_cores_viopt.h (the greedy-VI weight optimisation enqueued on the device)
+_VIOPT_SIGNATURES = {
+    'bc_vi_optimize_auto_chunk': [C.c_int32, C.c_int32, C.c_int64],      # returns a step count, not a status
+    'bc_vi_optimize_begin': [vp, vp, vp, C.c_int64, C.c_int, vp, C.c_int32, C.c_int, vp, C.c_int32, vp, C.c_int32, vp, C.c_int64,
+                             C.c_double, C.c_int],
+    'bc_vi_optimize_chunk_begin': [vp, vp, vp, C.c_int32],
+    'bc_vi_optimize_chunk_end': [vp],
+    'bc_vi_optimize_end': [vp, vp, vp],
+    'bc_vi_optimize_device_ms': [vp, c_dp],
+    'bc_vi_optimize': [vp, vp, vp, C.c_int64, C.c_int, vp, C.c_int32, C.c_int, vp, C.c_int32, vp, C.c_int32, vp, vp, vp, C.c_int64,
+                       C.c_double, C.c_int32, vp, vp],
+}
+VIOPT_EXPORTS = sorted(_VIOPT_SIGNATURES)
+
 _lib = None
 
 
@@ -188,7 +202,8 @@ def load():
     _preload_torch_hip_runtime()
     lib = C.CDLL(LIB_PATH)
     for name, argtypes in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_F32_SIGNATURES.items()) + list(_NNLS_SIGNATURES.items()) \
-            + list(_TAKE_SIGNATURES.items()) + list(_BETAGRAD_SIGNATURES.items()) + list(_ENCODE_SIGNATURES.items()):
+            + list(_TAKE_SIGNATURES.items()) + list(_BETAGRAD_SIGNATURES.items()) + list(_ENCODE_SIGNATURES.items()) \
+            + list(_VIOPT_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int

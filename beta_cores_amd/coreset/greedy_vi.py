@@ -42,7 +42,7 @@ def resident_copy_of_view(data, ll_projector):
 class GreedyVICoreset(Coreset):
     def __init__(self, data, ll_projector, n_subsample_select=None, n_subsample_opt=None, opt_itrs=100,
                  step_sched=lambda i: 1. / (1. + i), mup=None, SigpInv=None, groups=None, selected_groups=None,
-                 initialized=False, comm=None, pin_data=True, fused_gradient=True, **kw):
+                 initialized=False, comm=None, pin_data=True, fused_gradient=True, device_optimize=False, **kw):
         self.data = data
         self.ll_projector = ll_projector
         n = data.shape[0]
@@ -55,6 +55,10 @@ class GreedyVICoreset(Coreset):
         self.groups = groups
         self.selected_groups = []
         self.fused_gradient = bool(fused_gradient)     # False: every gradient materialises Phi (the general path)
+        # True: _optimize() hands the whole ADAM loop to the device where that is covered (_device_optimize); results equal the
+        # host loop's to rounding (weights within the parity contract, selections and the RNG position exactly)
+        self.device_optimize = bool(device_optimize)
+        self.device_optimize_calls = 0                 # _optimize() calls that took the native loop
         # BC_FORCE_EXCHANGE=1 keeps a 1-rank group on the collective paths (rehearsal of the RCCL code on one GPU)
         self.comm = comm if (comm is not None and (comm.world > 1 or os.environ.get('BC_FORCE_EXCHANGE') == '1')) else None
         self._dev_data = data if isinstance(data, DeviceData) else None      # rows already resident in HBM
@@ -329,10 +333,28 @@ class GreedyVICoreset(Coreset):
         enc = getattr(self.ll_projector, 'encoder', None)
         if enc is not None:                  # the gradient stages the ENCODED coreset rows
             dz = max(dz, enc.out_width(self.ll_projector.pass_cols))
-        return self.ll_projector.projection_dimension <= 256 and m * (dz + 1) <= 60000
+        from .projector import VI_MAX_CORE_DOUBLES, VI_MAX_SAMPLES
+        return self.ll_projector.projection_dimension <= VI_MAX_SAMPLES and m * (dz + 1) <= VI_MAX_CORE_DOUBLES
+
+    def _device_optimize(self, beta):
+        """The `opt_itrs` projected-ADAM steps in one run on the device (projector.vi_optimize: bc_vi_optimize_*), or None when
+        this coreset is not covered: a black-box projector, rows that are not resident, row shards, groups, a shape outside
+        vi_gradient's, and whatever vi_optimize itself declines (an encoder, a sampler without device_spec(), D > 128).
+        (learn_beta=True never gets here: BetaCoreset._optimize runs its own (w, beta) loop.)"""
+        run = getattr(self.ll_projector, 'vi_optimize', None)
+        if run is None or self.comm is not None or self.groups is not None or self._dev_data is None or not self._fused_ok():
+            return None
+        return run(self._dev_data, self.pts, self.wts, self.opt_itrs, self.step_sched, n_subsample=self.n_subsample_opt,
+                   n_total=self._n_total, beta=self._fused_beta(beta))
 
     def _optimize(self):
         beta = self._beta()
+        if self.device_optimize:
+            w = self._device_optimize(beta)      # (raises before self.wts is touched)
+            if w is not None:
+                self.device_optimize_calls += 1
+                self.wts = w
+                return
         fused = self._fused_ok() if hasattr(self.ll_projector, 'vi_gradient') else False
 
         # a sampler that can draw its next normals ahead of time (samplers.*PosteriorSampler.prefetch) does so while the GPU

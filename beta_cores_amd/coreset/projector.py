@@ -11,13 +11,16 @@ Two families, one protocol (bayesiancoresets/coreset/projector.py:5-66:
   leaves HBM (a DevicePhi is returned).
 """
 import ctypes as C
+import time
 import weakref
 
 import numpy as np
 
 from .. import _native as N
 from ..device import DeviceData, DevicePhi, _as_rows, _ptr, default_context
+from ..likelihoods import GaussianLocation, LinearRegression
 from ..util import numpy_bits
+from ..util.opt import adam_step_arrays
 
 
 class Projector(object):
@@ -201,6 +204,12 @@ def _resident_dtype(arr):
     return None
 
 
+# limits of the native gradient entry points (bc_vi_gradient, bc_vi_optimize: csrc/bc_project.hip, csrc/bc_viopt.hip)
+VI_MAX_SAMPLES = 256           # one pass of the store-free K1
+VI_MAX_CORE_DOUBLES = 60000    # m * (dz + 1): the coreset rows and their weights fit the native staging area
+VI_OPT_MAX_DIM = 128           # bc_vi_optimize: the factor and its inverse share one work-group's LDS (BC_VI_MAX_DIM)
+
+
 class _DeviceProjectorBase(Projector):
     def __init__(self, sampler, projection_dimension, model, ctx=None, encoder=None, pass_cols=1, encoded_dtype=np.float32):
         self.projection_dimension = projection_dimension
@@ -215,6 +224,7 @@ class _DeviceProjectorBase(Projector):
         self._enc_cache = {}       # id(resident rows) -> (weakref, encoder version, encoded DeviceData)
         self._enc_out = None       # the one re-used output buffer for transient rows
         self.encode_launches = 0   # bulk encodes this projector has issued (a cache hit issues none)
+        self.vi_optimize_calls = 0 # weight optimisations that ran on the device (vi_optimize)
         if encoder is not None and encoder.ctx is not self.ctx:
             raise ValueError('the encoder lives on another context than the projector')
         self._pins = {}            # id(ndarray) -> (weakref, DeviceData): arrays the caller pinned (see pin())
@@ -489,7 +499,7 @@ class _DeviceProjectorBase(Projector):
         m = int(core.shape[0])
         theta = self._theta_checked(dd)
         S = int(theta.shape[0])
-        if S > 256 or m == 0 or m * (core.shape[1] + 1) > 60000:      # (also keeps 2 m + S within the native staging area)
+        if S > VI_MAX_SAMPLES or m == 0 or m * (core.shape[1] + 1) > VI_MAX_CORE_DOUBLES:      # (also keeps 2 m + S within the native staging area)
             return None
         if core.shape[1] != dd.shape[1]:
             raise ValueError('coreset rows have %d columns, data rows %d' % (core.shape[1], dd.shape[1]))
@@ -521,6 +531,94 @@ class _DeviceProjectorBase(Projector):
         finally:
             N.call('bc_vi_gradient_end', self.ctx.h, _ptr(grad), _ptr(resid) if want_resid else None)
         return (grad, resid) if want_resid else grad
+
+    def vi_optimize(self, data, core_pts, w0, opt_itrs, step_sched, n_subsample=None, n_total=None, beta=None, chunk_steps=0,
+                    want_trace=False, timings=None):
+        """The whole weight optimisation of one greedy-VI step -- `nn_opt(w0, grd, opt_itrs, step_sched)` with a fresh posterior
+        draw and a fresh (sub-sampled) projection per gradient (bcores.py:141-150) -- enqueued on the device in chunks of steps
+        (bc_vi_optimize_begin / _chunk_begin / _chunk_end / _end): the draw (k_vi_sampler), both projections, the M x S algebra
+        and the ADAM update never leave the GPU, the host waits once per chunk.  Returns the new weights (with `want_trace`:
+        (weights, opt_itrs x m weights after every step)), equal to the host loop's to rounding, or None when the run is not
+        covered: rows that are not resident, an encoder, a sampler without `device_spec()`, D > 128, S > 256, a coreset too
+        large for the staging area, a model that does not go with the sampler, opt_itrs <= 0 (the host's nn_opt then returns
+        w0, and so does the caller's host loop).
+
+        The random numbers are the HOST's, in the reference's order, step by step: the sampler's S x D normals (`_normals`: a
+        prefetched block first, an injected rng honoured), then `np.random.randint(n_total, size=n_subsample)`.  The next chunk
+        is drawn while the device runs the current one; nothing is drawn past the last step.  A posterior precision matrix
+        that is not positive definite raises np.linalg.LinAlgError, as LAPACK does in the host loop.
+        Two things differ from the host loop and are not papered over: after such a LinAlgError the streams have advanced by
+        every chunk drawn so far (the failing step's whole chunk and the one drawn beside it), where the host loop stops at
+        the failing step; and `self.samples` is NOT the last step's Theta afterwards -- that never leaves the device -- but
+        what the last `update()` left (GreedyVICoreset calls update() before it reads samples, in _select).
+        `timings` (a dict): receives 'draw_s' (host seconds spent drawing) and 'device_ms' (GPU time of the chunks' steps)."""
+        spec = getattr(self.sampler, 'device_spec', None)
+        if spec is None or self.encoder is not None or not isinstance(data, DeviceData) or data._transient:
+            return None
+        kind, sp = spec()
+        sp = np.ascontiguousarray(sp, dtype=np.float64)
+        D = int(self.sampler._dim())
+        S = int(self.projection_dimension)
+        core = np.ascontiguousarray(np.atleast_2d(core_pts), dtype=np.float64)
+        m = int(core.shape[0])
+        model_id, params = self._ids(beta)
+        model_cls = LinearRegression if kind == 0 else GaussianLocation      # the likelihood each sampler kind is the posterior of
+        if not isinstance(self.model, model_cls) or int(model_id) not in (self.model.model_id, self.model.beta_model_id):
+            return None
+        if opt_itrs <= 0 or D > VI_OPT_MAX_DIM or S > VI_MAX_SAMPLES or m == 0 or m * (core.shape[1] + 1) > VI_MAX_CORE_DOUBLES \
+                or data.shape[1] != self.model.data_width(D) or core.shape[1] != data.shape[1]:
+            return None
+        w0 = np.ascontiguousarray(w0, dtype=np.float64)
+        if w0.shape != (m,):
+            raise ValueError('one weight per coreset row')
+        params = np.ascontiguousarray(params, dtype=np.float64)
+        n_sub = 0 if n_subsample is None else int(n_subsample)
+        n_total = int(data.shape[0] if n_total is None else n_total)
+        self._stage_host_constants(data, model_id, params, more=core)
+        steps = np.ascontiguousarray(adam_step_arrays(int(opt_itrs), step_sched))
+        lib = N.load()
+        chunk = int(chunk_steps) if chunk_steps else int(lib.bc_vi_optimize_auto_chunk(S, D, n_sub))
+        draw_s = [0.]
+
+        def draw(k):
+            t0 = time.perf_counter()
+            E = np.empty((k, S, D))
+            idx = np.empty((k, n_sub), dtype=np.int64) if n_sub else None
+            for t in range(k):
+                E[t] = self.sampler._normals(S, D)
+                if n_sub:
+                    idx[t] = np.random.randint(n_total, size=n_sub)
+            draw_s[0] += time.perf_counter() - t0
+            return E, idx
+        N.call('bc_vi_optimize_begin', self.ctx.h, data.h, _ptr(core), m, int(model_id), _ptr(params), int(params.shape[0]),
+               int(kind), _ptr(sp), S, _ptr(w0), int(opt_itrs), _ptr(steps), n_sub,
+               float(n_total) / n_sub if n_sub else 1., 1 if want_trace else 0)
+        try:
+            done = 0
+            nxt = draw(min(chunk, int(opt_itrs)))
+            while done < opt_itrs:
+                E, idx = nxt
+                N.call('bc_vi_optimize_chunk_begin', self.ctx.h, _ptr(E), _ptr(idx) if idx is not None else None, int(E.shape[0]))
+                done += E.shape[0]
+                try:
+                    nxt = draw(min(chunk, int(opt_itrs) - done)) if done < opt_itrs else None      # beside the GPU
+                finally:
+                    status = lib.bc_vi_optimize_chunk_end(self.ctx.h)
+                if status == N.BC_NUMERICAL_PRECISION:
+                    raise np.linalg.LinAlgError(N.last_error())
+                N.check(status)
+            out = np.empty(m)
+            trace = np.empty((int(opt_itrs), m)) if want_trace else None
+            N.call('bc_vi_optimize_end', self.ctx.h, _ptr(out), _ptr(trace) if want_trace else None)
+        except BaseException:
+            lib.bc_vi_optimize_end(self.ctx.h, None, None)      # (closes the run; a no-op status if _end itself has closed it)
+            raise
+        if timings is not None:
+            ms = C.c_double()
+            N.call('bc_vi_optimize_device_ms', self.ctx.h, C.byref(ms))
+            timings['draw_s'], timings['device_ms'] = draw_s[0], ms.value
+        self.vi_optimize_calls += 1
+        return (out, trace) if want_trace else out
 
 
 def is_device_projector(prj):

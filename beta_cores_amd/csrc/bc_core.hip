@@ -109,6 +109,7 @@ extern "C" int bc_ctx_destroy(bc_ctx* ctx) {
   if (ctx->pinned) (void)hipHostFree(ctx->pinned);
   bc_uploader_free(ctx);
   bc_take_free(ctx);
+  bc_viopt_free(ctx);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
   return BC_OK;

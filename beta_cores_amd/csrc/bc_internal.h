@@ -87,6 +87,7 @@ struct bc_ctx {
   size_t take_pinned_cap[2] = {0, 0};      // indices
   hipEvent_t take_ev[2] = {nullptr, nullptr};
   int take_turn = 0;
+  struct bc_viopt* viopt = nullptr;    // bc_vi_optimize (bc_viopt.hip): the buffers and the state of the run in progress
 };
 
 // bc_upload.hip: rows of a host array -> dst_dev through pinned staging and several copy threads; the hook (optional) is
@@ -98,6 +99,17 @@ int bc_upload_rows(bc_ctx* ctx, const void* src, void* dst_dev, int64_t n_rows, 
 int64_t bc_upload_default_chunk_rows(int64_t n_rows, size_t row_bytes);
 void bc_uploader_free(bc_ctx* ctx);
 void bc_take_free(bc_ctx* ctx);      // bc_take.hip: the two pinned index staging areas and their events
+void bc_viopt_free(bc_ctx* ctx);     // bc_viopt.hip
+// bc_take.hip: dst[j, :] = src[idx_dev[j], :] for indices that are already on the device and already checked; enqueued only
+int bc_take_rows_dev(bc_ctx* ctx, const bc_data* src, const long long* idx_dev, int64_t m, void* dst_z);
+// bc_project.hip: one gradient's projections and algebra for a Theta that is already on the device (bc_viopt.hip)
+struct bc_vi_plan;
+int bc_vi_plan_layout(int model, int32_t s, int dz, int* d, int* dk, int* nrsel, int* ntsel);
+int bc_vi_plan_create(bc_ctx* ctx, int model, const double* params, int32_t n_params, int dz, int32_t s, const double* theta_dev,
+                      const double* siginv_dev, bc_vi_plan** out);
+void bc_vi_plan_destroy(bc_vi_plan* p);
+int bc_vi_plan_step(bc_ctx* ctx, const bc_vi_plan* p, const struct bc_data* core, const struct bc_data* rows, const double* w_dev,
+                    double scale, double* resid_dev, double* grad_dev);
 
 int bc_scratch_grow(bc_ctx* ctx, bc_scratch* s, size_t doubles);   // contents are NOT kept when it grows
 

@@ -254,6 +254,54 @@ static bool model_has_y(int model) { return model == BC_MODEL_LINREG_LL || model
 // the beta-gradients of the regression models: materialising projections only (include/beta_cores_betagrad.h)
 static bool model_store_only(int model) { return model == BC_MODEL_LINREG_BETA_GRAD || model == BC_MODEL_LOGISTIC_BETA_GRAD; }
 
+// the zero-padded Theta [NRsel][dk] (and saux [NRsel]) a single pass over s samples of dimension d reads, and the K1
+// instantiation (NTsel sample tiles) that reads it
+static void theta_layout(int s, int d, bool raw, int* NTsel_out, int* NRsel_out, int* dk_out) {
+  const int nt = (s + 15) / 16;
+  static const int no_tail = getenv("BC_K1_NOTAIL") ? atoi(getenv("BC_K1_NOTAIL")) : 0;
+  const bool tail = !raw && s > 96 && s <= 100 && !no_tail;      // 6 MFMA tiles + one sample quad
+  const int NTsel = raw ? 16 : tail ? 6 : nt <= 4 ? 4 : nt <= 7 ? 7 : nt <= 13 ? 13 : 16;
+  const int NRsel = NTsel * 16 + (tail ? 4 : 0);                 // rows of the zero-padded Theta / saux
+  const int KC = NTsel <= 7 ? 32 : 16;
+  *NTsel_out = NTsel;
+  *NRsel_out = NRsel;
+  *dk_out = ((d + KC - 1) / KC) * KC;
+}
+
+// the model's constants and, where the host has evaluated them for exactly this model and these parameters, the constants of
+// the all-zero-feature rows, into the launch arguments (every plan starts here: plan_stage, bc_vi_plan_create)
+static int plan_constants(bc_ctx* ctx, int model, const double* params, int32_t n_params, int d, ProjArgs* a, const double** siginv) {
+  if (model_constants(model, params, n_params, d, a->c, siginv) != BC_OK) {
+    bc_set_error("bc_project: model %d expects a different number of parameters than %d (d = %d)", model, n_params, d);
+    return BC_INVALID_ARGUMENT;
+  }
+  if (ctx->n_const_rows > 0 && ctx->const_model == model && ctx->const_n_params == n_params &&
+      memcmp(ctx->const_params, params, (size_t)n_params * sizeof(double)) == 0) {
+    a->ck = ctx->const_rows.p;                  // host-evaluated constants for exactly this model and these parameters
+    a->cv = ctx->const_rows.p + ctx->n_const_rows;
+    a->nck = (int)ctx->n_const_rows;
+  }
+  return BC_OK;
+}
+
+// where a plan's Theta is, and what a launch needs to know of it (the tail of every plan)
+static void plan_bind(ProjPlan* pl, int model, int32_t s, int d, int dk, int NTsel, int NRsel, bool raw, const double* theta_dev,
+                      const double* siginv_dev) {
+  ProjArgs& a = pl->a;
+  a.theta = theta_dev;
+  a.saux = theta_dev + (size_t)NRsel * dk;
+  a.d = d;
+  a.dk = dk;
+  a.s = s;
+  a.model = model;
+  pl->model = model;
+  pl->s = s;
+  pl->d = d;
+  pl->ntsel = NTsel;
+  pl->raw = raw;
+  pl->siginv_dev = siginv_dev;
+}
+
 // `extra` (optional): further host arrays shipped in the same transfer (bc_vi_gradient: the coreset rows and their
 // weights); extra_dev[i] receives the device address of extra_src[i].  ONE pinned staging area, ONE device buffer, ONE
 // hipMemcpyAsync per plan: a copy call costs ~5 us of host time, a gradient step of the 1M-row configuration 350.
@@ -269,23 +317,9 @@ static int plan_stage(bc_ctx* ctx, int model, const double* theta, int32_t s, co
   a.stamps = getenv("BC_K1_STAMP_PTR") ? (unsigned long long*)strtoull(getenv("BC_K1_STAMP_PTR"), nullptr, 10) : nullptr;
 #endif
   const double* siginv = nullptr;
-  if (model_constants(model, params, n_params, d, a.c, &siginv) != BC_OK) {
-    bc_set_error("bc_project: model %d expects a different number of parameters than %d (d = %d)", model, n_params, d);
-    return BC_INVALID_ARGUMENT;
-  }
-  if (ctx->n_const_rows > 0 && ctx->const_model == model && ctx->const_n_params == n_params &&
-      memcmp(ctx->const_params, params, (size_t)n_params * sizeof(double)) == 0) {
-    a.ck = ctx->const_rows.p;                   // host-evaluated constants for exactly this model and these parameters
-    a.cv = ctx->const_rows.p + ctx->n_const_rows;
-    a.nck = (int)ctx->n_const_rows;
-  }
-  const int nt = (s + 15) / 16;
-  static const int no_tail = getenv("BC_K1_NOTAIL") ? atoi(getenv("BC_K1_NOTAIL")) : 0;
-  const bool tail = !raw && s > 96 && s <= 100 && !no_tail;      // 6 MFMA tiles + one sample quad
-  const int NTsel = raw ? 16 : tail ? 6 : nt <= 4 ? 4 : nt <= 7 ? 7 : nt <= 13 ? 13 : 16;
-  const int NRsel = NTsel * 16 + (tail ? 4 : 0);                 // rows of the zero-padded Theta / saux
-  const int KC = NTsel <= 7 ? 32 : 16;
-  const int dk = ((d + KC - 1) / KC) * KC;
+  if (plan_constants(ctx, model, params, n_params, d, &a, &siginv) != BC_OK) return BC_INVALID_ARGUMENT;
+  int NTsel, NRsel, dk;
+  theta_layout(s, d, raw, &NTsel, &NRsel, &dk);
   const size_t th_n = (size_t)NRsel * dk, sa_n = (size_t)NRsel, sg_n = siginv ? (size_t)d * d : 0;
   const size_t head_n = (th_n + sa_n + sg_n + 1) & ~(size_t)1;
   size_t total = head_n;
@@ -326,18 +360,7 @@ static int plan_stage(bc_ctx* ctx, int model, const double* theta, int32_t s, co
     off += (extra_n[i] + 1) & ~(size_t)1;
   }
   BC_HIP(hipMemcpyAsync(ctx->proj_theta.p, ctx->proj_pinned, total * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  a.theta = ctx->proj_theta.p;
-  a.saux = ctx->proj_theta.p + th_n;
-  a.d = d;
-  a.dk = dk;
-  a.s = s;
-  a.model = model;
-  pl->model = model;
-  pl->s = s;
-  pl->d = d;
-  pl->ntsel = NTsel;
-  pl->raw = raw;
-  pl->siginv_dev = siginv ? ctx->proj_theta.p + th_n + sa_n : nullptr;
+  plan_bind(pl, model, s, d, dk, NTsel, NRsel, raw, ctx->proj_theta.p, siginv ? ctx->proj_theta.p + th_n + sa_n : nullptr);      // (th_n = NRsel * dk)
   return BC_OK;
 }
 
@@ -1064,5 +1087,61 @@ extern "C" int bc_ctx_phase_times(bc_ctx* ctx, double* out_ms, int32_t n, int64_
     for (auto& v : ctx->vi_phase_ms) v = 0.;
     ctx->vi_calls_timed = 0;
   }
+  return BC_OK;
+}
+
+// ------------------------------------------------------------------ bc_viopt.hip's way into the projection
+// The steps 2 and 4-6 of one gradient (include/beta_cores_viopt.h) for a Theta that is ALREADY on the device -- k_vi_sampler
+// has written it there in the zero-padded layout the plan describes -- enqueued on ctx->stream without any host wait.
+struct bc_vi_plan {
+  ProjPlan pl;
+};
+
+int bc_vi_plan_layout(int model, int32_t s, int dz, int* d, int* dk, int* nrsel, int* ntsel) {
+  *d = dz - (model_has_y(model) ? 1 : 0);
+  if (*d <= 0 || s <= 0 || s > 256) return BC_INVALID_ARGUMENT;
+  theta_layout(s, *d, false, ntsel, nrsel, dk);
+  return BC_OK;
+}
+
+// theta_dev: [nrsel][dk] | saux [nrsel], zero outside the s x d block the sampler writes.  siginv_dev: the Gaussian models' Siginv.
+int bc_vi_plan_create(bc_ctx* ctx, int model, const double* params, int32_t n_params, int dz, int32_t s, const double* theta_dev,
+                      const double* siginv_dev, bc_vi_plan** out) {
+  if (model < 0 || model > BC_MODEL_LOGISTIC_BETA_GRAD || model_store_only(model)) {
+    bc_set_error("bc_vi_optimize: model %d has no store-free projection", model);
+    return BC_INVALID_ARGUMENT;
+  }
+  int d, dk, nrsel, ntsel;
+  if (bc_vi_plan_layout(model, s, dz, &d, &dk, &nrsel, &ntsel) != BC_OK) { bc_set_error("bc_vi_optimize: bad shape (S = %d, dz = %d)", s, dz); return BC_INVALID_ARGUMENT; }
+  bc_vi_plan* p = new bc_vi_plan();
+  memset(&p->pl.a, 0, sizeof(p->pl.a));
+  const double* siginv = nullptr;
+  if (plan_constants(ctx, model, params, n_params, d, &p->pl.a, &siginv) != BC_OK) { delete p; return BC_INVALID_ARGUMENT; }
+  if ((siginv != nullptr) != (siginv_dev != nullptr)) { bc_set_error("bc_vi_optimize: internal: Siginv"); delete p; return BC_INVALID_ARGUMENT; }
+  plan_bind(&p->pl, model, s, d, dk, ntsel, nrsel, false, theta_dev, siginv_dev);
+  *out = p;
+  return BC_OK;
+}
+
+void bc_vi_plan_destroy(bc_vi_plan* p) { delete p; }
+
+// resid = scale * colsum(K1(rows)) - w . K1(core), grad = -K1(core) . resid / S: everything on ctx->stream, nothing waited for
+int bc_vi_plan_step(bc_ctx* ctx, const bc_vi_plan* p, const bc_data* core, const bc_data* rows, const double* w_dev, double scale,
+                    double* resid_dev, double* grad_dev) {
+  const ProjPlan& pl = p->pl;
+  const int32_t s = pl.s;
+  bc_phi *cphi = nullptr, *phi = nullptr;
+  int rc = core_phi_for(ctx, &ctx->core_phi, core->n_rows, s, &cphi);
+  if (!rc) rc = colsum_phi_for(ctx, rows->n_rows, s, &phi);
+  const int saved_timing = ctx->timing;
+  ctx->timing = 0;                      // (no K1 samples of the kernel timer from inside the loop)
+  if (!rc) rc = plan_launch(ctx, pl, core, cphi, PROJ_FULL, s, 0, &ctx->proj_rowaux);
+  if (!rc) rc = plan_launch(ctx, pl, rows, phi, PROJ_COLSUM, s, 0, &ctx->proj_rowaux2);
+  ctx->timing = saved_timing;
+  if (!rc) rc = bc_phi_reduce_colsum(phi);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_vi_gradient, dim3(1), dim3(256), (size_t)s * sizeof(double), ctx->stream, phi->colsum, cphi->tiles, w_dev,
+                     (int)core->n_rows, s, scale, resid_dev, grad_dev);
+  BC_HIP(hipGetLastError());
   return BC_OK;
 }

@@ -115,6 +115,19 @@ void bc_take_free(bc_ctx* ctx) {
   }
 }
 
+// the launch alone: indices already on the device and already checked (take_enqueue below; bc_viopt.hip, once per step)
+int bc_take_rows_dev(bc_ctx* ctx, const bc_data* src, const long long* idx_dev, int64_t m, void* dst_z) {
+  const size_t pitch = (size_t)src->dz * (size_t)src->elem;
+  const int w = bc_take_word_bytes((uint64_t)(uintptr_t)src->z, (uint64_t)(uintptr_t)dst_z, src->dz, src->elem);
+  const bool flat = bc_take_flat(src->dz, src->elem) != 0;
+  hipError_t e;
+  if (w == 16) e = launch_take<uint4>(ctx, src->z, idx_dev, m, (int64_t)(pitch / 16), flat, dst_z);
+  else if (w == 8) e = launch_take<uint2>(ctx, src->z, idx_dev, m, (int64_t)(pitch / 8), flat, dst_z);
+  else e = launch_take<unsigned>(ctx, src->z, idx_dev, m, (int64_t)(pitch / 4), flat, dst_z);
+  if (e != hipSuccess) return bc_hip_fail(e, "k_take_rows", __FILE__, __LINE__);
+  return BC_OK;
+}
+
 // The indices (host, borrowed) -> one of two pinned staging areas of the context -> a device scratch buffer (all grow-only),
 // then the launch into dst_z.  `idx` has been read when this returns.  The staging areas take turns, so the only host wait
 // is for the index copy of the call BEFORE the previous one (an event): back-to-back takes do not block on each other.
@@ -138,15 +151,7 @@ static int take_enqueue(bc_ctx* ctx, const bc_data* src, const int64_t* idx, int
   BC_HIP(hipMemcpyAsync(didx, stage, (size_t)m * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
   BC_HIP(hipEventRecord(ctx->take_ev[h], ctx->stream));
   ctx->take_turn = h ^ 1;
-  const size_t pitch = (size_t)src->dz * (size_t)src->elem;
-  const int w = bc_take_word_bytes((uint64_t)(uintptr_t)src->z, (uint64_t)(uintptr_t)dst_z, src->dz, src->elem);
-  const bool flat = bc_take_flat(src->dz, src->elem) != 0;
-  hipError_t e;
-  if (w == 16) e = launch_take<uint4>(ctx, src->z, didx, m, (int64_t)(pitch / 16), flat, dst_z);
-  else if (w == 8) e = launch_take<uint2>(ctx, src->z, didx, m, (int64_t)(pitch / 8), flat, dst_z);
-  else e = launch_take<unsigned>(ctx, src->z, didx, m, (int64_t)(pitch / 4), flat, dst_z);
-  if (e != hipSuccess) return bc_hip_fail(e, "k_take_rows", __FILE__, __LINE__);
-  return BC_OK;
+  return bc_take_rows_dev(ctx, src, didx, m, dst_z);
 }
 
 extern "C" int bc_data_take_rows(const bc_data* src, const int64_t* idx, int64_t m, bc_data** inout) {

@@ -1,0 +1,401 @@
+// The weight optimisation of the greedy variational coresets as runs of steps enqueued on the device
+// (include/beta_cores_viopt.h): k_vi_sampler (the posterior draw: bc_vi_sampler_dev.h), k_vi_adam (util/opt.py's nn_opt), and
+// the entry points that chain them with the projections of bc_project.hip and the row gather of bc_take.hip.
+//
+// Nothing here waits for the device except bc_vi_optimize_chunk_end (once per chunk) and the buffer (re)allocations of a run's
+// first chunk.  The weights, both ADAM moments and the abort mark live in device memory for the whole run.
+#include "bc_internal.h"
+#include "bc_vi_sampler_dev.h"
+#include "../../include/beta_cores_viopt.h"
+#include <cmath>
+#include <cstring>
+
+#define BC_VIS_BLOCK 512
+
+// One block.  `flag` != 0: an earlier step of this run met a bad pivot; this launch (and every one behind it) does nothing.
+__global__ __launch_bounds__(BC_VIS_BLOCK) void k_vi_sampler(VisArgs a, int* __restrict__ flag, int step) {
+  extern __shared__ double vis_ws[];
+  if (*(volatile int*)flag != 0) return;      // (block-uniform)
+  if (bc_vi_sampler(a, vis_ws) && threadIdx.x == 0) *flag = step + 1;
+}
+
+// step[0][i] = step_sched(i), step[1][i] = 1 - b1^(i+1), step[2][i] = 1 - b2^(i+1).  trace: [itrs][m] or null.
+__global__ __launch_bounds__(256) void k_vi_adam(const int* __restrict__ flag, const double* __restrict__ g, double* __restrict__ w,
+                                                 double* __restrict__ mom1, double* __restrict__ mom2, int m, const double* __restrict__ step,
+                                                 int itrs, int i, double b1, double omb1, double b2, double omb2, double eps,
+                                                 double* __restrict__ trace) {
+  if (*(volatile const int*)flag != 0) return;
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  double x = w[j], m1 = mom1[j], m2 = mom2[j];
+  bc_vi_adam_elem(g[j], &x, &m1, &m2, b1, omb1, b2, omb2, eps, step[i], step[itrs + i], step[2 * itrs + i]);
+  w[j] = x;
+  mom1[j] = m1;
+  mom2[j] = m2;
+  if (trace) trace[(size_t)i * m + j] = x;
+}
+
+struct bc_viopt {
+  double* dev = nullptr;          // one slab: what _begin uploads, then the run's device-only state
+  size_t dev_cap = 0;             // doubles
+  double* pin = nullptr;          // pinned mirror of the uploaded head; later the landing area of w | trace | flag
+  size_t pin_cap = 0;
+  double* stage_dev = nullptr;    // a chunk's draws: normals [k][S][D], then indices [k][n_sub]
+  double* stage_pin = nullptr;
+  size_t stage_cap = 0;           // doubles (an index takes one)
+  void* sub = nullptr;            // the step's sub-sample of the data rows
+  size_t sub_cap = 0;             // bytes
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  bc_vi_plan* plan = nullptr;
+  // the run in progress
+  bool active = false, chunk_pending = false, failed = false, lds_set = false;
+  const bc_data* data = nullptr;
+  bc_data core_view, sub_view;
+  VisArgs va;
+  int64_t m = 0, n_sub = 0;
+  int32_t s = 0, itrs = 0, done = 0;
+  int d = 0, dz = 0;
+  double scale = 1., dev_ms = 0.;
+  double *d_w = nullptr, *d_mom1 = nullptr, *d_mom2 = nullptr, *d_grad = nullptr, *d_resid = nullptr, *d_step = nullptr, *d_trace = nullptr;
+  int* d_flag = nullptr;
+};
+
+void bc_viopt_free(bc_ctx* ctx) {
+  bc_viopt* v = ctx->viopt;
+  if (!v) return;
+  if (v->dev) (void)hipFree(v->dev);
+  if (v->pin) (void)hipHostFree(v->pin);
+  if (v->stage_dev) (void)hipFree(v->stage_dev);
+  if (v->stage_pin) (void)hipHostFree(v->stage_pin);
+  if (v->sub) (void)hipFree(v->sub);
+  for (auto& e : v->ev)
+    if (e) (void)hipEventDestroy(e);
+  bc_vi_plan_destroy(v->plan);
+  delete v;
+  ctx->viopt = nullptr;
+}
+
+extern "C" int bc_vi_optimize_auto_chunk(int32_t s, int32_t d, int64_t n_sub) {
+  if (s <= 0 || d <= 0 || n_sub < 0) return 1;
+  const double per_step = 8. * ((double)s * (double)d + (double)n_sub);
+  const double k = floor((double)BC_VI_STAGE_BYTES / per_step);
+  return k < 1. ? 1 : k > 1048576. ? 1048576 : (int)k;
+}
+
+// grow-only pairs; only called while nothing of this module is enqueued
+static int grow_dev(bc_ctx* ctx, double** p, size_t* cap, size_t need) {
+  if (need <= *cap) return BC_OK;
+  BC_HIP(hipStreamSynchronize(ctx->stream));
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  const size_t want = need + need / 2;
+  BC_HIP(hipMalloc((void**)p, want * sizeof(double)));
+  *cap = want;
+  return BC_OK;
+}
+
+static int grow_pin(bc_ctx* ctx, double** p, size_t* cap, size_t need) {
+  if (need <= *cap) return BC_OK;
+  BC_HIP(hipStreamSynchronize(ctx->stream));
+  if (*p) (void)hipHostFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  const size_t want = need + need / 2;
+  BC_HIP(hipHostMalloc((void**)p, want * sizeof(double), hipHostMallocDefault));
+  *cap = want;
+  return BC_OK;
+}
+
+static size_t even(size_t n) { return (n + 1) & ~(size_t)1; }      // 16-byte aligned pieces
+
+extern "C" int bc_vi_optimize_begin(bc_ctx* ctx, const bc_data* data, const double* core_rows, int64_t m, int model, const double* params,
+                                    int32_t n_params, int sampler_kind, const double* sampler_params, int32_t s, const double* w0,
+                                    int32_t opt_itrs, const double* step, int64_t n_sub, double sum_scaling, int want_trace) {
+  if (!ctx || !data || !core_rows || !w0 || !step || !sampler_params || (n_params > 0 && !params) || n_params < 0) {
+    bc_set_error("bc_vi_optimize_begin: bad argument");
+    return BC_INVALID_ARGUMENT;
+  }
+  if (data->ctx != ctx) { bc_set_error("bc_vi_optimize_begin: data belongs to another context"); return BC_INVALID_ARGUMENT; }
+  if (m <= 0 || opt_itrs <= 0 || n_sub < 0 || s <= 0 || s > 256) {
+    bc_set_error("bc_vi_optimize_begin: needs m > 0 coreset rows, opt_itrs > 0, n_sub >= 0 and 1 <= S <= 256 (m = %lld, opt_itrs = %d, n_sub = %lld, S = %d)",
+                 (long long)m, opt_itrs, (long long)n_sub, s);
+    return BC_INVALID_ARGUMENT;
+  }
+  if (sampler_kind != BC_VI_SAMPLER_LINREG && sampler_kind != BC_VI_SAMPLER_GAUSS) {
+    bc_set_error("bc_vi_optimize_begin: unknown sampler kind %d", sampler_kind);
+    return BC_INVALID_ARGUMENT;
+  }
+  const bool gauss = sampler_kind == BC_VI_SAMPLER_GAUSS;
+  const bool model_ok = gauss ? (model == BC_MODEL_GAUSS_LL || model == BC_MODEL_GAUSS_BETA)
+                              : (model == BC_MODEL_LINREG_LL || model == BC_MODEL_LINREG_BETA);
+  if (!model_ok) { bc_set_error("bc_vi_optimize_begin: model %d does not go with sampler kind %d", model, sampler_kind); return BC_INVALID_ARGUMENT; }
+  if (ctx->vi_pending_m > 0) { bc_set_error("bc_vi_optimize_begin: a bc_vi_gradient is pending on this context"); return BC_INVALID_ARGUMENT; }
+  const int dz = data->dz;
+  int d = 0, dk = 0, nrsel = 0, ntsel = 0;
+  if (bc_vi_plan_layout(model, s, dz, &d, &dk, &nrsel, &ntsel) != BC_OK || d > BC_VI_MAX_DIM) {
+    bc_set_error("bc_vi_optimize_begin: D = %d is outside 1..%d", d, BC_VI_MAX_DIM);
+    return BC_INVALID_ARGUMENT;
+  }
+  if ((size_t)m * (size_t)(dz + 1) > 60000) {
+    bc_set_error("bc_vi_optimize_begin: coreset of %lld rows x %d exceeds the staging area", (long long)m, dz);
+    return BC_INVALID_ARGUMENT;
+  }
+  const size_t lds = (size_t)BC_VIS_WS_DOUBLES(d) * sizeof(double);
+  if (lds > (size_t)ctx->max_lds) {
+    bc_set_error("bc_vi_optimize_begin: D = %d needs %zu bytes of LDS, the device offers %d", d, lds, ctx->max_lds);
+    return BC_INVALID_ARGUMENT;
+  }
+  bc_viopt* v = ctx->viopt;
+  if (!v) v = ctx->viopt = new bc_viopt();
+  if (v->active) { bc_set_error("bc_vi_optimize_begin: a run is already open on this context (call bc_vi_optimize_end first)"); return BC_INVALID_ARGUMENT; }
+  BC_HIP(hipSetDevice(ctx->device));
+  if (!v->lds_set) {
+    BC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vi_sampler), hipFuncAttributeMaxDynamicSharedMemorySize, ctx->max_lds));
+    v->lds_set = true;
+  }
+  for (auto& e : v->ev)
+    if (!e) BC_HIP(hipEventCreate(&e));
+  // ---- the slab: [uploaded head] core | w | step | Sig0inv | b0 | Siginv   [device-only] mom1 | mom2 | grad | resid | Theta, saux |
+  //      raw | trace | flag
+  const size_t dd = (size_t)d * d;
+  const size_t o_core = 0, o_w = o_core + even((size_t)m * dz), o_step = o_w + even((size_t)m), o_s0 = o_step + even(3 * (size_t)opt_itrs);
+  const size_t o_b0 = o_s0 + even(dd), o_sg = o_b0 + even((size_t)d), head = o_sg + (gauss ? even(dd) : 0);
+  const size_t o_m1 = head, o_m2 = o_m1 + even((size_t)m), o_g = o_m2 + even((size_t)m), o_r = o_g + even((size_t)m);
+  const size_t o_th = o_r + even((size_t)s), o_raw = o_th + even((size_t)nrsel * dk + nrsel), o_tr = o_raw + even((size_t)s * d);
+  const size_t o_flag = o_tr + (want_trace ? even((size_t)opt_itrs * m) : 0), total = o_flag + 2;
+  int rc = grow_dev(ctx, &v->dev, &v->dev_cap, total);
+  const size_t down = even((size_t)m) + (want_trace ? even((size_t)opt_itrs * m) : 0) + 2;
+  if (!rc) rc = grow_pin(ctx, &v->pin, &v->pin_cap, head > down ? head : down);
+  if (rc) return rc;
+  BC_HIP(hipStreamSynchronize(ctx->stream));      // nothing enqueued earlier still reads the slab or the pinned area
+  double* h = v->pin;
+  memset(h, 0, head * sizeof(double));
+  memcpy(h + o_core, core_rows, (size_t)m * dz * sizeof(double));
+  memcpy(h + o_w, w0, (size_t)m * sizeof(double));
+  memcpy(h + o_step, step, 3 * (size_t)opt_itrs * sizeof(double));
+  const double* th0 = sampler_params;
+  const double* sig0inv = sampler_params + d;
+  memcpy(h + o_s0, sig0inv, dd * sizeof(double));
+  for (int i = 0; i < d; ++i) {      // Sig0inv . th0
+    double acc = 0.;
+    for (int j = 0; j < d; ++j) acc = fma(sig0inv[(size_t)i * d + j], th0[j], acc);
+    h[o_b0 + i] = acc;
+  }
+  double sigsq = 1.;
+  if (gauss) memcpy(h + o_sg, sampler_params + d + dd, dd * sizeof(double));
+  else sigsq = sampler_params[d + dd];
+  BC_HIP(hipMemcpyAsync(v->dev, h, head * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  BC_HIP(hipMemsetAsync(v->dev + head, 0, (total - head) * sizeof(double), ctx->stream));
+  bc_vi_plan_destroy(v->plan);
+  v->plan = nullptr;
+  rc = bc_vi_plan_create(ctx, model, params, n_params, dz, s, v->dev + o_th, gauss ? v->dev + o_sg : nullptr, &v->plan);
+  if (rc) return rc;
+  if (n_sub > 0) {
+    const size_t need = (size_t)n_sub * dz * data->elem;
+    if (need > v->sub_cap) {
+      if (v->sub) (void)hipFree(v->sub);
+      v->sub = nullptr;
+      v->sub_cap = 0;
+      BC_HIP(hipMalloc(&v->sub, need + need / 2));
+      v->sub_cap = need + need / 2;
+    }
+  }
+  v->data = data;
+  v->core_view = bc_data();
+  v->core_view.ctx = ctx;
+  v->core_view.n_rows = m;
+  v->core_view.dz = dz;
+  v->core_view.z = v->dev + o_core;
+  v->core_view.owned = false;
+  v->sub_view = bc_data();
+  v->sub_view.ctx = ctx;
+  v->sub_view.n_rows = n_sub;
+  v->sub_view.dz = dz;
+  v->sub_view.z = reinterpret_cast<double*>(v->sub);
+  v->sub_view.owned = false;
+  v->sub_view.elem = data->elem;
+  VisArgs& a = v->va;
+  a.kind = gauss ? BC_VIS_GAUSS : BC_VIS_LINREG;
+  a.d = d;
+  a.m = (int)m;
+  a.dz = dz;
+  a.s = s;
+  a.dk = dk;
+  a.core = v->dev + o_core;
+  a.w = v->dev + o_w;
+  a.sig0inv = v->dev + o_s0;
+  a.b0 = v->dev + o_b0;
+  a.siginv = gauss ? v->dev + o_sg : nullptr;
+  a.sigsq = sigsq;
+  a.E = nullptr;
+  a.theta = v->dev + o_th;
+  a.saux = v->dev + o_th + (size_t)nrsel * dk;
+  a.raw = v->dev + o_raw;
+  v->m = m;
+  v->n_sub = n_sub;
+  v->s = s;
+  v->itrs = opt_itrs;
+  v->done = 0;
+  v->d = d;
+  v->dz = dz;
+  v->scale = sum_scaling;
+  v->dev_ms = 0.;
+  v->d_w = v->dev + o_w;
+  v->d_step = v->dev + o_step;
+  v->d_mom1 = v->dev + o_m1;
+  v->d_mom2 = v->dev + o_m2;
+  v->d_grad = v->dev + o_g;
+  v->d_resid = v->dev + o_r;
+  v->d_trace = want_trace ? v->dev + o_tr : nullptr;
+  v->d_flag = reinterpret_cast<int*>(v->dev + o_flag);
+  v->active = true;
+  v->chunk_pending = false;
+  v->failed = false;
+  return BC_OK;
+}
+
+extern "C" int bc_vi_optimize_chunk_begin(bc_ctx* ctx, const double* normals, const int64_t* sub_idx, int32_t k) {
+  bc_viopt* v = ctx ? ctx->viopt : nullptr;
+  if (!v || !v->active || !normals || k <= 0) { bc_set_error("bc_vi_optimize_chunk_begin: bad argument, or no run is open"); return BC_INVALID_ARGUMENT; }
+  if (v->chunk_pending) { bc_set_error("bc_vi_optimize_chunk_begin: a chunk is pending (call bc_vi_optimize_chunk_end first)"); return BC_INVALID_ARGUMENT; }
+  if (v->failed) { bc_set_error("bc_vi_optimize_chunk_begin: the run has failed (call bc_vi_optimize_end)"); return BC_INVALID_ARGUMENT; }
+  if (v->done + (int64_t)k > v->itrs) {
+    bc_set_error("bc_vi_optimize_chunk_begin: %d steps after %d exceed the run's %d", k, v->done, v->itrs);
+    return BC_INVALID_ARGUMENT;
+  }
+  const int64_t n_sub = v->n_sub;
+  if ((n_sub > 0) != (sub_idx != nullptr)) { bc_set_error("bc_vi_optimize_chunk_begin: sub_idx must be given exactly when n_sub > 0"); return BC_INVALID_ARGUMENT; }
+  const size_t n_idx = (size_t)k * (size_t)n_sub, n_e = (size_t)k * (size_t)v->s * (size_t)v->d;
+  for (size_t j = 0; j < n_idx; ++j)
+    if (sub_idx[j] < 0 || sub_idx[j] >= v->data->n_rows) {
+      bc_set_error("bc_vi_optimize_chunk_begin: index %lld (step %lld, position %lld) out of range [0,%lld)", (long long)sub_idx[j],
+                   (long long)(v->done + (int64_t)(j / (size_t)n_sub)), (long long)(j % (size_t)n_sub), (long long)v->data->n_rows);
+      return BC_INVALID_ARGUMENT;
+    }
+  // ---- nothing of this chunk has been enqueued up to here
+  BC_HIP(hipSetDevice(ctx->device));
+  const size_t need = even(n_e) + n_idx;
+  if (need > v->stage_cap) {
+    size_t c1 = v->stage_cap, c2 = v->stage_cap;
+    int rc = grow_dev(ctx, &v->stage_dev, &c1, need);
+    if (!rc) rc = grow_pin(ctx, &v->stage_pin, &c2, need);
+    if (rc) { v->stage_cap = 0; return rc; }
+    v->stage_cap = c1 < c2 ? c1 : c2;
+  }
+  memcpy(v->stage_pin, normals, n_e * sizeof(double));
+  long long* hidx = reinterpret_cast<long long*>(v->stage_pin + even(n_e));
+  for (size_t j = 0; j < n_idx; ++j) hidx[j] = (long long)sub_idx[j];
+  BC_HIP(hipMemcpyAsync(v->stage_dev, v->stage_pin, need * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  const long long* didx = reinterpret_cast<const long long*>(v->stage_dev + even(n_e));
+  BC_HIP(hipEventRecord(v->ev[0], ctx->stream));
+  v->chunk_pending = true;      // from here on something is enqueued: _chunk_end must wait even if a launch below fails
+  const double b1 = 0.9, b2 = 0.999, eps = 1e-8;
+  const size_t lds = (size_t)BC_VIS_WS_DOUBLES(v->d) * sizeof(double);
+  const int m = (int)v->m;
+  for (int t = 0; t < k; ++t) {
+    const int i = v->done + t;
+    VisArgs a = v->va;
+    a.E = v->stage_dev + (size_t)t * v->s * v->d;
+    hipLaunchKernelGGL(k_vi_sampler, dim3(1), dim3(BC_VIS_BLOCK), lds, ctx->stream, a, v->d_flag, i);
+    BC_HIP(hipGetLastError());
+    const bc_data* rows = v->data;
+    if (n_sub > 0) {
+      int rc = bc_take_rows_dev(ctx, v->data, didx + (size_t)t * n_sub, n_sub, v->sub);
+      if (rc) return rc;
+      rows = &v->sub_view;
+    }
+    int rc = bc_vi_plan_step(ctx, v->plan, &v->core_view, rows, v->d_w, v->scale, v->d_resid, v->d_grad);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_vi_adam, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, v->d_flag, v->d_grad, v->d_w, v->d_mom1,
+                       v->d_mom2, m, v->d_step, (int)v->itrs, i, b1, 1. - b1, b2, 1. - b2, eps, v->d_trace);
+    BC_HIP(hipGetLastError());
+  }
+  BC_HIP(hipEventRecord(v->ev[1], ctx->stream));
+  v->done += k;
+  return BC_OK;
+}
+
+extern "C" int bc_vi_optimize_chunk_end(bc_ctx* ctx) {
+  bc_viopt* v = ctx ? ctx->viopt : nullptr;
+  if (!v || !v->active || !v->chunk_pending) { bc_set_error("bc_vi_optimize_chunk_end: no chunk is pending"); return BC_INVALID_ARGUMENT; }
+  v->chunk_pending = false;
+  BC_HIP(hipSetDevice(ctx->device));
+  int* hflag = reinterpret_cast<int*>(v->pin + v->pin_cap - 2);
+  BC_HIP(hipMemcpyAsync(hflag, v->d_flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  BC_HIP(hipStreamSynchronize(ctx->stream));
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, v->ev[0], v->ev[1]) == hipSuccess) v->dev_ms += ms;
+  if (*hflag != 0) {
+    v->failed = true;
+    bc_set_error("bc_vi_optimize: step %d: the posterior precision matrix of the weighted coreset is not positive definite "
+                 "(a pivot of its Cholesky factorisation is not finite and positive)", *hflag - 1);
+    return BC_NUMERICAL_PRECISION;
+  }
+  return BC_OK;
+}
+
+extern "C" int bc_vi_optimize_end(bc_ctx* ctx, double* out_w, double* out_trace) {
+  bc_viopt* v = ctx ? ctx->viopt : nullptr;
+  if (!v || !v->active) { bc_set_error("bc_vi_optimize_end: no run is open"); return BC_INVALID_ARGUMENT; }
+  BC_HIP(hipSetDevice(ctx->device));
+  const bool pending = v->chunk_pending;
+  v->active = false;
+  v->chunk_pending = false;
+  v->data = nullptr;
+  if (pending) BC_HIP(hipStreamSynchronize(ctx->stream));      // abandoned mid-chunk: nothing may outlive the run's buffers
+  if (!out_w) return BC_OK;
+  if (v->failed || pending || v->done != v->itrs) {
+    bc_set_error("bc_vi_optimize_end: the run is not complete (%d of %d steps%s): no weights", v->done, v->itrs, v->failed ? ", failed" : "");
+    return BC_INVALID_ARGUMENT;
+  }
+  if (out_trace && !v->d_trace) { bc_set_error("bc_vi_optimize_end: the run was begun without a trace"); return BC_INVALID_ARGUMENT; }
+  const size_t m = (size_t)v->m;
+  BC_HIP(hipMemcpyAsync(v->pin, v->d_w, m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (out_trace) BC_HIP(hipMemcpyAsync(v->pin + even(m), v->d_trace, (size_t)v->itrs * m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  BC_HIP(hipStreamSynchronize(ctx->stream));
+  memcpy(out_w, v->pin, m * sizeof(double));
+  if (out_trace) memcpy(out_trace, v->pin + even(m), (size_t)v->itrs * m * sizeof(double));
+  return BC_OK;
+}
+
+extern "C" int bc_vi_optimize_device_ms(bc_ctx* ctx, double* out_ms) {
+  if (!ctx || !out_ms) { bc_set_error("bc_vi_optimize_device_ms: bad argument"); return BC_INVALID_ARGUMENT; }
+  *out_ms = ctx->viopt ? ctx->viopt->dev_ms : 0.;
+  return BC_OK;
+}
+
+extern "C" int bc_vi_optimize(bc_ctx* ctx, const bc_data* data, const double* core_rows, int64_t m, int model, const double* params,
+                              int32_t n_params, int sampler_kind, const double* sampler_params, int32_t s, const double* w0,
+                              int32_t opt_itrs, const double* step, const double* normals, const int64_t* sub_idx, int64_t n_sub,
+                              double sum_scaling, int32_t chunk_steps, double* out_w, double* out_trace) {
+  if (!out_w || !normals || chunk_steps < 0) { bc_set_error("bc_vi_optimize: bad argument"); return BC_INVALID_ARGUMENT; }
+  if (!ctx || !data || n_sub < 0 || (n_sub > 0) != (sub_idx != nullptr)) { bc_set_error("bc_vi_optimize: bad argument"); return BC_INVALID_ARGUMENT; }
+  // every index is checked before anything is enqueued (the chunks check theirs again, which costs nothing next to a step)
+  for (size_t j = 0; j < (size_t)(opt_itrs > 0 ? opt_itrs : 0) * (size_t)n_sub; ++j)
+    if (sub_idx[j] < 0 || sub_idx[j] >= data->n_rows) {
+      bc_set_error("bc_vi_optimize: index %lld (step %lld, position %lld) out of range [0,%lld)", (long long)sub_idx[j],
+                   (long long)(j / (size_t)n_sub), (long long)(j % (size_t)n_sub), (long long)data->n_rows);
+      return BC_INVALID_ARGUMENT;
+    }
+  int rc = bc_vi_optimize_begin(ctx, data, core_rows, m, model, params, n_params, sampler_kind, sampler_params, s, w0, opt_itrs, step,
+                                n_sub, sum_scaling, out_trace != nullptr);
+  if (rc) return rc;
+  const int d = ctx->viopt->d;
+  const int chunk = chunk_steps > 0 ? chunk_steps : bc_vi_optimize_auto_chunk(s, d, n_sub);
+  for (int32_t i0 = 0; i0 < opt_itrs && !rc; i0 += chunk) {
+    const int32_t k = opt_itrs - i0 < chunk ? opt_itrs - i0 : chunk;
+    rc = bc_vi_optimize_chunk_begin(ctx, normals + (size_t)i0 * s * d, sub_idx ? sub_idx + (size_t)i0 * n_sub : nullptr, k);
+    if (ctx->viopt->chunk_pending) {
+      const int rc2 = bc_vi_optimize_chunk_end(ctx);
+      if (!rc) rc = rc2;
+    }
+  }
+  if (rc) {
+    const std::string msg = bc_last_error();      // (closing the run must not replace the message of what failed)
+    (void)bc_vi_optimize_end(ctx, nullptr, nullptr);
+    bc_set_error("%s", msg.c_str());
+    return rc;
+  }
+  return bc_vi_optimize_end(ctx, out_w, out_trace);
+}

@@ -76,6 +76,11 @@ class LinregPosteriorSampler(_PosteriorSampler):
         muw, LSigw, _ = weighted_post(self.th0, self.Sig0inv, self.sigsq, pts, wts, ctx=self.ctx)
         return muw + self._normals(n, d).dot(LSigw.T)
 
+    def device_spec(self):
+        """(sampler kind, parameters) as bc_vi_optimize takes them (include/beta_cores_viopt.h): th0 | Sig0inv | sigsq.  A
+        sampler with this method can be evaluated by k_vi_sampler; its normals still come from `_normals`, on the host."""
+        return 0, np.concatenate((self.th0, self.Sig0inv.ravel(), [self.sigsq]))
+
 
 class GaussianPosteriorSampler(_PosteriorSampler):
     """The Gaussian location model's `sampler_w` (zellner_gaussian/main.py:90-95, gaussian.py:28-32)."""
@@ -95,6 +100,10 @@ class GaussianPosteriorSampler(_PosteriorSampler):
             wts, pts = np.zeros(1), np.zeros((1, d))
         muw, LSigw, _ = gaussian_weighted_post(self.mu0, self.Sig0inv, self.Siginv, pts, wts, ctx=self.ctx)
         return muw + self._normals(n, d).dot(LSigw.T)
+
+    def device_spec(self):
+        """(sampler kind, parameters) as bc_vi_optimize takes them: mu0 | Sig0inv | Siginv (see LinregPosteriorSampler)."""
+        return 1, np.concatenate((self.mu0, self.Sig0inv.ravel(), self.Siginv.ravel()))
 
 
 # ---- logistic regression: Laplace approximation around the mode of the weighted log-joint (<= M coreset rows: host work

@@ -21,6 +21,13 @@ def _adam_loop(x0, grd, opt_itrs, step_sched, b1, b2, eps, project):
     return x
 
 
+def adam_step_arrays(opt_itrs, step_sched, b1=0.9, b2=0.999):
+    """What the device form of nn_opt (bc_vi_optimize's k_vi_adam) takes instead of evaluating them itself, as a 3 x opt_itrs
+    array: step_sched(i), 1 - b1**(i+1) and 1 - b2**(i+1) exactly as _adam_loop evaluates them (Python float arithmetic)."""
+    return np.array([[step_sched(i) for i in range(opt_itrs)], [1. - b1 ** (i + 1) for i in range(opt_itrs)],
+                     [1. - b2 ** (i + 1) for i in range(opt_itrs)]], dtype=np.float64).reshape(3, opt_itrs)
+
+
 def nn_opt(x0, grd, opt_itrs=1000, step_sched=lambda i: 1. / (i + 1), b1=0.9, b2=0.999, eps=1e-8, verbose=False):
     """x <- max(x - upd, 0) on every coordinate (opt.py:36-54)."""
     return _adam_loop(x0, grd, opt_itrs, step_sched, b1, b2, eps, lambda x: np.maximum(x, 0.))

@@ -26,10 +26,15 @@ def gaussian_KL(mu0, Sig0, mu1, Sig1inv):
 
 
 def run(nm='BCORES', tr=1, N=5000, d=50, M=40, opt_itrs=200, n_subsample_opt=200, n_subsample_select=1000, proj_dim=200,
-        pihat_noise=0.75, i0=0.1, verbose=True):
+        pihat_noise=0.75, i0=0.1, verbose=True, device_optimize=False):
     """One trial of the experiment.  Statement order follows the reference script (main.py:15-108), so with the same
     seed the global NumPy RNG stream -- data, the four projectors' constructor draws, the noise of the 'realistic'
-    tangent space -- is the script's.  Returns dict(w, p, idcs (per m = 0..M), rkl, fkl, Xc)."""
+    tangent space -- is the script's.  Returns dict(w, p, idcs (per m = 0..M), rkl, fkl, Xc).
+
+    `device_optimize=True` (BCORES, SVI): the weight optimisation after every selected point runs on the device
+    (bc_vi_optimize).  That takes a sampler the device can evaluate -- bc.samplers.GaussianPosteriorSampler, the same
+    expression and the same draws from the global stream as the closure below -- and resident rows, so Xc is pinned on the two
+    weighted projectors (and is read-only from then on).  Same selections and RNG stream, weights equal to rounding."""
     np.random.seed(tr)
     mu0, Sig0 = np.zeros(d), np.eye(d)
     Sig = 500 * np.eye(d)
@@ -63,16 +68,21 @@ def run(nm='BCORES', tr=1, N=5000, d=50, M=40, opt_itrs=200, n_subsample_opt=200
         muw, LSigw, _ = bc.gaussian_weighted_post(mu0, Sig0inv, Siginv, pts, wts)
         return muw + np.random.randn(sz, muw.shape[0]).dot(LSigw.T)
 
+    if device_optimize:
+        sampler_w = bc.samplers.GaussianPosteriorSampler(mu0, Sig0inv, Siginv)
     prj_w = bc.DeviceProjector(sampler_w, proj_dim, model)
     prj_bw = bc.DeviceBetaProjector(sampler_w, proj_dim, model)
+    if device_optimize and nm in ('BCORES', 'SVI'):
+        (prj_bw if nm == 'BCORES' else prj_w).pin(Xc)
 
     sched = lambda i: i0 / (1. + i)
     if nm == 'BCORES':
         alg = bc.BetaCoreset(Xc, prj_bw, opt_itrs=opt_itrs, n_subsample_opt=n_subsample_opt,
-                             n_subsample_select=n_subsample_select, step_sched=sched, beta=.1, learn_beta=False)
+                             n_subsample_select=n_subsample_select, step_sched=sched, beta=.1, learn_beta=False,
+                             device_optimize=device_optimize)
     elif nm == 'SVI':
         alg = bc.SparseVICoreset(Xc, prj_w, opt_itrs=opt_itrs, n_subsample_opt=n_subsample_opt,
-                                 n_subsample_select=n_subsample_select, step_sched=sched)
+                                 n_subsample_select=n_subsample_select, step_sched=sched, device_optimize=device_optimize)
     elif nm == 'GIGAO':
         alg = bc.HilbertCoreset(Xc, prj_optimal)
     elif nm == 'GIGAR':
@@ -114,7 +124,7 @@ def run(nm='BCORES', tr=1, N=5000, d=50, M=40, opt_itrs=200, n_subsample_opt=200
         fkl[m] = gaussian_KL(mup, Sigp, muw, LSigwInv.dot(LSigwInv.T))
         if verbose and (m in (1, 2, 5, 10, 20, M) or m % 50 == 0):
             print('%4d %12.4f %12.4f' % (m, rkl[m], fkl[m]))
-    return dict(w=w, p=p, idcs=idl, rkl=rkl, fkl=fkl, Xc=Xc)
+    return dict(w=w, p=p, idcs=idl, rkl=rkl, fkl=fkl, Xc=Xc, device_optimize_calls=getattr(alg, 'device_optimize_calls', 0))
 
 
 def main():
