@@ -9,14 +9,12 @@ Every gradient needs (bpsvi.py:27-57)
     the optimiser (util/opt.py partial_nn_opt) updates them there.
 With a BlackBoxProjector the reference's NumPy expressions run on whatever the callables return and the N-row column
 sum still runs on the GPU."""
-import weakref
-
 import numpy as np
 
 from ..device import DeviceData, DevicePhi
 from ..util.opt import partial_nn_opt
 from .coreset import Coreset
-from .projector import is_device_projector
+from .residency import keep_resident, sub_rows
 
 
 class BatchPSVICoreset(Coreset):
@@ -30,16 +28,9 @@ class BatchPSVICoreset(Coreset):
         self.mup, self.SigpInv = mup, SigpInv
         n = data.shape[0]
         self.n_subsample_opt = n_subsample_opt if n_subsample_opt is None else min(n, n_subsample_opt)   # bpsvi.py:11
-        self._resident = None
         self._sub_buf = None         # sub-samples of resident rows are taken into this one device buffer
-        wants_pin = pin_data and self.n_subsample_opt is None and hasattr(ll_projector, 'pin')
-        if wants_pin and isinstance(data, np.ndarray) and data.base is None and data.ndim == 2 and n >= 4096:
-            # every gradient re-projects ALL rows: keep them in HBM (read-only on the host while pinned)
-            self._resident = ll_projector.pin(data)
-            self._unpin = weakref.finalize(self, ll_projector.unpin, data)
-        elif wants_pin and isinstance(data, np.ndarray) and data.base is not None and data.ndim == 2 and n >= 4096:
-            from .greedy_vi import resident_copy_of_view
-            self._resident = resident_copy_of_view(data, ll_projector)       # a view: copied once, with a warning
+        # every full-data gradient re-projects ALL rows: keep them in HBM (pinned: read-only on the host; a view: copied once)
+        self._resident = keep_resident(self, data, ll_projector, pin_data and self.n_subsample_opt is None)
         super().__init__(**kw)
 
     # ---- bpsvi.py:17-25: a fresh random initialisation of all `sz` points, then the optimisation (itrs is unused)
@@ -58,10 +49,9 @@ class BatchPSVICoreset(Coreset):
             rows, scale = (self._resident if self._resident is not None else self.data), 1.
         else:
             sub_idcs, scale = np.random.randint(self.data.shape[0], size=m), self.data.shape[0] / m
-            if isinstance(self.data, DeviceData) and is_device_projector(self.ll_projector):
-                rows = self._sub_buf = self.data.take(sub_idcs, out=self._sub_buf, transient=True)      # stays in HBM
-            else:
-                rows = self.data[sub_idcs]
+            rows = sub_rows(self.data, sub_idcs, self.ll_projector, out=self._sub_buf)      # resident rows stay in HBM
+            if isinstance(rows, DeviceData):
+                self._sub_buf = rows
         if hasattr(self.ll_projector, 'colsum'):        # device projector: store-free K1, the bits of project().sum(axis=0)
             b = self.ll_projector.colsum(rows)
             if b is not None:

@@ -10,33 +10,18 @@ touch the host; with a black-box projector the reference's NumPy expressions are
 on whatever array the callable returns.
 """
 import contextlib
-import os
-import warnings
-import weakref
 
 import numpy as np
 
 from ..device import DeviceData, DevicePhi
 from ..util.opt import nn_opt
 from .coreset import Coreset
+from .projector import VI_MAX_CORE_DOUBLES, VI_MAX_SAMPLES, is_device_projector
+from .residency import is_sharded, keep_resident, pin_for, resident_copy_of_view, sub_rows      # noqa: F401 (resident_copy_of_view: importable from here)
 
 
 def _flatten(groups):
     return [i for g in groups for i in g]
-
-
-def resident_copy_of_view(data, ll_projector):
-    """A VIEW (Z[:n], a reshaped or memory-mapped array: `data.base is not None`) cannot be guarded against in-place edits
-    the way a pinned array is -- writes through its base would go unseen -- so it is not pinned.  Left at that, every
-    full-data gradient would upload all N x Dz rows again (~10 GB per gradient at the headline size).  Instead the rows are
-    copied to the device ONCE into a DeviceData this coreset owns, and the caller is told: later edits of the host array
-    are not seen (pin_data=False keeps the reference's read-the-live-array-every-time behaviour, bcores.py:44)."""
-    warnings.warn('data is a view of another array: its %d rows were copied to the GPU once for this coreset; in-place edits of '
-                  'the host array after construction are not seen (pass pin_data=False to re-read it on every projection)'
-                  % data.shape[0], UserWarning, stacklevel=3)
-    f32 = data.dtype == np.float32             # float32 rows stay float32 on the device (bit-identical results, half the bytes)
-    return DeviceData(np.ascontiguousarray(data, dtype=np.float32 if f32 else np.float64), ctx=getattr(ll_projector, 'ctx', None),
-                      dtype=np.float32 if f32 else None)
 
 
 class GreedyVICoreset(Coreset):
@@ -59,8 +44,7 @@ class GreedyVICoreset(Coreset):
         # host loop's to rounding (weights within the parity contract, selections and the RNG position exactly)
         self.device_optimize = bool(device_optimize)
         self.device_optimize_calls = 0                 # _optimize() calls that took the native loop
-        # BC_FORCE_EXCHANGE=1 keeps a 1-rank group on the collective paths (rehearsal of the RCCL code on one GPU)
-        self.comm = comm if (comm is not None and (comm.world > 1 or os.environ.get('BC_FORCE_EXCHANGE') == '1')) else None
+        self.comm = comm if is_sharded(comm) else None
         self._dev_data = data if isinstance(data, DeviceData) else None      # rows already resident in HBM
         self._tmode, self._tpos = 'shard', None      # how the last tangent space is spread over ranks (see _tangent)
         self._n_total = n
@@ -75,21 +59,15 @@ class GreedyVICoreset(Coreset):
                 self._dev_data = DeviceData(data, ctx=getattr(ll_projector, 'ctx', None), row_offset=off)
             if groups is not None:        # the members of every group that live on this rank, as local row numbers, in member order
                 self._local_groups = [np.asarray([i - off for i in g if off <= i < off + n], dtype=np.int64) for g in groups]
-        elif pin_data and hasattr(ll_projector, 'pin') and isinstance(data, np.ndarray) and data.base is None and data.ndim == 2 \
-                and data.shape[0] >= 4096 and (n_subsample_select is None or n_subsample_opt is None or groups is not None):
-            # every full-data tangent space re-projects ALL rows: keep them in HBM instead of uploading per gradient
-            # step.  While pinned, `data` is read-only on the host (an in-place edit raises instead of going unseen);
-            # pin_data=False restores the reference's read-the-live-array-every-time behaviour (bcores.py:44).
-            self._dev_data = ll_projector.pin(data)
-            self._unpin = weakref.finalize(self, ll_projector.unpin, data)      # released with this coreset
-        elif pin_data and hasattr(ll_projector, 'pin') and isinstance(data, np.ndarray) and data.base is not None and data.ndim == 2 \
-                and data.shape[0] >= 4096 and (n_subsample_select is None or n_subsample_opt is None or groups is not None):
-            self._dev_data = resident_copy_of_view(data, ll_projector)
-        elif isinstance(data, np.ndarray) and getattr(ll_projector, 'pinned', lambda _: None)(data) is not None:
-            # sub-sampled everywhere, but the CALLER has pinned the array on this projector: the sub-samples are drawn from that
-            # copy on the device (uploading N rows to read a few hundred per step is the caller's decision, not ours)
-            self._dev_data = ll_projector.pin(data)      # (nests: the copy stays until this coreset lets go of it too)
-            self._unpin = weakref.finalize(self, ll_projector.unpin, data)
+        elif isinstance(data, np.ndarray):
+            # every full-data tangent space re-projects ALL rows; pin_data=False restores the reference's read-the-live-array-
+            # every-time behaviour (bcores.py:44)
+            self._dev_data = keep_resident(self, data, ll_projector, pin_data and (
+                n_subsample_select is None or n_subsample_opt is None or groups is not None))
+            if self._dev_data is None and getattr(ll_projector, 'pinned', lambda _: None)(data) is not None:
+                # sub-sampled everywhere, but the CALLER has pinned the array on this projector: the sub-samples are drawn from
+                # that copy on the device (uploading N rows to read a few hundred per step is the caller's decision, not ours)
+                self._dev_data = pin_for(self, data, ll_projector)      # (nests: the copy stays until this coreset lets go of it too)
         self._sub_buf = None         # the one device buffer the sub-samples of resident rows are taken into (DeviceData.take)
         super().__init__(**kw)
         self.initialized = int(initialized) * len(self.wts)
@@ -100,13 +78,15 @@ class GreedyVICoreset(Coreset):
 
     # -- pieces shared by select / gradient
     def _sub_rows(self, local_idcs):
-        """data[local_idcs] as the input of a projection.  Resident rows stay in HBM: they are gathered on the device into one
-        buffer this coreset keeps (same rows, same row count, hence the same K1 and the same bits as the host detour)."""
-        from .projector import is_device_projector
-        if self._dev_data is None or not is_device_projector(self.ll_projector):
-            return self.data[local_idcs]
-        self._sub_buf = self._dev_data.take(local_idcs, out=self._sub_buf, transient=True)      # (refilled in place from now on)
-        return self._sub_buf
+        """data[local_idcs] as the input of a projection; resident rows are gathered into one device buffer this coreset keeps."""
+        rows = sub_rows(self._all_rows(), local_idcs, self.ll_projector, out=self._sub_buf, host=self.data)
+        if isinstance(rows, DeviceData):
+            self._sub_buf = rows      # (refilled in place from now on)
+        return rows
+
+    def _all_rows(self):
+        """All data rows as the input of a projection: their resident copy where there is one."""
+        return self._dev_data if self._dev_data is not None else self.data
 
     def _tangent(self, n_subsample, w, p, beta, select=False, grad=False):
         """bcores.py:37-72 / sparsevi.py:35-70: returns (vecs, sum_scaling, sub_idcs, group_idcs, corevecs)
@@ -116,7 +96,7 @@ class GreedyVICoreset(Coreset):
         self._tmode, self._tpos = 'shard', None
         if n_subsample is None and self.groups is None:
             sub_idcs = None
-            vecs = self._proj(self._dev_data if self._dev_data is not None else self.data, beta)
+            vecs = self._proj(self._all_rows(), beta)
             sum_scaling = 1.
         elif n_subsample is None and self.groups:
             group_idcs = list(range(len(self.groups)))
@@ -154,14 +134,13 @@ class GreedyVICoreset(Coreset):
         the same order of additions; a black-box projector is called group by group like in the reference.
         Row-sharded: every rank sums the members it owns (member order), the partial sums are added in rank order
         (one G x S collective) and every rank continues with the same, complete group vectors."""
-        from .projector import _DeviceProjectorBase
         if self.comm is not None:
             full = self._proj(self._dev_data, beta)
             part = np.asarray(full.group_sum([self._local_groups[i] for i in group_idcs]))
             self._tmode = 'replicated'
             return self.comm.sum_in_rank_order(part)
-        if isinstance(self.ll_projector, _DeviceProjectorBase):
-            full = self._proj(self._dev_data if self._dev_data is not None else self.data, beta)
+        if is_device_projector(self.ll_projector):
+            full = self._proj(self._all_rows(), beta)
             if isinstance(full, DevicePhi):
                 return full.group_sum([self.groups[i] for i in group_idcs])
         return np.array([np.sum(np.asarray(self._proj(self.data[self.groups[i], :], beta)), axis=0) for i in group_idcs])
@@ -296,9 +275,8 @@ class GreedyVICoreset(Coreset):
         rows that are not resident or are sharded, a transport without a native communicator, no coreset rows yet).
         `want_beta_grad` (BetaCoreset, learn_beta): (grad, beta_dots) from bc_vi_beta_gradient instead, see vi_gradient."""
         kw = {'want_beta_grad': True} if want_beta_grad else {}
-        from .projector import _DeviceProjectorBase
         if not self.fused_gradient or self.groups is not None \
-                or self.pts.size == 0 or not isinstance(self.ll_projector, _DeviceProjectorBase):
+                or self.pts.size == 0 or not is_device_projector(self.ll_projector):
             return None
         if self.n_subsample_opt is not None:
             if self._dev_data is None or self.comm is not None:
@@ -316,7 +294,7 @@ class GreedyVICoreset(Coreset):
             if nc is None:
                 return None
         self.ll_projector.update(w, self.pts)
-        g = self.ll_projector.vi_gradient(self._dev_data if self._dev_data is not None else self.data, self.pts, w, 1.,
+        g = self.ll_projector.vi_gradient(self._all_rows(), self.pts, w, 1.,
                                           beta=self._fused_beta(beta), comm=nc, overlap=overlap, **kw)
         if g is None:
             raise RuntimeError('fused gradient not applicable after the sampler ran')      # guarded by the checks above
@@ -333,7 +311,6 @@ class GreedyVICoreset(Coreset):
         enc = getattr(self.ll_projector, 'encoder', None)
         if enc is not None:                  # the gradient stages the ENCODED coreset rows
             dz = max(dz, enc.out_width(self.ll_projector.pass_cols))
-        from .projector import VI_MAX_CORE_DOUBLES, VI_MAX_SAMPLES
         return self.ll_projector.projection_dimension <= VI_MAX_SAMPLES and m * (dz + 1) <= VI_MAX_CORE_DOUBLES
 
     def _device_optimize(self, beta):

@@ -1,10 +1,9 @@
-import os
-
 import numpy as np
 
 from ..device import DeviceData, DevicePhi
 from ..snnls.giga import GIGA
 from .coreset import Coreset
+from .residency import is_sharded, sub_rows
 
 
 class HilbertCoreset(Coreset):
@@ -28,7 +27,7 @@ class HilbertCoreset(Coreset):
 
     def __init__(self, data, ll_projector, n_subsample=None, snnls=GIGA, comm=None, **kw):
         self.comm = comm
-        sharded = comm is not None and (comm.world > 1 or os.environ.get('BC_FORCE_EXCHANGE') == '1')
+        sharded = is_sharded(comm)
         self._sub_rows = None
         if n_subsample is None:
             sub_idcs = None
@@ -37,8 +36,7 @@ class HilbertCoreset(Coreset):
             n_subsample = min(data.shape[0], n_subsample)
             sub_idcs = np.random.randint(data.shape[0], size=n_subsample)
             # resident rows are sub-sampled on the device (the same rows, so the same Phi); anything else on the host
-            from .projector import is_device_projector
-            src = data.take(sub_idcs) if isinstance(data, DeviceData) and is_device_projector(ll_projector) else data[sub_idcs]
+            src = sub_rows(data, sub_idcs, ll_projector, transient=False)
         else:
             # row-sharded sub-sample (hilbert.py:12-15): every rank draws the same global indices (shared seed of the global
             # stream), the drawn rows are collected once (each rank contributes the ones it owns; n_subsample x Dz doubles),

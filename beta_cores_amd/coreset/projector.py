@@ -12,15 +12,15 @@ Two families, one protocol (bayesiancoresets/coreset/projector.py:5-66:
 """
 import ctypes as C
 import time
-import weakref
 
 import numpy as np
 
 from .. import _native as N
-from ..device import DeviceData, DevicePhi, _as_rows, _ptr, default_context
+from ..device import DeviceData, _as_rows, _ptr, default_context, upload_slot
 from ..likelihoods import GaussianLocation, LinearRegression
 from ..util import numpy_bits
 from ..util.opt import adam_step_arrays
+from .residency import _BIG_ROWS, _PIPE_ROWS, _SMALL_ROWS, Pin, WeakIdMap, _PhiPool, _resident_dtype      # noqa: F401 (names kept importable from here)
 
 
 class Projector(object):
@@ -86,124 +86,6 @@ class BetaBlackBoxProjector(Projector):
         self.samples = self.sampler(self.projection_dimension, wts, pts)
 
 
-_SMALL_ROWS = 4096     # below this an input is treated as transient (coreset points, sub-samples)
-_PIPE_ROWS = 65536     # live host arrays from this size on are uploaded and projected in one pipelined call
-_BIG_ROWS = 65536      # Phi buffers above this are not hoarded: at most one free buffer per S is kept
-
-
-def _pool_shutdown(state):
-    state['alive'] = False
-    destroy = N.load().bc_phi_destroy
-    for lst in state['free'].values():
-        for _, h in lst:
-            destroy(h)
-    state['free'].clear()
-
-
-class _PhiPool:
-    """Phi buffers recycled instead of hipMalloc'ed / hipFree'd per projection.
-    A handle is lent to exactly one DevicePhi wrapper; when that wrapper is garbage collected the
-    handle comes back -- so two live results never alias: a solver that still holds the Phi of an
-    earlier project() keeps its buffer, and the next project() gets another one (the reference
-    returns a fresh array per call, projector.py:24).  Handles still on loan when the pool dies
-    stay valid and are destroyed by their wrapper."""
-
-    def __init__(self, ctx):
-        self.ctx = ctx
-        self.state = {'alive': True, 'free': {}}     # shared with the release callbacks
-        self._fin = weakref.finalize(self, _pool_shutdown, self.state)
-
-    def acquire(self, n_rows, s):
-        lst = self.state['free'].setdefault(s, [])
-        best = None
-        for i, (cap, h) in enumerate(lst):
-            if cap >= n_rows and (best is None or cap < lst[best][0]):
-                best = i
-        if best is not None and (n_rows < _BIG_ROWS or lst[best][0] <= 2 * n_rows):
-            return lst.pop(best)
-        if n_rows < _BIG_ROWS:
-            cap = max(256, 1 << int(np.ceil(np.log2(max(n_rows, 1)))))
-        else:
-            cap = ((n_rows + N.TILE_ROWS - 1) // N.TILE_ROWS) * N.TILE_ROWS      # large shards: no power-of-two slack
-        h = C.c_void_p()
-        N.call('bc_phi_create', self.ctx.h, int(cap), int(s), C.byref(h))
-        return cap, h
-
-    def releaser(self, cap, s):
-        state = self.state
-
-        def release(handle):
-            if not state['alive']:
-                N.load().bc_phi_destroy(handle)
-                return
-            lst = state['free'].setdefault(s, [])
-            if cap >= _BIG_ROWS and any(c >= _BIG_ROWS for c, _ in lst):
-                N.load().bc_phi_destroy(handle)      # one spare large buffer per S is enough for a gradient loop
-                return
-            lst.append((cap, handle))
-        return release
-
-    def clear(self):
-        destroy = N.load().bc_phi_destroy
-        for lst in self.state['free'].values():
-            for _, h in lst:
-                destroy(h)
-        self.state['free'].clear()
-
-
-# ---- host arrays pinned on the device.  While an ndarray is pinned its device copy is what gets projected, so an
-# in-place edit of the array would go unseen; the array is therefore made read-only for as long as any pin holds it
-# (NumPy then raises on assignment instead of the device silently serving stale rows).
-_pin_guard = {}      # id(ndarray) -> entry [count, original writeable flag, weakref]; an entry is only trusted while its
-                     # weakref still points at the array (ids are recycled once an array dies)
-
-
-def _guard_acquire(arr):
-    """Make `arr` read-only while pinned; returns the guard entry to hand to _guard_release."""
-    key = id(arr)
-    ent = _pin_guard.get(key)
-    if ent is not None and ent[2]() is arr:
-        ent[0] += 1
-        return ent
-    was = bool(arr.flags.writeable)
-    try:
-        arr.flags.writeable = False
-    except ValueError:
-        pass
-    ent = [1, was, None]
-    try:
-        ent[2] = weakref.ref(arr, lambda _, k=key, e=ent: _pin_guard.pop(k, None) if _pin_guard.get(k) is e else None)
-    except TypeError:
-        ent[2] = lambda: arr
-    _pin_guard[key] = ent
-    return ent
-
-
-def _guard_release(ent):
-    """Drop one pin of the array this ENTRY guards (not whatever array carries the same id() today)."""
-    if ent is None:
-        return
-    ent[0] -= 1
-    if ent[0] <= 0:
-        arr = ent[2]()
-        if arr is not None:
-            if ent[1]:
-                try:
-                    arr.flags.writeable = True
-                except ValueError:
-                    pass
-            if _pin_guard.get(id(arr)) is ent:
-                _pin_guard.pop(id(arr), None)
-
-
-def _resident_dtype(arr):
-    """Storage dtype of the device copy of a host array: a float32 ndarray of _SMALL_ROWS rows or more stays float32 (results
-    are bit-identical to the widened rows', only the upload time and the memory change); everything else is float64 (None)."""
-    if isinstance(arr, np.ndarray) and arr.dtype == np.float32 and arr.ndim == 2 and arr.shape[0] >= _SMALL_ROWS:
-        return np.float32
-    return None
-
-
 # limits of the native gradient entry points (bc_vi_gradient, bc_vi_optimize: csrc/bc_project.hip, csrc/bc_viopt.hip)
 VI_MAX_SAMPLES = 256           # one pass of the store-free K1
 VI_MAX_CORE_DOUBLES = 60000    # m * (dz + 1): the coreset rows and their weights fit the native staging area
@@ -221,19 +103,19 @@ class _DeviceProjectorBase(Projector):
         self.encoder = encoder
         self.pass_cols = int(pass_cols)
         self.encoded_dtype = np.dtype(encoded_dtype)
-        self._enc_cache = {}       # id(resident rows) -> (weakref, encoder version, encoded DeviceData)
+        self._enc_cache = WeakIdMap()   # resident rows -> (encoder version, encoded DeviceData)
         self._enc_out = None       # the one re-used output buffer for transient rows
         self.encode_launches = 0   # bulk encodes this projector has issued (a cache hit issues none)
         self.vi_optimize_calls = 0 # weight optimisations that ran on the device (vi_optimize)
         if encoder is not None and encoder.ctx is not self.ctx:
             raise ValueError('the encoder lives on another context than the projector')
-        self._pins = {}            # id(ndarray) -> (weakref, DeviceData): arrays the caller pinned (see pin())
+        self._pins = WeakIdMap(strong=True)      # ndarray -> residency.Pin: arrays the caller pinned (see pin())
         self._slots = {}           # dz -> DeviceData slot for small transient inputs
         self._pool = _PhiPool(self.ctx)
         # constant rows whose value holds an np.exp: on a host whose NumPy is not the one the library restates they are
         # evaluated on the host (util/numpy_bits.py); `_key_cache`: the y's of the all-zero-feature rows of large inputs
         self._host_constants = numpy_bits.warn_if_constant_bits_differ(model) and getattr(model, 'host_constants', None) is not None
-        self._key_cache = {}
+        self._key_cache = WeakIdMap()
         self.constant_rows_from_host = 0      # how many (y, value) pairs the last beta-projection handed to the kernel
         self.update(np.array([]), np.array([]))
 
@@ -248,51 +130,41 @@ class _DeviceProjectorBase(Projector):
         (ndarray.flags.writeable = False) until unpin(pts) / forget(), or until the projector dies."""
         if isinstance(pts, DeviceData):
             return pts
-        key = id(pts)
-        hit = self._pins.get(key)
-        if hit is not None and hit[0]() is pts:
-            hit[3] += 1                     # pins nest: the copy goes when the last holder unpins
-            return hit[1]
+        hit = self._pins.get(pts)
+        if hit is not None:
+            hit.count += 1
+            return hit.data
         if isinstance(pts, np.ndarray) and pts.base is not None:
             # a view: edits through its base array would go unseen by the device copy (the read-only flag only guards
             # the view itself), so views are not pinned -- they are uploaded per call like any live array
             raise ValueError('pin(): the array is a view of another array; pin the base array or pass a copy')
         arr = np.atleast_2d(pts)
         dd = DeviceData(arr, ctx=self.ctx, dtype=_resident_dtype(arr))      # a float32 array keeps a float32 device copy
-        ent = _guard_acquire(pts)
-        fin = weakref.finalize(self, _guard_release, ent)      # a dying projector lets go of its pins
-        try:
-            ref = weakref.ref(pts, lambda _, k=key, pins=self._pins: pins.pop(k, None))
-        except TypeError:
-            ref = lambda: pts
-        self._pins[key] = [ref, dd, fin, 1, ent]
-        return dd
+        return self._pins.put(pts, Pin(self, pts, dd)).data
 
     def pinned(self, pts):
         """The DeviceData of an array the caller has pinned on this projector (pin()), or None."""
-        hit = self._pins.get(id(pts))
-        return hit[1] if hit is not None and hit[0]() is pts else None
+        hit = self._pins.get(pts)
+        return hit.data if hit is not None else None
 
     def unpin(self, pts):
-        hit = self._pins.get(id(pts))
-        if hit is None or hit[0]() is not pts:
+        hit = self._pins.get(pts)
+        if hit is None:
             return
-        hit[3] -= 1
-        if hit[3] <= 0:
-            self._pins.pop(id(pts), None)
-            self._enc_cache.pop(id(hit[1]), None)      # the encoded copy of the pinned rows goes with them
-            hit[2].detach()
-            _guard_release(hit[4])
+        hit.count -= 1
+        if hit.count <= 0:
+            self._pins.pop(pts)
+            self._enc_cache.pop(hit.data)      # the encoded copy of the pinned rows goes with them
+            hit.drop()
 
     def forget(self, pts=None):
         """Drop the pinned device copy of `pts` (or of everything) and the spare Phi buffers."""
         if pts is not None:
             self.unpin(pts)
             return
-        for key in list(self._pins):
-            hit = self._pins.pop(key)
-            hit[2].detach()
-            _guard_release(hit[4])
+        for hit in self._pins:
+            hit.drop()
+        self._pins.clear()
         self._enc_cache.clear()
         self._pool.clear()
 
@@ -314,77 +186,60 @@ class _DeviceProjectorBase(Projector):
             self.encode_launches += 1
             self._enc_out = dd.encode(enc, pass_cols=self.pass_cols, dtype=self.encoded_dtype, out=self._enc_out, transient=True)
             return self._enc_out
-        key = id(dd)
-        hit = self._enc_cache.get(key)
-        if hit is not None and hit[0]() is dd and hit[1] == enc.version:
-            return hit[2]
-        self.encode_launches += 1
-        out = dd.encode(enc, pass_cols=self.pass_cols, dtype=self.encoded_dtype)
-        self._enc_cache[key] = (weakref.ref(dd, lambda _, k=key, c=self._enc_cache: c.pop(k, None)), enc.version, out)
+        version, out = self._enc_cache.get(dd, (None, None))
+        if version != enc.version:
+            self.encode_launches += 1
+            out = dd.encode(enc, pass_cols=self.pass_cols, dtype=self.encoded_dtype)
+            self._enc_cache.put(dd, (enc.version, out))
         return out
 
     def _raw_device_data(self, pts):
         """(DeviceData, transient): transient inputs live in a re-used upload slot that the next call overwrites."""
         if isinstance(pts, DeviceData):
             return pts, False
-        hit = self._pins.get(id(pts))
-        if hit is not None and hit[0]() is pts:
-            return hit[1], False
+        dd = self.pinned(pts)
+        if dd is not None:
+            return dd, False
         pts = np.atleast_2d(pts)
         if pts.shape[0] < _SMALL_ROWS:
-            slot = self._slots.get(pts.shape[1])
-            if slot is None:
-                slot = self._slots[pts.shape[1]] = DeviceData.slot(pts.shape[1], cap_rows=256, ctx=self.ctx)
-            return slot.update(pts), True
+            return upload_slot(self._slots, pts.shape[1], self.ctx).update(pts), True
         return DeviceData(pts, ctx=self.ctx, dtype=_resident_dtype(pts)), False      # live array, uploaded for this call
 
     def _zero_feature_keys(self, pts, d, encoded=False):
         """Sorted unique y of the rows of `pts` whose d features are all zero (host array: NumPy; resident rows: one device scan).
         With an encoder the ENCODED features are what counts (ReLU features are all zero for whole regions of x): host rows
-        go through enc(pts) -- the device's bits --, device rows are encoded first; `encoded`: `pts` already holds features."""
-        if self.encoder is not None and not encoded:
-            if isinstance(pts, DeviceData):
-                pts = self._encoded(pts, pts._transient)
+        go through enc(pts) -- the device's bits --, device rows are encoded first; `encoded`: `pts` already holds features.
+        Cached per resident DeviceData and per large ndarray; a buffer that take(out=) refills in place is scanned every time."""
+        if self.encoder is not None and not encoded:      # what holds the features: the encoded device copy, or enc(host rows)
+            if isinstance(pts, DeviceData) or self.pinned(pts) is not None:
+                pts = self.device_data(pts)[0]
             else:
-                hit = self._pins.get(id(pts))
-                if hit is not None and hit[0]() is pts:
-                    pts = self._encoded(hit[1], False)
-                else:
-                    pts = self.encoder(np.atleast_2d(pts), pass_cols=self.pass_cols, dtype=self.encoded_dtype)
-        if isinstance(pts, DeviceData):
-            cached = not pts._transient       # a buffer that take(out=) refills in place is scanned every time
-            hit = self._key_cache.get(id(pts)) if cached else None
-            if hit is not None and hit[0]() is pts:
-                return hit[1]
-            cap = 65536
-            out, n = np.empty(cap), C.c_int64()
-            N.call('bc_data_zero_feature_keys', pts.h, int(d), cap, _ptr(out), C.byref(n))
-            if n.value > cap:
-                raise ValueError('%d data rows have all-zero features: more than the %d the host route for constant rows handles'
-                                 % (n.value, cap))
-            keys = np.unique(out[:n.value])
-            if not cached:
-                return keys
-            try:
-                self._key_cache[id(pts)] = (weakref.ref(pts, lambda _, k=id(pts), c=self._key_cache: c.pop(k, None)), keys)
-            except TypeError:
-                pass
-            return keys
+                pts = self.encoder(np.atleast_2d(pts), pass_cols=self.pass_cols, dtype=self.encoded_dtype)
+        on_device = isinstance(pts, DeviceData)
+        cached = not pts._transient if on_device else isinstance(pts, np.ndarray) and np.atleast_2d(pts).shape[0] >= _SMALL_ROWS
+        keys = self._key_cache.get(pts) if cached else None
+        if keys is None:
+            keys = self._scan_device(pts, d) if on_device else self._scan_host(pts, d)
+            if cached:
+                self._key_cache.put(pts, keys)
+        return keys
+
+    @staticmethod
+    def _scan_device(dd, d):
+        cap = 65536
+        out, n = np.empty(cap), C.c_int64()
+        N.call('bc_data_zero_feature_keys', dd.h, int(d), cap, _ptr(out), C.byref(n))
+        if n.value > cap:
+            raise ValueError('%d data rows have all-zero features: more than the %d the host route for constant rows handles'
+                             % (n.value, cap))
+        return np.unique(out[:n.value])
+
+    @staticmethod
+    def _scan_host(pts, d):
         arr = np.atleast_2d(np.asarray(pts))
         if arr.dtype != np.float32 or arr.shape[0] < _SMALL_ROWS:      # (a large float32 array is scanned as it is: the zero test
             arr = np.atleast_2d(np.asarray(pts, dtype=np.float64))     # is exact in either type, the few keys are widened below)
-        big = arr.shape[0] >= _SMALL_ROWS and isinstance(pts, np.ndarray)
-        if big:
-            hit = self._key_cache.get(id(pts))
-            if hit is not None and hit[0]() is pts:
-                return hit[1]
-        keys = np.unique(arr[~arr[:, :d].any(axis=1), d].astype(np.float64))
-        if big:
-            try:
-                self._key_cache[id(pts)] = (weakref.ref(pts, lambda _, k=id(pts), c=self._key_cache: c.pop(k, None)), keys)
-            except TypeError:
-                pass
-        return keys
+        return np.unique(arr[~arr[:, :d].any(axis=1), d].astype(np.float64))
 
     def _stage_host_constants(self, pts, model_id, params, more=None):
         """Before a beta-projection on a host whose NumPy the library does not restate: the constants of the all-zero-feature
@@ -402,6 +257,14 @@ class _DeviceProjectorBase(Projector):
         N.call('bc_ctx_set_constant_row_values', self.ctx.h, int(model_id), _ptr(params), int(params.shape[0]),
                _ptr(np.ascontiguousarray(keys)), _ptr(vals), int(keys.size))
 
+    def _theta(self, shape):
+        """(Theta as K1 reads it, S) for data rows of `shape` (a DeviceData's or a host array's)."""
+        theta = self.model.theta_for_device(self.samples)
+        if shape[1] != self.model.data_width(theta.shape[1]):
+            raise ValueError('data rows have %d columns, model expects %d for %d-dimensional samples'
+                             % (shape[1], self.model.data_width(theta.shape[1]), theta.shape[1]))
+        return theta, int(theta.shape[0])
+
     def _run_from_host(self, pts, model_id, params, keep=False):
         """project(ndarray) for a LARGE live host array: upload and K1 pipelined in one native call (bc_project_from_host;
         Phi, norms and column sums are the resident path's bit for bit).  Returns (DevicePhi, DeviceData of the uploaded
@@ -409,57 +272,36 @@ class _DeviceProjectorBase(Projector):
         self._stage_host_constants(pts, model_id, params)
         f32 = _resident_dtype(pts) is not None       # a float32 array goes up as it is: no float64 host copy, half the bytes
         pts = _as_rows(np.atleast_2d(pts), np.dtype(np.float32 if f32 else np.float64), 'data')
-        theta = self.model.theta_for_device(self.samples)
-        if pts.shape[1] != self.model.data_width(theta.shape[1]):
-            raise ValueError('data rows have %d columns, model expects %d for %d-dimensional samples'
-                             % (pts.shape[1], self.model.data_width(theta.shape[1]), theta.shape[1]))
+        theta, S = self._theta(pts.shape)
         params = np.ascontiguousarray(params, dtype=np.float64)
-        S = int(theta.shape[0])
-        cap, h = self._pool.acquire(pts.shape[0], S)
-        dh = C.c_void_p()
-        try:
+        rows = []
+
+        def fill(h):
+            dh = C.c_void_p()
             N.call('bc_project_from_host_f32' if f32 else 'bc_project_from_host', self.ctx.h, _ptr(pts), int(pts.shape[0]), int(pts.shape[1]), int(model_id), _ptr(theta), S,
                    _ptr(params), int(params.shape[0]), 0, C.byref(dh), C.byref(h))
-        except Exception:
-            self._pool.releaser(cap, S)(h)
-            raise
-        dd = DeviceData._adopt(dh, pts.shape, self.ctx)
-        return DevicePhi(h, self.ctx, release=self._pool.releaser(cap, S)), dd
+            rows.append(DeviceData._adopt(dh, pts.shape, self.ctx))
+        return self._pool.lend(pts.shape[0], S, fill), rows[0]
 
     def _run(self, pts, model_id, params):
         if (self.encoder is None and isinstance(pts, np.ndarray) and pts.ndim == 2 and pts.shape[0] >= _PIPE_ROWS
-                and self._pins.get(id(pts)) is None):
+                and self.pinned(pts) is None):
             return self._run_from_host(pts, model_id, params)[0]      # (with an encoder: upload, encode, bc_project -- below)
         self._stage_host_constants(pts, model_id, params)
         dd, transient = self.device_data(pts)
-        theta = self.model.theta_for_device(self.samples)
-        if dd.shape[1] != self.model.data_width(theta.shape[1]):
-            raise ValueError('data rows have %d columns, model expects %d for %d-dimensional samples'
-                             % (dd.shape[1], self.model.data_width(theta.shape[1]), theta.shape[1]))
+        theta, S = self._theta(dd.shape)
         params = np.ascontiguousarray(params, dtype=np.float64)
-        S = int(theta.shape[0])
-        cap, h = self._pool.acquire(dd.shape[0], S)
-        try:
-            N.call('bc_project', self.ctx.h, dd.h, int(model_id), _ptr(theta), S, _ptr(params), int(params.shape[0]),
-                   0 if transient else int(dd.row_offset), C.byref(h))
-        except Exception:
-            self._pool.releaser(cap, S)(h)
-            raise
-        return DevicePhi(h, self.ctx, release=self._pool.releaser(cap, S))
+        return self._pool.lend(dd.shape[0], S, lambda h: N.call(
+            'bc_project', self.ctx.h, dd.h, int(model_id), _ptr(theta), S, _ptr(params), int(params.shape[0]),
+            0 if transient else int(dd.row_offset), C.byref(h)))
 
     # -- the store-free paths of the gradient loop (bcores.py:141-146, sparsevi.py:129-134): of the N x S projection of
     # the data rows only the S column sums are needed there, so K1 keeps its column partials and writes no Phi
     def _ids(self, beta):
-        if beta is None:
-            return self.model.model_id, self.model.params()
-        return self.model.beta_model_id, self.model.params(beta=beta)
-
-    def _theta_checked(self, dd):
-        theta = self.model.theta_for_device(self.samples)
-        if dd.shape[1] != self.model.data_width(theta.shape[1]):
-            raise ValueError('data rows have %d columns, model expects %d for %d-dimensional samples'
-                             % (dd.shape[1], self.model.data_width(theta.shape[1]), theta.shape[1]))
-        return theta
+        """(model id, its parameters as the native calls take them) of the plain (beta None) or the beta-likelihood."""
+        model_id, params = (self.model.model_id, self.model.params()) if beta is None \
+            else (self.model.beta_model_id, self.model.params(beta=beta))
+        return model_id, np.ascontiguousarray(params, dtype=np.float64)
 
     def colsum(self, pts, beta=None, comm=None):
         """`project(pts).sum(axis=0)` (beta None) / `project_f(pts, beta).sum(axis=0)` without materialising the
@@ -467,12 +309,10 @@ class _DeviceProjectorBase(Projector):
         communicator handle (ShardComm.native_comm) -- the sum then runs over all ranks' shards.  Returns None when the
         store-free kernel does not cover the request (S > 256); the caller projects and sums instead."""
         dd, _ = self.device_data(pts)
-        theta = self._theta_checked(dd)
-        S = int(theta.shape[0])
+        theta, S = self._theta(dd.shape)
         if S > 256:
             return None
         model_id, params = self._ids(beta)
-        params = np.ascontiguousarray(params, dtype=np.float64)
         self._stage_host_constants(pts, model_id, params)
         out = np.empty(S)
         N.call('bc_project_colsum', self.ctx.h, dd.h, int(model_id), _ptr(theta), S, _ptr(params), int(params.shape[0]),
@@ -497,8 +337,7 @@ class _DeviceProjectorBase(Projector):
         if self.encoder is not None and core.size:      # the coreset rows arrive raw: the device's own features of them
             core = np.ascontiguousarray(self.encoder(core, pass_cols=self.pass_cols, dtype=self.encoded_dtype))
         m = int(core.shape[0])
-        theta = self._theta_checked(dd)
-        S = int(theta.shape[0])
+        theta, S = self._theta(dd.shape)
         if S > VI_MAX_SAMPLES or m == 0 or m * (core.shape[1] + 1) > VI_MAX_CORE_DOUBLES:      # (also keeps 2 m + S within the native staging area)
             return None
         if core.shape[1] != dd.shape[1]:
@@ -507,30 +346,24 @@ class _DeviceProjectorBase(Projector):
         if w.shape != (m,):
             raise ValueError('one weight per coreset row')
         model_id, params = self._ids(beta)
-        params = np.ascontiguousarray(params, dtype=np.float64)
         self._stage_host_constants(data, model_id, params, more=core)
-        grad = np.empty(m)
-        resid = np.empty(S) if want_resid else None
+        entry, out = 'bc_vi_gradient', [np.empty(m)]
         if want_beta_grad:
             if N.load().bc_model_beta_grad(int(model_id)) != int(self.model.beta_grad_model_id):
                 raise ValueError('model %d is not the beta-gradient of model %d' % (self.model.beta_grad_model_id, model_id))
-            dots = np.empty(m)
-            N.call('bc_vi_beta_gradient_begin', self.ctx.h, dd.h, _ptr(core), m, int(model_id), _ptr(theta), S, _ptr(params),
-                   int(params.shape[0]), _ptr(w), float(sum_scaling), comm)
-            try:
-                if overlap is not None:
-                    overlap()
-            finally:
-                N.call('bc_vi_beta_gradient_end', self.ctx.h, _ptr(grad), _ptr(dots), _ptr(resid) if want_resid else None)
-            return (grad, dots, resid) if want_resid else (grad, dots)
-        N.call('bc_vi_gradient_begin', self.ctx.h, dd.h, _ptr(core), m, int(model_id), _ptr(theta), S, _ptr(params),
+            entry = 'bc_vi_beta_gradient'
+            out.append(np.empty(m))      # beta_dots
+        N.call(entry + '_begin', self.ctx.h, dd.h, _ptr(core), m, int(model_id), _ptr(theta), S, _ptr(params),
                int(params.shape[0]), _ptr(w), float(sum_scaling), comm)
+        resid = np.empty(S) if want_resid else None
         try:
             if overlap is not None:
                 overlap()
         finally:
-            N.call('bc_vi_gradient_end', self.ctx.h, _ptr(grad), _ptr(resid) if want_resid else None)
-        return (grad, resid) if want_resid else grad
+            N.call(entry + '_end', self.ctx.h, *[_ptr(a) for a in out + [resid]])
+        if want_resid:
+            out.append(resid)
+        return tuple(out) if len(out) > 1 else out[0]
 
     def vi_optimize(self, data, core_pts, w0, opt_itrs, step_sched, n_subsample=None, n_total=None, beta=None, chunk_steps=0,
                     want_trace=False, timings=None):
@@ -571,7 +404,6 @@ class _DeviceProjectorBase(Projector):
         w0 = np.ascontiguousarray(w0, dtype=np.float64)
         if w0.shape != (m,):
             raise ValueError('one weight per coreset row')
-        params = np.ascontiguousarray(params, dtype=np.float64)
         n_sub = 0 if n_subsample is None else int(n_subsample)
         n_total = int(data.shape[0] if n_total is None else n_total)
         self._stage_host_constants(data, model_id, params, more=core)

@@ -285,6 +285,15 @@ class DeviceData:
         return cls(ctx=ctx, device_ptr=t.data_ptr(), shape=tuple(t.shape), keepalive=t, row_offset=row_offset, dtype=dt)
 
 
+def upload_slot(slots, dz, ctx):
+    """The DeviceData.slot for small transient row sets of `dz` columns on `ctx`, kept in the owner's map `slots` and created
+    on first use.  (One map per owner: two owners sharing a slot would overwrite each other's rows between their calls.)"""
+    slot = slots.get(dz)
+    if slot is None:
+        slot = slots[dz] = DeviceData.slot(dz, cap_rows=256, ctx=ctx)
+    return slot
+
+
 class _PhiT:
     """`vecs.T`: the S x N view handed to the solvers as A (hilbert.py:17)."""
 

@@ -15,7 +15,7 @@ import weakref
 import numpy as np
 
 from . import _native as N
-from .device import DeviceData, _ptr, default_context
+from .device import _ptr, default_context, upload_slot
 
 MAX_LAYERS = 4
 MAX_WIDTH = 512
@@ -183,9 +183,7 @@ class MLPEncoder:
             return np.zeros((0, self.out_width(pass_cols)))
         if pts.shape[1] != self.widths[0] + pass_cols:
             raise ValueError('rows have %d columns, the encoder takes %d + %d pass-through' % (pts.shape[1], self.widths[0], pass_cols))
-        slot = self._slots.get(pts.shape[1])
-        if slot is None:
-            slot = self._slots[pts.shape[1]] = DeviceData.slot(pts.shape[1], cap_rows=256, ctx=self.ctx)
+        slot = upload_slot(self._slots, pts.shape[1], self.ctx)
         key = (int(pass_cols), np.dtype(dtype).str)
         out = self._outs[key] = slot.update(pts).encode(self, pass_cols=pass_cols, dtype=dtype, out=self._outs.get(key))
         return out.rows(np.arange(pts.shape[0]))

@@ -429,6 +429,40 @@ def test_live_arrays_are_read_and_pins_are_loud(bc):
     assert Z.flags.writeable
 
 
+def test_recycled_id_of_a_dead_pinned_array_is_not_trusted(bc):
+    """ids are recycled once an array dies: a new array that lands on the id of one that was pinned, projected, unpinned and
+    deleted is a stranger to the projector -- projected from its own rows (bit for bit what a fresh projector gives), not
+    pinned, not read-only.  4100 rows: just over _SMALL_ROWS, so the rows take the resident route."""
+    import gc
+    rng = np.random.RandomState(36)
+    n, d, s = 4100, 4, 8
+    th = rng.randn(s, d) * 0.3
+    prj = bc.DeviceProjector(fixed(th), s, bc.likelihoods.LinearRegression(1.0))
+    A = rng.randn(n, d + 1)
+    prj.pin(A)
+    first = np.asarray(prj.project(A))
+    prj.unpin(A)
+    old_id = id(A)
+    del A
+    gc.collect()
+    B, others = None, []
+    for _ in range(300):
+        cand = np.empty((n, d + 1))
+        if id(cand) == old_id:
+            B = cand
+            break
+        others.append(cand)              # (kept alive, so that the allocator moves on)
+    del others
+    if B is None:
+        pytest.skip('no new array landed on the dead array\'s id')
+    B[:] = rng.randn(n, d + 1)
+    got = np.asarray(prj.project(B))
+    want = np.asarray(bc.DeviceProjector(fixed(th), s, bc.likelihoods.LinearRegression(1.0)).project(B))
+    assert np.array_equal(got, want) and not np.array_equal(got, first)
+    assert B.flags.writeable
+    assert prj.pinned(B) is None
+
+
 def test_view_data_is_copied_once_with_a_warning(bc):
     """A view (Z[:n]) cannot be made read-only through its base, so it is not pinned -- but a coreset that re-projects all
     rows per gradient must not upload them per gradient either: the rows are copied to the device once, with a UserWarning."""
