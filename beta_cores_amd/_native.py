@@ -165,6 +165,7 @@ _VIOPT_SIGNATURES = {
     'bc_vi_optimize_chunk_end': [vp],
     'bc_vi_optimize_end': [vp, vp, vp],
     'bc_vi_optimize_device_ms': [vp, c_dp],
+    'bc_vi_optimize_last_draw': [vp, C.c_int32, C.c_int32, vp, vp, vp, c_dp],
     'bc_vi_optimize': [vp, vp, vp, C.c_int64, C.c_int, vp, C.c_int32, C.c_int, vp, C.c_int32, vp, C.c_int32, vp, vp, vp, C.c_int64,
                        C.c_double, C.c_int32, vp, vp],
 }

@@ -452,6 +452,18 @@ class _DeviceProjectorBase(Projector):
         self.vi_optimize_calls += 1
         return (out, trace) if want_trace else out
 
+    def vi_last_draw(self):
+        """What the last posterior draw of the most recent `vi_optimize` run on this projector's context left on the device
+        (bc_vi_optimize_last_draw; a seam for tests, nothing is launched): a dict of `theta` (S x D, what K1 read: for the
+        Gaussian sampler Theta . Siginv^T), `saux` (S) and `raw` (S x D) -- the Gaussian sampler's theta^T Siginv theta and its
+        draw before Siginv is applied, zeros for the linear-regression sampler -- and `pad_max`, the largest magnitude left
+        in the zero padding of the block K1 reads (anything but 0.0 is a defect).  After a run whose first step raised
+        LinAlgError everything reads 0.  Raises when the context's last run was not one of this projector's shape (S, D)."""
+        S, D = int(self.projection_dimension), int(self.sampler._dim())
+        theta, saux, raw, pad = np.empty((S, D)), np.empty(S), np.empty((S, D)), C.c_double()
+        N.call('bc_vi_optimize_last_draw', self.ctx.h, S, D, _ptr(theta), _ptr(saux), _ptr(raw), C.byref(pad))
+        return dict(theta=theta, saux=saux, raw=raw, pad_max=pad.value)
+
 
 def is_device_projector(prj):
     """True for the projectors whose input may be a DeviceData (K1 on the GPU): what decides whether a coreset sub-samples

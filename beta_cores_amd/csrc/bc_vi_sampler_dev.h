@@ -52,6 +52,16 @@ struct VisArgs {
 
 BC_VIS_FN inline int bc_vis_tri(int i, int k) { return i * (i + 1) / 2 + k; }
 
+// b0 = Sig0inv . th0 for VisArgs::b0, on the HOST (bc_vi_optimize_begin, once per run): the full matrix row by row -- both
+// triangles, where the factorisation reads the lower one only -- each entry one fixed-order fma chain.
+inline void bc_vi_prior_rhs(const double* sig0inv, const double* th0, int d, double* b0) {
+  for (int i = 0; i < d; ++i) {
+    double acc = 0.;
+    for (int j = 0; j < d; ++j) acc = fma(sig0inv[(size_t)i * d + j], th0[j], acc);
+    b0[i] = acc;
+  }
+}
+
 // Returns 1 (block-uniform) when a pivot of the factorisation is not finite and positive; nothing has been written to
 // theta / saux then.  ws: BC_VIS_WS_DOUBLES(d) doubles.
 BC_VIS_FN inline int bc_vi_sampler(const VisArgs& a, double* ws) {

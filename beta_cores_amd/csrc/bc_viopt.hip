@@ -9,6 +9,7 @@
 #include "../../include/beta_cores_viopt.h"
 #include <cmath>
 #include <cstring>
+#include <vector>
 
 #define BC_VIS_BLOCK 512
 
@@ -49,6 +50,8 @@ struct bc_viopt {
   bc_vi_plan* plan = nullptr;
   // the run in progress
   bool active = false, chunk_pending = false, failed = false, lds_set = false;
+  bool laid_out = false;          // va / nrsel describe the slab as the last _begin left it (bc_vi_optimize_last_draw)
+  int nrsel = 0;                  // rows of the zero-padded Theta block K1 reads
   const bc_data* data = nullptr;
   bc_data core_view, sub_view;
   VisArgs va;
@@ -156,6 +159,7 @@ extern "C" int bc_vi_optimize_begin(bc_ctx* ctx, const bc_data* data, const doub
   }
   for (auto& e : v->ev)
     if (!e) BC_HIP(hipEventCreate(&e));
+  v->laid_out = false;      // (the slab may move below)
   // ---- the slab: [uploaded head] core | w | step | Sig0inv | b0 | Siginv   [device-only] mom1 | mom2 | grad | resid | Theta, saux |
   //      raw | trace | flag
   const size_t dd = (size_t)d * d;
@@ -177,11 +181,7 @@ extern "C" int bc_vi_optimize_begin(bc_ctx* ctx, const bc_data* data, const doub
   const double* th0 = sampler_params;
   const double* sig0inv = sampler_params + d;
   memcpy(h + o_s0, sig0inv, dd * sizeof(double));
-  for (int i = 0; i < d; ++i) {      // Sig0inv . th0
-    double acc = 0.;
-    for (int j = 0; j < d; ++j) acc = fma(sig0inv[(size_t)i * d + j], th0[j], acc);
-    h[o_b0 + i] = acc;
-  }
+  bc_vi_prior_rhs(sig0inv, th0, d, h + o_b0);
   double sigsq = 1.;
   if (gauss) memcpy(h + o_sg, sampler_params + d + dd, dd * sizeof(double));
   else sigsq = sampler_params[d + dd];
@@ -239,6 +239,8 @@ extern "C" int bc_vi_optimize_begin(bc_ctx* ctx, const bc_data* data, const doub
   v->done = 0;
   v->d = d;
   v->dz = dz;
+  v->nrsel = nrsel;
+  v->laid_out = true;
   v->scale = sum_scaling;
   v->dev_ms = 0.;
   v->d_w = v->dev + o_w;
@@ -356,6 +358,41 @@ extern "C" int bc_vi_optimize_end(bc_ctx* ctx, double* out_w, double* out_trace)
   BC_HIP(hipStreamSynchronize(ctx->stream));
   memcpy(out_w, v->pin, m * sizeof(double));
   if (out_trace) memcpy(out_trace, v->pin + even(m), (size_t)v->itrs * m * sizeof(double));
+  return BC_OK;
+}
+
+extern "C" int bc_vi_optimize_last_draw(bc_ctx* ctx, int32_t s, int32_t d, double* out_theta, double* out_saux, double* out_raw,
+                                        double* out_pad_max) {
+  if (!ctx || !out_theta || !out_pad_max) { bc_set_error("bc_vi_optimize_last_draw: bad argument"); return BC_INVALID_ARGUMENT; }
+  bc_viopt* v = ctx->viopt;
+  if (!v || !v->laid_out) { bc_set_error("bc_vi_optimize_last_draw: no run has been begun on this context"); return BC_INVALID_ARGUMENT; }
+  if (v->chunk_pending) { bc_set_error("bc_vi_optimize_last_draw: a chunk is pending (call bc_vi_optimize_chunk_end first)"); return BC_INVALID_ARGUMENT; }
+  if (s != v->s || d != v->d) {
+    bc_set_error("bc_vi_optimize_last_draw: the last run had S = %d, D = %d, not S = %d, D = %d", v->s, v->d, s, d);
+    return BC_INVALID_ARGUMENT;
+  }
+  BC_HIP(hipSetDevice(ctx->device));
+  const size_t dk = (size_t)v->va.dk, nr = (size_t)v->nrsel, n_th = nr * dk + nr, n_raw = (size_t)s * d;
+  std::vector<double> h(n_th + n_raw);      // Theta [nrsel][dk] | saux [nrsel] (contiguous in the slab), then raw [s][d]
+  BC_HIP(hipStreamSynchronize(ctx->stream));
+  BC_HIP(hipMemcpy(h.data(), v->va.theta, n_th * sizeof(double), hipMemcpyDeviceToHost));
+  BC_HIP(hipMemcpy(h.data() + n_th, v->va.raw, n_raw * sizeof(double), hipMemcpyDeviceToHost));
+  double pad = 0.;
+  bool pad_nan = false;
+  for (size_t q = 0; q < nr; ++q) {
+    for (size_t c = 0; c < dk; ++c) {
+      const double x = h[q * dk + c];
+      if (q < (size_t)s && c < (size_t)d) { out_theta[q * d + c] = x; continue; }
+      if (x != x) pad_nan = true;
+      else if (fabs(x) > pad) pad = fabs(x);
+    }
+    const double x = h[nr * dk + q];
+    if (q < (size_t)s) { if (out_saux) out_saux[q] = x; continue; }
+    if (x != x) pad_nan = true;
+    else if (fabs(x) > pad) pad = fabs(x);
+  }
+  if (out_raw) memcpy(out_raw, h.data() + n_th, n_raw * sizeof(double));
+  *out_pad_max = pad_nan ? NAN : pad;
   return BC_OK;
 }
 

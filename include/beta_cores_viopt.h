@@ -67,6 +67,19 @@ int bc_vi_optimize_end(bc_ctx* ctx, double* out_w, double* out_trace);
 /* GPU milliseconds of the chunks of the last run, between HIP events around each chunk's steps (upload excluded). */
 int bc_vi_optimize_device_ms(bc_ctx* ctx, double* out_ms);
 
+/* What the last executed k_vi_sampler of the most recent run left in that run's own buffers -- a seam for tests of the draw;
+ * nothing is launched.  Valid once a run has been begun and no chunk is pending: after _chunk_end and after _end, until the next
+ * _begin (before the run's first chunk everything reads 0).  Refused with BC_INVALID_ARGUMENT when no run has ever been begun on
+ * the context, while a chunk is pending, and when s / d are not that run's S / D.
+ *   out_theta: s x d, rows < S and columns < D of the zero-padded Theta block K1 reads (Gaussian kind: Theta' = Theta . Siginv^T).
+ *   out_saux: s, or NULL (Gaussian kind: theta^T Siginv theta per sample; else 0).
+ *   out_raw: s x d, or NULL (Gaussian kind: the draw before Siginv is applied; else 0).
+ *   out_pad_max: the largest |value| of every OTHER element of that block and of the rows >= S of saux (NaN if one of them is
+ *     NaN).  _begin zero-fills them, the kernel never writes there and K1 relies on it: anything but 0 is a defect.
+ * After a run that failed in its first step (BC_NUMERICAL_PRECISION) all of it reads 0: the sampler writes nothing then. */
+int bc_vi_optimize_last_draw(bc_ctx* ctx, int32_t s, int32_t d, double* out_theta, double* out_saux, double* out_raw,
+                             double* out_pad_max);
+
 /* The whole run in one call: the four above, chunk after chunk.  chunk_steps: 0 = bc_vi_optimize_auto_chunk.
  *   out_w: m (left alone unless the call returns BC_OK).   out_trace: opt_itrs x m, the weights after every step, or NULL. */
 int bc_vi_optimize(bc_ctx* ctx, const bc_data* data, const double* core_rows, int64_t m, int model, const double* params,

@@ -7,6 +7,7 @@ deviations seen are recorded in profiles/vi_optimize_notes.md."""
 import numpy as np
 import pytest
 
+import vi_sampler_cases as vc
 from conftest import load_golden
 from oracle import coreset_ref as C
 from oracle import models_ref as M
@@ -35,9 +36,11 @@ def gauss_rows(n, d, seed):
     return rng.randn(n, d) * 2. + 1.
 
 
-def make_alg(bc, kind, rows, dd, S, m, seed, nsub, device, sched=None, itrs=ITRS, Sig0_sign=1., w_scale=None):
+def make_alg(bc, kind, rows, dd, S, m, seed, nsub, device, sched=None, itrs=ITRS, Sig0_sign=1., w_scale=None, th0=None, Sig0inv=None,
+             sigsq=1.0, mu0=None):
     """A coreset of m given rows with weights w0, ready for _optimize().  kind: 'svi' / 'bcores' (linear regression, rows
-    [x, y]) or 'gauss' (SparseVI on the Gaussian location model).  The sampler draws its normals from RandomState(seed)."""
+    [x, y]) or 'gauss' (SparseVI on the Gaussian location model).  The sampler draws its normals from RandomState(seed).
+    The prior: th0 (linear regression) / mu0 (Gaussian) default to 0, Sig0inv to Sig0_sign * I, sigsq to 1."""
     n, dz = rows.shape
     rng = np.random.RandomState(seed + 77)
     if kind == 'gauss':
@@ -45,12 +48,14 @@ def make_alg(bc, kind, rows, dd, S, m, seed, nsub, device, sched=None, itrs=ITRS
         q = rng.randn(d, d)
         Siginv = np.linalg.inv(q.dot(q.T) / d + 2. * np.eye(d))
         Siginv = (Siginv + Siginv.T) / 2.
-        sampler = bc.samplers.GaussianPosteriorSampler(np.zeros(d), Sig0_sign * np.eye(d), Siginv, rng=np.random.RandomState(seed))
+        sampler = bc.samplers.GaussianPosteriorSampler(np.zeros(d) if mu0 is None else mu0, Sig0_sign * np.eye(d) if Sig0inv is None else Sig0inv,
+                                                       Siginv, rng=np.random.RandomState(seed))
         model = bc.likelihoods.GaussianLocation(Siginv, -np.linalg.slogdet(Siginv)[1])
     else:
         d = dz - 1
-        sampler = bc.samplers.LinregPosteriorSampler(np.zeros(d), Sig0_sign * np.eye(d), 1.0, rng=np.random.RandomState(seed))
-        model = bc.likelihoods.LinearRegression(1.0)
+        sampler = bc.samplers.LinregPosteriorSampler(np.zeros(d) if th0 is None else th0, Sig0_sign * np.eye(d) if Sig0inv is None else Sig0inv,
+                                                     sigsq, rng=np.random.RandomState(seed))
+        model = bc.likelihoods.LinearRegression(sigsq)
     kw = dict(opt_itrs=itrs, n_subsample_opt=nsub, device_optimize=device)
     if sched is not None:
         kw['step_sched'] = sched
@@ -106,6 +111,8 @@ def compare(host, dev, tag):
     with np.errstate(divide='ignore', invalid='ignore'):
         rel = np.where(ht != 0., np.abs(dt - ht) / np.abs(ht), np.abs(dt - ht))
     print('%s: worst relative deviation of the trace %.3e, of the final weights %.3e' % (tag, rel.max(), rel[-1].max()))
+    # (a weight below ATOL can be far off relatively and still inside the contract; this figure is <= 1 exactly when it holds)
+    print('%s: worst |device - host| / (ATOL + RTOL |host|) of the trace %.3e' % (tag, (np.abs(dt - ht) / (ATOL + RTOL * np.abs(ht))).max()))
     assert np.array_equal(dt[-1], dw)
     np.testing.assert_allclose(dt, ht, rtol=RTOL, atol=ATOL)
     np.testing.assert_allclose(dw, hw, rtol=RTOL, atol=ATOL)
@@ -319,10 +326,27 @@ class _FixedTheta:
         return 0, np.concatenate((np.zeros(D), np.eye(D).ravel(), [1.0]))
 
 
-@pytest.mark.parametrize('why', ['closure', 'encoder', 'groups', 'D129'])
+class _KindOfAnotherModel:
+    """A linear-regression sampler whose device_spec() claims the Gaussian kind (which goes with GaussianLocation only)."""
+
+    def __init__(self, inner):
+        self.inner = inner
+
+    def __call__(self, n, w, p):
+        return self.inner(n, w, p)
+
+    def _dim(self):
+        return self.inner._dim()
+
+    def device_spec(self):
+        D = self.inner._dim()
+        return 1, np.concatenate((np.zeros(D), np.eye(D).ravel(), np.eye(D).ravel()))
+
+
+@pytest.mark.parametrize('why', ['closure', 'encoder', 'groups', 'D129', 'S257', 'core60001', 'kind'])
 def test_not_covered_means_unchanged(bc, why):
     rng = np.random.RandomState(8)
-    n, D, S = 3000, (129 if why == 'D129' else 6), 32
+    n, D, S = 3000, (129 if why == 'D129' else 27 if why == 'core60001' else 6), (257 if why == 'S257' else 32)
     Z = linreg_rows(n, D, 50 + D)
     lin = bc.likelihoods.LinearRegression(1.0)
     kw = dict(opt_itrs=4, n_subsample_opt=100)
@@ -339,6 +363,8 @@ def test_not_covered_means_unchanged(bc, why):
             if why == 'closure':
                 inner = bc.samplers.LinregPosteriorSampler(np.zeros(D), np.eye(D), 1.0)
                 sampler = lambda sz, w, p: inner(sz, w, p)
+            elif why == 'kind':
+                sampler = _KindOfAnotherModel(bc.samplers.LinregPosteriorSampler(np.zeros(D), np.eye(D), 1.0))
             else:
                 sampler = bc.samplers.LinregPosteriorSampler(np.zeros(D), np.eye(D), 1.0)
             prj = bc.DeviceProjector(sampler, S, lin)
@@ -347,9 +373,16 @@ def test_not_covered_means_unchanged(bc, why):
         else:
             kw2 = kw
         alg = bc.SparseVICoreset(dd, prj, device_optimize=device, **kw2)
-        for m in range(3):
-            alg.build(1, 30)
-        if device and why in ('closure', 'encoder', 'D129'):      # asked directly, too: the projector declines
+        if why == 'core60001':      # m (dz + 1) = 2069 * 29 = 60001, one past the staging area: rows put in place, then one _optimize()
+            idcs = np.random.RandomState(5).choice(n, 2069, replace=False)
+            alg._append(list(idcs), Z[idcs])
+            alg.wts = np.random.RandomState(6).rand(2069) * (float(n) / 2069)
+            assert alg.pts.shape[0] * (alg.pts.shape[1] + 1) == 60001
+            alg._optimize()
+        else:
+            for m in range(3):
+                alg.build(1, 30)
+        if device and why in ('closure', 'encoder', 'D129', 'S257', 'core60001', 'kind'):      # asked directly, too: the projector declines
             assert prj.vi_optimize(dd, alg.pts, alg.wts, 4, lambda i: 1. / (1. + i), n_subsample=100, n_total=n) is None
         return alg.idcs.copy(), alg.wts.copy(), np.random.rand(), alg.device_optimize_calls
     off, on = build(False), build(True)
@@ -381,11 +414,11 @@ def test_precision_matrix_that_is_not_positive_definite_raises_and_leaves_the_co
 
 
 # ---------------------------------------------------------------- the one-call export, and its index check
-def _one_call_args(bc, nsub, itrs=7, seed=5):
+def _one_call_args(bc, nsub, itrs=7, seed=5, **prior):
     """Everything bc_vi_optimize takes for the problem of the chunk-boundary test, drawn the way vi_optimize draws."""
     from beta_cores_amd.util.opt import adam_step_arrays
     rows, dd = resident(bc, ('lin', 9000, 8), lambda: linreg_rows(9000, 8, 18))
-    alg = make_alg(bc, 'svi', rows, dd, 64, 20, seed, nsub, device=True, itrs=itrs)
+    alg = make_alg(bc, 'svi', rows, dd, 64, 20, seed, nsub, device=True, itrs=itrs, **prior)
     prj, S, D, n = alg.ll_projector, 64, 8, rows.shape[0]
     np.random.seed(seed)
     E = np.empty((itrs, S, D))
@@ -460,3 +493,219 @@ def test_zero_steps_take_the_host_loop(bc):
     w0 = alg.wts.copy()
     alg._optimize()
     assert alg.device_optimize_calls == 0 and np.array_equal(alg.wts, w0)
+
+
+# ---------------------------------------------------------------- the draw itself, read back from the run's slab
+# One-step runs of vi_optimize, then vi_last_draw(): what k_vi_sampler left for K1 from (coreset rows, w0, E[0]) against the
+# formulas in long double (vi_sampler_cases.reference_ld), under the bound of tests/test_vi_sampler_cpu.py.  The data rows do not
+# enter the draw, so they are 3000 resident rows per (kind, D).  Ratios seen are recorded in profiles/vi_optimize_notes.md.
+DRAW_DIMS = (1, 2, 3, 16, 33, 64, 127, 128)
+DRAW_SHAPES = ((1, 1), (7, 5), (130, 100), (300, 256))      # (m, S); m (dz + 1) <= 39 000
+
+
+def draw_data(bc, kind, D):
+    if kind == vc.GAUSS:
+        return resident(bc, ('gauss', 3000, D), lambda: gauss_rows(3000, D, 4))[1]
+    return resident(bc, ('lin', 3000, D), lambda: linreg_rows(3000, D, 10 + D))[1]
+
+
+def draw_projector(bc, c):
+    """A projector whose sampler holds case c's prior and hands out c['E'] as its next normals."""
+    if c['kind'] == vc.GAUSS:
+        sampler = bc.samplers.GaussianPosteriorSampler(c['th0'], c['Sig0inv'], c['Siginv'], rng=np.random.RandomState(0))
+        model = bc.likelihoods.GaussianLocation(c['Siginv'], -np.linalg.slogdet(c['Siginv'])[1])
+    else:
+        sampler = bc.samplers.LinregPosteriorSampler(c['th0'], c['Sig0inv'], c['sigsq'], rng=np.random.RandomState(0))
+        model = bc.likelihoods.LinearRegression(c['sigsq'])
+    prj = bc.DeviceProjector(sampler, c['s'], model)
+    prj.sampler._rng = _FixedNormals(c['E'])
+    return prj
+
+
+def one_step_draw(bc, c, dd):
+    prj = draw_projector(bc, c)
+    assert prj.vi_optimize(dd, c['rows'], c['w'], 1, lambda i: 1.) is not None and prj.vi_optimize_calls == 1
+    return prj.vi_last_draw()
+
+
+def check_draw(c, draw, tag):
+    """The assertions on one draw; returns error / bound."""
+    d = c['d']
+    ref, kappa = vc.high_precision_reference(c)
+    bound = vc.draw_bound(d, kappa, ref)
+    got = draw['theta'] if c['kind'] == vc.LINREG else draw['raw']
+    err = np.abs(got - ref).max()
+    print('%s: max error %.3e, bound %.3e, ratio %.3f, kappa %.3e' % (tag, err, bound, err / bound, kappa))
+    assert err <= bound, (tag, err, bound)
+    assert draw['pad_max'] == 0.0, (tag, draw['pad_max'])
+    if c['kind'] == vc.GAUSS:
+        Si, raw = c['Siginv'], draw['raw']
+        scale = np.abs(Si).sum(axis=1).max() * np.abs(raw).max()
+        assert np.abs(draw['theta'] - raw.dot(Si.T)).max() <= 4. * d * 2. ** -53 * scale
+        assert np.abs(draw['saux'] - (raw * raw.dot(Si)).sum(axis=1)).max() <= 4. * d * 2. ** -53 * scale * d * np.abs(raw).max()
+    else:
+        assert not draw['saux'].any() and not draw['raw'].any()      # the linear-regression kind never touches them
+    return err / bound
+
+
+def same_bits(a, b):
+    return all(a[k].tobytes() == b[k].tobytes() for k in ('theta', 'saux', 'raw')) and a['pad_max'] == b['pad_max']
+
+
+@pytest.mark.parametrize('prior', ['identity', 'general'])
+@pytest.mark.parametrize('D', DRAW_DIMS)
+@pytest.mark.parametrize('kind', [vc.LINREG, vc.GAUSS], ids=['linreg', 'gauss'])
+def test_device_draw_matches_the_long_double_reference(bc, kind, D, prior):
+    dd = draw_data(bc, kind, D)
+    worst = 0.
+    for i, (m, S) in enumerate(DRAW_SHAPES):
+        c = vc.make_case(kind, D, m, S) if prior == 'identity' else vc.make_general_case(kind, D, m, S, variant=i + D)
+        draw = one_step_draw(bc, c, dd)
+        worst = max(worst, check_draw(c, draw, 'kind %d D %3d m %3d S %3d %s prior' % (kind, D, m, S, prior)))
+        assert same_bits(one_step_draw(bc, c, dd), draw), 'a second identical run gave other bits'
+    print('worst ratio on the device, kind %d, D = %d, %s prior: %.3f' % (kind, D, prior, worst))
+
+
+@pytest.mark.parametrize('kind', ['svi', 'gauss'])
+def test_last_draw_of_a_multi_step_run_is_drawn_from_the_weights_adam_just_wrote(bc, kind):
+    D, S, m, itrs = 16, 64, 20, 4
+    k = vc.GAUSS if kind == 'gauss' else vc.LINREG
+    rows, dd = resident(bc, ('gauss', 3000, D), lambda: gauss_rows(3000, D, 4)) if kind == 'gauss' else \
+        resident(bc, ('lin', 3000, D), lambda: linreg_rows(3000, D, 10 + D))
+    p = vc.make_general_case(k, D, 1, 1)
+    prior = dict(mu0=p['th0'], Sig0inv=p['Sig0inv']) if kind == 'gauss' else dict(th0=p['th0'], Sig0inv=p['Sig0inv'], sigsq=2.5)
+    alg = make_alg(bc, kind, rows, dd, S, m, 21, 200, device=True, itrs=itrs, **prior)
+    prj, E = alg.ll_projector, []
+    normals = prj.sampler._normals
+    prj.sampler._normals = lambda n, d: E.append(normals(n, d)) or E[-1]
+    np.random.seed(21)
+    w, trace = prj.vi_optimize(dd, alg.pts, alg.wts, itrs, alg.step_sched, n_subsample=200, n_total=rows.shape[0], want_trace=True)
+    assert len(E) == itrs and np.array_equal(trace[-1], w)
+    draw = prj.vi_last_draw()
+    c = {'kind': k, 'd': D, 'm': m, 's': S, 'rows': alg.pts, 'th0': p['th0'], 'Sig0inv': p['Sig0inv'], 'E': E[3], 'w': trace[2]}
+    if kind == 'gauss':
+        c['Siginv'] = prj.sampler.Siginv
+    else:
+        c['sigsq'] = 2.5
+    check_draw(c, draw, '%s, the fourth step of four' % kind)
+    # ... and from no other weights: the same normals with the weights of one step earlier are far outside the bound
+    ref, kappa = vc.high_precision_reference(c)
+    stale = vc.high_precision_reference(dict(c, w=trace[1]))[0]
+    assert np.abs(stale - ref).max() > 1e3 * vc.draw_bound(D, kappa, ref)
+
+
+@pytest.mark.parametrize('prior', ['identity', 'general'])
+@pytest.mark.parametrize('kind', [vc.LINREG, vc.GAUSS], ids=['linreg', 'gauss'])
+def test_all_zero_weights_draw_from_the_prior(bc, kind, prior):
+    """G = 0: Theta = (L L^T) Sig0inv th0 + E . L^T with L = chol(Sig0inv)^-1; with Sig0inv = I that is th0 + E, exactly."""
+    for D, m, S in ((3, 7, 5), (33, 130, 100)):
+        c = vc.make_case(kind, D, m, S) if prior == 'identity' else vc.make_general_case(kind, D, m, S, variant=1)
+        c['w'] = np.zeros(m)
+        draw = one_step_draw(bc, c, draw_data(bc, kind, D))
+        check_draw(c, draw, 'kind %d D %d, zero weights, %s prior' % (kind, D, prior))
+        if prior == 'identity':
+            assert np.array_equal(draw['theta'] if kind == vc.LINREG else draw['raw'], c['th0'] + c['E'])
+
+
+@pytest.mark.parametrize('what', ['not positive definite', 'NaN weight'])
+@pytest.mark.parametrize('kind', [vc.LINREG, vc.GAUSS], ids=['linreg', 'gauss'])
+def test_a_failed_first_step_leaves_the_draw_at_zero(bc, kind, what):
+    D, m, S = 16, 7, 5
+    dd = draw_data(bc, kind, D)
+    good = vc.make_general_case(kind, D, m, S)
+    first = one_step_draw(bc, good, dd)
+    assert np.abs(first['theta']).min() > 0.      # the slab of this shape held a draw just before
+    if what == 'NaN weight':
+        bad = vc.make_general_case(kind, D, m, S)
+        bad['w'][3] = np.nan
+    else:
+        bad = vc.make_case(kind, D, m, S, sig0_sign=-1.)
+        bad['w'] = bad['w'] * (0. if kind == vc.LINREG else 1e-3)
+    prj = draw_projector(bc, good)      # (the projector's constructor draws on the host: it takes the valid prior)
+    prj.sampler.Sig0inv, prj.sampler._rng = bad['Sig0inv'], _FixedNormals(bad['E'])
+    with pytest.raises(np.linalg.LinAlgError):
+        prj.vi_optimize(dd, bad['rows'], bad['w'], 1, lambda i: 1.)
+    assert prj.vi_optimize_calls == 0
+    draw = prj.vi_last_draw()
+    assert not draw['theta'].any() and not draw['saux'].any() and not draw['raw'].any() and draw['pad_max'] == 0.0
+    assert same_bits(one_step_draw(bc, good, dd), first)      # the next valid run is right
+
+
+def test_last_draw_is_refused_before_any_run_and_for_another_shape(bc):
+    import ctypes
+    from beta_cores_amd import _native as N
+    lib, out, pad = N.load(), np.full(4, -1.), ctypes.c_double(-1.)
+    p = lambda x: x.ctypes.data_as(ctypes.c_void_p)
+    fresh = bc.Context()
+    assert lib.bc_vi_optimize_last_draw(fresh.h, 2, 2, p(out), None, None, ctypes.byref(pad)) == N.BC_INVALID_ARGUMENT
+    assert 'no run has been begun' in N.last_error()
+    c = vc.make_case(vc.LINREG, 3, 7, 5)
+    prj = draw_projector(bc, c)
+    prj.vi_optimize(draw_data(bc, vc.LINREG, 3), c['rows'], c['w'], 1, lambda i: 1.)
+    assert lib.bc_vi_optimize_last_draw(prj.ctx.h, 2, 2, p(out), None, None, ctypes.byref(pad)) == N.BC_INVALID_ARGUMENT
+    assert 'S = 5, D = 3' in N.last_error() and np.all(out == -1.) and pad.value == -1.
+    th = np.empty((5, 3))      # saux and raw may be left out
+    assert lib.bc_vi_optimize_last_draw(prj.ctx.h, 5, 3, p(th), None, None, ctypes.byref(pad)) == N.BC_OK
+    assert np.array_equal(th, prj.vi_last_draw()['theta']) and pad.value == 0.0
+
+
+# ---------------------------------------------------------------- the loop with general priors
+def general_prior(kind, D, sigsq=0.37):
+    p = vc.make_general_case(vc.GAUSS if kind == 'gauss' else vc.LINREG, D, 1, 1)
+    if kind == 'gauss':
+        return dict(mu0=p['th0'], Sig0inv=p['Sig0inv'])
+    return dict(th0=p['th0'], Sig0inv=p['Sig0inv'], sigsq=sigsq)
+
+
+@pytest.mark.parametrize('nsub', [None, 50])
+@pytest.mark.parametrize('shape', [(3000, 3, 16, 7), (5000, 64, 100, 100)], ids=lambda s: 'n%d-D%d-S%d-m%d' % s)
+@pytest.mark.parametrize('kind', ['svi', 'bcores'])
+def test_general_prior_device_loop_equals_the_host_loop(bc, kind, shape, nsub):
+    n, D, S, m = shape
+    rows, dd = resident(bc, ('lin', n, D), lambda: linreg_rows(n, D, 10 + D))
+    args = (kind, rows, dd, S, m, 100 + D, nsub)
+    prior = general_prior(kind, D, sigsq=0.37 if nsub else 2.5)
+    compare(host_run(bc, *args, **prior), device_run(bc, *args, **prior), 'general prior %s n=%d D=%d S=%d m=%d nsub=%s' % (kind, n, D, S, m, nsub))
+
+
+@pytest.mark.parametrize('S', [64, 256])
+@pytest.mark.parametrize('d', [1, 33, 128])
+def test_general_prior_gaussian_location(bc, d, S):
+    rows, dd = resident(bc, ('gauss', 3000, d), lambda: gauss_rows(3000, d, 4))
+    args = ('gauss', rows, dd, S, 30, 11, 300)
+    prior = general_prior('gauss', d)
+    compare(host_run(bc, *args, **prior), device_run(bc, *args, **prior), 'general prior gaussian d=%d S=%d' % (d, S))
+
+
+def test_general_prior_one_call_export(bc):
+    from beta_cores_amd import _native as N
+    prior = general_prior('svi', 8, sigsq=2.5)
+    args = ('svi',) + resident(bc, ('lin', 9000, 8), lambda: linreg_rows(9000, 8, 18)) + (64, 20, 5, 200)
+    want = device_run(bc, *args, itrs=7, **prior)
+    compare(host_run(bc, *args, itrs=7, **prior), want, 'general prior, the chunked calls')
+    a = _one_call_args(bc, 200, **prior)
+    out, trace = np.full(20, -1.), np.full((7, 20), -1.)
+    assert _one_call(bc, a, 3, out, trace) == N.BC_OK, N.last_error()
+    assert np.array_equal(out, want[0]) and np.array_equal(trace, want[1])
+
+
+def test_upper_triangle_of_the_prior_precision_is_read_by_its_product_with_th0_only(bc):
+    """Host and device factor the LOWER triangle of Sig0inv + G / sigsq and take Sig0inv . th0 with the full matrix."""
+    rows, dd = resident(bc, ('lin', 9000, 8), lambda: linreg_rows(9000, 8, 18))
+    args = ('svi', rows, dd, 64, 20, 5, 200)
+    prior = general_prior('svi', 8, sigsq=2.5)
+    prior['Sig0inv'] = prior['Sig0inv'] + np.triu(np.random.RandomState(3).randn(8, 8) * 0.05, 1)
+    host = host_run(bc, *args, **prior)
+    compare(host, device_run(bc, *args, **prior), 'asymmetric Sig0inv')
+    sym = dict(prior, Sig0inv=np.tril(prior['Sig0inv']) + np.tril(prior['Sig0inv'], -1).T)
+    assert not np.allclose(host_run(bc, *args, **sym)[1], host[1], rtol=1e-3, atol=0.)      # (the perturbation is not lost in rounding)
+
+
+# ---------------------------------------------------------------- the largest coresets the staging area takes
+@pytest.mark.parametrize('shape', [(3000, 128, 64, 461), (20000, 1, 16, 20000)], ids=lambda s: 'n%d-D%d-S%d-m%d' % s)
+def test_largest_accepted_coreset_runs_on_the_device(bc, shape):
+    n, D, S, m = shape
+    assert m * (D + 2) <= 60000 < (m + 1) * (D + 2)
+    rows, dd = resident(bc, ('lin', n, D), lambda: linreg_rows(n, D, 10 + D))
+    args = ('svi', rows, dd, S, m, 100 + D, 50)
+    compare(host_run(bc, *args), device_run(bc, *args), 'largest coreset D=%d m=%d' % (D, m))

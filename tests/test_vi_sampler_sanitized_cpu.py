@@ -24,6 +24,16 @@ def test_sanitized_draw_ends_clean(harness, tmp_path, kind, d, m, s):
     assert vc.run_sampler(harness, bad, tmp_path)[0] == 1
 
 
+@pytest.mark.parametrize('kind', [vc.LINREG, vc.GAUSS])
+def test_sanitized_general_prior_draw_ends_clean(harness, tmp_path, kind):
+    """A dense Sig0inv and th0 != 0 (bc_vi_prior_rhs runs in the harness), scaled weights, nearly collinear columns."""
+    c = vc.make_general_case(kind, 33, 130, 5, variant=4)
+    status, theta, pad, _, raw = vc.run_sampler(harness, c, tmp_path)
+    ref, kappa = vc.high_precision_reference(c)
+    assert status == 0 and np.all(pad == 7.0)
+    assert np.abs((theta if kind == vc.LINREG else raw) - ref).max() <= vc.draw_bound(33, kappa, ref)
+
+
 def test_sanitized_adam_ends_clean(harness, tmp_path):
     rng = np.random.RandomState(2)
     out = vc.run_adam(harness, rng.rand(9) + .1, rng.randn(9), rng.rand(9), adam_step_arrays(12, lambda i: 1. / (1. + i)), tmp_path)

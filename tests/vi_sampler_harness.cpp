@@ -2,7 +2,8 @@
 // the device's, so the posterior draw and the ADAM body can be checked against the oracle without a GPU
 // (tests/test_vi_sampler_cpu.py).  Files are raw doubles.
 //   vi_sampler_harness sampler IN OUT
-//     IN : kind, d, m, s, then core[m][dz], w[m], Sig0inv[d][d], b0[d], (kind 0: sigsq | kind 1: Siginv[d][d]), E[s][d]
+//     IN : kind, d, m, s, then core[m][dz], w[m], Sig0inv[d][d], th0[d], (kind 0: sigsq | kind 1: Siginv[d][d]), E[s][d]
+//          (b0 = Sig0inv . th0 is formed here by bc_vi_prior_rhs, the function bc_vi_optimize_begin calls)
 //     OUT: status, then (status 0) theta[s][dk] with dk = d + 3 (the padding keeps the 7.0 it was filled with), saux[s], raw[s][d]
 //   vi_sampler_harness adam IN OUT
 //     IN : m, itrs, q[m], c[m], x0[m], step[3][itrs]          gradient of the separable quadratic: g = q * x - c
@@ -52,7 +53,9 @@ static int run_sampler(const std::vector<double>& in, std::vector<double>* out) 
   a.core = p; p += (size_t)m * dz;
   a.w = p; p += m;
   a.sig0inv = p; p += dd;
-  a.b0 = p; p += d;
+  std::vector<double> b0(d, 0.);
+  bc_vi_prior_rhs(a.sig0inv, p, d, b0.data()); p += d;
+  a.b0 = b0.data();
   if (kind == BC_VIS_GAUSS) { a.siginv = p; p += dd; } else { a.sigsq = *p; p += 1; }
   a.E = p;
   std::vector<double> theta((size_t)s * dk, 7.0), saux(s, 0.), raw((size_t)s * d, 0.), ws(BC_VIS_WS_DOUBLES(d), 0.);
