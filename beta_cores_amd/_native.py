@@ -78,6 +78,7 @@ _SIGNATURES = {
     'bc_snnls_bind_comm': [vp, vp],
     'bc_snnls_prefilter_active': [vp, c_ip],
     'bc_snnls_prefilter_form': [vp, c_ip],
+    'bc_snnls_finish_form': [vp, c_ip],
     'bc_snnls_prefilter_fallbacks': [vp, C.POINTER(C.c_int64)],
     'bc_snnls_prefilter_stats': [vp, c_i64p, c_i64p, c_i64p],
     'bc_snnls_prefilter_levels': [vp, c_i64p, c_i64p, c_i64p],

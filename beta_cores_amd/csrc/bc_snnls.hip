@@ -145,6 +145,9 @@ struct bc_snnls {
   int consec_overflow = 0;
   bool dev_refit = false;         // bc_snnls_device_refit: an OrthoPursuit handle runs the fused loop with the device NNLS refit
   void* nnls_slab = nullptr;      // gram | gram_c | nnls_stats
+  bool no_pf = false;             // BC_FINISH_NOPF / BC_FINISH_NOFUSE as the environment had them at creation: no one-round
+  bool no_fuse = false;           // finish kernel / no rescoring inside it (tests and A/B measurements choose the form with them)
+  int finish_form = 0;            // BC_FINISH_* of the last step_finish (bc_snnls_finish_form)
 };
 
 // ------------------------------------------------------------------ device building blocks (single block)
@@ -644,6 +647,176 @@ __device__ bool dev_records_overflow(const double* cand_all, int world, int rec_
   return ovf != 0;
 }
 
+// ------------------------------------------------------------------ device NNLS refit (OrthoPursuit, optimize())
+#include "bc_nnls_dev.h"
+#define BC_ST_LIST_LIMIT 100      // last_status of k_refit: the list would outgrow BC_NNLS_MAXP (the host words the error)
+
+// would column f find a slot (dev_omp_place below): it is listed, or a slot has weight 0, or the list may grow
+__device__ bool dev_omp_room(const SnnlsDev& P, const SnnlsState& S, long long f, long long limit) {
+  __shared__ int room;
+  const long long nnz = S.nnz;
+  if (threadIdx.x == 0) room = nnz < limit ? 1 : 0;
+  __syncthreads();
+  for (long long j = threadIdx.x; j < nnz; j += blockDim.x)
+    if (P.idx[j] == f || !(P.val[j] > 0.)) room = 1;
+  __syncthreads();
+  return room != 0;
+}
+
+// orthopursuit.py:38 `w[f] = 1` on the sparse list: make sure the picked column (S.sel_f, in P.xf) has a slot -- with weight
+// 0 when it is new: the refit lets it enter.  A slot whose weight is 0 is reused before the list grows.  Returns the slot, or
+// -1 when the list is full; *fresh: the slot's column was (re)written, so its Gram row is stale (the callers go straight on to
+// dev_gram_update, which recomputes it).
+__device__ long long dev_omp_place(const SnnlsDev& P, SnnlsState& S, long long limit, int* fresh) {
+  __shared__ int hit, zero;
+  const int s = P.s;
+  const long long f = S.sel_f, nnz = S.nnz;
+  if (threadIdx.x == 0) { hit = INT_MAX; zero = INT_MAX; }
+  __syncthreads();
+  for (long long j = threadIdx.x; j < nnz; j += blockDim.x) {
+    if (P.idx[j] == f) atomicMin(&hit, (int)j);
+    else if (!(P.val[j] > 0.)) atomicMin(&zero, (int)j);
+  }
+  __syncthreads();
+  *fresh = 0;
+  if (hit != INT_MAX) return hit;
+  const long long at = zero != INT_MAX ? (long long)zero : nnz;
+  if (at == nnz && at >= limit) return -1;
+  for (int k = threadIdx.x; k < s; k += blockDim.x) P.cols[(size_t)at * s + k] = P.xf[k];
+  if (threadIdx.x == 0) {
+    P.idx[at] = f;
+    P.val[at] = 0.;
+    P.colnorm[at] = S.sel_norm;
+    if (at == nnz) S.nnz = at + 1;
+  }
+  __syncthreads();
+  *fresh = 1;
+  return at;
+}
+
+// bring the Gram state up to the list: entries [covered, n) are new to it (covered = P.nnls_stats[3], never trusted beyond
+// the list as it was when this kernel started), and so is a slot below them that was reused in this kernel
+__device__ void dev_gram_update(const SnnlsDev& P, long long nnz0, long long n, long long at, int fresh) {
+  const long long covered = P.nnls_stats[3];
+  const long long from = covered < nnz0 ? covered : nnz0;
+  __syncthreads();                 // every thread has read the mark before thread 0 moves it
+  if (from < n) bc_nnls_gram_rows(P.cols, P.s, P.b, P.gram, P.gram_c, (int)n, (int)from, (int)n);
+  if (fresh && at < from) bc_nnls_gram_rows(P.cols, P.s, P.b, P.gram, P.gram_c, (int)n, (int)at, (int)at + 1);
+  if (threadIdx.x == 0) P.nnls_stats[3] = n;
+}
+
+// ------------------------------------------------------------------ stages of one guarded greedy iteration (snnls.py:41-74)
+// Written once for the finish kernels below: the kernels differ in where the vectors and the list live and in the reweight in
+// the middle, not in the guard, the retry rule or the close -- which is what keeps the fused loop and its forms bit-identical.
+
+// the five S-vectors into dynamic LDS: P points there, b / bn / xw are copied in (the caller's barrier publishes them)
+__device__ __forceinline__ void fin_stage_vecs(SnnlsDev& P, const SnnlsDev& P0, double* vec_lds) {
+  const int s = P.s;
+  P.b = vec_lds;
+  P.bn = vec_lds + s;
+  P.xw = vec_lds + 2 * s;
+  P.xf = vec_lds + 3 * s;
+  P.xw_prev = vec_lds + 4 * s;
+  for (int k = threadIdx.x; k < s; k += blockDim.x) {
+    P.b[k] = P0.b[k];
+    P.bn[k] = P0.bn[k];
+    P.xw[k] = P0.xw[k];
+  }
+}
+
+// snnls.py:32-34 / :73-74: over the limit, or a pending exact redo: the step consumes nothing
+__device__ __forceinline__ bool fin_idle(const SnnlsState& S) { return S.reached_limit || S.pf_overflow; }
+
+// a pre-filter's candidate lists overflowed in this step: mark it (sticky until the host's exact redo) and consume nothing
+__device__ __forceinline__ void fin_refuse_overflow(SnnlsState& S, SnnlsState* st) {
+  if (threadIdx.x == 0) { S.pf_overflow = 1; S.skip = 1; *st = S; }
+}
+
+// the winner (column -> P.xf, index -> f); returns 1 when _select raised or nothing is selectable
+template <int ALG>
+__device__ __forceinline__ int fin_pick(const SnnlsDev& P, SnnlsState& S, double* red, long long& f) {
+  int fail = S.select_fail;                          // _select raised
+  f = -1;
+  if (!fail) {
+    if (ALG != BC_ALG_OMP && P.fuse_winner) dev_pick_blocks(P, S);
+    else dev_pick<ALG>(P, S, red);
+    if (!S.sel_valid) fail = 1;
+    f = S.sel_f;
+  }
+  return fail;
+}
+
+// what a revert puts back (snnls.py:46-47)
+struct FinSaved {
+  long long nnz0, npos0;
+  double err0, xwsq0;
+};
+__device__ __forceinline__ FinSaved fin_save(const SnnlsState& S) { return {S.nnz, S.npos, S.err_cur, S.xw_sq}; }
+
+// ... and the vectors: xw -> xw_prev, and val -> prev_val where the kernel reweights the global list in place (LIST).  (No
+// barrier needed: each thread later rewrites exactly the val[j] it saved, and xw is only overwritten behind dev_xw_err's barriers)
+template <bool LIST>
+__device__ __forceinline__ void fin_keep_prev(const SnnlsDev& P, long long nnz0) {
+  if (LIST)
+    for (long long j = threadIdx.x; j < nnz0; j += blockDim.x) P.prev_val[j] = P.val[j];
+  for (int k = threadIdx.x; k < P.s; k += blockDim.x) P.xw_prev[k] = P.xw[k];
+}
+
+// the monotone-error guard (snnls.py:58-62) behind a reweight: returns 1 after reverting a step that raised the error
+template <bool LIST>
+__device__ __forceinline__ int fin_guard(const SnnlsDev& P, SnnlsState& S, const FinSaved& sv, bool guard) {
+  int fail = 0;
+  if (guard) {
+    if (S.err_cur > sv.err0) {                       // snnls.py:58-61
+      if (LIST)
+        for (long long j = threadIdx.x; j < sv.nnz0; j += blockDim.x) P.val[j] = P.prev_val[j];
+      for (int k = threadIdx.x; k < P.s; k += blockDim.x) P.xw[k] = P.xw_prev[k];
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        S.nnz = sv.nnz0;
+        S.npos = sv.npos0;
+        S.err_cur = sv.err0;
+        S.xw_sq = sv.xwsq0;
+      }
+      fail = 1;
+    } else if (threadIdx.x == 0) {
+      S.retried = 0;                                 // snnls.py:62
+    }
+    __syncthreads();
+  }
+  return fail;
+}
+
+// retry-once-then-stop (snnls.py:63-72), the trace entry, the next sweep vectors, and xw back to global memory where it
+// lived in LDS
+template <int ALG>
+__device__ __forceinline__ void fin_close(const SnnlsDev& P, SnnlsState& S, double* red, int fail, long long f, double* xw_out) {
+  __shared__ int sh_fail;
+  if (threadIdx.x == 0) {
+    if (fail) {
+      if (S.retried) S.reached_limit = 1;
+      else S.retried = 1;
+    }
+    sh_fail = fail;
+  }
+  __syncthreads();
+  FSTAMP(7);
+  dev_trace(P, S, f, sh_fail);
+  __syncthreads();
+  dev_prep<ALG>(P, S, red);
+  FSTAMP(8);
+  if (xw_out)
+    for (int k = threadIdx.x; k < P.s; k += blockDim.x) xw_out[k] = P.xw[k];
+}
+
+// the picked column lived in LDS: a later step-wise reweight / refit must fetch it again
+__device__ __forceinline__ void fin_store_state(SnnlsState& S, SnnlsState* st) {
+  if (threadIdx.x == 0) {
+    S.sel_valid = 0;
+    *st = S;
+  }
+}
+
 // ------------------------------------------------------------------ kernels (grid = 1 block)
 template <int ALG>
 __global__ __launch_bounds__(BC_FIN_THREADS) void k_prep(SnnlsDev P, int reset_retry) {
@@ -661,91 +834,61 @@ __global__ __launch_bounds__(BC_FIN_THREADS) void k_prep(SnnlsDev P, int reset_r
 // one guarded greedy iteration, snnls.py:41-74.  The S-vectors (b, bn, xw, xf, previous xw) live in
 // LDS for the duration of the kernel (lds_vecs != 0): one parallel load at the start instead of a
 // global-memory round trip per use.
+// ALG == BC_ALG_OMP (orthopursuit.py:17-41): the closed-form step in the middle is replaced by "give the picked column a slot,
+// extend the Gram state, NNLS refit", whose workspace sits in front of the vectors in dynamic LDS; the winner comes from the
+// gathered candidate record(s).
 template <int ALG>
 __global__ __launch_bounds__(BC_FIN_THREADS) void k_step_finish(SnnlsDev P0, int lds_vecs) {
-  extern __shared__ double vec_lds[];
+  extern __shared__ double fin_lds[];
   __shared__ SnnlsState S;
   __shared__ double red[64];
-  __shared__ int sh_fail;
+  constexpr bool OMP = ALG == BC_ALG_OMP;
   if (threadIdx.x == 0) S = *P0.st;
   SnnlsDev P = P0;
-  const int s = P.s;
-  if (lds_vecs) {
-    P.b = vec_lds;
-    P.bn = vec_lds + s;
-    P.xw = vec_lds + 2 * s;
-    P.xf = vec_lds + 3 * s;
-    P.xw_prev = vec_lds + 4 * s;
-    for (int k = threadIdx.x; k < s; k += blockDim.x) {
-      P.b[k] = P0.b[k];
-      P.bn[k] = P0.bn[k];
-      P.xw[k] = P0.xw[k];
-    }
-  }
+  if (lds_vecs) fin_stage_vecs(P, P0, fin_lds + (OMP ? BC_NNLS_WS_DOUBLES : 0));
   __syncthreads();
-  if (S.reached_limit || S.pf_overflow) return;      // snnls.py:32-34 / :73-74; a pending exact redo consumes nothing
-  if (!P.fuse_winner && !S.select_fail && dev_records_overflow(P0.cand_all, P.world, P.rec_len)) {
-    if (threadIdx.x == 0) { S.pf_overflow = 1; S.skip = 1; *P0.st = S; }
+  if (fin_idle(S)) return;
+  if ((OMP || !P.fuse_winner) && !S.select_fail && dev_records_overflow(P0.cand_all, P.world, P.rec_len)) {
+    fin_refuse_overflow(S, P0.st);
     return;
   }
-  const bool guard = S.npos > 0;                     // snnls.py:44-45 (check_error_monotone is True for GIGA/FW)
-  int fail = S.select_fail;                          // _select raised
-  long long f = -1;
+  const bool guard = S.npos > 0;                     // snnls.py:44-45 (check_error_monotone is True for GIGA/FW/OMP)
+  long long f;
+  int fail = fin_pick<ALG>(P, S, red, f);
   if (!fail) {
-    if (P.fuse_winner) dev_pick_blocks(P, S);
-    else dev_pick<ALG>(P, S, red);
-    if (!S.sel_valid) fail = 1;
-    f = S.sel_f;
-  }
-  if (!fail) {
-    double alpha = 0., beta = 0.;
-    fail = dev_step_sizes<ALG>(P, S, red, alpha, beta);
-    if (!fail) {
-      // keep what is needed to revert (snnls.py:46-47)
-      const long long nnz0 = S.nnz, npos0 = S.npos;
-      const double err0 = S.err_cur, xwsq0 = S.xw_sq;
-      // (no barrier needed here: each thread later rescales exactly the val[j] it saved, and xw is only
-      //  overwritten behind dev_xw_err's barriers)
-      for (long long j = threadIdx.x; j < nnz0; j += blockDim.x) P.prev_val[j] = P.val[j];
-      for (int k = threadIdx.x; k < s; k += blockDim.x) P.xw_prev[k] = P.xw[k];
-      dev_apply(P, S, alpha, beta);
-      dev_xw_err(P, S, red);
-      if (guard) {
-        if (S.err_cur > err0) {                      // snnls.py:58-61
-          for (long long j = threadIdx.x; j < nnz0; j += blockDim.x) P.val[j] = P.prev_val[j];
-          for (int k = threadIdx.x; k < s; k += blockDim.x) P.xw[k] = P.xw_prev[k];
-          __syncthreads();
-          if (threadIdx.x == 0) {
-            S.nnz = nnz0;
-            S.npos = npos0;
-            S.err_cur = err0;
-            S.xw_sq = xwsq0;
-          }
-          fail = 1;
-        } else if (threadIdx.x == 0) {
-          S.retried = 0;                             // snnls.py:62
-        }
+    FinSaved sv;
+    if constexpr (OMP) {
+      sv = fin_save(S);
+      const long long limit = P.cap < BC_NNLS_MAXP ? P.cap : BC_NNLS_MAXP;
+      int fresh = 0;
+      const long long at = sv.nnz0 <= BC_NNLS_MAXP ? dev_omp_place(P, S, limit, &fresh) : -1;
+      if (at < 0) {                                  // the host's bound on the list length was wrong: refuse
+        if (threadIdx.x == 0) { S.overflow = 1; *P0.st = S; }
+        return;
+      }
+      fin_keep_prev<true>(P, sv.nnz0);
+      dev_gram_update(P, sv.nnz0, S.nnz, at, fresh);
+      fail = bc_nnls_solve(P.gram, P.gram_c, (int)S.nnz, P.val, (int)at, 0, P.bnorm, bc_nnls_ws(fin_lds), P.nnls_stats);
+      if (fail) {                                    // like a NumericalPrecisionError out of _reweight: w was not touched
+        if (threadIdx.x == 0) S.nnz = sv.nnz0;
         __syncthreads();
       }
+    } else {
+      double alpha = 0., beta = 0.;
+      fail = dev_step_sizes<ALG>(P, S, red, alpha, beta);
+      if (!fail) {
+        sv = fin_save(S);
+        fin_keep_prev<true>(P, sv.nnz0);
+        dev_apply(P, S, alpha, beta);
+      }
+    }
+    if (!fail) {
+      dev_xw_err(P, S, red);
+      fail = fin_guard<true>(P, S, sv, guard);
     }
   }
-  if (threadIdx.x == 0) {
-    if (fail) {                                      // snnls.py:63-72
-      if (S.retried) S.reached_limit = 1;
-      else S.retried = 1;
-    }
-    sh_fail = fail;
-  }
-  __syncthreads();
-  dev_trace(P, S, f, sh_fail);
-  __syncthreads();
-  dev_prep<ALG>(P, S, red);
-  if (lds_vecs)
-    for (int k = threadIdx.x; k < s; k += blockDim.x) P0.xw[k] = P.xw[k];
-  if (threadIdx.x == 0) {
-    S.sel_valid = 0;      // the picked column lived in LDS: a later step-wise reweight must fetch it again
-    *P0.st = S;
-  }
+  fin_close<ALG>(P, S, red, fail, f, lds_vecs ? P0.xw : nullptr);
+  fin_store_state(S, P0.st);
 }
 
 // The same step with ONE round of global loads up front: state, S-vectors, all candidate records (with their
@@ -766,7 +909,6 @@ __global__ __launch_bounds__(BC_FIN_THREADS) void k_step_finish_pf(SnnlsDev P0, 
   extern __shared__ double pf_lds[];
   __shared__ SnnlsState S;
   __shared__ double red[64];
-  __shared__ int sh_fail;
   const int s = P0.s;
   const int nrec = RS ? P0.rec_len : (P0.fuse_winner ? 0 : P0.world * P0.rec_len);
   FSTAMP(0);
@@ -852,7 +994,7 @@ __global__ __launch_bounds__(BC_FIN_THREADS) void k_step_finish_pf(SnnlsDev P0, 
   // then has nothing to copy (and no barrier to pass)
   if (RS && ALG != BC_ALG_OMP) P.xf = l_rec + BC_REC_HDR;
   FSTAMP(1);
-  if (S.reached_limit || S.pf_overflow) return;      // snnls.py:32-34 / :73-74; a pending exact redo consumes nothing
+  if (fin_idle(S)) return;
   bool pf_ovf = false;
   if (RS) {
     if (RS == 2) {
@@ -866,7 +1008,7 @@ __global__ __launch_bounds__(BC_FIN_THREADS) void k_step_finish_pf(SnnlsDev P0, 
     pf_ovf = dev_records_overflow(l_rec, P.world, P.rec_len);
   }
   if (pf_ovf) {
-    if (threadIdx.x == 0) { S.pf_overflow = 1; S.skip = 1; *P0.st = S; }
+    fin_refuse_overflow(S, P0.st);
     return;
   }
   if (S.nnz > nnz_hint) {                            // the host's bound on the list length was wrong: refuse
@@ -874,73 +1016,34 @@ __global__ __launch_bounds__(BC_FIN_THREADS) void k_step_finish_pf(SnnlsDev P0, 
     return;
   }
   const bool guard = S.npos > 0;                     // snnls.py:44-45
-  int fail = S.select_fail;                          // _select raised
-  long long f = -1;
   bool wrote = false;
-  const long long nnz0 = S.nnz, npos0 = S.npos;
-  const double err0 = S.err_cur, xwsq0 = S.xw_sq;
-  if (!fail) {
-    if (P.fuse_winner) dev_pick_blocks(P, S);
-    else dev_pick<ALG>(P, S, red);
-    if (!S.sel_valid) fail = 1;
-    f = S.sel_f;
-  }
+  const FinSaved sv = fin_save(S);
+  long long f;
+  int fail = fin_pick<ALG>(P, S, red, f);
   FSTAMP(3);
   if (!fail) {
     double alpha = 0., beta = 0.;
     fail = dev_step_sizes<ALG>(P, S, red, alpha, beta);
     FSTAMP(4);
     if (!fail) {
-      for (int k = threadIdx.x; k < s; k += blockDim.x) P.xw_prev[k] = P.xw[k];
+      fin_keep_prev<false>(P, sv.nnz0);
       dev_apply(P, S, alpha, beta);                  // on the LDS copy of (val, idx); a new column goes to global cols
       FSTAMP(5);
-      const long long at_new = (S.nnz == nnz0 + 1) ? nnz0 : -1;
+      const long long at_new = (S.nnz == sv.nnz0 + 1) ? sv.nnz0 : -1;
       dev_xw_err_t<true>(P, S, red, c16, at_new);
       FSTAMP(6);
-      wrote = true;
-      if (guard) {
-        if (S.err_cur > err0) {                      // snnls.py:58-61: nothing was written back yet, just drop it
-          for (int k = threadIdx.x; k < s; k += blockDim.x) P.xw[k] = P.xw_prev[k];
-          __syncthreads();
-          if (threadIdx.x == 0) {
-            S.nnz = nnz0;
-            S.npos = npos0;
-            S.err_cur = err0;
-            S.xw_sq = xwsq0;
-          }
-          fail = 1;
-          wrote = false;
-        } else if (threadIdx.x == 0) {
-          S.retried = 0;                             // snnls.py:62
-        }
-        __syncthreads();
-      }
+      fail = fin_guard<false>(P, S, sv, guard);      // nothing was written back yet: a revert just drops the LDS list
+      wrote = !fail;
     }
   }
-  if (threadIdx.x == 0) {
-    if (fail) {                                      // snnls.py:63-72
-      if (S.retried) S.reached_limit = 1;
-      else S.retried = 1;
-    }
-    sh_fail = fail;
-  }
-  __syncthreads();
-  FSTAMP(7);
-  dev_trace(P, S, f, sh_fail);
-  __syncthreads();
-  dev_prep<ALG>(P, S, red);
-  FSTAMP(8);
+  fin_close<ALG>(P, S, red, fail, f, P0.xw);
   // ---- write back
-  for (int k = threadIdx.x; k < s; k += blockDim.x) P0.xw[k] = P.xw[k];
   if (wrote) {
     const long long nnz = S.nnz;
     for (long long j = threadIdx.x; j < nnz; j += blockDim.x) P0.val[j] = l_val[j];
-    if (nnz == nnz0 + 1 && threadIdx.x == 0) P0.idx[nnz0] = l_idx[nnz0];
+    if (nnz == sv.nnz0 + 1 && threadIdx.x == 0) P0.idx[sv.nnz0] = l_idx[sv.nnz0];
   }
-  if (threadIdx.x == 0) {
-    S.sel_valid = 0;
-    *P0.st = S;
-  }
+  fin_store_state(S, P0.st);
   FSTAMP(9);
 }
 
@@ -1095,159 +1198,6 @@ __global__ __launch_bounds__(BC_FIN_THREADS) void k_reset(SnnlsDev P) {
   __syncthreads();
   dev_xw_err(P, S, red);   // nnz = 0 -> xw = 0, err = ||b||
   if (threadIdx.x == 0) *P.st = S;
-}
-
-// ------------------------------------------------------------------ device NNLS refit (OrthoPursuit, optimize())
-#include "bc_nnls_dev.h"
-#define BC_ST_LIST_LIMIT 100      // last_status of k_refit: the list would outgrow BC_NNLS_MAXP (the host words the error)
-
-// would column f find a slot (dev_omp_place below): it is listed, or a slot has weight 0, or the list may grow
-__device__ bool dev_omp_room(const SnnlsDev& P, const SnnlsState& S, long long f, long long limit) {
-  __shared__ int room;
-  const long long nnz = S.nnz;
-  if (threadIdx.x == 0) room = nnz < limit ? 1 : 0;
-  __syncthreads();
-  for (long long j = threadIdx.x; j < nnz; j += blockDim.x)
-    if (P.idx[j] == f || !(P.val[j] > 0.)) room = 1;
-  __syncthreads();
-  return room != 0;
-}
-
-// orthopursuit.py:38 `w[f] = 1` on the sparse list: make sure the picked column (S.sel_f, in P.xf) has a slot -- with weight
-// 0 when it is new: the refit lets it enter.  A slot whose weight is 0 is reused before the list grows.  Returns the slot, or
-// -1 when the list is full; *fresh: the slot's column was (re)written, so its Gram row is stale (the callers go straight on to
-// dev_gram_update, which recomputes it).
-__device__ long long dev_omp_place(const SnnlsDev& P, SnnlsState& S, long long limit, int* fresh) {
-  __shared__ int hit, zero;
-  const int s = P.s;
-  const long long f = S.sel_f, nnz = S.nnz;
-  if (threadIdx.x == 0) { hit = INT_MAX; zero = INT_MAX; }
-  __syncthreads();
-  for (long long j = threadIdx.x; j < nnz; j += blockDim.x) {
-    if (P.idx[j] == f) atomicMin(&hit, (int)j);
-    else if (!(P.val[j] > 0.)) atomicMin(&zero, (int)j);
-  }
-  __syncthreads();
-  *fresh = 0;
-  if (hit != INT_MAX) return hit;
-  const long long at = zero != INT_MAX ? (long long)zero : nnz;
-  if (at == nnz && at >= limit) return -1;
-  for (int k = threadIdx.x; k < s; k += blockDim.x) P.cols[(size_t)at * s + k] = P.xf[k];
-  if (threadIdx.x == 0) {
-    P.idx[at] = f;
-    P.val[at] = 0.;
-    P.colnorm[at] = S.sel_norm;
-    if (at == nnz) S.nnz = at + 1;
-  }
-  __syncthreads();
-  *fresh = 1;
-  return at;
-}
-
-// bring the Gram state up to the list: entries [covered, n) are new to it (covered = P.nnls_stats[3], never trusted beyond
-// the list as it was when this kernel started), and so is a slot below them that was reused in this kernel
-__device__ void dev_gram_update(const SnnlsDev& P, long long nnz0, long long n, long long at, int fresh) {
-  const long long covered = P.nnls_stats[3];
-  const long long from = covered < nnz0 ? covered : nnz0;
-  __syncthreads();                 // every thread has read the mark before thread 0 moves it
-  if (from < n) bc_nnls_gram_rows(P.cols, P.s, P.b, P.gram, P.gram_c, (int)n, (int)from, (int)n);
-  if (fresh && at < from) bc_nnls_gram_rows(P.cols, P.s, P.b, P.gram, P.gram_c, (int)n, (int)at, (int)at + 1);
-  if (threadIdx.x == 0) P.nnls_stats[3] = n;
-}
-
-// one guarded OrthoPursuit iteration (snnls.py:41-74 with orthopursuit.py:17-41): k_step_finish with the closed-form step
-// replaced by "give the picked column a slot, extend the Gram state, NNLS refit".  Dynamic LDS: the refit's workspace, then
-// the five S-vectors (lds_vecs != 0).  The winner comes from the gathered candidate record(s).
-__global__ __launch_bounds__(BC_FIN_THREADS) void k_step_finish_omp(SnnlsDev P0, int lds_vecs) {
-  extern __shared__ double omp_lds[];
-  __shared__ SnnlsState S;
-  __shared__ double red[64];
-  __shared__ int sh_fail;
-  if (threadIdx.x == 0) S = *P0.st;
-  SnnlsDev P = P0;
-  const int s = P.s;
-  double* vec_lds = omp_lds + BC_NNLS_WS_DOUBLES;
-  if (lds_vecs) {
-    P.b = vec_lds;
-    P.bn = vec_lds + s;
-    P.xw = vec_lds + 2 * s;
-    P.xf = vec_lds + 3 * s;
-    P.xw_prev = vec_lds + 4 * s;
-    for (int k = threadIdx.x; k < s; k += blockDim.x) {
-      P.b[k] = P0.b[k];
-      P.bn[k] = P0.bn[k];
-      P.xw[k] = P0.xw[k];
-    }
-  }
-  __syncthreads();
-  if (S.reached_limit || S.pf_overflow) return;      // snnls.py:32-34 / :73-74; a pending exact redo consumes nothing
-  if (!S.select_fail && dev_records_overflow(P0.cand_all, P.world, P.rec_len)) {
-    if (threadIdx.x == 0) { S.pf_overflow = 1; S.skip = 1; *P0.st = S; }
-    return;
-  }
-  const bool guard = S.npos > 0;                     // snnls.py:44-45
-  int fail = S.select_fail;
-  long long f = -1;
-  if (!fail) {
-    dev_pick<BC_ALG_OMP>(P, S, red);
-    if (!S.sel_valid) fail = 1;
-    f = S.sel_f;
-  }
-  if (!fail) {
-    const long long nnz0 = S.nnz, npos0 = S.npos;
-    const double err0 = S.err_cur, xwsq0 = S.xw_sq;
-    const long long limit = P.cap < BC_NNLS_MAXP ? P.cap : BC_NNLS_MAXP;
-    int fresh = 0;
-    const long long at = nnz0 <= BC_NNLS_MAXP ? dev_omp_place(P, S, limit, &fresh) : -1;
-    if (at < 0) {                                    // the host's bound on the list length was wrong: refuse
-      if (threadIdx.x == 0) { S.overflow = 1; *P0.st = S; }
-      return;
-    }
-    for (long long j = threadIdx.x; j < nnz0; j += blockDim.x) P.prev_val[j] = P.val[j];
-    for (int k = threadIdx.x; k < s; k += blockDim.x) P.xw_prev[k] = P.xw[k];
-    dev_gram_update(P, nnz0, S.nnz, at, fresh);
-    fail = bc_nnls_solve(P.gram, P.gram_c, (int)S.nnz, P.val, (int)at, 0, P.bnorm, bc_nnls_ws(omp_lds), P.nnls_stats);
-    if (fail) {                                      // like a NumericalPrecisionError out of _reweight: w was not touched
-      if (threadIdx.x == 0) S.nnz = nnz0;
-      __syncthreads();
-    } else {
-      dev_xw_err(P, S, red);
-      if (guard) {
-        if (S.err_cur > err0) {                      // snnls.py:58-61
-          for (long long j = threadIdx.x; j < nnz0; j += blockDim.x) P.val[j] = P.prev_val[j];
-          for (int k = threadIdx.x; k < s; k += blockDim.x) P.xw[k] = P.xw_prev[k];
-          __syncthreads();
-          if (threadIdx.x == 0) {
-            S.nnz = nnz0;
-            S.npos = npos0;
-            S.err_cur = err0;
-            S.xw_sq = xwsq0;
-          }
-          fail = 1;
-        } else if (threadIdx.x == 0) {
-          S.retried = 0;                             // snnls.py:62
-        }
-        __syncthreads();
-      }
-    }
-  }
-  if (threadIdx.x == 0) {
-    if (fail) {                                      // snnls.py:63-72
-      if (S.retried) S.reached_limit = 1;
-      else S.retried = 1;
-    }
-    sh_fail = fail;
-  }
-  __syncthreads();
-  dev_trace(P, S, f, sh_fail);
-  __syncthreads();
-  dev_prep<BC_ALG_OMP>(P, S, red);
-  if (lds_vecs)
-    for (int k = threadIdx.x; k < s; k += blockDim.x) P0.xw[k] = P.xw[k];
-  if (threadIdx.x == 0) {
-    S.sel_valid = 0;      // the picked column lived in LDS: a later step-wise refit must fetch it again
-    *P0.st = S;
-  }
 }
 
 // The same refit behind a single launch, for the step-wise protocol and optimize():
@@ -1492,6 +1442,10 @@ extern "C" int bc_snnls_create(bc_ctx* ctx, bc_phi* phi, const double* b, int al
     const bool pwant = penv ? preq != 0 : phi->n_rows >= 163840;
     const int pprec = (preq == 8 || preq == 16 || preq == 32) ? preq : BC_PREF_DEFAULT_PREC;      // (4: the int8 mirror behind a 4-bit first level)
     const bool ptwo = bc_want_two_level(preq, phi->n_rows, s);
+    const char* fenv = getenv("BC_FINISH_NOPF");         // finish-kernel forms ruled out for this solver (tests, A/B)
+    h->no_pf = fenv && atoi(fenv) != 0;
+    fenv = getenv("BC_FINISH_NOFUSE");
+    h->no_fuse = fenv && atoi(fenv) != 0;
     const char* qenv = getenv("BC_I8_QV");               // =0: sweeps quantise in their own prologue (A/B, tests)
     d.sp4 = bc_lay_i8_sp4(s);
     d.qv = (pwant && pprec == 8 && phi->n_rows > 0 && (s + 3) / 4 <= BC_LAY_IMAXG - BC_LAY_IU && !(qenv && atoi(qenv) == 0)) ? (int*)(slab + o_qv) : nullptr;
@@ -1546,6 +1500,12 @@ int bc_pref_bb(const bc_pref* p);
 extern "C" int bc_snnls_prefilter_form(const bc_snnls* h, int* form) {
   if (!h || !form) { bc_set_error("bc_snnls_prefilter_form: bad argument"); return BC_INVALID_ARGUMENT; }
   *form = !h->pref ? 0 : (bc_pref_bb(h->pref) ? 2 : (bc_pref_two_level_active(h->pref) ? 3 : 1));      // (3 put aside by the watch: 1)
+  return BC_OK;
+}
+
+extern "C" int bc_snnls_finish_form(const bc_snnls* h, int* form) {
+  if (!h || !form) { bc_set_error("bc_snnls_finish_form: bad argument"); return BC_INVALID_ARGUMENT; }
+  *form = h->finish_form;
   return BC_OK;
 }
 
@@ -1663,13 +1623,11 @@ static bool use_pref(const bc_snnls* h) { return h->pref && !h->pref_suspended &
 #define BC_RS_MAX_DYN_LDS (48 * 1024)   // dynamic LDS the fused kernel may ask for (on top of ~42 KB static: rescoring strips, lists)
 // one-round-of-loads finish kernel (k_step_finish_pf) possible for the step in flight?
 static bool finish_pf_ok(const bc_snnls* h, long long nrec) {
-  static const int no_pf = getenv("BC_FINISH_NOPF") ? atoi(getenv("BC_FINISH_NOPF")) : 0;
-  return !no_pf && h->d.s <= BC_FIN_THREADS && h->nnz_upper + 1 <= BC_PF_MAXNNZ && nrec <= BC_PF_MAXREC && h->nnz_upper + 1 <= h->d.cap;
+  return !h->no_pf && h->d.s <= BC_FIN_THREADS && h->nnz_upper + 1 <= BC_PF_MAXNNZ && nrec <= BC_PF_MAXREC && h->nnz_upper + 1 <= h->d.cap;
 }
 // ... with the rescoring stage inside the same launch (single rank, pre-filtered sweep)?
 static bool fused_rescore_ok(const bc_snnls* h) {
-  static const int no_fuse = getenv("BC_FINISH_NOFUSE") ? atoi(getenv("BC_FINISH_NOFUSE")) : 0;
-  if (no_fuse || !use_pref(h) || h->d.world != 1 || h->comm || !h->cand_send_owned) return false;
+  if (h->no_fuse || !use_pref(h) || h->d.world != 1 || h->comm || !h->cand_send_owned) return false;
   if (!finish_pf_ok(h, h->d.rec_len)) return false;
   const size_t lds = ((size_t)5 * h->d.s + h->d.rec_len + 2 * (size_t)(h->nnz_upper + 1)) * sizeof(double);
   // static LDS of the fused kernel (rescoring strips 32 KB, current / best row 16 KB, tile list 4 KB, ...) + the dynamic part
@@ -1713,7 +1671,7 @@ static int ensure_nnls(bc_snnls* h, const char* who) {
   }
   static unsigned attr_done_mask = 0;      // per device
   if (!((attr_done_mask >> (h->ctx->device & 31)) & 1u)) {
-    BC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_step_finish_omp), hipFuncAttributeMaxDynamicSharedMemorySize,
+    BC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_step_finish<BC_ALG_OMP>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)nnls_lds_bytes(1024)));
     BC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_refit), hipFuncAttributeMaxDynamicSharedMemorySize, (int)nnls_lds_bytes(0)));
     attr_done_mask |= 1u << (h->ctx->device & 31);
@@ -1820,7 +1778,7 @@ extern "C" int bc_snnls_build_begin(bc_snnls* h, int itrs) {
 extern "C" int bc_snnls_step_local(bc_snnls* h) {
   if (!h) return BC_INVALID_ARGUMENT;
   h->exact_step = false;
-  if (h->alg == BC_ALG_OMP) return launch_sweep(h, true, false);      // k_step_finish_omp consumes the candidate record
+  if (h->alg == BC_ALG_OMP) return launch_sweep(h, true, false);      // k_step_finish<BC_ALG_OMP> consumes the candidate record
   return launch_sweep(h, !fuse_winner(h), true);
 }
 
@@ -1832,11 +1790,28 @@ extern "C" int bc_snnls_step_local_exact(bc_snnls* h) {
   return launch_sweep(h, true, false);
 }
 
+// which finish kernel serves the step in flight (`fused`: step_local ran the sweep only); bc_snnls_finish_form reports it
+static int finish_form(const bc_snnls* h, bool fused, long long nrec) {
+  if (h->alg == BC_ALG_OMP) return BC_FINISH_OMP;
+  if (fused) return h->rs.bb.rec != nullptr ? BC_FINISH_ONE_ROUND_BB : BC_FINISH_ONE_ROUND_RESCORE;      // (bb: bc_prefilter_bb.h's sweep)
+  return finish_pf_ok(h, nrec) ? BC_FINISH_ONE_ROUND : BC_FINISH_PLAIN;
+}
+
+#define FIN_KERNEL(...) reinterpret_cast<const void*>(&__VA_ARGS__)
+static const void* const fin_kernels[BC_FINISH_OMP + 1][3] = {
+    {nullptr, nullptr, nullptr},
+    {FIN_KERNEL(k_step_finish<BC_ALG_GIGA>), FIN_KERNEL(k_step_finish<BC_ALG_FW>), nullptr},
+    {FIN_KERNEL(k_step_finish_pf<BC_ALG_GIGA, 0>), FIN_KERNEL(k_step_finish_pf<BC_ALG_FW, 0>), nullptr},
+    {FIN_KERNEL(k_step_finish_pf<BC_ALG_GIGA, 1>), FIN_KERNEL(k_step_finish_pf<BC_ALG_FW, 1>), nullptr},
+    {FIN_KERNEL(k_step_finish_pf<BC_ALG_GIGA, 2>), FIN_KERNEL(k_step_finish_pf<BC_ALG_FW, 2>), nullptr},
+    {nullptr, nullptr, FIN_KERNEL(k_step_finish<BC_ALG_OMP>)},
+};
+
 extern "C" int bc_snnls_step_finish(bc_snnls* h) {
   if (!h) return BC_INVALID_ARGUMENT;
   SnnlsDev d = h->d;
   const bool rec_based = h->exact_step || h->pref != nullptr;
-  d.fuse_winner = (fuse_winner(h) && !rec_based) ? 1 : 0;
+  d.fuse_winner = (fuse_winner(h) && !rec_based && h->alg != BC_ALG_OMP) ? 1 : 0;
   d.blk_val = h->phi->blk_val;
   d.blk_idx = h->phi->blk_idx;
   d.nblk = h->phi->sweep_blocks;
@@ -1848,62 +1823,27 @@ extern "C" int bc_snnls_step_finish(bc_snnls* h) {
     bc_set_error("bc_snnls_step_finish: OrthoPursuit without bc_snnls_device_refit");
     return BC_INVALID_ARGUMENT;
   }
-  int rct = bc_timer_begin(h->ctx, 5);
-  if (rct) return rct;
-  if (h->alg == BC_ALG_OMP) {
-    d.fuse_winner = 0;
-    const int lds_vecs = d.s <= 1024 ? 1 : 0;
-    const size_t lds = nnls_lds_bytes(lds_vecs ? d.s : 0);
-    hipLaunchKernelGGL(k_step_finish_omp, dim3(1), dim3(BC_FIN_THREADS), lds, h->ctx->stream, d, lds_vecs);
-    BC_HIP(hipGetLastError());
-    h->nnz_upper += 1;
-    h->iter_upper += 1;
-    return bc_timer_end(h->ctx, 5);
-  }
-  if (fused || finish_pf_ok(h, nrec)) {
-    const int hint = (int)h->nnz_upper;
-    const size_t lds = ((size_t)5 * d.s + nrec + 2 * (size_t)(hint + 1)) * sizeof(double);
-    const long long n_rows = h->phi->n_rows;
-    if (fused) {
-      static unsigned attr_done_mask = 0;  // 42 KB static + up to 48 KB dynamic LDS: above the 64 KB default limit; per device
-      const bool attr_done = (attr_done_mask >> (h->ctx->device & 31)) & 1u;
-      if (!attr_done) {
-        BC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_step_finish_pf<BC_ALG_GIGA, 1>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, BC_RS_MAX_DYN_LDS));
-        BC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_step_finish_pf<BC_ALG_FW, 1>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, BC_RS_MAX_DYN_LDS));
-        BC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_step_finish_pf<BC_ALG_GIGA, 2>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, BC_RS_MAX_DYN_LDS));
-        BC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_step_finish_pf<BC_ALG_FW, 2>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, BC_RS_MAX_DYN_LDS));
-        attr_done_mask |= 1u << (h->ctx->device & 31);
-      }
-      const bool bb = h->rs.bb.rec != nullptr;      // the sweep in flight was the branch-and-bound one (bc_prefilter_bb.h)
-      if (h->alg == BC_ALG_GIGA) {
-        if (bb) hipLaunchKernelGGL((k_step_finish_pf<BC_ALG_GIGA, 2>), dim3(1), dim3(BC_FIN_THREADS), lds, h->ctx->stream, d, hint, h->rs, n_rows);
-        else hipLaunchKernelGGL((k_step_finish_pf<BC_ALG_GIGA, 1>), dim3(1), dim3(BC_FIN_THREADS), lds, h->ctx->stream, d, hint, h->rs, n_rows);
-      } else {
-        if (bb) hipLaunchKernelGGL((k_step_finish_pf<BC_ALG_FW, 2>), dim3(1), dim3(BC_FIN_THREADS), lds, h->ctx->stream, d, hint, h->rs, n_rows);
-        else hipLaunchKernelGGL((k_step_finish_pf<BC_ALG_FW, 1>), dim3(1), dim3(BC_FIN_THREADS), lds, h->ctx->stream, d, hint, h->rs, n_rows);
-      }
-    } else {
-      if (h->alg == BC_ALG_GIGA)
-        hipLaunchKernelGGL((k_step_finish_pf<BC_ALG_GIGA, 0>), dim3(1), dim3(BC_FIN_THREADS), lds, h->ctx->stream, d, hint, h->rs, n_rows);
-      else
-        hipLaunchKernelGGL((k_step_finish_pf<BC_ALG_FW, 0>), dim3(1), dim3(BC_FIN_THREADS), lds, h->ctx->stream, d, hint, h->rs, n_rows);
+  const int form = finish_form(h, fused, nrec);
+  const bool one_round = form != BC_FINISH_PLAIN && form != BC_FINISH_OMP;
+  if (fused) {
+    static unsigned attr_done_mask = 0;  // 42 KB static + up to 48 KB dynamic LDS: above the 64 KB default limit; per device
+    if (!((attr_done_mask >> (h->ctx->device & 31)) & 1u)) {
+      for (int f = BC_FINISH_ONE_ROUND_RESCORE; f <= BC_FINISH_ONE_ROUND_BB; ++f)
+        for (int a = BC_ALG_GIGA; a <= BC_ALG_FW; ++a)
+          BC_HIP(hipFuncSetAttribute(fin_kernels[f][a], hipFuncAttributeMaxDynamicSharedMemorySize, BC_RS_MAX_DYN_LDS));
+      attr_done_mask |= 1u << (h->ctx->device & 31);
     }
-    BC_HIP(hipGetLastError());
-    h->nnz_upper += 1;
-    h->iter_upper += 1;
-    return bc_timer_end(h->ctx, 5);
   }
-  const int lds_vecs = d.s <= 1024 ? 1 : 0;
-  const size_t lds = lds_vecs ? (size_t)5 * d.s * sizeof(double) : 0;
-  if (h->alg == BC_ALG_GIGA)
-    hipLaunchKernelGGL(k_step_finish<BC_ALG_GIGA>, dim3(1), dim3(BC_FIN_THREADS), lds, h->ctx->stream, d, lds_vecs);
-  else
-    hipLaunchKernelGGL(k_step_finish<BC_ALG_FW>, dim3(1), dim3(BC_FIN_THREADS), lds, h->ctx->stream, d, lds_vecs);
-  BC_HIP(hipGetLastError());
+  // the one-round kernels take (list-length bound, rescoring arguments, rows); the others whether the S-vectors fit LDS
+  int hint_or_vecs = one_round ? (int)h->nnz_upper : (d.s <= 1024 ? 1 : 0);
+  long long n_rows = h->phi->n_rows;
+  const size_t lds_doubles = one_round ? (size_t)5 * d.s + nrec + 2 * (size_t)(hint_or_vecs + 1)
+                                       : (form == BC_FINISH_OMP ? BC_NNLS_WS_DOUBLES : 0) + (hint_or_vecs ? (size_t)5 * d.s : 0);
+  void* args[] = {&d, &hint_or_vecs, &h->rs, &n_rows};
+  int rc = bc_timer_begin(h->ctx, 5);
+  if (rc) return rc;
+  BC_HIP(hipLaunchKernel(fin_kernels[form][h->alg], dim3(1), dim3(BC_FIN_THREADS), args, lds_doubles * sizeof(double), h->ctx->stream));
+  h->finish_form = form;
   h->nnz_upper += 1;
   h->iter_upper += 1;
   return bc_timer_end(h->ctx, 5);

@@ -226,6 +226,13 @@ class HipEngine:
         N.call('bc_snnls_prefilter_stats', self.h, C.byref(a), C.byref(b), C.byref(c))
         return int(a.value), int(b.value), int(c.value)
 
+    def finish_form(self):
+        """Which single-block kernel served the last step of build_fused() (include/beta_cores.h: BC_FINISH_*): 0 none yet,
+        1 plain, 2 one round of loads, 3 / 4 one round with the two-pass / branch-and-bound rescoring inside, 5 OrthoPursuit."""
+        form = C.c_int()
+        N.call('bc_snnls_finish_form', self.h, C.byref(form))
+        return int(form.value)
+
     def prefilter_levels(self):
         """Two-level form (prefilter_form 3): (first-level sweeps, rows they listed, rows re-bounded from the int8 records)."""
         a, b, c = C.c_int64(), C.c_int64(), C.c_int64()

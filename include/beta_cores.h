@@ -297,6 +297,19 @@ int bc_snnls_build_begin(bc_snnls* h, int itrs);      /* resets the per-call ret
 int bc_snnls_step_local(bc_snnls* h);                 /* K3 sweep + local winner -> cand_send */
 int bc_snnls_step_local_exact(bc_snnls* h);           /* the same through the fp64 sweep: redo of a step whose pre-filter overflowed */
 int bc_snnls_step_finish(bc_snnls* h);                /* winner over cand_all, reweight, guard, prep next */
+/* Diagnostic: which single-block kernel served the last bc_snnls_step_finish (0 before any step).  Every form runs the same
+ * guarded iteration (snnls.py:41-74) and leaves the same bits; they differ in where the step's vectors and list live:
+ * PLAIN reads them phase by phase; ONE_ROUND requests all of them up front (list of <= 1024 entries, S <= 512);
+ * ONE_ROUND_RESCORE / ONE_ROUND_BB also run the pre-filter's fp64 rescoring (two-pass / branch-and-bound sweep) in that launch
+ * (single rank); OMP is PLAIN with the NNLS refit of orthopursuit.py:37-41 in place of the closed-form step.
+ * BC_FINISH_NOPF=1 / BC_FINISH_NOFUSE=1 in the environment when the solver is created rule out the one-round forms / the
+ * rescoring inside the launch (tests, A/B measurements). */
+#define BC_FINISH_PLAIN 1
+#define BC_FINISH_ONE_ROUND 2
+#define BC_FINISH_ONE_ROUND_RESCORE 3
+#define BC_FINISH_ONE_ROUND_BB 4
+#define BC_FINISH_OMP 5
+int bc_snnls_finish_form(const bc_snnls* h, int* form);
 /* pending_exact (may be NULL): 1 when the enqueued steps stopped at a pre-filter overflow -- the caller runs ONE
  * step as step_local_exact / all-gather / step_finish and then continues with the remaining iterations
  * (iterations_consumed tells how many are done); bc_snnls_build does all of that by itself. */

@@ -24,7 +24,8 @@ while time.time() < t_end:
     steps = min(n, rng.randint(1, 30))
     pref = rng.choice([0, 4, 8, 16])        # (4: the two-level form, csrc/bc_prefilter_i4.h)
     os.environ['BC_PREFILTER'] = str(pref)
-    os.environ['BC_FINISH_NOPF'] = str(rng.randint(2))
+    os.environ['BC_FINISH_NOPF'] = str(rng.randint(2))           # (both are read when a solver is created)
+    os.environ['BC_FINISH_NOFUSE'] = str(rng.randint(2))
     a = cls(phi.T, phi.sum(axis=0)); a.build(steps)
     b = cls(phi.T, phi.sum(axis=0)); b.build_stepwise(steps)
     ref = ref_cls(phi.T, phi.sum(axis=0)); ref.build(steps)

@@ -167,6 +167,7 @@ def test_dense_phi_vs_oracle(bc, n, s_):
     ref.build(steps)
     dev = bc.snnls.DeviceOrthoPursuit(phi.T, phi.sum(axis=0))
     dev.build(steps)
+    assert dev._eng.finish_form() == 5          # BC_FINISH_OMP: k_step_finish<BC_ALG_OMP> served the fused loop
     assert_matches(dev, ref.w, ref.error())
 
 

@@ -210,6 +210,102 @@ def test_seeded_parity_vs_oracle(bc, alg, steps):
         np.testing.assert_array_equal(st, [t[1] for t in ref.trace])
 
 
+# ------------------------------------------------------------------ the finish kernel's forms: one iteration, one result
+PLAIN, ONE_ROUND, ONE_ROUND_RESCORE = 1, 2, 3       # include/beta_cores.h: BC_FINISH_*
+KNOBS = (None, 'BC_FINISH_NOFUSE', 'BC_FINISH_NOPF')
+
+
+def _build_in_every_form(bc, monkeypatch, alg, phi, steps):
+    """build(steps) under every (BC_PREFILTER, knob) setting -- the environment is read when a solver is created -- and once
+    through the step-wise protocol: [(label, finish form, pre-filter precision, solver)]."""
+    s_ = phi.shape[1]
+    b = phi.sum(axis=0)
+    monkeypatch.delenv('BC_I8_BB', raising=False)
+    runs = []
+    for pref in (0, 8) + ((4,) if s_ <= 256 else ()):
+        for knob in KNOBS:
+            monkeypatch.setenv('BC_PREFILTER', str(pref))
+            for k in KNOBS[1:]:
+                monkeypatch.delenv(k, raising=False)
+            if knob:
+                monkeypatch.setenv(knob, '1')
+            sv = _algs(bc)[alg](phi.T, b)
+            sv.build(steps)
+            runs.append(('BC_PREFILTER=%d %s' % (pref, knob or 'default'), sv._eng.finish_form(), sv._eng.prefilter, sv))
+    for k in KNOBS[1:]:
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv('BC_PREFILTER', '0')
+    sv = _algs(bc)[alg](phi.T, b)
+    sv.build_stepwise(steps)
+    runs.append(('step-wise', 0, 0, sv))
+    return runs
+
+
+def _assert_bit_identical(runs):
+    first = runs[0][3]
+    f0, st0, er0 = first._eng.trace()
+    i0, v0 = first.sparse_weights()
+    for label, _, _, sv in runs[1:]:
+        f, st, er = sv._eng.trace()
+        i, v = sv.sparse_weights()
+        if label == 'step-wise':                    # its loop runs on the host: the device keeps a trace of the fused loop only
+            assert len(f) == 0
+        else:
+            assert np.array_equal(f, f0) and np.array_equal(st, st0) and np.array_equal(er, er0), label
+        assert np.array_equal(i, i0) and np.array_equal(v, v0) and sv.error() == first.error(), label
+    return f0, st0
+
+
+@pytest.mark.parametrize('n,s_', [(129, 33), (300, 257), (200, 600), (64, 1100)])
+@pytest.mark.parametrize('alg', ['giga', 'fw'])
+def test_finish_kernels_agree(bc, monkeypatch, alg, n, s_):
+    """Every form of the finish kernel (plain -- above BC_FIN_THREADS = 512 columns, and without its LDS vectors above 1024 --,
+    one round of loads, one round with the rescoring inside) leaves the bits of every other and of the step-wise protocol, and
+    the oracle's selections."""
+    steps = 12
+    phi = np.random.RandomState(1000 * n + s_).randn(n, s_)
+    phi -= phi.mean(axis=1)[:, None]
+    runs = _build_in_every_form(bc, monkeypatch, alg, phi, steps)
+    for label, form, prefilter, _ in runs[:-1]:
+        print(label, 'finish form', form, 'pre-filter', prefilter)
+    for label, form, prefilter, _ in runs[:-1]:
+        if 'NOPF' in label or s_ > 512:
+            want = PLAIN
+        elif 'NOFUSE' in label or not prefilter:
+            want = ONE_ROUND                        # (with a pre-filter: records from k_rescore)
+        else:
+            want = ONE_ROUND_RESCORE
+        assert form == want, label
+    f, st = _assert_bit_identical(runs)
+    ref = _oracle_algs()[alg](phi.T, phi.sum(axis=0))
+    ref.build(steps)
+    np.testing.assert_array_equal(f, [t[0] for t in ref.trace])
+    dev = runs[0][3]
+    np.testing.assert_allclose(dev.weights(), ref.w, rtol=WTOL, atol=1e-12)
+
+
+@pytest.mark.parametrize('s_', [9, 600])
+@pytest.mark.parametrize('alg', ['giga', 'fw'])
+def test_finish_kernels_agree_on_failure_branches(bc, monkeypatch, alg, s_):
+    """A colinear design (every row a positive multiple of one vector): the first pick matches b, after which GIGA's _select
+    raises (f = -1, status 1) and FrankWolfe's picked column is rejected -- the retry, then the stop.  Every form takes those
+    branches to the same bits.  (The oracle is not compared on this input: DESIGN.md section 2, ties decided by a last bit.)"""
+    rng = np.random.RandomState(3)
+    d = rng.randn(1, s_)
+    phi = np.abs(rng.randn(40, 1)) * d
+    runs = _build_in_every_form(bc, monkeypatch, alg, phi, 12)
+    forms = set(r[1] for r in runs[:-1])
+    print('finish forms', sorted(forms))
+    assert forms >= ({PLAIN, ONE_ROUND} if s_ <= 512 else {PLAIN})
+    f, st = _assert_bit_identical(runs)
+    print('trace', list(zip(f.tolist(), st.tolist())))
+    for r in runs:
+        assert r[3].reached_numeric_limit, r[0]
+    assert (st == 1).any()
+    if alg == 'giga':
+        assert ((st == 1) & (f == -1)).any()
+
+
 def test_incremental_equals_oneshot(bc):
     rng = np.random.RandomState(5)
     phi = rng.randn(5000, 40)
