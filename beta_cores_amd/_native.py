@@ -172,6 +172,14 @@ _VIOPT_SIGNATURES = {
 }
 VIOPT_EXPORTS = sorted(_VIOPT_SIGNATURES)
 
+# entry points of the extension header include/beta_cores_psvi.h (BatchPSVICoreset's gradient, weights and points, in one call)
+_PSVI_SIGNATURES = {
+    'bc_psvi_gradient': [vp, vp, vp, C.c_int64, C.c_int, vp, C.c_int32, vp, C.c_int32, vp, C.c_double, vp, vp, vp],
+    'bc_psvi_gradient_begin': [vp, vp, vp, C.c_int64, C.c_int, vp, C.c_int32, vp, C.c_int32, vp, C.c_double],
+    'bc_psvi_gradient_end': [vp, vp, vp, vp],
+}
+PSVI_EXPORTS = sorted(_PSVI_SIGNATURES)
+
 _lib = None
 
 
@@ -205,7 +213,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, argtypes in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_F32_SIGNATURES.items()) + list(_NNLS_SIGNATURES.items()) \
             + list(_TAKE_SIGNATURES.items()) + list(_BETAGRAD_SIGNATURES.items()) + list(_ENCODE_SIGNATURES.items()) \
-            + list(_VIOPT_SIGNATURES.items()):
+            + list(_VIOPT_SIGNATURES.items()) + list(_PSVI_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int

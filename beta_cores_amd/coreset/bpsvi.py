@@ -19,7 +19,7 @@ from .residency import keep_resident, sub_rows
 
 class BatchPSVICoreset(Coreset):
     def __init__(self, data, ll_projector, opt_itrs, n_subsample_opt=None, step_sched=lambda m: lambda i: 1. / (1. + i),
-                 mup=None, Zmean=None, SigpInv=None, diagnostics=False, comm=None, pin_data=True, **kw):
+                 mup=None, Zmean=None, SigpInv=None, diagnostics=False, comm=None, pin_data=True, fused_gradient=False, **kw):
         if comm is not None and comm.world > 1:
             raise NotImplementedError('BatchPSVICoreset initialises its points from rows of the whole data set; '
                                       'row shards are not supported')
@@ -28,6 +28,9 @@ class BatchPSVICoreset(Coreset):
         self.mup, self.SigpInv = mup, SigpInv
         n = data.shape[0]
         self.n_subsample_opt = n_subsample_opt if n_subsample_opt is None else min(n, n_subsample_opt)   # bpsvi.py:11
+        # opt-in: the whole gradient in one native call (DeviceProjector.psvi_gradient) where the projector offers it and covers
+        # the shape; every other gradient takes the path below it.  fused_gradient_calls counts those that took it.
+        self.fused_gradient, self.fused_gradient_calls, self._grad_calls = bool(fused_gradient), 0, 0
         self._sub_buf = None         # sub-samples of resident rows are taken into this one device buffer
         # every full-data gradient re-projects ALL rows: keep them in HBM (pinned: read-only on the host; a view: copied once)
         self._resident = keep_resident(self, data, ll_projector, pin_data and self.n_subsample_opt is None)
@@ -43,16 +46,21 @@ class BatchPSVICoreset(Coreset):
 
     # ---- bpsvi.py:27-43.  Of the data's projection the gradient only uses its column sums (bpsvi.py:52), so that
     # S-vector (K2, on the device) is what this returns, already scaled to the whole data set.
-    def _data_term(self):
+    def _rows(self):
+        """(the rows this gradient projects, their scale to the whole data set): all rows, or a fresh random sub-sample"""
         m = self.n_subsample_opt
         if m is None:
-            rows, scale = (self._resident if self._resident is not None else self.data), 1.
-        else:
-            sub_idcs, scale = np.random.randint(self.data.shape[0], size=m), self.data.shape[0] / m
-            rows = sub_rows(self.data, sub_idcs, self.ll_projector, out=self._sub_buf)      # resident rows stay in HBM
-            if isinstance(rows, DeviceData):
-                self._sub_buf = rows
-        if hasattr(self.ll_projector, 'colsum'):        # device projector: store-free K1, the bits of project().sum(axis=0)
+            return (self._resident if self._resident is not None else self.data), 1.
+        sub_idcs, scale = np.random.randint(self.data.shape[0], size=m), self.data.shape[0] / m
+        rows = sub_rows(self.data, sub_idcs, self.ll_projector, out=self._sub_buf)      # resident rows stay in HBM
+        if isinstance(rows, DeviceData):
+            self._sub_buf = rows
+        return rows, scale
+
+    def _data_term(self, rows=None, scale=None):
+        if rows is None:
+            rows, scale = self._rows()
+        if hasattr(self.ll_projector, 'colsum'):       # device projector: store-free K1, the bits of project().sum(axis=0)
             b = self.ll_projector.colsum(rows)
             if b is not None:
                 return scale * b
@@ -71,8 +79,20 @@ class BatchPSVICoreset(Coreset):
     def _gradient(self, x, sz, d):
         """bpsvi.py:47-57: d/d(weights, points) of the squared tangent-space residual, estimated over the S samples"""
         w, p = x[:sz], x[sz:].reshape(sz, d)
-        self.ll_projector.update(w, p)                  # new Theta first (bpsvi.py:29), then the RNG draws of _data_term
-        target = self._data_term()
+        self.ll_projector.update(w, p)                  # new Theta first (bpsvi.py:29), then the RNG draws of _rows
+        rows, scale = self._rows()
+        self._grad_calls += 1
+        fused = getattr(self.ll_projector, 'psvi_gradient', None) if self.fused_gradient else None
+        if fused is not None:
+            # one native call: only g_w and the sz x d point-gradient come back.  A sampler that can draw its next normals ahead
+            # of time does so beside the GPU -- except after the LAST gradient of an _optimize(): what follows that one is not
+            # this loop's next sampler call (GreedyVICoreset._optimize)
+            prefetch = getattr(getattr(self.ll_projector, 'sampler', None), 'prefetch', None)
+            g = fused(rows, p, w, scale, overlap=prefetch if self._grad_calls < self.opt_itrs else None)
+            if g is not None:
+                self.fused_gradient_calls += 1
+                return np.concatenate((g[0], g[1].ravel()))
+        target = self._data_term(rows, scale)           # (declined, or not asked for: the same Theta, the same rows)
         corevecs, pgrads = self._point_terms(p, target.shape[0])
         resid = target - w.dot(corevecs)
         S = corevecs.shape[1]
@@ -83,6 +103,7 @@ class BatchPSVICoreset(Coreset):
     def _optimize(self):
         sz, d = self.wts.shape[0], self.pts.shape[1]
         x0 = np.concatenate((self.wts, self.pts.ravel()))
+        self._grad_calls = 0
         x = partial_nn_opt(x0, lambda v: self._gradient(v, sz, d), np.arange(sz), self.opt_itrs, step_sched=self.step_sched(sz))
         self.wts, self.pts = x[:sz].copy(), x[sz:].reshape(sz, d).copy()
 

@@ -89,7 +89,8 @@ class BetaBlackBoxProjector(Projector):
 # limits of the native gradient entry points (bc_vi_gradient, bc_vi_optimize: csrc/bc_project.hip, csrc/bc_viopt.hip)
 VI_MAX_SAMPLES = 256           # one pass of the store-free K1
 VI_MAX_CORE_DOUBLES = 60000    # m * (dz + 1): the coreset rows and their weights fit the native staging area
-VI_OPT_MAX_DIM = 128           # bc_vi_optimize: the factor and its inverse share one work-group's LDS (BC_VI_MAX_DIM)
+PSVI_MAX_ROW_DOUBLES = 3840    # bc_psvi_gradient: widest point row (csrc/bc_psvi_dev.h: BC_PSVI_MAX_DZ, the kernel's LDS work space)
+VI_OPT_MAX_DIM = 128          # bc_vi_optimize: the factor and its inverse share one work-group's LDS (BC_VI_MAX_DIM)
 
 
 class _DeviceProjectorBase(Projector):
@@ -495,6 +496,40 @@ class DeviceProjector(_DeviceProjectorBase):
         N.call('bc_project_grad_x', self.ctx.h, dd.h, int(self.model.model_id), _ptr(theta), int(theta.shape[0]),
                _ptr(params), int(params.shape[0]), _ptr(out))
         return out
+
+    def psvi_gradient(self, data, pts, w, sum_scaling=1., want_resid=False, overlap=None):
+        """BatchPSVICoreset's gradient (bpsvi.py:47-57) in one native call (bc_psvi_gradient): with the current samples,
+        resid = sum_scaling * project(data).sum(axis=0) - w.dot(corevecs), g_w = -corevecs.dot(resid) / S and
+        g_p = -(w[:, None, None] * pgrads * resid[None, :, None]).sum(axis=1) / S for (corevecs, pgrads) =
+        project(pts, grad=True) -- without the M x S x W tensor `pgrads`: only the M x W result comes back, in the same download
+        as g_w.  g_w and resid carry the bits of vi_gradient on the same inputs.  Returns (g_w, g_p[, resid]), or None when the
+        call is not covered: S > 256, no points, points too many or too wide for the staging area, a model without an
+        x-gradient, an encoder.  `overlap`: as in vi_gradient."""
+        if self.encoder is not None or not self.model.has_grad_x:
+            return None
+        dd, _ = self.device_data(data)
+        core = np.ascontiguousarray(np.atleast_2d(pts), dtype=np.float64)
+        m = int(core.shape[0])
+        theta, S = self._theta(dd.shape)
+        if S > VI_MAX_SAMPLES or core.size == 0 or m * (core.shape[1] + 1) > VI_MAX_CORE_DOUBLES or core.shape[1] > PSVI_MAX_ROW_DOUBLES:
+            return None
+        if core.shape[1] != dd.shape[1]:
+            raise ValueError('points have %d columns, data rows %d' % (core.shape[1], dd.shape[1]))
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if w.shape != (m,):
+            raise ValueError('one weight per point')
+        model_id, params = self._ids(None)
+        self._stage_host_constants(data, model_id, params, more=core)
+        N.call('bc_psvi_gradient_begin', self.ctx.h, dd.h, _ptr(core), m, int(model_id), _ptr(theta), S, _ptr(params),
+               int(params.shape[0]), _ptr(w), float(sum_scaling))
+        g_w, g_p = np.empty(m), np.empty(core.shape)
+        resid = np.empty(S) if want_resid else None
+        try:
+            if overlap is not None:
+                overlap()
+        finally:
+            N.call('bc_psvi_gradient_end', self.ctx.h, _ptr(g_w), _ptr(g_p), _ptr(resid))
+        return (g_w, g_p, resid) if want_resid else (g_w, g_p)
 
 
 class DeviceBetaProjector(_DeviceProjectorBase):

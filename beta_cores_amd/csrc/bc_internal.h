@@ -40,6 +40,11 @@ struct bc_scratch {
 // phases of bc_vi_gradient, timed with HIP events when the context's timing is on (bc_ctx_phase_times)
 #define BC_VI_PHASES 5           // upload (Theta, coreset rows, w) | K1 of the coreset rows | K1 over the data rows (store-free) |
                                  // column-sum reduction (+ rank-order sum over ranks) | M x S algebra + download
+// the three kinds of pending gradient: bc_vi_gradient (grad | resid), bc_vi_beta_gradient (grad | resid | beta_dots),
+// bc_psvi_gradient (grad_w | resid | grad_p [m][dz])
+#define BC_VI_KIND_PLAIN 0
+#define BC_VI_KIND_BETA 1
+#define BC_VI_KIND_PSVI 2
 struct bc_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -69,7 +74,8 @@ struct bc_ctx {
   int64_t vi_pending_m = 0;      // bc_vi_gradient_begin enqueued a gradient of this many rows (bc_vi_gradient_end fetches it)
   int32_t vi_pending_s = 0;
   bool vi_pending_timed = false;
-  bool vi_pending_beta = false;  // the pending gradient is a bc_vi_beta_gradient (grad | resid | beta_dots in vi_pinned)
+  int vi_pending_kind = 0;       // BC_VI_KIND_*: what the pending gradient left in vi_pinned
+  int32_t vi_pending_dz = 0;     // (BC_VI_KIND_PSVI: the width of the rows of grad_p)
   double* vi_pinned = nullptr;   // pinned landing area of the pending gradient
   hipStream_t vi_side = nullptr;  // bc_vi_gradient: the coreset rows' K1 runs here, beside the data rows' launch on `stream`
   hipEvent_t vi_ev_staged = nullptr, vi_ev_core = nullptr;
@@ -110,6 +116,13 @@ int bc_vi_plan_create(bc_ctx* ctx, int model, const double* params, int32_t n_pa
 void bc_vi_plan_destroy(bc_vi_plan* p);
 int bc_vi_plan_step(bc_ctx* ctx, const bc_vi_plan* p, const struct bc_data* core, const struct bc_data* rows, const double* w_dev,
                     double scale, double* resid_dev, double* grad_dev);
+
+// bc_psvi.hip: k_psvi_point_grad behind k_vi_gradient (bc_psvi_gradient_begin); everything is already on the device
+int bc_psvi_kind(int model);      // BC_PSVI_* of a model with an x-gradient, -1 otherwise
+int bc_psvi_max_dz(void);
+int bc_psvi_point_grad_launch(bc_ctx* ctx, int model, const double* pts_dev, const double* w_dev, int64_t m, int dz, int d,
+                              int32_t s, const double* theta_dev, int dk, const double* siginv_dev, double sigsq,
+                              const double* resid_dev, double* out_dev);
 
 int bc_scratch_grow(bc_ctx* ctx, bc_scratch* s, size_t doubles);   // contents are NOT kept when it grows
 

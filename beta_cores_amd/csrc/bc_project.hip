@@ -21,7 +21,9 @@
 #include "bc_k1_math.h"
 #include "../../include/beta_cores_f32.h"
 #include "../../include/beta_cores_betagrad.h"
+#include "../../include/beta_cores_psvi.h"
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
@@ -856,30 +858,45 @@ static int core_phi_for(bc_ctx* ctx, bc_phi** slot, int64_t m, int32_t s, bc_phi
   return BC_OK;
 }
 
-// both kinds of gradient.  grad_model < 0: bc_vi_gradient.  Otherwise (bc_vi_beta_gradient) the coreset rows are projected a
-// second time, with grad_model, and the algebra also leaves beta_dots behind grad and resid.
+static const char* vi_kind_name(int kind) {
+  return kind == BC_VI_KIND_BETA ? "bc_vi_beta_gradient" : kind == BC_VI_KIND_PSVI ? "bc_psvi_gradient" : "bc_vi_gradient";
+}
+
+// the three kinds of gradient.  BC_VI_KIND_PLAIN: bc_vi_gradient.  BC_VI_KIND_BETA (bc_vi_beta_gradient): the coreset rows are
+// projected a second time, with grad_model, and the algebra also leaves beta_dots behind grad and resid.  BC_VI_KIND_PSVI
+// (bc_psvi_gradient): k_psvi_point_grad runs behind the algebra and leaves the M x dz point-gradient behind grad and resid.
 static int vi_gradient_begin(bc_ctx* ctx, const bc_data* data, const double* core_rows, int64_t m, int model, int grad_model,
                              const double* theta, int32_t s, const double* params, int32_t n_params, const double* w,
-                             double sum_scaling, bc_comm* comm) {
-  const bool with_beta = grad_model >= 0;
-  int rc = project_check(ctx, data, model, theta, s, params, n_params, with_beta ? "bc_vi_beta_gradient" : "bc_vi_gradient");
+                             double sum_scaling, bc_comm* comm, int kind = -1) {
+  if (kind < 0) kind = grad_model >= 0 ? BC_VI_KIND_BETA : BC_VI_KIND_PLAIN;
+  const bool with_beta = kind == BC_VI_KIND_BETA, psvi = kind == BC_VI_KIND_PSVI;
+  int rc = project_check(ctx, data, model, theta, s, params, n_params, vi_kind_name(kind));
   if (rc) return rc;
+  if (psvi && bc_psvi_kind(model) < 0) {
+    bc_set_error("bc_psvi_gradient: model %d has no x-gradient in the reference", model);
+    return BC_INVALID_ARGUMENT;
+  }
   if (model_store_only(model)) {
     bc_set_error("bc_vi_gradient: model %d (a beta-gradient) has no store-free form for the data rows", model);
     return BC_INVALID_ARGUMENT;
   }
-  if (m <= 0 || !core_rows || !w) { bc_set_error("bc_vi_gradient: needs a non-empty coreset (m = %lld)", (long long)m); return BC_INVALID_ARGUMENT; }
-  if (s > 256) { bc_set_error("bc_vi_gradient: at most 256 samples (S = %d)", s); return BC_INVALID_ARGUMENT; }
+  const char* who = psvi ? "bc_psvi_gradient" : "bc_vi_gradient";
+  if (m <= 0 || !core_rows || !w) { bc_set_error("%s: needs a non-empty coreset (m = %lld)", who, (long long)m); return BC_INVALID_ARGUMENT; }
+  if (s > 256) { bc_set_error("%s: at most 256 samples (S = %d)", who, s); return BC_INVALID_ARGUMENT; }
   if (comm && bc_comm_ctx(comm) != ctx) { bc_set_error("bc_vi_gradient: the communicator belongs to another context"); return BC_INVALID_ARGUMENT; }
   const int dz = data->dz;
-  const size_t n_core = (size_t)m * dz, n_down = (with_beta ? 2 : 1) * (size_t)m + (size_t)s;      // grad | resid [| beta_dots]
+  if (psvi && dz > bc_psvi_max_dz()) {
+    bc_set_error("bc_psvi_gradient: rows of %d doubles do not fit the point-gradient's work space (at most %d)", dz, bc_psvi_max_dz());
+    return BC_INVALID_ARGUMENT;
+  }
+  // grad | resid [| beta_dots] [| grad_p]
+  const size_t n_core = (size_t)m * dz, n_down = (with_beta ? 2 : 1) * (size_t)m + (size_t)s + (psvi ? n_core : 0);
   if (ctx->vi_pending_m > 0) {
-    bc_set_error("bc_vi_gradient_begin: a gradient is already pending on this context (call %s first)",
-                 ctx->vi_pending_beta ? "bc_vi_beta_gradient_end" : "bc_vi_gradient_end");
+    bc_set_error("%s_begin: a gradient is already pending on this context (call %s_end first)", who, vi_kind_name(ctx->vi_pending_kind));
     return BC_INVALID_ARGUMENT;
   }
   if (n_down > ctx->pinned_doubles) {
-    bc_set_error("bc_vi_gradient: coreset of %lld rows x %d exceeds the staging area", (long long)m, dz);
+    bc_set_error("%s: coreset of %lld rows x %d exceeds the staging area", who, (long long)m, dz);
     return BC_INVALID_ARGUMENT;
   }
   BC_HIP(hipSetDevice(ctx->device));
@@ -913,6 +930,7 @@ static int vi_gradient_begin(bc_ctx* ctx, const bc_data* data, const double* cor
   double* d_grad = ctx->vi_buf.p;
   double* d_resid = d_grad + m;
   double* d_bdots = d_resid + s;           // (with_beta)
+  double* d_gradp = d_resid + s;           // (psvi) [m][dz]
   // the beta-gradient's plan: the value model's staged Theta, saux and Siginv (nothing is uploaded twice), its own constants
   ProjPlan gpl = pl;
   if (with_beta) {
@@ -988,6 +1006,11 @@ static int vi_gradient_begin(bc_ctx* ctx, const bc_data* data, const double* cor
       hipLaunchKernelGGL(k_vi_beta_dots, dim3(1), dim3(256), (size_t)s * sizeof(double), ctx->stream, gphi->tiles, d_resid, (int)m, s, d_bdots);
       BC_HIP(hipGetLastError());
     }
+    if (psvi) {      // the points, their weights, Theta (Gaussian: Theta') and Siginv are where plan_stage has put them
+      rc = bc_psvi_point_grad_launch(ctx, model, edev[0], d_w, m, dz, pl.d, s, pl.a.theta, pl.a.dk, pl.siginv_dev,
+                                     model == BC_MODEL_LINREG_LL ? params[0] : 0., d_resid, d_gradp);
+      if (rc) return rc;
+    }
     // the result lands in a pinned area of its own: whatever the host does between _begin and _end (it may well call into this
     // library, whose other entry points stage through ctx->pinned) cannot overwrite it
     if (!ctx->vi_pinned) BC_HIP(hipHostMalloc((void**)&ctx->vi_pinned, ctx->pinned_doubles * sizeof(double), hipHostMallocDefault));
@@ -1002,7 +1025,8 @@ static int vi_gradient_begin(bc_ctx* ctx, const bc_data* data, const double* cor
   ctx->vi_pending_m = m;
   ctx->vi_pending_s = s;
   ctx->vi_pending_timed = timed;
-  ctx->vi_pending_beta = with_beta;
+  ctx->vi_pending_kind = kind;
+  ctx->vi_pending_dz = dz;
   return BC_OK;
 }
 
@@ -1025,12 +1049,14 @@ extern "C" int bc_vi_beta_gradient_begin(bc_ctx* ctx, const bc_data* data, const
 
 // second half: wait for the enqueued gradient and hand it out (whatever the host did meanwhile -- e.g. drawing the next
 // sample matrix's normals -- ran beside the GPU)
-static int vi_gradient_end(bc_ctx* ctx, double* out_grad, double* out_beta_dots, double* out_resid, bool beta_kind) {
-  const char* who = beta_kind ? "bc_vi_beta_gradient_end" : "bc_vi_gradient_end";
-  if (!ctx || !out_grad || (beta_kind && !out_beta_dots)) { bc_set_error("%s: bad argument", who); return BC_INVALID_ARGUMENT; }
+// out_extra: beta_dots [m] (BC_VI_KIND_BETA) or grad_p [m][dz] (BC_VI_KIND_PSVI)
+static int vi_gradient_end(bc_ctx* ctx, double* out_grad, double* out_extra, double* out_resid, int kind) {
+  char who[40];
+  snprintf(who, sizeof(who), "%s_end", vi_kind_name(kind));
+  if (!ctx || !out_grad || (kind != BC_VI_KIND_PLAIN && !out_extra)) { bc_set_error("%s: bad argument", who); return BC_INVALID_ARGUMENT; }
   if (ctx->vi_pending_m <= 0) { bc_set_error("%s: no gradient is pending on this context", who); return BC_INVALID_ARGUMENT; }
-  if (ctx->vi_pending_beta != beta_kind) {       // the pending gradient stays pending
-    bc_set_error("%s: the pending gradient was begun by %s", who, ctx->vi_pending_beta ? "bc_vi_beta_gradient_begin" : "bc_vi_gradient_begin");
+  if (ctx->vi_pending_kind != kind) {       // the pending gradient stays pending
+    bc_set_error("%s: the pending gradient was begun by %s_begin", who, vi_kind_name(ctx->vi_pending_kind));
     return BC_INVALID_ARGUMENT;
   }
   const int64_t m = ctx->vi_pending_m;
@@ -1041,7 +1067,8 @@ static int vi_gradient_end(bc_ctx* ctx, double* out_grad, double* out_beta_dots,
   BC_HIP(hipStreamSynchronize(ctx->stream));
   memcpy(out_grad, ctx->vi_pinned, (size_t)m * sizeof(double));
   if (out_resid) memcpy(out_resid, ctx->vi_pinned + m, (size_t)s * sizeof(double));
-  if (beta_kind) memcpy(out_beta_dots, ctx->vi_pinned + m + s, (size_t)m * sizeof(double));
+  if (kind == BC_VI_KIND_BETA) memcpy(out_extra, ctx->vi_pinned + m + s, (size_t)m * sizeof(double));
+  if (kind == BC_VI_KIND_PSVI) memcpy(out_extra, ctx->vi_pinned + m + s, (size_t)m * ctx->vi_pending_dz * sizeof(double));
   if (timed) {
     for (int i = 0; i < BC_VI_PHASES; ++i) {
       float ms = 0.f;
@@ -1054,11 +1081,32 @@ static int vi_gradient_end(bc_ctx* ctx, double* out_grad, double* out_beta_dots,
 }
 
 extern "C" int bc_vi_gradient_end(bc_ctx* ctx, double* out_grad, double* out_resid) {
-  return vi_gradient_end(ctx, out_grad, nullptr, out_resid, false);
+  return vi_gradient_end(ctx, out_grad, nullptr, out_resid, BC_VI_KIND_PLAIN);
 }
 
 extern "C" int bc_vi_beta_gradient_end(bc_ctx* ctx, double* out_grad, double* out_beta_dots, double* out_resid) {
-  return vi_gradient_end(ctx, out_grad, out_beta_dots, out_resid, true);
+  return vi_gradient_end(ctx, out_grad, out_beta_dots, out_resid, BC_VI_KIND_BETA);
+}
+
+// ---- include/beta_cores_psvi.h: BatchPSVICoreset's whole gradient.  The same staging, the same projections and the same
+// k_vi_gradient launch as bc_vi_gradient (grad_w and resid carry its bits), k_psvi_point_grad behind it, one download.
+extern "C" int bc_psvi_gradient_begin(bc_ctx* ctx, const bc_data* data, const double* points, int64_t m, int model,
+                                      const double* theta, int32_t s, const double* params, int32_t n_params, const double* w,
+                                      double sum_scaling) {
+  return vi_gradient_begin(ctx, data, points, m, model, -1, theta, s, params, n_params, w, sum_scaling, nullptr, BC_VI_KIND_PSVI);
+}
+
+extern "C" int bc_psvi_gradient_end(bc_ctx* ctx, double* out_grad_w, double* out_grad_p, double* out_resid) {
+  return vi_gradient_end(ctx, out_grad_w, out_grad_p, out_resid, BC_VI_KIND_PSVI);
+}
+
+extern "C" int bc_psvi_gradient(bc_ctx* ctx, const bc_data* data, const double* points, int64_t m, int model,
+                                const double* theta, int32_t s, const double* params, int32_t n_params, const double* w,
+                                double sum_scaling, double* out_grad_w, double* out_grad_p, double* out_resid) {
+  if (!out_grad_w || !out_grad_p) { bc_set_error("bc_psvi_gradient: bad argument"); return BC_INVALID_ARGUMENT; }
+  int rc = bc_psvi_gradient_begin(ctx, data, points, m, model, theta, s, params, n_params, w, sum_scaling);
+  if (rc) return rc;
+  return bc_psvi_gradient_end(ctx, out_grad_w, out_grad_p, out_resid);
 }
 
 extern "C" int bc_vi_beta_gradient(bc_ctx* ctx, const bc_data* data, const double* core_rows, int64_t m, int beta_model,
