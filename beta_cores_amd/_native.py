@@ -180,6 +180,12 @@ _PSVI_SIGNATURES = {
 }
 PSVI_EXPORTS = sorted(_PSVI_SIGNATURES)
 
+# entry points of the extension header include/beta_cores_vilaplace.h (the seam behind the logistic sampler of the device loop)
+_VILAPLACE_SIGNATURES = {
+    'bc_vi_laplace_last_mode': [vp, C.c_int32, vp, vp],
+}
+VILAPLACE_EXPORTS = sorted(_VILAPLACE_SIGNATURES)
+
 _lib = None
 
 
@@ -213,7 +219,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, argtypes in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_F32_SIGNATURES.items()) + list(_NNLS_SIGNATURES.items()) \
             + list(_TAKE_SIGNATURES.items()) + list(_BETAGRAD_SIGNATURES.items()) + list(_ENCODE_SIGNATURES.items()) \
-            + list(_VIOPT_SIGNATURES.items()) + list(_PSVI_SIGNATURES.items()):
+            + list(_VIOPT_SIGNATURES.items()) + list(_PSVI_SIGNATURES.items()) + list(_VILAPLACE_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int

@@ -17,7 +17,7 @@ import numpy as np
 
 from .. import _native as N
 from ..device import DeviceData, _as_rows, _ptr, default_context, upload_slot
-from ..likelihoods import GaussianLocation, LinearRegression
+from ..likelihoods import GaussianLocation, LinearRegression, LogisticRegression
 from ..util import numpy_bits
 from ..util.opt import adam_step_arrays
 from .residency import _BIG_ROWS, _PIPE_ROWS, _SMALL_ROWS, Pin, WeakIdMap, _PhiPool, _resident_dtype      # noqa: F401 (names kept importable from here)
@@ -370,7 +370,8 @@ class _DeviceProjectorBase(Projector):
                     want_trace=False, timings=None):
         """The whole weight optimisation of one greedy-VI step -- `nn_opt(w0, grd, opt_itrs, step_sched)` with a fresh posterior
         draw and a fresh (sub-sampled) projection per gradient (bcores.py:141-150) -- enqueued on the device in chunks of steps
-        (bc_vi_optimize_begin / _chunk_begin / _chunk_end / _end): the draw (k_vi_sampler), both projections, the M x S algebra
+        (bc_vi_optimize_begin / _chunk_begin / _chunk_end / _end): the draw (k_vi_sampler, or k_vi_laplace for a
+        LogisticLaplaceSampler(solver='newton'), whose `_mode` afterwards is the last step's mode), both projections, the M x S algebra
         and the ADAM update never leave the GPU, the host waits once per chunk.  Returns the new weights (with `want_trace`:
         (weights, opt_itrs x m weights after every step)), equal to the host loop's to rounding, or None when the run is not
         covered: rows that are not resident, an encoder, a sampler without `device_spec()`, D > 128, S > 256, a coreset too
@@ -389,14 +390,17 @@ class _DeviceProjectorBase(Projector):
         spec = getattr(self.sampler, 'device_spec', None)
         if spec is None or self.encoder is not None or not isinstance(data, DeviceData) or data._transient:
             return None
-        kind, sp = spec()
+        spec = spec()
+        if spec is None:                # (a sampler the device cannot restate as configured: the logistic one with BFGS)
+            return None
+        kind, sp = spec
         sp = np.ascontiguousarray(sp, dtype=np.float64)
         D = int(self.sampler._dim())
         S = int(self.projection_dimension)
         core = np.ascontiguousarray(np.atleast_2d(core_pts), dtype=np.float64)
         m = int(core.shape[0])
         model_id, params = self._ids(beta)
-        model_cls = LinearRegression if kind == 0 else GaussianLocation      # the likelihood each sampler kind is the posterior of
+        model_cls = (LinearRegression, GaussianLocation, LogisticRegression)[kind]      # the likelihood each sampler kind is the posterior of
         if not isinstance(self.model, model_cls) or int(model_id) not in (self.model.model_id, self.model.beta_model_id):
             return None
         if opt_itrs <= 0 or D > VI_OPT_MAX_DIM or S > VI_MAX_SAMPLES or m == 0 or m * (core.shape[1] + 1) > VI_MAX_CORE_DOUBLES \
@@ -451,6 +455,9 @@ class _DeviceProjectorBase(Projector):
             N.call('bc_vi_optimize_device_ms', self.ctx.h, C.byref(ms))
             timings['draw_s'], timings['device_ms'] = draw_s[0], ms.value
         self.vi_optimize_calls += 1
+        if kind == 2:
+            # the mode the last step ended at: where the sampler's next call -- on the host or in the next run -- starts
+            self.sampler._mode = self.vi_last_mode()['mode']
         return (out, trace) if want_trace else out
 
     def vi_last_draw(self):
@@ -464,6 +471,17 @@ class _DeviceProjectorBase(Projector):
         theta, saux, raw, pad = np.empty((S, D)), np.empty(S), np.empty((S, D)), C.c_double()
         N.call('bc_vi_optimize_last_draw', self.ctx.h, S, D, _ptr(theta), _ptr(saux), _ptr(raw), C.byref(pad))
         return dict(theta=theta, saux=saux, raw=raw, pad_max=pad.value)
+
+
+    def vi_last_mode(self):
+        """What the last Laplace fit of the most recent `vi_optimize` run with the logistic sampler left on the device
+        (bc_vi_laplace_last_mode; a seam for tests, nothing is launched): a dict of `mode` (D), `newton` (the Newton steps of
+        that fit), `halvings` (of its last line search) and `newton_total` (the Newton steps of the whole run).  Raises when
+        the context's last run was of another sampler kind or dimension."""
+        D = int(self.sampler._dim())
+        mode, counts = np.empty(D), np.zeros(3, dtype=np.int32)
+        N.call('bc_vi_laplace_last_mode', self.ctx.h, D, _ptr(mode), _ptr(counts))
+        return dict(mode=mode, newton=int(counts[0]), halvings=int(counts[1]), newton_total=int(counts[2]))
 
 
 def is_device_projector(prj):

@@ -1,12 +1,15 @@
 // The weight optimisation of the greedy variational coresets as runs of steps enqueued on the device
-// (include/beta_cores_viopt.h): k_vi_sampler (the posterior draw: bc_vi_sampler_dev.h), k_vi_adam (util/opt.py's nn_opt), and
-// the entry points that chain them with the projections of bc_project.hip and the row gather of bc_take.hip.
+// (include/beta_cores_viopt.h): k_vi_sampler (the posterior draw: bc_vi_sampler_dev.h), k_vi_laplace (the logistic Laplace
+// sampler: bc_vi_laplace_dev.h), k_vi_adam (util/opt.py's nn_opt), and the entry points that chain them with the projections of
+// bc_project.hip and the row gather of bc_take.hip.
 //
 // Nothing here waits for the device except bc_vi_optimize_chunk_end (once per chunk) and the buffer (re)allocations of a run's
 // first chunk.  The weights, both ADAM moments and the abort mark live in device memory for the whole run.
 #include "bc_internal.h"
 #include "bc_vi_sampler_dev.h"
+#include "bc_vi_laplace_dev.h"
 #include "../../include/beta_cores_viopt.h"
+#include "../../include/beta_cores_vilaplace.h"
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -18,6 +21,14 @@ __global__ __launch_bounds__(BC_VIS_BLOCK) void k_vi_sampler(VisArgs a, int* __r
   extern __shared__ double vis_ws[];
   if (*(volatile int*)flag != 0) return;      // (block-uniform)
   if (bc_vi_sampler(a, vis_ws) && threadIdx.x == 0) *flag = step + 1;
+}
+
+// The logistic kind's draw in the place of k_vi_sampler: one block, the Newton solve of the <= M weighted coreset rows included.
+// The mode it ends at stays in a.mode, the next step's start point.
+__global__ __launch_bounds__(BC_VIL_BLOCK) void k_vi_laplace(VilArgs a, int* __restrict__ flag, int step) {
+  extern __shared__ double vil_ws[];
+  if (*(volatile int*)flag != 0) return;      // (block-uniform)
+  if (bc_vi_laplace(a, vil_ws) && threadIdx.x == 0) *flag = step + 1;
 }
 
 // step[0][i] = step_sched(i), step[1][i] = 1 - b1^(i+1), step[2][i] = 1 - b2^(i+1).  trace: [itrs][m] or null.
@@ -55,6 +66,8 @@ struct bc_viopt {
   const bc_data* data = nullptr;
   bc_data core_view, sub_view;
   VisArgs va;
+  VilArgs la;                     // (logistic kind; va then only names the Theta block for bc_vi_optimize_last_draw)
+  int kind = 0;                   // BC_VI_SAMPLER_* of the run
   int64_t m = 0, n_sub = 0;
   int32_t s = 0, itrs = 0, done = 0;
   int d = 0, dz = 0;
@@ -125,13 +138,14 @@ extern "C" int bc_vi_optimize_begin(bc_ctx* ctx, const bc_data* data, const doub
                  (long long)m, opt_itrs, (long long)n_sub, s);
     return BC_INVALID_ARGUMENT;
   }
-  if (sampler_kind != BC_VI_SAMPLER_LINREG && sampler_kind != BC_VI_SAMPLER_GAUSS) {
+  if (sampler_kind != BC_VI_SAMPLER_LINREG && sampler_kind != BC_VI_SAMPLER_GAUSS && sampler_kind != BC_VI_SAMPLER_LOGISTIC) {
     bc_set_error("bc_vi_optimize_begin: unknown sampler kind %d", sampler_kind);
     return BC_INVALID_ARGUMENT;
   }
-  const bool gauss = sampler_kind == BC_VI_SAMPLER_GAUSS;
-  const bool model_ok = gauss ? (model == BC_MODEL_GAUSS_LL || model == BC_MODEL_GAUSS_BETA)
-                              : (model == BC_MODEL_LINREG_LL || model == BC_MODEL_LINREG_BETA);
+  const bool gauss = sampler_kind == BC_VI_SAMPLER_GAUSS, logistic = sampler_kind == BC_VI_SAMPLER_LOGISTIC;
+  const bool model_ok = gauss      ? (model == BC_MODEL_GAUSS_LL || model == BC_MODEL_GAUSS_BETA)
+                        : logistic ? (model == BC_MODEL_LOGISTIC_LL || model == BC_MODEL_LOGISTIC_BETA)
+                                   : (model == BC_MODEL_LINREG_LL || model == BC_MODEL_LINREG_BETA);
   if (!model_ok) { bc_set_error("bc_vi_optimize_begin: model %d does not go with sampler kind %d", model, sampler_kind); return BC_INVALID_ARGUMENT; }
   if (ctx->vi_pending_m > 0) { bc_set_error("bc_vi_optimize_begin: a bc_vi_gradient is pending on this context"); return BC_INVALID_ARGUMENT; }
   const int dz = data->dz;
@@ -144,7 +158,11 @@ extern "C" int bc_vi_optimize_begin(bc_ctx* ctx, const bc_data* data, const doub
     bc_set_error("bc_vi_optimize_begin: coreset of %lld rows x %d exceeds the staging area", (long long)m, dz);
     return BC_INVALID_ARGUMENT;
   }
-  const size_t lds = (size_t)BC_VIS_WS_DOUBLES(d) * sizeof(double);
+  if (logistic && !(sampler_params[d] == 0. || sampler_params[d] == 1.)) {
+    bc_set_error("bc_vi_optimize_begin: the diag flag of the logistic sampler must be 0.0 or 1.0");
+    return BC_INVALID_ARGUMENT;
+  }
+  const size_t lds = (size_t)(logistic ? BC_VIL_WS_DOUBLES(d) : BC_VIS_WS_DOUBLES(d)) * sizeof(double);
   if (lds > (size_t)ctx->max_lds) {
     bc_set_error("bc_vi_optimize_begin: D = %d needs %zu bytes of LDS, the device offers %d", d, lds, ctx->max_lds);
     return BC_INVALID_ARGUMENT;
@@ -155,6 +173,7 @@ extern "C" int bc_vi_optimize_begin(bc_ctx* ctx, const bc_data* data, const doub
   BC_HIP(hipSetDevice(ctx->device));
   if (!v->lds_set) {
     BC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vi_sampler), hipFuncAttributeMaxDynamicSharedMemorySize, ctx->max_lds));
+    BC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vi_laplace), hipFuncAttributeMaxDynamicSharedMemorySize, ctx->max_lds));
     v->lds_set = true;
   }
   for (auto& e : v->ev)
@@ -162,12 +181,15 @@ extern "C" int bc_vi_optimize_begin(bc_ctx* ctx, const bc_data* data, const doub
   v->laid_out = false;      // (the slab may move below)
   // ---- the slab: [uploaded head] core | w | step | Sig0inv | b0 | Siginv   [device-only] mom1 | mom2 | grad | resid | Theta, saux |
   //      raw | trace | flag
-  const size_t dd = (size_t)d * d;
+  //      logistic kind: Sig0inv and b0 are the start point [d + 1] (then the run's mode) and nothing; behind the trace: the row
+  //      scratch of k_vi_laplace [3 m] | its counts (4 ints), then the flag
+  const size_t dd = logistic ? (size_t)d + 1 : (size_t)d * d;
   const size_t o_core = 0, o_w = o_core + even((size_t)m * dz), o_step = o_w + even((size_t)m), o_s0 = o_step + even(3 * (size_t)opt_itrs);
-  const size_t o_b0 = o_s0 + even(dd), o_sg = o_b0 + even((size_t)d), head = o_sg + (gauss ? even(dd) : 0);
+  const size_t o_b0 = o_s0 + even(dd), o_sg = o_b0 + (logistic ? 0 : even((size_t)d)), head = o_sg + (gauss ? even(dd) : 0);
   const size_t o_m1 = head, o_m2 = o_m1 + even((size_t)m), o_g = o_m2 + even((size_t)m), o_r = o_g + even((size_t)m);
   const size_t o_th = o_r + even((size_t)s), o_raw = o_th + even((size_t)nrsel * dk + nrsel), o_tr = o_raw + even((size_t)s * d);
-  const size_t o_flag = o_tr + (want_trace ? even((size_t)opt_itrs * m) : 0), total = o_flag + 2;
+  const size_t o_rowc = o_tr + (want_trace ? even((size_t)opt_itrs * m) : 0), o_cnt = o_rowc + (logistic ? even(BC_VIL_ROW_DOUBLES(m)) : 0);
+  const size_t o_flag = o_cnt + (logistic ? 2 : 0), total = o_flag + 2;
   int rc = grow_dev(ctx, &v->dev, &v->dev_cap, total);
   const size_t down = even((size_t)m) + (want_trace ? even((size_t)opt_itrs * m) : 0) + 2;
   if (!rc) rc = grow_pin(ctx, &v->pin, &v->pin_cap, head > down ? head : down);
@@ -178,13 +200,17 @@ extern "C" int bc_vi_optimize_begin(bc_ctx* ctx, const bc_data* data, const doub
   memcpy(h + o_core, core_rows, (size_t)m * dz * sizeof(double));
   memcpy(h + o_w, w0, (size_t)m * sizeof(double));
   memcpy(h + o_step, step, 3 * (size_t)opt_itrs * sizeof(double));
-  const double* th0 = sampler_params;
-  const double* sig0inv = sampler_params + d;
-  memcpy(h + o_s0, sig0inv, dd * sizeof(double));
-  bc_vi_prior_rhs(sig0inv, th0, d, h + o_b0);
   double sigsq = 1.;
-  if (gauss) memcpy(h + o_sg, sampler_params + d + dd, dd * sizeof(double));
-  else sigsq = sampler_params[d + dd];
+  if (logistic) {
+    memcpy(h + o_s0, sampler_params, (size_t)d * sizeof(double));      // the start point; [d] (the last decrement) starts at 0
+  } else {
+    const double* th0 = sampler_params;
+    const double* sig0inv = sampler_params + d;
+    memcpy(h + o_s0, sig0inv, dd * sizeof(double));
+    bc_vi_prior_rhs(sig0inv, th0, d, h + o_b0);
+    if (gauss) memcpy(h + o_sg, sampler_params + d + dd, dd * sizeof(double));
+    else sigsq = sampler_params[d + dd];
+  }
   BC_HIP(hipMemcpyAsync(v->dev, h, head * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   BC_HIP(hipMemsetAsync(v->dev + head, 0, (total - head) * sizeof(double), ctx->stream));
   bc_vi_plan_destroy(v->plan);
@@ -232,6 +258,21 @@ extern "C" int bc_vi_optimize_begin(bc_ctx* ctx, const bc_data* data, const doub
   a.theta = v->dev + o_th;
   a.saux = v->dev + o_th + (size_t)nrsel * dk;
   a.raw = v->dev + o_raw;
+  VilArgs& l = v->la;
+  l.d = d;
+  l.m = (int)m;
+  l.dz = dz;
+  l.s = s;
+  l.dk = dk;
+  l.diag = logistic && sampler_params[d] != 0.;
+  l.core = a.core;
+  l.w = a.w;
+  l.E = nullptr;
+  l.theta = a.theta;
+  l.mode = v->dev + o_s0;
+  l.rowc = v->dev + o_rowc;
+  l.counts = reinterpret_cast<int*>(v->dev + o_cnt);
+  v->kind = sampler_kind;
   v->m = m;
   v->n_sub = n_sub;
   v->s = s;
@@ -293,13 +334,20 @@ extern "C" int bc_vi_optimize_chunk_begin(bc_ctx* ctx, const double* normals, co
   BC_HIP(hipEventRecord(v->ev[0], ctx->stream));
   v->chunk_pending = true;      // from here on something is enqueued: _chunk_end must wait even if a launch below fails
   const double b1 = 0.9, b2 = 0.999, eps = 1e-8;
-  const size_t lds = (size_t)BC_VIS_WS_DOUBLES(v->d) * sizeof(double);
+  const bool logistic = v->kind == BC_VI_SAMPLER_LOGISTIC;
+  const size_t lds = (size_t)(logistic ? BC_VIL_WS_DOUBLES(v->d) : BC_VIS_WS_DOUBLES(v->d)) * sizeof(double);
   const int m = (int)v->m;
   for (int t = 0; t < k; ++t) {
     const int i = v->done + t;
-    VisArgs a = v->va;
-    a.E = v->stage_dev + (size_t)t * v->s * v->d;
-    hipLaunchKernelGGL(k_vi_sampler, dim3(1), dim3(BC_VIS_BLOCK), lds, ctx->stream, a, v->d_flag, i);
+    if (logistic) {
+      VilArgs a = v->la;
+      a.E = v->stage_dev + (size_t)t * v->s * v->d;
+      hipLaunchKernelGGL(k_vi_laplace, dim3(1), dim3(BC_VIL_BLOCK), lds, ctx->stream, a, v->d_flag, i);
+    } else {
+      VisArgs a = v->va;
+      a.E = v->stage_dev + (size_t)t * v->s * v->d;
+      hipLaunchKernelGGL(k_vi_sampler, dim3(1), dim3(BC_VIS_BLOCK), lds, ctx->stream, a, v->d_flag, i);
+    }
     BC_HIP(hipGetLastError());
     const bc_data* rows = v->data;
     if (n_sub > 0) {
@@ -330,8 +378,12 @@ extern "C" int bc_vi_optimize_chunk_end(bc_ctx* ctx) {
   if (hipEventElapsedTime(&ms, v->ev[0], v->ev[1]) == hipSuccess) v->dev_ms += ms;
   if (*hflag != 0) {
     v->failed = true;
-    bc_set_error("bc_vi_optimize: step %d: the posterior precision matrix of the weighted coreset is not positive definite "
-                 "(a pivot of its Cholesky factorisation is not finite and positive)", *hflag - 1);
+    if (v->kind == BC_VI_SAMPLER_LOGISTIC)
+      bc_set_error("bc_vi_optimize: step %d: the Laplace fit of the weighted coreset met a weight, a value of the log-joint, a gradient "
+                   "or a pivot of the Hessian's Cholesky factorisation that is not finite (a pivot must also be positive)", *hflag - 1);
+    else
+      bc_set_error("bc_vi_optimize: step %d: the posterior precision matrix of the weighted coreset is not positive definite "
+                   "(a pivot of its Cholesky factorisation is not finite and positive)", *hflag - 1);
     return BC_NUMERICAL_PRECISION;
   }
   return BC_OK;
@@ -393,6 +445,24 @@ extern "C" int bc_vi_optimize_last_draw(bc_ctx* ctx, int32_t s, int32_t d, doubl
   }
   if (out_raw) memcpy(out_raw, h.data() + n_th, n_raw * sizeof(double));
   *out_pad_max = pad_nan ? NAN : pad;
+  return BC_OK;
+}
+
+extern "C" int bc_vi_laplace_last_mode(bc_ctx* ctx, int32_t d, double* out_mu, int32_t* out_counts) {
+  if (!ctx || !out_mu || !out_counts) { bc_set_error("bc_vi_laplace_last_mode: bad argument"); return BC_INVALID_ARGUMENT; }
+  bc_viopt* v = ctx->viopt;
+  if (!v || !v->laid_out) { bc_set_error("bc_vi_laplace_last_mode: no run has been begun on this context"); return BC_INVALID_ARGUMENT; }
+  if (v->chunk_pending) { bc_set_error("bc_vi_laplace_last_mode: a chunk is pending (call the run's chunk_end first)"); return BC_INVALID_ARGUMENT; }
+  if (v->kind != BC_VI_SAMPLER_LOGISTIC) { bc_set_error("bc_vi_laplace_last_mode: the last run had sampler kind %d, not the logistic one", v->kind); return BC_INVALID_ARGUMENT; }
+  if (d != v->d) { bc_set_error("bc_vi_laplace_last_mode: the last run had D = %d, not D = %d", v->d, d); return BC_INVALID_ARGUMENT; }
+  BC_HIP(hipSetDevice(ctx->device));
+  int cnt[4] = {0, 0, 0, 0};
+  BC_HIP(hipStreamSynchronize(ctx->stream));
+  BC_HIP(hipMemcpy(out_mu, v->la.mode, (size_t)d * sizeof(double), hipMemcpyDeviceToHost));
+  BC_HIP(hipMemcpy(cnt, v->la.counts, sizeof(cnt), hipMemcpyDeviceToHost));
+  out_counts[0] = cnt[0];
+  out_counts[1] = cnt[1];
+  out_counts[2] = cnt[2];
   return BC_OK;
 }
 

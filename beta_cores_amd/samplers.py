@@ -331,6 +331,14 @@ class LogisticLaplaceSampler(_PosteriorSampler):
         if self.solver != 'bfgs':
             super().prefetch()
 
+    def device_spec(self):
+        """(sampler kind, parameters) as bc_vi_optimize takes them: start [D] | diag flag, with the start point this sampler's
+        next call would begin at.  Only for solver='newton' (k_vi_laplace restates that search); None with the reference's
+        optimiser, which stops elsewhere and may draw restart perturbations from the stream: the host loop keeps it."""
+        if self.solver != 'newton':
+            return None
+        return 2, np.concatenate((self.mu0 if self._mode is None else self._mode, [1. if self.diag else 0.]))
+
     def __call__(self, n, wts, pts):
         d = self.mu0.shape[0]
         if pts.shape[0] == 0:

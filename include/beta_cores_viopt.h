@@ -11,6 +11,8 @@
  * per run.  One step is, on the context's stream, in order:
  *
  *   1. k_vi_sampler    Theta = mu_w + E . L_w^T from the coreset rows and the CURRENT weights (one block; Cholesky in LDS)
+ *      k_vi_laplace    (logistic kind) the same draw around the mode of the weighted log-joint: a damped Newton solve in the
+ *                      block, started at the previous step's mode, which stays on the device (beta_cores_vilaplace.h)
  *   2. K1              of the coreset rows, materialised
  *   3. k_take_rows     the step's sub-sample of the resident rows (when sub-sampled)
  *   4. K1, store-free  of the data rows
@@ -22,9 +24,9 @@
  * uploaded per chunk of steps.  Results equal the host loop's to rounding (the Cholesky and E . L^T have neither LAPACK's nor
  * BLAS's bits), not bit for bit.
  *
- * Out of scope (the host loop serves them): the logistic Laplace sampler (a Newton solve on the device), feature encoders,
- * groups, row shards (communicators), learn_beta = True, and a device-side random number generator (it would leave the
- * reference's stream).
+ * Out of scope (the host loop serves them): the reference's BFGS mode search of the logistic sampler, feature encoders, groups,
+ * row shards (communicators), learn_beta = True, and a device-side random number generator (it would leave the reference's
+ * stream).
  */
 #ifndef BETA_CORES_VIOPT_H
 #define BETA_CORES_VIOPT_H
@@ -37,6 +39,9 @@ extern "C" {
 
 #define BC_VI_SAMPLER_LINREG 0      /* sampler_params = th0 [D] | Sig0inv [D][D] | sigsq;   rows [x (D), y] */
 #define BC_VI_SAMPLER_GAUSS 1       /* sampler_params = mu0 [d] | Sig0inv [d][d] | Siginv [d][d];   rows x (d) */
+#define BC_VI_SAMPLER_LOGISTIC 2    /* sampler_params = start [D] | diag flag (0.0 or 1.0);   rows z = y * x (D); prior N(0, I).
+                                     * The Laplace approximation by damped Newton steps (samplers.logistic_laplace, solver='newton');
+                                     * start: where the first step's search begins, every later step begins at the mode before it. */
 #define BC_VI_MAX_DIM 128           /* largest D: the factor and its inverse share one work-group's LDS */
 #define BC_VI_STAGE_BYTES (32u << 20)      /* automatic chunks keep the staged draws (normals + indices) of a chunk under this */
 
@@ -51,13 +56,15 @@ int bc_vi_optimize_auto_chunk(int32_t s, int32_t d, int64_t n_sub);
  * weights (and the trace) and closes the run; call it after a failure too (out_w = NULL: nothing is copied).
  *   core_rows: host, m x dz doubles (dz = the data's column count).     w0: host, m.
  *   model / params: as bc_vi_gradient takes them (a value model: LINREG_LL/_BETA with the linreg sampler, GAUSS_LL/_BETA with
- *     the Gaussian one).  s <= 256, D <= BC_VI_MAX_DIM, m (dz + 1) <= 60000.
+ *     the Gaussian one, LOGISTIC_LL (no params) / LOGISTIC_BETA ({beta, value at zero}) with the logistic one; any other pair
+ *     is refused with BC_INVALID_ARGUMENT).  s <= 256, D <= BC_VI_MAX_DIM, m (dz + 1) <= 60000.
  *   step: host, [3][opt_itrs]: step_sched(i) | 1 - b1^(i+1) | 1 - b2^(i+1) with b1 = 0.9, b2 = 0.999, eps = 1e-8 (nn_opt).
  *   n_sub: rows per sub-sample, 0 = every step projects all rows of `data` (sum_scaling is then usually 1).
  *   normals: host, k x S x D.    sub_idx: host, k x n_sub (NULL iff n_sub == 0), local row numbers of `data`.
  * A pivot of the Cholesky that is not finite and positive marks the run on the device: the sampler and the ADAM kernel of
  * every later step return at once (the projections between them run on the previous Theta and their result is dropped),
- * _chunk_end returns BC_NUMERICAL_PRECISION and _end copies nothing. */
+ * _chunk_end returns BC_NUMERICAL_PRECISION and _end copies nothing.  The logistic kind marks the run the same way on a weight,
+ * a value of the log-joint, a component of its gradient or a pivot that is not finite. */
 int bc_vi_optimize_begin(bc_ctx* ctx, const bc_data* data, const double* core_rows, int64_t m, int model, const double* params,
                          int32_t n_params, int sampler_kind, const double* sampler_params, int32_t s, const double* w0,
                          int32_t opt_itrs, const double* step, int64_t n_sub, double sum_scaling, int want_trace);
