@@ -12,6 +12,7 @@
 // deterministic.  Coreset-sized inputs (the samplers, once per gradient) take one launch,
 // k_gram_small, with no partials at all.
 #include "bc_internal.h"
+#include "bc_gram_plan.h"
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -404,7 +405,7 @@ __global__ __launch_bounds__(256, BC_GD_BLOCKS) void k_gram_dma(GramArgs a) {
 // and scatters the tile (and its mirror image) into the dense d x d matrix.  The association is fixed by (splits, SEG):
 // run-to-run deterministic.  (One level with one thread per element walked 2 048 splits serially: 0.81 ms at N = 10M,
 // D = 128, 13 % on top of the Gram kernel itself.)
-#define BC_GRAM_SEG 16
+// (BC_GRAM_SEG: bc_gram_plan.h)
 __global__ __launch_bounds__(256) void k_gram_reduce1(const double* __restrict__ partial, long long splits, long long nruns,
                                                      size_t tile_elems /* ntri*bt*bt */, int nt, int bt, double* __restrict__ part2) {
   const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -564,16 +565,8 @@ static int run_gram(bc_ctx* ctx, const bc_data* data, const double* w_dev, doubl
   static const int waves_env = getenv("BC_GRAM_WAVES") ? atoi(getenv("BC_GRAM_WAVES")) : 0;
   const int waves = waves_env > 0 ? waves_env : (ntri == 1 ? 1 : 8);
   const int slots = use_dma ? BC_GD_BLOCKS : (BT == 64 ? 3 : 2);      // resident blocks per CU (the kernels' launch bounds)
-  long long want_splits = ((long long)ctx->n_cu * slots * (waves > 0 ? waves : 1) + ntri - 1) / ntri;
-  long long max_splits = (data->n_rows + 2 * KR - 1) / (2 * KR);
-  long long splits = want_splits < max_splits ? want_splits : max_splits;
-  if (splits < 1) splits = 1;
-  long long rps = (data->n_rows + splits - 1) / splits;
-  rps = ((rps + KR - 1) / KR) * KR;
-  if (rps < KR) rps = KR;
-  splits = (data->n_rows + rps - 1) / rps;
-  if (splits < 1) splits = 1;
-  const long long nruns = (splits + BC_GRAM_SEG - 1) / BC_GRAM_SEG;
+  long long rps = 0, splits = 0, nruns = 0;
+  bc_gram_plan(data->n_rows, ntri, ctx->n_cu, slots, waves, KR, &rps, &splits, &nruns);
   const size_t tile_elems = (size_t)ntri * BT * BT;
   double* partial = nullptr;
   double* partial_y = nullptr;
