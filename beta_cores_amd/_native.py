@@ -186,6 +186,19 @@ _VILAPLACE_SIGNATURES = {
 }
 VILAPLACE_EXPORTS = sorted(_VILAPLACE_SIGNATURES)
 
+# entry points of the extension header include/beta_cores_hmc.h (multi-chain HMC of the logistic posterior, the multi-chain rows pass)
+_HMC_SIGNATURES = {
+    'bc_logistic_logjoint_batch': [vp, vp, vp, vp, C.c_int32, vp, vp],
+    'bc_hmc_auto_chunk': [C.c_int32, C.c_int32],      # returns an iteration count, not a status
+    'bc_hmc_begin': [vp, vp, vp, vp, C.c_int32, vp, C.c_int32, C.c_int64],
+    'bc_hmc_chunk_begin': [vp, vp, vp, C.c_int32, C.c_double],
+    'bc_hmc_chunk_end': [vp, vp, vp, vp],
+    'bc_hmc_end': [vp],
+    'bc_hmc_device_ms': [vp, c_dp],
+    'bc_hmc_logistic': [vp, vp, vp, vp, C.c_int32, vp, C.c_int32, C.c_double, C.c_int64, vp, vp, C.c_int32, vp, vp, vp],
+}
+HMC_EXPORTS = sorted(_HMC_SIGNATURES)
+
 _lib = None
 
 
@@ -219,7 +232,8 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, argtypes in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_F32_SIGNATURES.items()) + list(_NNLS_SIGNATURES.items()) \
             + list(_TAKE_SIGNATURES.items()) + list(_BETAGRAD_SIGNATURES.items()) + list(_ENCODE_SIGNATURES.items()) \
-            + list(_VIOPT_SIGNATURES.items()) + list(_PSVI_SIGNATURES.items()) + list(_VILAPLACE_SIGNATURES.items()):
+            + list(_VIOPT_SIGNATURES.items()) + list(_PSVI_SIGNATURES.items()) + list(_VILAPLACE_SIGNATURES.items()) \
+            + list(_HMC_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int

@@ -110,6 +110,7 @@ extern "C" int bc_ctx_destroy(bc_ctx* ctx) {
   bc_uploader_free(ctx);
   bc_take_free(ctx);
   bc_viopt_free(ctx);
+  bc_hmc_free(ctx);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
   return BC_OK;

@@ -94,6 +94,7 @@ struct bc_ctx {
   hipEvent_t take_ev[2] = {nullptr, nullptr};
   int take_turn = 0;
   struct bc_viopt* viopt = nullptr;    // bc_vi_optimize (bc_viopt.hip): the buffers and the state of the run in progress
+  struct bc_hmc* hmc = nullptr;        // bc_hmc_* (bc_hmc.hip): the buffers and the state of the HMC run in progress
 };
 
 // bc_upload.hip: rows of a host array -> dst_dev through pinned staging and several copy threads; the hook (optional) is
@@ -106,6 +107,9 @@ int64_t bc_upload_default_chunk_rows(int64_t n_rows, size_t row_bytes);
 void bc_uploader_free(bc_ctx* ctx);
 void bc_take_free(bc_ctx* ctx);      // bc_take.hip: the two pinned index staging areas and their events
 void bc_viopt_free(bc_ctx* ctx);     // bc_viopt.hip
+bool bc_viopt_active(const bc_ctx* ctx);   // a bc_vi_optimize run is open on the context
+void bc_hmc_free(bc_ctx* ctx);       // bc_hmc.hip
+bool bc_hmc_active(const bc_ctx* ctx);     // a bc_hmc run is open on the context
 // bc_take.hip: dst[j, :] = src[idx_dev[j], :] for indices that are already on the device and already checked; enqueued only
 int bc_take_rows_dev(bc_ctx* ctx, const bc_data* src, const long long* idx_dev, int64_t m, void* dst_z);
 // bc_project.hip: one gradient's projections and algebra for a Theta that is already on the device (bc_viopt.hip)
@@ -129,6 +133,8 @@ int bc_scratch_grow(bc_ctx* ctx, bc_scratch* s, size_t doubles);   // contents a
 int bc_timer_begin(bc_ctx* ctx, int which);
 int bc_gram_no_y(bc_ctx* ctx, const bc_data* data, const double* w_dev, double** out_dev);   // bc_gram.hip
 int bc_timer_end(bc_ctx* ctx, int which);
+// bc_laplace.hip: out[e] = sum over blocks of part[b][e] in block order (k_lr_reduce), enqueued on the context's stream
+int bc_lr_reduce_launch(bc_ctx* ctx, const double* part_dev, long long blocks, int elems, double* out_dev);
 
 struct bc_data {
   bc_ctx* ctx = nullptr;

@@ -15,6 +15,7 @@
 // in block order by k_lr_reduce: the association is fixed by (n_rows, grid), a call is bit-reproducible run to run.  The pass
 // optionally writes the curvature weights w_n c_n to an N-vector, from which H is K4 (bc_gram.hip) in its no-y-column mode.
 #include "bc_internal.h"
+#include "bc_lr_terms.h"
 #include "../../include/beta_cores_laplace.h"
 #include <cmath>
 #include <cstring>
@@ -33,20 +34,6 @@ struct LrArgs {
   long long rows_per_block;   // multiple of 4 R
   int d;
 };
-
-// the per-row terms for a wave-uniform m: log-likelihood, p, c -- overflow-free (exp of a non-positive argument only)
-__device__ __forceinline__ void lr_terms(double m, double& ll, double& p, double& c) {
-  if (m < 100.) {
-    const double e = exp(-fabs(m)), ope = 1. + e;
-    ll = -(fmax(m, 0.) + log1p(e));
-    p = m >= 0. ? 1. / ope : e / ope;
-    c = e / (ope * ope);
-  } else {
-    ll = -m;
-    p = 1.;
-    c = 0.;
-  }
-}
 
 template <int NC, int R, bool DIAG, typename ZT = double>   // R: a power of two <= 64; ZT: the rows' storage type (float: widened as read)
 __global__ __launch_bounds__(256) void k_lr_rows(LrArgs a) {
@@ -165,6 +152,12 @@ __global__ __launch_bounds__(256) void k_lr_reduce(const double* __restrict__ pa
   }
 }
 
+int bc_lr_reduce_launch(bc_ctx* ctx, const double* part_dev, long long blocks, int elems, double* out_dev) {
+  hipLaunchKernelGGL(k_lr_reduce, dim3((unsigned)((elems + 15) / 16)), dim3(256), 0, ctx->stream, part_dev, blocks, elems, out_dev);
+  BC_HIP(hipGetLastError());
+  return BC_OK;
+}
+
 template <int NC, int R>
 static void launch_rows(bool diag, bool f32, dim3 grid, hipStream_t s, const LrArgs& a) {
   if (f32) {
@@ -248,9 +241,8 @@ extern "C" int bc_logistic_newton_pass(bc_ctx* ctx, const bc_data* data, const b
     default: launch_rows<16, 2>(diag, f32, grid, ctx->stream, a); break;
   }
   BC_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_lr_reduce, dim3((unsigned)((elems + 15) / 16)), dim3(256), 0, ctx->stream, (const double*)a.part, blocks, elems,
-                     red_dev);
-  BC_HIP(hipGetLastError());
+  rc = bc_lr_reduce_launch(ctx, a.part, blocks, elems, red_dev);
+  if (rc) return rc;
   rc = bc_timer_end(ctx, 6);
   if (rc) return rc;
   double* hess_dev = nullptr;

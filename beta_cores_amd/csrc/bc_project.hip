@@ -895,6 +895,7 @@ static int vi_gradient_begin(bc_ctx* ctx, const bc_data* data, const double* cor
     bc_set_error("%s_begin: a gradient is already pending on this context (call %s_end first)", who, vi_kind_name(ctx->vi_pending_kind));
     return BC_INVALID_ARGUMENT;
   }
+  if (bc_hmc_active(ctx)) { bc_set_error("%s_begin: a bc_hmc run is open on this context (call bc_hmc_end first)", who); return BC_INVALID_ARGUMENT; }
   if (n_down > ctx->pinned_doubles) {
     bc_set_error("%s: coreset of %lld rows x %d exceeds the staging area", who, (long long)m, dz);
     return BC_INVALID_ARGUMENT;

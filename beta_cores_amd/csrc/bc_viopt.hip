@@ -76,6 +76,8 @@ struct bc_viopt {
   int* d_flag = nullptr;
 };
 
+bool bc_viopt_active(const bc_ctx* ctx) { return ctx->viopt && ctx->viopt->active; }
+
 void bc_viopt_free(bc_ctx* ctx) {
   bc_viopt* v = ctx->viopt;
   if (!v) return;
@@ -148,6 +150,7 @@ extern "C" int bc_vi_optimize_begin(bc_ctx* ctx, const bc_data* data, const doub
                                    : (model == BC_MODEL_LINREG_LL || model == BC_MODEL_LINREG_BETA);
   if (!model_ok) { bc_set_error("bc_vi_optimize_begin: model %d does not go with sampler kind %d", model, sampler_kind); return BC_INVALID_ARGUMENT; }
   if (ctx->vi_pending_m > 0) { bc_set_error("bc_vi_optimize_begin: a bc_vi_gradient is pending on this context"); return BC_INVALID_ARGUMENT; }
+  if (bc_hmc_active(ctx)) { bc_set_error("bc_vi_optimize_begin: a bc_hmc run is open on this context (call bc_hmc_end first)"); return BC_INVALID_ARGUMENT; }
   const int dz = data->dz;
   int d = 0, dk = 0, nrsel = 0, ntsel = 0;
   if (bc_vi_plan_layout(model, s, dz, &d, &dk, &nrsel, &ntsel) != BC_OK || d > BC_VI_MAX_DIM) {

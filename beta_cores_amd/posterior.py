@@ -172,3 +172,43 @@ def _weights_on_device(w, n, ctx):
     if w.shape != (n,):
         raise ValueError('w must have one weight per row (%d), got shape %r' % (n, w.shape))
     return DeviceData(w.reshape(n, 1), ctx=ctx)
+
+
+HMC_MAX_CHAINS, HMC_MAX_DIM = 64, 256      # the limits of the multi-chain rows pass (include/beta_cores_hmc.h)
+
+
+def check_hmc_problem(shape, n_chains, comm=None, ctx=None, rows_ctx=None):
+    """The argument checks shared by logistic_logjoint_batch and samplers.logistic_hmc, before anything reaches the device."""
+    if comm is not None and comm.world > 1:
+        raise NotImplementedError('the multi-chain logistic pass serves one device: row shards (comm.world > 1) are not implemented')
+    if ctx is not None and ctx is not rows_ctx:
+        raise ValueError('ctx must be the context the rows live on')
+    if not 1 <= int(n_chains) <= HMC_MAX_CHAINS:
+        raise ValueError('1 .. %d chains are served, got %d' % (HMC_MAX_CHAINS, int(n_chains)))
+    if len(shape) != 2 or not 1 <= shape[1] <= HMC_MAX_DIM:
+        raise ValueError('the rows must be n x D with 1 <= D <= %d, got shape %r' % (HMC_MAX_DIM, tuple(shape)))
+
+
+def logistic_logjoint_batch(dz, thetas, w=None, comm=None, ctx=None, value=True):
+    """The weighted logistic log-joint with the N(0, I) prior (model_lr.py:88-93) of resident rows z = y*x at C parameter
+    vectors at once, and its gradients: (values [C], grads [C, D]) from ONE pass over the rows (k_lr_rows_mc: both contractions
+    on the fp64 matrix cores, 16 chains per tile).  `dz`: a DeviceData (an ndarray is uploaded first; float32 rows stay
+    float32); `thetas`: C x D with 1 <= C <= 64, D <= 256; `w`: n_rows host weights, a DeviceData of n_rows x 1, or None = all
+    ones.  value=False: the gradient-only pass the inner leapfrog steps of the HMC run use, (None, grads).  The bits of one theta's
+    results do not depend on the others in the batch."""
+    if not isinstance(dz, DeviceData):
+        if isinstance(dz, np.ndarray) and dz.dtype == np.float32 and dz.ndim == 2:
+            dz = DeviceData(dz, ctx=ctx, dtype=np.float32)
+        else:
+            dz = DeviceData(np.atleast_2d(np.asarray(dz, dtype=np.float64)), ctx=ctx)
+    n, d = dz.shape
+    th = np.ascontiguousarray(np.atleast_2d(thetas), dtype=np.float64)
+    check_hmc_problem(dz.shape, th.shape[0], comm=comm, ctx=ctx, rows_ctx=dz.ctx)
+    if th.ndim != 2 or th.shape[1] != d:
+        raise ValueError('thetas must be C x %d (one column per column of the rows), got shape %r' % (d, th.shape))
+    wd = _weights_on_device(w, n, dz.ctx)
+    vals = np.empty(th.shape[0]) if value else None
+    grads = np.empty(th.shape)
+    N.call('bc_logistic_logjoint_batch', dz.ctx.h, dz.h, wd.h if wd is not None else None, _ptr(th), int(th.shape[0]), _ptr(vals),
+           _ptr(grads))
+    return vals, grads

@@ -13,13 +13,16 @@ enqueueing a gradient on the GPU and waiting for it -- the ~60-120 us of `randn(
 two launches.  The draws come from the same stream in the same order, and a prefetched matrix is always consumed by the very
 next call, so the results and the RNG position after a build are the reference's (tests/test_gpu_storefree.py).
 """
+import ctypes
+
 import numpy as np
 
 import scipy.linalg as sl
 from scipy.optimize import minimize
 
-from .device import DeviceData
-from .posterior import gaussian_weighted_post, logistic_newton_pass, small_lapack_scope, weighted_post, _weights_on_device
+from . import _native as N
+from .device import DeviceData, _ptr
+from .posterior import check_hmc_problem, gaussian_weighted_post, logistic_newton_pass, small_lapack_scope, weighted_post, _weights_on_device
 
 
 class _PosteriorSampler:
@@ -370,3 +373,141 @@ class LaplaceFullDataSampler(_PosteriorSampler):
 
     def __call__(self, n, wts=None, pts=None):
         return self.mu + self._normals(n, self.mu.shape[0]).dot(self.LSig.T)
+
+
+# ---- exact-posterior samples of the logistic model: multi-chain HMC with every pass over the rows on the device
+class HMCResult:
+    """What logistic_hmc returns.  samples: n_samples x n_chains x D (the position of every chain after every kept iteration);
+    logjoint: n_samples x n_chains; accept: n_samples x n_chains (bool); accept_rate: per chain, over the kept iterations;
+    step_size: the step the kept iterations ran with (frozen after warm-up); warmup_steps: the step of every warm-up chunk;
+    start, inv_mass: what the run began with; device_ms: GPU milliseconds of the run's chunks (None from a stand-in engine)."""
+
+    def __init__(self, samples, logjoint, accept, step_size, warmup_steps, start, inv_mass, device_ms):
+        self.samples, self.logjoint, self.accept = samples, logjoint, accept
+        self.accept_rate = accept.mean(axis=0) if accept.shape[0] else np.zeros(accept.shape[1])
+        self.step_size, self.warmup_steps, self.start, self.inv_mass, self.device_ms = step_size, warmup_steps, start, inv_mass, device_ms
+
+    def pooled(self):
+        """All chains' samples as one (n_samples * n_chains) x D array, the `thetas` the drivers score."""
+        return self.samples.reshape(-1, self.samples.shape[2])
+
+
+class _DeviceHMC:
+    """The engine behind logistic_hmc: the chunked entry points of include/beta_cores_hmc.h."""
+
+    def __init__(self, Z, wd):
+        self.Z, self.wd = Z, wd
+
+    def begin(self, start, inv_mass, n_leapfrog, n_iter):
+        self._cd = start.shape
+        N.call('bc_hmc_begin', self.Z.ctx.h, self.Z.h, self.wd.h if self.wd is not None else None, _ptr(start), int(start.shape[0]),
+               _ptr(inv_mass), int(n_leapfrog), int(n_iter))
+
+    def auto_chunk(self, c, d):
+        return int(N.load().bc_hmc_auto_chunk(int(c), int(d)))
+
+    def chunk(self, normals, log_u, step_size):
+        k = normals.shape[0]
+        N.call('bc_hmc_chunk_begin', self.Z.ctx.h, _ptr(normals), _ptr(log_u), int(k), float(step_size))
+        samples, lj, acc = np.empty((k,) + self._cd), np.empty((k, self._cd[0])), np.empty((k, self._cd[0]), dtype=np.int32)
+        N.call('bc_hmc_chunk_end', self.Z.ctx.h, _ptr(samples), _ptr(lj), _ptr(acc))
+        return samples, lj, acc
+
+    def end(self):
+        N.load().bc_hmc_end(self.Z.ctx.h)      # (status ignored: also called to close a failed run)
+        ms = ctypes.c_double()
+        N.call('bc_hmc_device_ms', self.Z.ctx.h, ctypes.byref(ms))
+        return ms.value
+
+
+def hmc_warmup_step(step, accept_fraction, rate=1.0, target=0.8):
+    """The warm-up rule of logistic_hmc: step <- step * exp(rate * (accept_fraction - target))."""
+    return float(step) * float(np.exp(rate * (accept_fraction - target)))
+
+
+def logistic_hmc(Z, wts=None, n_samples=1000, n_chains=16, step_size=0.1, n_leapfrog=8, inv_mass=None, start=None, warmup=0, rng=None,
+                 ctx=None, comm=None, adapt_every=25, adapt_rate=1.0, chunk=None, engine=None):
+    """Samples of the logistic posterior of the rows Z = y*x with weights wts under the N(0, I) prior -- the reference's weighted
+    log-joint (model_lr.py:88-93; the Stan programs of zellner_logreg/main.py:24-62 with the intercept as a column) -- by plain
+    HMC: `n_chains` chains in lock-step, a diagonal inverse mass, a fixed step and `n_leapfrog` leapfrog steps.  Not NUTS, no
+    dual averaging.  Every pass over the rows serves all chains at once on the device (k_lr_rows_mc); a chunk of iterations is
+    enqueued whole and waited for once.  No CPU fallback.
+
+    Z: a DeviceData (the full data, resident), or an ndarray, which is uploaded -- a weighted coreset of a few hundred points goes
+      through the same call.  wts: one weight per row (zeros allowed: such a row contributes exactly nothing), None = all ones.
+    start: n_chains x D; None = draws mu + randn(n_chains, D).LSig^T from the device Laplace fit
+      (logistic_laplace(..., solver='newton') started at 0).
+    inv_mass: D positive numbers, None = ones, 'laplace' = 1 / (1 + diag) with diag from logistic_newton_pass(..., diag=True) at
+      the Laplace mode (the posterior variances of the diagonal Laplace approximation).
+    Warm-up: `warmup` iterations in chunks of `adapt_every`; after every such chunk
+      step <- step * exp(adapt_rate * (acc - 0.8)),   acc = the fraction of accepted proposals of that chunk over all chains
+    (hmc_warmup_step: deterministic, host arithmetic between chunks).  Warm-up iterations are discarded, and the step is frozen for
+    the n_samples kept iterations.
+    Draws (NumPy's stream `rng`, or the global one), in this order: the start's normals (start=None only); then per chunk of k
+    iterations randn(k, n_chains, D) followed by log(rand(k, n_chains)).  Kept iterations are chunked by `chunk` (None = as many
+    as keep the staged draws under 32 MB).
+    Limits: 1 <= n_chains <= 64, D <= 256, one device (comm.world > 1 raises NotImplementedError).
+    Returns an HMCResult."""
+    if engine is None and not isinstance(Z, DeviceData):
+        if isinstance(Z, np.ndarray) and Z.dtype == np.float32 and Z.ndim == 2:
+            Z = DeviceData(Z, ctx=ctx, dtype=np.float32)
+        else:
+            Z = DeviceData(np.atleast_2d(np.asarray(Z, dtype=np.float64)), ctx=ctx)
+    check_hmc_problem(Z.shape, n_chains, comm=comm, ctx=ctx, rows_ctx=getattr(Z, 'ctx', None))
+    n, d = Z.shape
+    c = int(n_chains)
+    if n_samples < 1 or warmup < 0 or n_leapfrog < 1 or adapt_every < 1:
+        raise ValueError('needs n_samples >= 1, warmup >= 0, n_leapfrog >= 1 and adapt_every >= 1')
+    if not (np.isfinite(step_size) and step_size > 0.):
+        raise ValueError('step_size must be finite and positive, got %r' % (step_size,))
+    if wts is not None:
+        wts = np.ascontiguousarray(wts, dtype=np.float64)
+        if wts.shape != (n,):
+            raise ValueError('wts must have one weight per row of Z (%d), got shape %r' % (n, wts.shape))
+    randn = np.random.randn if rng is None else rng.randn
+    rand = np.random.rand if rng is None else rng.rand
+    mode = None
+    if start is None or (isinstance(inv_mass, str) and inv_mass == 'laplace'):
+        if engine is not None:
+            raise ValueError('a stand-in engine has no Laplace fit: pass start and inv_mass')
+        mode, LSig, _ = logistic_laplace(wts, Z, np.zeros(d), solver='newton')
+    if isinstance(inv_mass, str):
+        if inv_mass != 'laplace':
+            raise ValueError("inv_mass must be D positive numbers, None or 'laplace'")
+        inv_mass = 1. / (1. + logistic_newton_pass(Z, mode, None if wts is None else np.where(wts > 0, wts, 0.), hessian=False, diag=True)[3])
+    inv_mass = np.ones(d) if inv_mass is None else np.ascontiguousarray(inv_mass, dtype=np.float64)
+    if inv_mass.shape != (d,) or not np.all(np.isfinite(inv_mass)) or not np.all(inv_mass > 0.):
+        raise ValueError('inv_mass must be %d finite positive numbers' % d)
+    if start is None:
+        start = mode + randn(c, d).dot(LSig.T)
+    start = np.ascontiguousarray(start, dtype=np.float64)
+    if start.shape != (c, d):
+        raise ValueError('start must be n_chains x D = %d x %d, got shape %r' % (c, d, start.shape))
+    eng = engine(Z, wts) if engine is not None else _DeviceHMC(Z, None if wts is None else _weights_on_device(wts, n, Z.ctx))
+    if chunk is None:
+        chunk = eng.auto_chunk(c, d)
+    if chunk < 1:
+        raise ValueError('chunk must be >= 1')
+    step = float(step_size)
+    warm_steps = []
+    out_s, out_l, out_a = np.empty((n_samples, c, d)), np.empty((n_samples, c)), np.empty((n_samples, c), dtype=bool)
+    eng.begin(start, inv_mass, int(n_leapfrog), int(warmup) + int(n_samples))
+    try:
+        left = int(warmup)
+        while left > 0:
+            k = min(left, int(adapt_every))
+            e, u = randn(k, c, d), np.log(rand(k, c))
+            _, _, acc = eng.chunk(np.ascontiguousarray(e), np.ascontiguousarray(u), step)
+            warm_steps.append(step)
+            step = hmc_warmup_step(step, float(np.mean(acc != 0)), adapt_rate)
+            left -= k
+        i0 = 0
+        while i0 < n_samples:
+            k = min(n_samples - i0, int(chunk))
+            e, u = randn(k, c, d), np.log(rand(k, c))
+            s, lj, acc = eng.chunk(np.ascontiguousarray(e), np.ascontiguousarray(u), step)
+            out_s[i0:i0 + k], out_l[i0:i0 + k], out_a[i0:i0 + k] = s, lj, acc != 0
+            i0 += k
+    finally:
+        ms = eng.end()
+    return HMCResult(out_s, out_l, out_a, step, np.array(warm_steps), start, inv_mass, ms)

@@ -1,0 +1,98 @@
+#!/usr/bin/env python3
+"""The logistic drivers' evaluation with exact-posterior samples drawn on the GPU.
+
+    python examples/logistic_mcmc_eval.py [--n 200000] [--d 10] [--m 200] [--samples 250] [--chains 16] [--seed 1]
+
+The reference's logistic drivers end by drawing ~1 000 posterior samples with MCMC -- of the full data as ground truth
+(examples/common/mcmc.py:21), of the weighted coreset as the thing to judge (zellner_logreg/main.py:225-230) -- and scoring them
+on a held-out split.  Here both come from samplers.logistic_hmc (multi-chain HMC, every pass over the rows on the device), next
+to samples of the coreset's Laplace approximation:
+
+  full      HMC over all N resident training rows                          (the ground truth)
+  coreset   HMC over the M weighted coreset rows (GIGA on a Laplace tangent space), an ndarray through the same call
+  laplace   mu + randn . LSig^T from the coreset's Laplace fit
+
+Scores, in plain NumPy on the small test split as the drivers compute them (model_lr.py:32-42, main.py:229-230): the accuracy
+of the max-likelihood prediction under each sampled theta, averaged (compute_accuracy), and the test log-likelihood summed over
+the points and averaged over the samples.  Also the distance of each sample set's mean from the ground truth's, in units of the
+ground truth's posterior standard deviations.
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
+import beta_cores_amd as bc
+
+
+def log_likelihood(z, th):
+    """model_lr.py:72-79"""
+    m = -np.atleast_2d(z).dot(np.atleast_2d(th).T)
+    small = m < 100
+    m[small] = -np.log1p(np.exp(m[small]))
+    m[np.logical_not(small)] = -m[np.logical_not(small)]
+    return m
+
+
+def compute_accuracy(Xt, Yt, thetas):
+    """model_lr.py:32-42"""
+    loglikep, logliken = log_likelihood(Xt, thetas), log_likelihood(-Xt, thetas)
+    predictions = np.ones(loglikep.shape)
+    predictions[logliken > loglikep] = -1
+    return np.mean(Yt[:, np.newaxis] == predictions)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--n', type=int, default=200_000)
+    ap.add_argument('--n-test', type=int, default=2000)
+    ap.add_argument('--d', type=int, default=10)
+    ap.add_argument('--m', type=int, default=200, help='coreset size')
+    ap.add_argument('--samples', type=int, default=250, help='kept iterations per chain')
+    ap.add_argument('--warmup', type=int, default=150)
+    ap.add_argument('--chains', type=int, default=16)
+    ap.add_argument('--leapfrog', type=int, default=8)
+    ap.add_argument('--proj-dim', type=int, default=200)
+    ap.add_argument('--seed', type=int, default=1)
+    a = ap.parse_args()
+    rng = np.random.RandomState(a.seed)
+    X = rng.randn(a.n + a.n_test, a.d)
+    X[:, -1] = 1.                                              # the intercept is the last column
+    th_true = rng.randn(a.d) * 2. / np.sqrt(a.d)
+    Y = np.where(rng.rand(X.shape[0]) < 1. / (1. + np.exp(-X.dot(th_true))), 1., -1.)
+    Xt, Yt = X[a.n:], Y[a.n:]
+    Z, Zt = Y[:a.n, None] * X[:a.n], Yt[:, None] * Xt
+    dz = bc.DeviceData(Z)
+    mu0 = np.zeros(a.d)
+    hmc = dict(n_samples=a.samples, n_chains=a.chains, n_leapfrog=a.leapfrog, step_size=0.3, inv_mass='laplace', warmup=a.warmup)
+
+    t0 = time.perf_counter()
+    full = bc.samplers.logistic_hmc(dz, None, rng=rng, **hmc)
+    t_full = time.perf_counter() - t0
+    truth = full.pooled()
+    mu_t, sd_t = truth.mean(axis=0), truth.std(axis=0)
+
+    smp = bc.samplers.LaplaceFullDataSampler(dz, mu0, rng=rng)
+    alg = bc.HilbertCoreset(Z, bc.DeviceProjector(smp, a.proj_dim, bc.likelihoods.LogisticRegression()))
+    alg.build(a.m, a.m)
+    wts, pts, _ = alg.get()
+    t0 = time.perf_counter()
+    core = bc.samplers.logistic_hmc(pts, wts, rng=rng, **hmc)
+    t_core = time.perf_counter() - t0
+    mu_c, LSig_c, _ = bc.samplers.logistic_laplace(wts, pts, mu0, solver='newton')
+    lap = mu_c + rng.randn(truth.shape[0], a.d).dot(LSig_c.T)
+
+    print('N = %d, D = %d, test split %d; coreset of %d points (Hilbert error %.3e)' % (a.n, a.d, a.n_test, len(wts), alg.error()))
+    print('HMC: %d chains x (%d warm-up + %d kept) iterations of %d leapfrog steps: full data %.2f s (step %.4g, acceptance %.2f), '
+          'coreset %.2f s (step %.4g, acceptance %.2f)' % (a.chains, a.warmup, a.samples, a.leapfrog, t_full, full.step_size,
+                                                           full.accept_rate.mean(), t_core, core.step_size, core.accept_rate.mean()))
+    for name, th in (('full', truth), ('coreset', core.pooled()), ('laplace', lap)):
+        print('%-8s accuracy %.4f   test log-likelihood %.3f   |mean - truth| / sd: max %.3f' %
+              (name, compute_accuracy(Xt, Yt, th), log_likelihood(Zt, th).sum(axis=0).mean(), np.abs((th.mean(axis=0) - mu_t) / sd_t).max()))
+
+
+if __name__ == '__main__':
+    main()
