@@ -199,6 +199,18 @@ _HMC_SIGNATURES = {
 }
 HMC_EXPORTS = sorted(_HMC_SIGNATURES)
 
+# entry points of the extension header include/beta_cores_hmc_small.h (many small logistic posteriors sampled at once, one block each)
+_HMC_SMALL_SIGNATURES = {
+    'bc_hmc_small_fits': [vp, C.c_int64, C.c_int32],      # returns 1 / 0, not a status
+    'bc_hmc_small_logjoint': [vp, vp, vp, vp, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp],
+    'bc_hmc_small_begin': [vp, vp, vp, vp, C.c_int32, C.c_int32, vp, C.c_int32, vp, C.c_int32, C.c_int64],
+    'bc_hmc_small_chunk_begin': [vp, vp, vp, C.c_int64, C.c_int32, vp],
+    'bc_hmc_small_chunk_end': [vp, vp, vp, vp, vp],
+    'bc_hmc_small_end': [vp],
+    'bc_hmc_small_device_ms': [vp, c_dp],
+}
+HMC_SMALL_EXPORTS = sorted(_HMC_SMALL_SIGNATURES)
+
 _lib = None
 
 
@@ -233,7 +245,7 @@ def load():
     for name, argtypes in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_F32_SIGNATURES.items()) + list(_NNLS_SIGNATURES.items()) \
             + list(_TAKE_SIGNATURES.items()) + list(_BETAGRAD_SIGNATURES.items()) + list(_ENCODE_SIGNATURES.items()) \
             + list(_VIOPT_SIGNATURES.items()) + list(_PSVI_SIGNATURES.items()) + list(_VILAPLACE_SIGNATURES.items()) \
-            + list(_HMC_SIGNATURES.items()):
+            + list(_HMC_SIGNATURES.items()) + list(_HMC_SMALL_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int

@@ -111,6 +111,7 @@ extern "C" int bc_ctx_destroy(bc_ctx* ctx) {
   bc_take_free(ctx);
   bc_viopt_free(ctx);
   bc_hmc_free(ctx);
+  bc_hmc_small_free(ctx);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
   return BC_OK;

@@ -423,6 +423,7 @@ extern "C" int bc_logistic_logjoint_batch(bc_ctx* ctx, const bc_data* data, cons
   int rc = check_problem(ctx, data, w, c, "bc_logistic_logjoint_batch");
   if (rc) return rc;
   if (bc_hmc_active(ctx)) { bc_set_error("bc_logistic_logjoint_batch: a bc_hmc run is open on this context (call bc_hmc_end first)"); return BC_INVALID_ARGUMENT; }
+  if (bc_hmc_small_active(ctx)) { bc_set_error("bc_logistic_logjoint_batch: a bc_hmc_small run is open on this context (call bc_hmc_small_end first)"); return BC_INVALID_ARGUMENT; }
   BC_HIP(hipSetDevice(ctx->device));
   bc_hmc* h = hmc_of(ctx);
   rc = layout_state(ctx, h, data, c);
@@ -466,6 +467,7 @@ extern "C" int bc_hmc_begin(bc_ctx* ctx, const bc_data* data, const bc_data* w, 
   if (ctx->vi_pending_m > 0) { bc_set_error("bc_hmc_begin: a bc_vi_gradient is pending on this context"); return BC_INVALID_ARGUMENT; }
   if (bc_viopt_active(ctx)) { bc_set_error("bc_hmc_begin: a bc_vi_optimize run is open on this context (call bc_vi_optimize_end first)"); return BC_INVALID_ARGUMENT; }
   if (bc_hmc_active(ctx)) { bc_set_error("bc_hmc_begin: a run is already open on this context (call bc_hmc_end first)"); return BC_INVALID_ARGUMENT; }
+  if (bc_hmc_small_active(ctx)) { bc_set_error("bc_hmc_begin: a bc_hmc_small run is open on this context (call bc_hmc_small_end first)"); return BC_INVALID_ARGUMENT; }
   BC_HIP(hipSetDevice(ctx->device));
   bc_hmc* h = hmc_of(ctx);
   for (auto& e : h->ev)

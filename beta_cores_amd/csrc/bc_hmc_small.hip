@@ -1,0 +1,521 @@
+// Batched HMC of many small logistic posteriors (include/beta_cores_hmc_small.h): a thread block holds ONE problem's rows in LDS
+// and runs a whole chunk of iterations of its chains there -- momentum draw, every leapfrog step with its rows pass, the accept
+// step -- without returning to global memory in between.
+//
+// k_hmc_small, one launch per chunk.  A block serves one problem and CPB of its chains (1, 2 or 4: a divisor of C); each chain is
+// worked by its own BC_SM_BLOCK threads (a "slot"), the slots share the rows and the weights.  Grid = P * C / CPB blocks of
+// CPB * BC_SM_BLOCK threads, dynamic LDS = the largest problem's need:
+//
+//   rows [n][ld] | w [n] || per slot: w p [n] | ll [n] | part [nseg][1 + D] | theta g theta' r g' im [6][D] | red [1 + D] |
+//                                     ws [2 D + 2] | lj lj' H0 -
+//
+// The rows pass is bc_hmc_small_rows_pass (bc_hmc_small_dev.h: row stride, bank behaviour and summation order are described
+// there); the leapfrog and accept arithmetic is bc_hmc_dev.h's, unchanged, with `red` and the work space in LDS: both headers
+// are compiled here with BC_HMC_TID / BC_HMC_NT = the thread's index within its slot / BC_SM_BLOCK, and BC_HMC_SYNC the block's
+// barrier (the slots of a block run the same sequence of barriers: trip counts depend on the chunk only, and the accept branch
+// holds none).  A chain's arithmetic is the same text for every CPB, so its bits do not depend on how chains are packed.
+// Blocks never wait for each other: no flags between blocks, no cooperative launch; a block whose problem was marked at the
+// start returns at once.  At these sizes a leapfrog step is a few dependent LDS round trips and barriers, not flops, so the fp64
+// VALU serves it; packing chains buys occupancy where one problem's rows fill most of a CU's LDS (at D = 128 one block per CU:
+// four waves on four SIMDs with nothing to hide a barrier or an LDS round trip behind; with four chains, sixteen).
+//
+// The same kernel serves the start pass (mode BC_SM_INIT: log-joint and gradient at the start, marks a problem whose are not
+// finite) and the pass on its own (BC_SM_PASS: bc_hmc_small_logjoint, the test seam).
+#define BC_SM_BLOCK 256
+#define BC_HMC_FN __device__
+#define BC_HMC_TID ((int)(threadIdx.x & (BC_SM_BLOCK - 1)))
+#define BC_HMC_NT BC_SM_BLOCK
+#define BC_HMC_SYNC() do { __threadfence_block(); __syncthreads(); } while (0)
+#include "bc_internal.h"
+#include "bc_hmc_dev.h"
+#include "bc_hmc_small_dev.h"
+#include "../../include/beta_cores_hmc_small.h"
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#define BC_SM_INIT 0
+#define BC_SM_CHUNK 1
+#define BC_SM_PASS 2
+// the doubles of LDS a chain's state needs (the capacity rule is lds_doubles below)
+#define BC_SM_STATE_DOUBLES(d) (6 * (size_t)(d) + (1 + (size_t)(d)) + BC_HMC_WS_DOUBLES((size_t)(d)) + 4)
+
+struct SmArgs {
+  const double* rows;           // packed rows [sum n][d]
+  const double* w;              // [sum n]
+  const long long* row_ptr;     // [P + 1]
+  double *theta, *g, *lj;       // the chains' state: [P * C][d], [P * C][d], [P * C]
+  const double* im;             // [P][d]
+  const double* step;           // [P]
+  int* flag;                    // [P]: 1 = the problem's start is not finite
+  const double* e;              // the chunk's normals
+  const double* logu;           // the chunk's log-uniforms
+  long long e_stride, u_stride; // per problem (0: shared)
+  double* out_s;                // [P][k][C][d]
+  double* out_l;                // [P][k][C]
+  int* out_a;                   // [P][k][C]
+  double half_d_log_2pi;
+  int d, c, k, n_leapfrog, mode, value;
+};
+
+template <int CPB>
+__global__ __launch_bounds__(CPB * BC_SM_BLOCK) void k_hmc_small(SmArgs a) {
+  extern __shared__ double sm_lds[];
+  const int tid = BC_HMC_TID, nt = BC_HMC_NT, slot = threadIdx.x / BC_SM_BLOCK;
+  const int groups = a.c / CPB, p = blockIdx.x / groups, ch = (blockIdx.x - p * groups) * CPB + slot;
+  const int bid = p * a.c + ch;                        // the chain's index in the state and the outputs
+  if (a.mode == BC_SM_CHUNK && a.flag[p] != 0) return;      // (block-uniform; written by an earlier launch)
+  const int d = a.d, ld = BC_HMC_SMALL_LD(d);
+  const long long r0 = a.row_ptr[p];
+  const int n = (int)(a.row_ptr[p + 1] - r0);
+  double* zs = sm_lds;
+  double* w = zs + (size_t)n * ld;
+  double* wp = w + n + (size_t)slot * (BC_HMC_SMALL_CHAIN_DOUBLES(n, d) + BC_SM_STATE_DOUBLES(d));
+  double* ll = wp + n;
+  double* part = ll + n;
+  double* th = part + (size_t)BC_HMC_SMALL_NSEG(n) * (d + 1);
+  double* g = th + d;
+  double* thp = g + d;
+  double* r = thp + d;
+  double* gp = r + d;
+  double* im = gp + d;
+  double* red = im + d;
+  double* ws = red + 1 + d;
+  double* sc = ws + BC_HMC_WS_DOUBLES(d);      // lj | lj' | H0
+  const double* __restrict__ src = a.rows + (size_t)r0 * d;
+  for (int e = threadIdx.x; e < n * d; e += blockDim.x) {      // (the rows and the weights: filled by all slots together)
+    const int i = e / d, k = e - i * d;
+    zs[(size_t)i * ld + k] = src[e];
+  }
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    if (ld > d) zs[(size_t)i * ld + d] = 0.;
+    w[i] = a.w[r0 + i];
+  }
+  const size_t o = (size_t)bid * d;
+  for (int k = tid; k < d; k += nt) {
+    th[k] = a.theta[o + k];
+    if (a.mode == BC_SM_CHUNK) {
+      g[k] = a.g[o + k];
+      im[k] = a.im[(size_t)p * d + k];
+    }
+  }
+  if (tid == 0) {
+    red[0] = 0.;
+    sc[0] = a.mode == BC_SM_CHUNK ? a.lj[bid] : 0.;
+  }
+  BC_HMC_SYNC();
+  if (a.mode != BC_SM_CHUNK) {
+    bc_hmc_small_rows_pass(zs, w, n, d, th, a.value, wp, ll, part, red);
+    const int bad = bc_hmc_logjoint_chain(red, th, d, a.half_d_log_2pi, sc, g, ws);
+    for (int k = tid; k < d; k += nt) a.g[o + k] = g[k];      // (element k: written by this thread)
+    if (tid == 0) {
+      a.lj[bid] = sc[0];
+      if (bad && a.mode == BC_SM_INIT) a.flag[p] = 1;      // (every chain of the problem that finds it writes the same 1)
+    }
+    return;
+  }
+  const double eps = a.step[p];
+  const double* __restrict__ en = a.e + (size_t)p * a.e_stride;
+  const double* __restrict__ un = a.logu + (size_t)p * a.u_stride;
+  const size_t ob = (size_t)p * a.k * a.c;
+  for (int t = 0; t < a.k; ++t) {
+    const size_t tc = (size_t)t * a.c + ch;
+    bc_hmc_start_chain(th, sc, g, en + tc * d, im, eps, d, r, thp, sc + 2, ws);
+    for (int l = 1; l <= a.n_leapfrog; ++l) {
+      const bool last = l == a.n_leapfrog;
+      bc_hmc_small_rows_pass(zs, w, n, d, thp, last ? 1 : 0, wp, ll, part, red);
+      if (!last) {
+        bc_hmc_inner_chain(red, eps, im, d, r, thp);
+        BC_HMC_SYNC();
+      }
+    }
+    const int acc = bc_hmc_last_chain(red, eps, im, d, a.half_d_log_2pi, sc + 2, un[tc], r, thp, gp, sc + 1, th, sc, g, ws);
+    for (int k = tid; k < d; k += nt) a.out_s[(ob + tc) * d + k] = th[k];
+    if (tid == 0) {
+      a.out_l[ob + tc] = sc[0];
+      a.out_a[ob + tc] = acc;
+    }
+  }
+  for (int k = tid; k < d; k += nt) {
+    a.theta[o + k] = th[k];
+    a.g[o + k] = g[k];
+  }
+  if (tid == 0) a.lj[bid] = sc[0];
+}
+
+// ------------------------------------------------------------------ host side
+struct bc_hmc_small {
+  double* prob = nullptr;         // rows | w | row_ptr (int64)
+  size_t prob_cap = 0;
+  double* state = nullptr;        // theta | g | lj | inverse masses | flags (ints)
+  size_t state_cap = 0;
+  double* stage_dev = nullptr;    // a chunk's draws and steps: normals | log-uniforms | step [P]
+  double* stage_pin = nullptr;
+  size_t stage_cap = 0;
+  double* out_dev = nullptr;      // a chunk's results: samples | log-joints | accept flags (ints)
+  size_t out_cap = 0;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  bool active = false, chunk_pending = false;
+  SmArgs a;
+  size_t lds = 0;
+  int cpb = 1;                    // chains per block of the run's launches
+  int32_t n_problems = 0, pending_k = 0;
+  int64_t n_iter = 0, done = 0;
+  double dev_ms = 0.;
+};
+
+bool bc_hmc_small_active(const bc_ctx* ctx) { return ctx->hmc_small && ctx->hmc_small->active; }
+
+void bc_hmc_small_free(bc_ctx* ctx) {
+  bc_hmc_small* h = ctx->hmc_small;
+  if (!h) return;
+  if (h->prob) (void)hipFree(h->prob);
+  if (h->state) (void)hipFree(h->state);
+  if (h->stage_dev) (void)hipFree(h->stage_dev);
+  if (h->stage_pin) (void)hipHostFree(h->stage_pin);
+  if (h->out_dev) (void)hipFree(h->out_dev);
+  for (auto& e : h->ev)
+    if (e) (void)hipEventDestroy(e);
+  delete h;
+  ctx->hmc_small = nullptr;
+}
+
+// grow-only; only called while nothing of this module is enqueued on the buffer
+static int grow_dev(bc_ctx* ctx, double** p, size_t* cap, size_t need) {
+  if (need <= *cap) return BC_OK;
+  BC_HIP(hipStreamSynchronize(ctx->stream));
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  const size_t want = need + need / 2;
+  BC_HIP(hipMalloc((void**)p, want * sizeof(double)));
+  *cap = want;
+  return BC_OK;
+}
+
+static int grow_pin(bc_ctx* ctx, double** p, size_t* cap, size_t need) {
+  if (need <= *cap) return BC_OK;
+  BC_HIP(hipStreamSynchronize(ctx->stream));
+  if (*p) (void)hipHostFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  const size_t want = need + need / 2;
+  BC_HIP(hipHostMalloc((void**)p, want * sizeof(double), hipHostMallocDefault));
+  *cap = want;
+  return BC_OK;
+}
+
+static size_t even(size_t n) { return (n + 1) & ~(size_t)1; }
+
+// the doubles of LDS a block of cpb chains needs for a problem of n rows and d columns; with cpb = 1: the capacity rule
+static size_t lds_doubles(int64_t n, int d, int cpb = 1) {
+  return BC_HMC_SMALL_ROWS_DOUBLES(n, d) + (size_t)cpb * (BC_HMC_SMALL_CHAIN_DOUBLES(n, d) + BC_SM_STATE_DOUBLES(d));
+}
+
+static const void* kernel_of(int cpb) {
+  return cpb == 4 ? reinterpret_cast<const void*>(&k_hmc_small<4>)
+                  : cpb == 2 ? reinterpret_cast<const void*>(&k_hmc_small<2>) : reinterpret_cast<const void*>(&k_hmc_small<1>);
+}
+
+// Chains per block: of 1, 2, 4 (divisors of c whose block fits the LDS for the largest problem) the smallest that keeps the most
+// waves resident per CU, as the runtime's occupancy query counts them for the launch's block size and LDS.  Where a problem's
+// rows fill most of a CU's LDS that is 4; where several one-chain blocks fit a CU anyway it is 1 (measurements:
+// profiles/hmc_many_notes.md).  Packing changes no chain's bits.  BC_HMC_SMALL_CHAINS_PER_BLOCK = 1, 2 or 4 forces a count
+// (lowered to one that divides c and fits).
+static int chains_per_block(const bc_ctx* ctx, int64_t max_n, int d, int c) {
+  int forced = 0;
+  if (const char* e = getenv("BC_HMC_SMALL_CHAINS_PER_BLOCK")) forced = atoi(e);
+  int best = 1, best_waves = -1;
+  for (int cpb = 1; cpb <= 4; cpb <<= 1) {
+    const size_t lds = lds_doubles(max_n, d, cpb) * sizeof(double);
+    if (c % cpb != 0 || lds > (size_t)ctx->max_lds) continue;
+    if (forced == 1 || forced == 2 || forced == 4) {
+      if (cpb <= forced) best = cpb;
+      continue;
+    }
+    int blocks = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kernel_of(cpb), cpb * BC_SM_BLOCK, lds) != hipSuccess) {
+      (void)hipGetLastError();
+      continue;
+    }
+    if (blocks * cpb > best_waves) {
+      best_waves = blocks * cpb;
+      best = cpb;
+    }
+  }
+  return best;
+}
+
+static bool fits(const bc_ctx* ctx, int64_t n, int32_t d) {
+  if (n < 1 || d < 1 || d > BC_HMC_MAX_DIM || n > (int64_t)1 << 24) return false;
+  return lds_doubles(n, d) * sizeof(double) <= (size_t)ctx->max_lds;
+}
+
+extern "C" int bc_hmc_small_fits(bc_ctx* ctx, int64_t n, int32_t d) { return ctx && fits(ctx, n, d) ? 1 : 0; }
+
+static bc_hmc_small* small_of(bc_ctx* ctx) {
+  if (!ctx->hmc_small) ctx->hmc_small = new bc_hmc_small();
+  return ctx->hmc_small;
+}
+
+// the checks of a batch, before anything is touched; *max_n: the largest problem
+static int check_batch(bc_ctx* ctx, const int64_t* row_ptr, int32_t n_problems, int32_t d, int32_t c, const char* who, int64_t* max_n) {
+  if (n_problems < 1) { bc_set_error("%s: needs at least one problem, got %d", who, n_problems); return BC_INVALID_ARGUMENT; }
+  if (c < 1 || c > BC_HMC_MAX_CHAINS) { bc_set_error("%s: 1 .. %d chains are served, got %d", who, BC_HMC_MAX_CHAINS, c); return BC_INVALID_ARGUMENT; }
+  if (d < 1 || d > BC_HMC_MAX_DIM) { bc_set_error("%s: rows must have 1 .. %d columns, got %d", who, BC_HMC_MAX_DIM, d); return BC_INVALID_ARGUMENT; }
+  if (row_ptr[0] != 0) { bc_set_error("%s: row_ptr[0] must be 0, got %lld", who, (long long)row_ptr[0]); return BC_INVALID_ARGUMENT; }
+  if ((int64_t)n_problems * c > (int64_t)1 << 30) { bc_set_error("%s: %d problems x %d chains are too many blocks for one launch", who, n_problems, c); return BC_INVALID_ARGUMENT; }
+  int64_t mx = 0;
+  for (int32_t p = 0; p < n_problems; ++p) {
+    const int64_t n = row_ptr[p + 1] - row_ptr[p];
+    if (n < 1) {
+      bc_set_error("%s: row_ptr must increase strictly (every problem has at least one row): row_ptr[%d] = %lld, row_ptr[%d] = %lld", who, p,
+                   (long long)row_ptr[p], p + 1, (long long)row_ptr[p + 1]);
+      return BC_INVALID_ARGUMENT;
+    }
+    if (!fits(ctx, n, d)) {
+      bc_set_error("%s: problem %d (%lld rows x %d) needs %zu bytes of LDS, a block has %d", who, p, (long long)n, d,
+                   lds_doubles(n, d) * sizeof(double), ctx->max_lds);
+      return BC_INVALID_ARGUMENT;
+    }
+    if (n > mx) mx = n;
+  }
+  *max_n = mx;
+  return BC_OK;
+}
+
+static int check_idle(bc_ctx* ctx, const char* who) {
+  if (ctx->vi_pending_m > 0) { bc_set_error("%s: a fused gradient is pending on this context", who); return BC_INVALID_ARGUMENT; }
+  if (bc_viopt_active(ctx)) { bc_set_error("%s: a weight-optimisation run is open on this context", who); return BC_INVALID_ARGUMENT; }
+  if (bc_hmc_small_active(ctx)) { bc_set_error("%s: a bc_hmc_small run is already open on this context (call bc_hmc_small_end first)", who); return BC_INVALID_ARGUMENT; }
+  if (bc_hmc_active(ctx)) { bc_set_error("%s: a bc_hmc run is open on this context (call bc_hmc_end first)", who); return BC_INVALID_ARGUMENT; }
+  return BC_OK;
+}
+
+// uploads the batch and the C x D vectors per problem, lays the state out and fills h->a except the chunk's fields; enqueued only
+static int stage_batch(bc_ctx* ctx, bc_hmc_small* h, const double* rows, const double* w, const int64_t* row_ptr, int32_t P, int32_t d,
+                       const double* theta, int32_t c, const double* inv_mass, int64_t max_n) {
+  const size_t n_all = (size_t)row_ptr[P];
+  const size_t o_w = even(n_all * d), o_ptr = o_w + even(n_all);
+  int rc = grow_dev(ctx, &h->prob, &h->prob_cap, o_ptr + (size_t)P + 2);
+  const size_t pc = (size_t)P * c, cd = even(pc * d), cc = even(pc), pd = even((size_t)P * d);
+  if (!rc) rc = grow_dev(ctx, &h->state, &h->state_cap, 2 * cd + cc + pd + even(((size_t)P + 1) / 2) + 2);
+  if (rc) return rc;
+  // (per device, and cheap beside the uploads below: set at every begin instead of remembering where it was set)
+  for (int cpb = 1; cpb <= 4; cpb <<= 1) BC_HIP(hipFuncSetAttribute(kernel_of(cpb), hipFuncAttributeMaxDynamicSharedMemorySize, ctx->max_lds));
+  BC_HIP(hipStreamSynchronize(ctx->stream));
+  // (pageable sources: the copies below have read them when they return)
+  BC_HIP(hipMemcpyAsync(h->prob, rows, n_all * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  BC_HIP(hipMemcpyAsync(h->prob + o_w, w, n_all * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  BC_HIP(hipMemcpyAsync(h->prob + o_ptr, row_ptr, ((size_t)P + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+  SmArgs& a = h->a;
+  memset(&a, 0, sizeof(a));
+  a.rows = h->prob;
+  a.w = h->prob + o_w;
+  a.row_ptr = reinterpret_cast<const long long*>(h->prob + o_ptr);
+  double* s = h->state;
+  a.theta = s; s += cd;
+  a.g = s; s += cd;
+  a.lj = s; s += cc;
+  a.im = s; s += pd;
+  a.flag = reinterpret_cast<int*>(s);
+  BC_HIP(hipMemcpyAsync(a.theta, theta, pc * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  if (inv_mass) BC_HIP(hipMemcpyAsync(const_cast<double*>(a.im), inv_mass, (size_t)P * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  BC_HIP(hipMemsetAsync(a.flag, 0, ((size_t)P + 1) * sizeof(int), ctx->stream));
+  a.half_d_log_2pi = 0.5 * d * log(2. * M_PI);
+  a.d = d;
+  a.c = c;
+  h->cpb = chains_per_block(ctx, max_n, d, c);
+  h->n_problems = P;
+  h->lds = lds_doubles(max_n, d, h->cpb) * sizeof(double);
+  return BC_OK;
+}
+
+static int launch(bc_ctx* ctx, const bc_hmc_small* h, const SmArgs& a) {
+  const dim3 grid((unsigned)((size_t)h->n_problems * (a.c / h->cpb))), block(h->cpb * BC_SM_BLOCK);
+  if (h->cpb == 4) hipLaunchKernelGGL(k_hmc_small<4>, grid, block, h->lds, ctx->stream, a);
+  else if (h->cpb == 2) hipLaunchKernelGGL(k_hmc_small<2>, grid, block, h->lds, ctx->stream, a);
+  else hipLaunchKernelGGL(k_hmc_small<1>, grid, block, h->lds, ctx->stream, a);
+  BC_HIP(hipGetLastError());
+  return BC_OK;
+}
+
+extern "C" int bc_hmc_small_logjoint(bc_ctx* ctx, const double* rows, const double* w, const int64_t* row_ptr, int32_t n_problems, int32_t d,
+                                     const double* theta, int32_t c, double* out_value, double* out_grad) {
+  if (!ctx || !rows || !w || !row_ptr || !theta || !out_grad) {
+    bc_set_error("bc_hmc_small_logjoint: bad argument (context, rows, weights, row_ptr, theta and gradients are required)");
+    return BC_INVALID_ARGUMENT;
+  }
+  int64_t max_n = 0;
+  int rc = check_batch(ctx, row_ptr, n_problems, d, c, "bc_hmc_small_logjoint", &max_n);
+  if (!rc) rc = check_idle(ctx, "bc_hmc_small_logjoint");
+  if (rc) return rc;
+  BC_HIP(hipSetDevice(ctx->device));
+  bc_hmc_small* h = small_of(ctx);
+  rc = stage_batch(ctx, h, rows, w, row_ptr, n_problems, d, theta, c, nullptr, max_n);
+  if (rc) return rc;
+  SmArgs a = h->a;
+  a.mode = BC_SM_PASS;
+  a.value = out_value != nullptr;
+  rc = launch(ctx, h, a);
+  if (rc) return rc;
+  const size_t pc = (size_t)n_problems * c;
+  if (out_value) BC_HIP(hipMemcpyAsync(out_value, a.lj, pc * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  BC_HIP(hipMemcpyAsync(out_grad, a.g, pc * d * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  BC_HIP(hipStreamSynchronize(ctx->stream));
+  return BC_OK;
+}
+
+extern "C" int bc_hmc_small_begin(bc_ctx* ctx, const double* rows, const double* w, const int64_t* row_ptr, int32_t n_problems, int32_t d,
+                                  const double* start, int32_t c, const double* inv_mass, int32_t n_leapfrog, int64_t n_iter) {
+  if (!ctx || !rows || !w || !row_ptr || !start || !inv_mass) {
+    bc_set_error("bc_hmc_small_begin: bad argument (context, rows, weights, row_ptr, start and inv_mass are required)");
+    return BC_INVALID_ARGUMENT;
+  }
+  int64_t max_n = 0;
+  int rc = check_batch(ctx, row_ptr, n_problems, d, c, "bc_hmc_small_begin", &max_n);
+  if (rc) return rc;
+  if (n_leapfrog < 1 || n_iter < 1) {
+    bc_set_error("bc_hmc_small_begin: needs n_leapfrog >= 1 and n_iter >= 1 (n_leapfrog = %d, n_iter = %lld)", n_leapfrog, (long long)n_iter);
+    return BC_INVALID_ARGUMENT;
+  }
+  for (size_t k = 0; k < (size_t)n_problems * d; ++k)
+    if (!(inv_mass[k] > 0.) || !std::isfinite(inv_mass[k])) {
+      bc_set_error("bc_hmc_small_begin: inv_mass[%zu][%zu] = %g is not finite and positive", k / d, k % d, inv_mass[k]);
+      return BC_INVALID_ARGUMENT;
+    }
+  rc = check_idle(ctx, "bc_hmc_small_begin");
+  if (rc) return rc;
+  BC_HIP(hipSetDevice(ctx->device));
+  bc_hmc_small* h = small_of(ctx);
+  for (auto& e : h->ev)
+    if (!e) BC_HIP(hipEventCreate(&e));
+  rc = stage_batch(ctx, h, rows, w, row_ptr, n_problems, d, start, c, inv_mass, max_n);
+  if (rc) return rc;
+  SmArgs a = h->a;
+  a.mode = BC_SM_INIT;
+  a.value = 1;
+  rc = launch(ctx, h, a);
+  if (rc) return rc;
+  h->a.n_leapfrog = n_leapfrog;
+  h->n_iter = n_iter;
+  h->done = 0;
+  h->dev_ms = 0.;
+  h->pending_k = 0;
+  h->active = true;
+  h->chunk_pending = false;
+  return BC_OK;
+}
+
+extern "C" int bc_hmc_small_chunk_begin(bc_ctx* ctx, const double* normals, const double* log_u, int64_t problem_stride, int32_t k,
+                                        const double* step) {
+  bc_hmc_small* h = ctx ? ctx->hmc_small : nullptr;
+  if (!h || !h->active || !normals || !log_u || !step || k <= 0) { bc_set_error("bc_hmc_small_chunk_begin: bad argument, or no run is open"); return BC_INVALID_ARGUMENT; }
+  if (h->chunk_pending) { bc_set_error("bc_hmc_small_chunk_begin: a chunk is pending (call bc_hmc_small_chunk_end first)"); return BC_INVALID_ARGUMENT; }
+  if (h->done + (int64_t)k > h->n_iter) {
+    bc_set_error("bc_hmc_small_chunk_begin: %d iterations after %lld exceed the run's %lld", k, (long long)h->done, (long long)h->n_iter);
+    return BC_INVALID_ARGUMENT;
+  }
+  const size_t P = (size_t)h->n_problems, c = (size_t)h->a.c, d = (size_t)h->a.d;
+  const size_t kcd = (size_t)k * c * d, kc = (size_t)k * c;
+  if (problem_stride != 0 && (problem_stride < 0 || (size_t)problem_stride < kcd)) {
+    bc_set_error("bc_hmc_small_chunk_begin: problem_stride must be 0 or at least k C D = %zu, got %lld", kcd, (long long)problem_stride);
+    return BC_INVALID_ARGUMENT;
+  }
+  for (size_t p = 0; p < P; ++p)
+    if (!(step[p] > 0.) || !std::isfinite(step[p])) {
+      bc_set_error("bc_hmc_small_chunk_begin: step[%zu] = %g is not finite and positive", p, step[p]);
+      return BC_INVALID_ARGUMENT;
+    }
+  // ---- nothing of this chunk has been enqueued up to here
+  BC_HIP(hipSetDevice(ctx->device));
+  const bool shared = problem_stride == 0;
+  const size_t n_e = shared ? kcd : P * kcd, n_u = shared ? kc : P * kc;
+  const size_t o_u = even(n_e), o_st = o_u + even(n_u), need = o_st + even(P);
+  if (need > h->stage_cap) {
+    size_t c1 = h->stage_cap, c2 = h->stage_cap;
+    int rc = grow_dev(ctx, &h->stage_dev, &c1, need);
+    if (!rc) rc = grow_pin(ctx, &h->stage_pin, &c2, need);
+    if (rc) { h->stage_cap = 0; return rc; }
+    h->stage_cap = c1 < c2 ? c1 : c2;
+  }
+  const size_t o_e = P * kcd, o_l = even(o_e), o_a = o_l + even(P * kc);
+  int rc = grow_dev(ctx, &h->out_dev, &h->out_cap, o_a + even((P * kc + 1) / 2));
+  if (rc) return rc;
+  if (shared) memcpy(h->stage_pin, normals, kcd * sizeof(double));
+  else
+    for (size_t p = 0; p < P; ++p) memcpy(h->stage_pin + p * kcd, normals + p * (size_t)problem_stride, kcd * sizeof(double));
+  memcpy(h->stage_pin + o_u, log_u, n_u * sizeof(double));
+  memcpy(h->stage_pin + o_st, step, P * sizeof(double));
+  BC_HIP(hipMemcpyAsync(h->stage_dev, h->stage_pin, need * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  h->chunk_pending = true;      // from here on something is enqueued: _chunk_end must wait even if the launch below fails
+  h->pending_k = k;
+  SmArgs a = h->a;
+  a.mode = BC_SM_CHUNK;
+  a.k = k;
+  a.e = h->stage_dev;
+  a.logu = h->stage_dev + o_u;
+  a.step = h->stage_dev + o_st;
+  a.e_stride = shared ? 0 : (long long)kcd;
+  a.u_stride = shared ? 0 : (long long)kc;
+  a.out_s = h->out_dev;
+  a.out_l = h->out_dev + o_l;
+  a.out_a = reinterpret_cast<int*>(h->out_dev + o_a);
+  BC_HIP(hipEventRecord(h->ev[0], ctx->stream));
+  rc = launch(ctx, h, a);
+  if (rc) return rc;
+  BC_HIP(hipEventRecord(h->ev[1], ctx->stream));
+  h->done += k;
+  return BC_OK;
+}
+
+extern "C" int bc_hmc_small_chunk_end(bc_ctx* ctx, double* out_samples, double* out_logjoint, int32_t* out_accept, int32_t* out_status) {
+  bc_hmc_small* h = ctx ? ctx->hmc_small : nullptr;
+  if (!h || !h->active || !h->chunk_pending) { bc_set_error("bc_hmc_small_chunk_end: no chunk is pending"); return BC_INVALID_ARGUMENT; }
+  // (checked first: the chunk stays pending, a second call with the outputs can still fetch it)
+  if (!out_samples || !out_logjoint || !out_accept || !out_status) { bc_set_error("bc_hmc_small_chunk_end: the four outputs are required"); return BC_INVALID_ARGUMENT; }
+  h->chunk_pending = false;
+  BC_HIP(hipSetDevice(ctx->device));
+  BC_HIP(hipStreamSynchronize(ctx->stream));
+  const size_t P = (size_t)h->n_problems, c = (size_t)h->a.c, d = (size_t)h->a.d;
+  std::vector<int> flag(P);
+  BC_HIP(hipMemcpy(flag.data(), h->a.flag, P * sizeof(int), hipMemcpyDeviceToHost));
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess) h->dev_ms += ms;
+  const size_t kc = (size_t)h->pending_k * c, kcd = kc * d;
+  const size_t o_l = even(P * kcd), o_a = o_l + even(P * kc);
+  const int* acc_dev = reinterpret_cast<const int*>(h->out_dev + o_a);
+  // runs of consecutive unmarked problems are copied together (one run of all P when nothing is marked)
+  size_t p = 0;
+  while (p < P) {
+    if (flag[p] != 0) {
+      out_status[p++] = BC_NUMERICAL_PRECISION;
+      continue;
+    }
+    size_t q = p;
+    while (q < P && flag[q] == 0) out_status[q++] = BC_OK;
+    BC_HIP(hipMemcpy(out_samples + p * kcd, h->out_dev + p * kcd, (q - p) * kcd * sizeof(double), hipMemcpyDeviceToHost));
+    BC_HIP(hipMemcpy(out_logjoint + p * kc, h->out_dev + o_l + p * kc, (q - p) * kc * sizeof(double), hipMemcpyDeviceToHost));
+    BC_HIP(hipMemcpy(out_accept + p * kc, acc_dev + p * kc, (q - p) * kc * sizeof(int32_t), hipMemcpyDeviceToHost));
+    p = q;
+  }
+  return BC_OK;
+}
+
+extern "C" int bc_hmc_small_end(bc_ctx* ctx) {
+  bc_hmc_small* h = ctx ? ctx->hmc_small : nullptr;
+  if (!h || !h->active) { bc_set_error("bc_hmc_small_end: no run is open"); return BC_INVALID_ARGUMENT; }
+  BC_HIP(hipSetDevice(ctx->device));
+  const bool pending = h->chunk_pending;
+  h->active = false;
+  h->chunk_pending = false;
+  if (pending) BC_HIP(hipStreamSynchronize(ctx->stream));      // abandoned mid-chunk: nothing may outlive the run's buffers
+  return BC_OK;
+}
+
+extern "C" int bc_hmc_small_device_ms(bc_ctx* ctx, double* out_ms) {
+  if (!ctx || !out_ms) { bc_set_error("bc_hmc_small_device_ms: bad argument"); return BC_INVALID_ARGUMENT; }
+  *out_ms = ctx->hmc_small ? ctx->hmc_small->dev_ms : 0.;
+  return BC_OK;
+}

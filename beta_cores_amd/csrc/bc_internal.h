@@ -95,6 +95,7 @@ struct bc_ctx {
   int take_turn = 0;
   struct bc_viopt* viopt = nullptr;    // bc_vi_optimize (bc_viopt.hip): the buffers and the state of the run in progress
   struct bc_hmc* hmc = nullptr;        // bc_hmc_* (bc_hmc.hip): the buffers and the state of the HMC run in progress
+  struct bc_hmc_small* hmc_small = nullptr;   // bc_hmc_small_* (bc_hmc_small.hip): the same for the batched small-problem run
 };
 
 // bc_upload.hip: rows of a host array -> dst_dev through pinned staging and several copy threads; the hook (optional) is
@@ -110,6 +111,8 @@ void bc_viopt_free(bc_ctx* ctx);     // bc_viopt.hip
 bool bc_viopt_active(const bc_ctx* ctx);   // a bc_vi_optimize run is open on the context
 void bc_hmc_free(bc_ctx* ctx);       // bc_hmc.hip
 bool bc_hmc_active(const bc_ctx* ctx);     // a bc_hmc run is open on the context
+void bc_hmc_small_free(bc_ctx* ctx); // bc_hmc_small.hip
+bool bc_hmc_small_active(const bc_ctx* ctx);   // a bc_hmc_small run is open on the context
 // bc_take.hip: dst[j, :] = src[idx_dev[j], :] for indices that are already on the device and already checked; enqueued only
 int bc_take_rows_dev(bc_ctx* ctx, const bc_data* src, const long long* idx_dev, int64_t m, void* dst_z);
 // bc_project.hip: one gradient's projections and algebra for a Theta that is already on the device (bc_viopt.hip)

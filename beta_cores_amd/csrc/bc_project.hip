@@ -896,6 +896,7 @@ static int vi_gradient_begin(bc_ctx* ctx, const bc_data* data, const double* cor
     return BC_INVALID_ARGUMENT;
   }
   if (bc_hmc_active(ctx)) { bc_set_error("%s_begin: a bc_hmc run is open on this context (call bc_hmc_end first)", who); return BC_INVALID_ARGUMENT; }
+  if (bc_hmc_small_active(ctx)) { bc_set_error("%s_begin: a bc_hmc_small run is open on this context (call bc_hmc_small_end first)", who); return BC_INVALID_ARGUMENT; }
   if (n_down > ctx->pinned_doubles) {
     bc_set_error("%s: coreset of %lld rows x %d exceeds the staging area", who, (long long)m, dz);
     return BC_INVALID_ARGUMENT;

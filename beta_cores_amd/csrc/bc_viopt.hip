@@ -151,6 +151,7 @@ extern "C" int bc_vi_optimize_begin(bc_ctx* ctx, const bc_data* data, const doub
   if (!model_ok) { bc_set_error("bc_vi_optimize_begin: model %d does not go with sampler kind %d", model, sampler_kind); return BC_INVALID_ARGUMENT; }
   if (ctx->vi_pending_m > 0) { bc_set_error("bc_vi_optimize_begin: a bc_vi_gradient is pending on this context"); return BC_INVALID_ARGUMENT; }
   if (bc_hmc_active(ctx)) { bc_set_error("bc_vi_optimize_begin: a bc_hmc run is open on this context (call bc_hmc_end first)"); return BC_INVALID_ARGUMENT; }
+  if (bc_hmc_small_active(ctx)) { bc_set_error("bc_vi_optimize_begin: a bc_hmc_small run is open on this context (call bc_hmc_small_end first)"); return BC_INVALID_ARGUMENT; }
   const int dz = data->dz;
   int d = 0, dk = 0, nrsel = 0, ntsel = 0;
   if (bc_vi_plan_layout(model, s, dz, &d, &dk, &nrsel, &ntsel) != BC_OK || d > BC_VI_MAX_DIM) {

@@ -511,3 +511,270 @@ def logistic_hmc(Z, wts=None, n_samples=1000, n_chains=16, step_size=0.1, n_leap
     finally:
         ms = eng.end()
     return HMCResult(out_s, out_l, out_a, step, np.array(warm_steps), start, inv_mass, ms)
+
+
+# ---- the same for MANY small problems at once: the weighted coresets of an evaluation curve (include/beta_cores_hmc_small.h)
+class HMCManyResult(list):
+    """What logistic_hmc_many returns: a list with one HMCResult per problem (None for a marked problem under strict=False).
+    Every HMCResult carries `route`: 'small' (sampled by the batched in-LDS kernel) or 'single' (too large for one block's LDS:
+    sampled by logistic_hmc's engine on the same draws).  fallback: the indices that took the 'single' route; marked: the
+    indices whose start was not finite; device_ms: GPU milliseconds of the batched launches (None from a stand-in engine)."""
+
+    def __init__(self, results, fallback, marked, device_ms):
+        super().__init__(results)
+        self.fallback, self.marked, self.device_ms = list(fallback), list(marked), device_ms
+
+
+class _SingleAsBatch:
+    """One logistic_hmc engine (begin / auto_chunk / chunk / end) behind the batched protocol of _run_hmc_group, as a batch of one."""
+
+    def __init__(self, eng):
+        self.eng = eng
+
+    def begin(self, starts, inv_mass, n_leapfrog, n_iter):
+        self.eng.begin(np.ascontiguousarray(starts[0]), np.ascontiguousarray(inv_mass[0]), n_leapfrog, n_iter)
+
+    def auto_chunk(self, c, d):
+        return self.eng.auto_chunk(c, d)
+
+    def chunk(self, normals, log_u, steps, shared):
+        e, u = (normals, log_u) if shared else (normals[0], log_u[0])
+        try:
+            s, lj, acc = self.eng.chunk(np.ascontiguousarray(e), np.ascontiguousarray(u), float(steps[0]))
+        except N.NumericalPrecisionError:
+            return None, None, None, np.array([N.BC_NUMERICAL_PRECISION], dtype=np.int32)
+        return s[None], lj[None], acc[None], np.zeros(1, dtype=np.int32)
+
+    def end(self):
+        return self.eng.end()
+
+
+class _DeviceHMCMany:
+    """The batched engine: the chunked entry points of include/beta_cores_hmc_small.h over packed host problems."""
+
+    def __init__(self, ctx, probs):
+        self.ctx = ctx
+        self.rows = np.ascontiguousarray(np.concatenate([z for z, _ in probs], axis=0))
+        self.w = np.ascontiguousarray(np.concatenate([w for _, w in probs]))
+        self.row_ptr = np.concatenate(([0], np.cumsum([z.shape[0] for z, _ in probs]))).astype(np.int64)
+        self.P, self.d = len(probs), probs[0][0].shape[1]
+
+    def begin(self, starts, inv_mass, n_leapfrog, n_iter):
+        self.c = starts.shape[1]
+        N.call('bc_hmc_small_begin', self.ctx.h, _ptr(self.rows), _ptr(self.w), _ptr(self.row_ptr), self.P, self.d,
+               _ptr(np.ascontiguousarray(starts)), self.c, _ptr(np.ascontiguousarray(inv_mass)), int(n_leapfrog), int(n_iter))
+
+    def auto_chunk(self, c, d):
+        return int(N.load().bc_hmc_auto_chunk(int(c), int(d)))
+
+    def chunk(self, normals, log_u, steps, shared):
+        k = normals.shape[0] if shared else normals.shape[1]
+        normals, log_u = np.ascontiguousarray(normals), np.ascontiguousarray(log_u)
+        steps = np.ascontiguousarray(steps, dtype=np.float64)
+        N.call('bc_hmc_small_chunk_begin', self.ctx.h, _ptr(normals), _ptr(log_u), 0 if shared else k * self.c * self.d, int(k), _ptr(steps))
+        s, lj = np.empty((self.P, k, self.c, self.d)), np.empty((self.P, k, self.c))
+        acc, status = np.zeros((self.P, k, self.c), dtype=np.int32), np.empty(self.P, dtype=np.int32)
+        N.call('bc_hmc_small_chunk_end', self.ctx.h, _ptr(s), _ptr(lj), _ptr(acc), _ptr(status))
+        return s, lj, acc, status
+
+    def end(self):
+        N.load().bc_hmc_small_end(self.ctx.h)      # (status ignored: also called to close a failed run)
+        ms = ctypes.c_double()
+        N.call('bc_hmc_small_device_ms', self.ctx.h, ctypes.byref(ms))
+        return ms.value
+
+
+class _ManyDraws:
+    """The draws of logistic_hmc_many, made once per chunk in the documented order and kept while a later group still needs them.
+    shared: randn(k, C, D) then log(rand(k, C)), for all problems.  independent: the same pair for p = 0 .. P - 1 in order."""
+
+    def __init__(self, rng, shared, P, c, d, keep):
+        self.randn = np.random.randn if rng is None else rng.randn
+        self.rand = np.random.rand if rng is None else rng.rand
+        self.shared, self.P, self.c, self.d, self.keep, self.made = shared, P, c, d, keep, []
+
+    def get(self, i, k, idx):
+        if i == len(self.made):
+            if self.shared:
+                pair = (self.randn(k, self.c, self.d), np.log(self.rand(k, self.c)))
+            else:
+                e, u = np.empty((self.P, k, self.c, self.d)), np.empty((self.P, k, self.c))
+                for p in range(self.P):
+                    e[p], u[p] = self.randn(k, self.c, self.d), np.log(self.rand(k, self.c))
+                pair = (e, u)
+            self.made.append(pair)
+        e, u = self.made[i]
+        assert (e.shape[0] if self.shared else e.shape[1]) == k
+        if not self.keep:
+            self.made[i] = None
+        return (e, u) if self.shared else (e[idx], u[idx])
+
+
+def _run_hmc_group(eng, idx, starts, ims, steps0, draws, c, d, n_samples, n_leapfrog, warmup, adapt_every, adapt_rate, chunk):
+    """logistic_hmc's loop -- warm-up chunks with hmc_warmup_step per problem, then the kept chunks at frozen steps -- for the
+    problems `idx` of one engine.  Returns ({p: (samples, logjoint, accept, step, warm_steps)}, marked indices, device ms)."""
+    G = len(idx)
+    step = [float(steps0[p]) for p in idx]
+    warm = [[] for _ in idx]
+    out = [(np.empty((n_samples, c, d)), np.empty((n_samples, c)), np.empty((n_samples, c), dtype=bool)) for _ in idx]
+    bad = np.zeros(G, dtype=bool)
+    eng.begin(np.ascontiguousarray(starts[idx]), np.ascontiguousarray(ims[idx]), int(n_leapfrog), int(warmup) + int(n_samples))
+    try:
+        ci, left = 0, int(warmup)
+        while left > 0 and not bad.all():
+            k = min(left, int(adapt_every))
+            e, u = draws.get(ci, k, idx)
+            _, _, acc, status = eng.chunk(e, u, np.array(step), draws.shared)
+            bad |= status != 0
+            for j in range(G):
+                if not bad[j]:
+                    warm[j].append(step[j])
+                    step[j] = hmc_warmup_step(step[j], float(np.mean(acc[j] != 0)), adapt_rate)
+            left -= k
+            ci += 1
+        i0 = 0
+        while i0 < n_samples and not bad.all():
+            k = min(n_samples - i0, int(chunk))
+            e, u = draws.get(ci, k, idx)
+            s, lj, acc, status = eng.chunk(e, u, np.array(step), draws.shared)
+            bad |= status != 0
+            for j in range(G):
+                if not bad[j]:
+                    out[j][0][i0:i0 + k], out[j][1][i0:i0 + k], out[j][2][i0:i0 + k] = s[j], lj[j], acc[j] != 0
+            i0 += k
+            ci += 1
+    finally:
+        ms = eng.end()
+    res = {p: out[j] + (step[j], np.array(warm[j])) for j, p in enumerate(idx) if not bad[j]}
+    return res, [p for j, p in enumerate(idx) if bad[j]], ms
+
+
+def _per_problem(x, P, shape, what):
+    """x as a P x shape array: one value / array for all problems, or one per problem."""
+    a = np.asarray(x, dtype=np.float64)
+    if a.shape == shape:
+        return np.ascontiguousarray(np.broadcast_to(a, (P,) + shape))
+    if a.shape == (P,) + shape:
+        return np.ascontiguousarray(a)
+    raise ValueError('%s must have shape %r (for all problems) or %r (one per problem), got %r' % (what, shape, (P,) + shape, a.shape))
+
+
+def logistic_hmc_many(problems, n_samples=1000, n_chains=16, step_size=0.1, n_leapfrog=8, inv_mass=None, start=None, warmup=0, rng=None,
+                      draws='shared', adapt_every=25, adapt_rate=1.0, chunk=None, strict=True, ctx=None, engine=None):
+    """logistic_hmc for MANY small problems in one batched run: the posteriors of the weighted coresets of an evaluation curve
+    (`for m in range(M + 1): sample the coreset of size m` in the logistic drivers).  One thread block per problem and group of
+    up to four chains holds the problem's rows in LDS and runs whole chunks of iterations there (k_hmc_small); a chunk is one
+    launch for all problems.  No CPU fallback.
+
+    problems: a sequence of (Z_p, wts_p): rows z = y*x (n_p x D, D common; float32 rows are widened) and one weight per row, or
+      None = all ones.  An empty coreset (0 x D) is taken as one zero row with weight 0: the prior, the drivers' convention.
+    start, inv_mass, step_size: as logistic_hmc's, one for all problems or one per problem (start: C x D or P x C x D; inv_mass:
+      D, P x D, None or 'laplace'; step_size: a number or P numbers).  start=None and 'laplace' use the device Laplace fit of each
+      problem, as logistic_hmc does.
+    draws='shared' (default): the draws are made ONCE, in logistic_hmc's order and chunking -- the start's normals randn(C, D)
+      if start is None; then per chunk randn(k, C, D) followed by log(rand(k, C)); warm-up chunks of adapt_every iterations, kept
+      chunks of `chunk` (None = bc_hmc_auto_chunk(C, D)) -- and every problem reads the same ones: entry p equals, to rounding,
+      logistic_hmc(Z_p, wts_p, ..., rng=RandomState(seed)) with every problem seeded alike (common random numbers).
+    draws='independent': per chunk (and for the start) the pair is drawn for p = 0 .. P - 1 in order; the automatic chunk is
+      divided by P so that the staged draws stay under 32 MB.
+    Warm-up: hmc_warmup_step per problem, from that problem's own accepted fraction; the steps diverge per problem and are frozen
+      for the kept iterations.
+    A problem that does not fit one block's LDS (bc_hmc_small_fits says; INTEGRATION.md has the formula) is sampled by
+      logistic_hmc's engine on the same draws after the batched run; the returned list names those in `.fallback`, and each result
+      has `.route`.
+    A problem whose start is not finite (a non-finite weight shows there) is marked on the device and costs the others nothing:
+      strict=True raises NumericalPrecisionError naming the indices after the run is closed, strict=False leaves None there.
+    engine: a stand-in `engine(Z_p, wts_p)` per problem with logistic_hmc's engine protocol (CPU tests).
+    Limits: 1 <= n_chains <= 64, D <= 256, one device.  Returns an HMCManyResult."""
+    if draws not in ('shared', 'independent'):
+        raise ValueError("draws must be 'shared' or 'independent'")
+    probs, d = [], None
+    for p, pair in enumerate(problems):
+        Z, w = pair
+        Z = np.asarray(Z)
+        if Z.ndim != 2:
+            raise ValueError('problem %d: the rows must be n x D, got shape %r' % (p, Z.shape))
+        if d is None:
+            d = Z.shape[1]
+        if Z.shape[1] != d:
+            raise ValueError('problem %d: %d columns, the problems before it have %d' % (p, Z.shape[1], d))
+        Z = np.ascontiguousarray(Z, dtype=np.float64)
+        n = Z.shape[0]
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float64)
+            if w.shape != (n,):
+                raise ValueError('problem %d: wts must have one weight per row of Z (%d), got shape %r' % (p, n, w.shape))
+        if n == 0:
+            Z, w = np.zeros((1, d)), np.zeros(1)
+        probs.append((Z, np.ones(Z.shape[0]) if w is None else w))
+    P = len(probs)
+    if P == 0:
+        raise ValueError('needs at least one problem')
+    c = int(n_chains)
+    check_hmc_problem((1, d), c)
+    if n_samples < 1 or warmup < 0 or n_leapfrog < 1 or adapt_every < 1:
+        raise ValueError('needs n_samples >= 1, warmup >= 0, n_leapfrog >= 1 and adapt_every >= 1')
+    steps0 = _per_problem(step_size, P, (), 'step_size')
+    if not (np.all(np.isfinite(steps0)) and np.all(steps0 > 0.)):
+        raise ValueError('step_size must be finite and positive, got %r' % (step_size,))
+    shared = draws == 'shared'
+    randn = np.random.randn if rng is None else rng.randn
+    want_laplace = isinstance(inv_mass, str) and inv_mass == 'laplace'
+    if isinstance(inv_mass, str) and not want_laplace:
+        raise ValueError("inv_mass must be D positive numbers (or P x D), None or 'laplace'")
+    if engine is None:
+        from .device import default_context
+        ctx = default_context() if ctx is None else ctx
+    fits = [True] * P if engine is not None else [bool(N.load().bc_hmc_small_fits(ctx.h, int(z.shape[0]), int(d))) for z, _ in probs]
+    resident = {}
+
+    def on_device(p):      # (the rows of p on the device: the Laplace fit and the single-problem route share them)
+        if p not in resident:
+            resident[p] = DeviceData(probs[p][0], ctx=ctx)
+        return resident[p]
+    if start is None or want_laplace:
+        if engine is not None:
+            raise ValueError('a stand-in engine has no Laplace fit: pass start and inv_mass')
+        fit = [logistic_laplace(w, on_device(p), np.zeros(d), solver='newton')[:2] for p, (z, w) in enumerate(probs)]
+        if want_laplace:
+            inv_mass = np.array([1. / (1. + logistic_newton_pass(on_device(p), fit[p][0], np.where(w > 0, w, 0.), hessian=False, diag=True)[3])
+                                 for p, (z, w) in enumerate(probs)])
+    ims = _per_problem(np.ones(d) if inv_mass is None else inv_mass, P, (d,), 'inv_mass')
+    if not np.all(np.isfinite(ims)) or not np.all(ims > 0.):
+        raise ValueError('inv_mass must be %d finite positive numbers' % d)
+    if start is None:
+        e0 = randn(c, d) if shared else None
+        starts = np.array([fit[p][0] + (e0 if shared else randn(c, d)).dot(fit[p][1].T) for p in range(P)])
+    else:
+        starts = _per_problem(start, P, (c, d), 'start')
+    # the groups: the problems that fit go through the batched engine together, every other problem through its own engine
+    if engine is not None:
+        groups = [(_SingleAsBatch(engine(z, w)), [p]) for p, (z, w) in enumerate(probs)]
+    else:
+        small = [p for p in range(P) if fits[p]]
+        groups = [(_DeviceHMCMany(ctx, [probs[p] for p in small]), small)] if small else []
+        for p in range(P):
+            if not fits[p]:
+                groups.append((_SingleAsBatch(_DeviceHMC(on_device(p), _weights_on_device(probs[p][1], probs[p][0].shape[0], ctx))), [p]))
+    if chunk is None:
+        chunk = groups[0][0].auto_chunk(c, d)
+        if not shared:
+            chunk = max(1, chunk // P)
+    if chunk < 1:
+        raise ValueError('chunk must be >= 1')
+    stream = _ManyDraws(rng, shared, P, c, d, keep=len(groups) > 1)
+    done, marked, ms_small = {}, [], None
+    for eng, idx in groups:
+        res, bad, ms = _run_hmc_group(eng, idx, starts, ims, steps0, stream, c, d, int(n_samples), n_leapfrog, warmup, adapt_every,
+                                      adapt_rate, chunk)
+        for p, (s, lj, acc, step, warm) in res.items():
+            done[p] = HMCResult(s, lj, acc, step, warm, starts[p], ims[p], ms)
+            done[p].route = 'small' if fits[p] else 'single'
+        marked += bad
+        if isinstance(eng, _DeviceHMCMany):
+            ms_small = ms
+    marked.sort()
+    if marked and strict:
+        raise N.NumericalPrecisionError('logistic_hmc_many: the log-joint or its gradient at the start of problem(s) %s is not finite '
+                                        '(a weight or a start point that is not finite)' % ', '.join(str(p) for p in marked))
+    return HMCManyResult([done.get(p) for p in range(P)], [p for p in range(P) if not fits[p]], marked, ms_small)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The logistic drivers' evaluation with exact-posterior samples drawn on the GPU.
 
-    python examples/logistic_mcmc_eval.py [--n 200000] [--d 10] [--m 200] [--samples 250] [--chains 16] [--seed 1]
+    python examples/logistic_mcmc_eval.py [--n 200000] [--d 10] [--m 200] [--samples 250] [--chains 16] [--seed 1] [--curve K]
 
 The reference's logistic drivers end by drawing ~1 000 posterior samples with MCMC -- of the full data as ground truth
 (examples/common/mcmc.py:21), of the weighted coreset as the thing to judge (zellner_logreg/main.py:225-230) -- and scoring them
@@ -16,6 +16,10 @@ Scores, in plain NumPy on the small test split as the drivers compute them (mode
 of the max-likelihood prediction under each sampled theta, averaged (compute_accuracy), and the test log-likelihood summed over
 the points and averaged over the samples.  Also the distance of each sample set's mean from the ground truth's, in units of the
 ground truth's posterior standard deviations.
+
+--curve K (opt-in) adds the drivers' evaluation curve (zellner_logreg/main.py:219-230: `for m in range(M + 1)`): K nested coreset
+sizes between 0 and M -- the coresets after m greedy steps of the same construction -- sampled by ONE batched call,
+samplers.logistic_hmc_many, on common random numbers, and scored as above.
 """
 import argparse
 import os
@@ -57,6 +61,7 @@ def main():
     ap.add_argument('--leapfrog', type=int, default=8)
     ap.add_argument('--proj-dim', type=int, default=200)
     ap.add_argument('--seed', type=int, default=1)
+    ap.add_argument('--curve', type=int, default=0, help='score this many nested coreset sizes 0 .. m from one batched call (0: off)')
     a = ap.parse_args()
     rng = np.random.RandomState(a.seed)
     X = rng.randn(a.n + a.n_test, a.d)
@@ -77,7 +82,17 @@ def main():
 
     smp = bc.samplers.LaplaceFullDataSampler(dz, mu0, rng=rng)
     alg = bc.HilbertCoreset(Z, bc.DeviceProjector(smp, a.proj_dim, bc.likelihoods.LogisticRegression()))
-    alg.build(a.m, a.m)
+    curve_at = sorted(set(int(round(v)) for v in np.linspace(0, a.m, a.curve))) if a.curve > 0 else []
+    nested = []
+    done = 0
+    for m in curve_at:                                         # (the greedy construction is incremental: m - done more steps)
+        if m > done:
+            alg.build(m - done, m)
+            done = m
+        w_m, p_m, _ = alg.get() if done > 0 else (np.zeros(0), np.zeros((0, a.d)), None)      # (m = 0: the empty coreset, the prior)
+        nested.append((np.array(p_m, dtype=np.float64).reshape(-1, a.d), np.array(w_m, dtype=np.float64)))
+    if a.m > done:
+        alg.build(a.m - done, a.m)
     wts, pts, _ = alg.get()
     t0 = time.perf_counter()
     core = bc.samplers.logistic_hmc(pts, wts, rng=rng, **hmc)
@@ -92,6 +107,17 @@ def main():
     for name, th in (('full', truth), ('coreset', core.pooled()), ('laplace', lap)):
         print('%-8s accuracy %.4f   test log-likelihood %.3f   |mean - truth| / sd: max %.3f' %
               (name, compute_accuracy(Xt, Yt, th), log_likelihood(Zt, th).sum(axis=0).mean(), np.abs((th.mean(axis=0) - mu_t) / sd_t).max()))
+    if nested:
+        t0 = time.perf_counter()
+        curve = bc.samplers.logistic_hmc_many(nested, rng=rng, **hmc)
+        t_curve = time.perf_counter() - t0
+        print('curve: %d coreset sizes in one batched call, %.2f s (%.1f ms on the GPU); through the single-problem engine: %s' %
+              (len(nested), t_curve, curve.device_ms or 0., curve.fallback or 'none'))
+        for m, (p_m, w_m), res in zip(curve_at, nested, curve):
+            th = res.pooled()
+            print('m = %-4d points %-4d accuracy %.4f   test log-likelihood %.3f   |mean - truth| / sd: max %.3f   step %.4g' %
+                  (m, len(w_m), compute_accuracy(Xt, Yt, th), log_likelihood(Zt, th).sum(axis=0).mean(),
+                   np.abs((th.mean(axis=0) - mu_t) / sd_t).max(), res.step_size))
 
 
 if __name__ == '__main__':
