@@ -74,16 +74,81 @@ static void timer_free(bc_timer& t) {
   t.used = 0;
 }
 
-int bc_scratch_grow(bc_ctx* ctx, bc_scratch* s, size_t doubles) {
-  if (doubles <= s->cap) return BC_OK;
-  BC_HIP(hipStreamSynchronize(ctx->stream));       // an enqueued kernel may still read the old buffer
-  if (s->p) (void)hipFree(s->p);
-  s->p = nullptr;
-  s->cap = 0;
+// grow-only, 1.5 x what is asked for; contents are not kept
+static int grow(bc_ctx* ctx, double** p, size_t* cap, size_t doubles, bool pinned) {
+  if (doubles <= *cap) return BC_OK;
+  BC_HIP(hipStreamSynchronize(ctx->stream));       // an enqueued kernel or copy may still use the old buffer
+  if (*p) (void)(pinned ? hipHostFree(*p) : hipFree(*p));
+  *p = nullptr;
+  *cap = 0;
   const size_t want = doubles + doubles / 2;
-  BC_HIP(hipMalloc((void**)&s->p, want * sizeof(double)));
-  s->cap = want;
+  BC_HIP(pinned ? hipHostMalloc((void**)p, want * sizeof(double), hipHostMallocDefault) : hipMalloc((void**)p, want * sizeof(double)));
+  *cap = want;
   return BC_OK;
+}
+int bc_scratch_grow(bc_ctx* ctx, bc_scratch* s, size_t doubles) { return grow(ctx, &s->p, &s->cap, doubles, false); }
+int bc_pinned_grow(bc_ctx* ctx, bc_pinned* s, size_t doubles) { return grow(ctx, &s->p, &s->cap, doubles, true); }
+
+int bc_stage_reserve(bc_ctx* ctx, bc_stage* st, size_t doubles) {
+  const int rc = bc_scratch_grow(ctx, &st->dev, doubles);
+  return rc ? rc : bc_pinned_grow(ctx, &st->pin, doubles);
+}
+
+void bc_scratch_free(bc_scratch* s) { if (s->p) (void)hipFree(s->p); *s = bc_scratch(); }
+void bc_pinned_free(bc_pinned* s) { if (s->p) (void)hipHostFree(s->p); *s = bc_pinned(); }
+void bc_stage_free(bc_stage* st) { bc_scratch_free(&st->dev); bc_pinned_free(&st->pin); }
+
+int bc_run_clock::create() {
+  for (auto& e : ev)
+    if (!e) BC_HIP(hipEventCreate(&e));
+  return BC_OK;
+}
+int bc_run_clock::start(hipStream_t s) { BC_HIP(hipEventRecord(ev[0], s)); return BC_OK; }
+int bc_run_clock::stop(hipStream_t s) { BC_HIP(hipEventRecord(ev[1], s)); return BC_OK; }
+void bc_run_clock::collect() { float t = 0.f; if (hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) ms += t; }
+void bc_run_clock::free() {
+  for (auto& e : ev)
+    if (e) (void)hipEventDestroy(e);
+}
+
+const char* bc_vi_kind_name(int kind) {
+  return kind == BC_VI_KIND_BETA ? "bc_vi_beta_gradient" : kind == BC_VI_KIND_PSVI ? "bc_psvi_gradient" : "bc_vi_gradient";
+}
+
+// Who is refused while what is held on a context.  G: a fused gradient is pending; V, H, S: a bc_vi_optimize / bc_hmc /
+// bc_hmc_small run is open.
+//
+//   entrant                                                                  G        V        H        S
+//   bc_vi_gradient_begin, bc_vi_beta_gradient_begin, bc_psvi_gradient_begin  refuse   allow    refuse   refuse
+//   bc_vi_optimize_begin                                                     refuse   refuse   refuse   refuse
+//   bc_hmc_begin                                                             refuse   refuse   refuse   refuse
+//   bc_logistic_logjoint_batch                                               allow    allow    refuse   refuse
+//   bc_hmc_small_begin, bc_hmc_small_logjoint                                refuse   refuse   refuse   refuse
+//
+// An entrant passes the holders of its row that refuse it; they are looked at in the order G, V, H, S, and the first one found
+// is named.  Nothing is enqueued, allocated or changed by a refusal.
+int bc_ctx_refuse_busy(const bc_ctx* ctx, const char* who, unsigned holders, unsigned own) {
+  if ((holders & BC_HOLD_GRADIENT) && ctx->vi_pending_m > 0) {
+    bc_set_error("%s: a gradient is %spending on this context (call %s_end first)", who, (own & BC_HOLD_GRADIENT) ? "already " : "",
+                 bc_vi_kind_name(ctx->vi_pending_kind));
+    return BC_INVALID_ARGUMENT;
+  }
+  const struct { unsigned bit; bool open; const char* kind; } runs[3] = {{BC_HOLD_VIOPT, bc_viopt_active(ctx), "bc_vi_optimize"},
+                                                                        {BC_HOLD_HMC, bc_hmc_active(ctx), "bc_hmc"},
+                                                                        {BC_HOLD_HMC_SMALL, bc_hmc_small_active(ctx), "bc_hmc_small"}};
+  for (const auto& r : runs)
+    if ((holders & r.bit) && r.open) {
+      bc_set_error("%s: a %s run is %sopen on this context (call %s_end first)", who, r.kind, (own & r.bit) ? "already " : "", r.kind);
+      return BC_INVALID_ARGUMENT;
+    }
+  return BC_OK;
+}
+
+int bc_close_failed_run(int rc, const std::function<int()>& end) {
+  const std::string msg = bc_last_error();      // (closing the run must not replace the message of what failed)
+  (void)end();
+  bc_set_error("%s", msg.c_str());
+  return rc;
 }
 
 extern "C" int bc_ctx_destroy(bc_ctx* ctx) {
@@ -99,8 +164,7 @@ extern "C" int bc_ctx_destroy(bc_ctx* ctx) {
   bc_scratch* all[] = {&ctx->proj_theta, &ctx->proj_rowaux, &ctx->proj_rowaux2, &ctx->gradx, &ctx->vi_buf, &ctx->const_rows,
                        &ctx->gram[0], &ctx->gram[1], &ctx->gram[2], &ctx->gram[3], &ctx->gram[4],
                        &ctx->lap[0], &ctx->lap[1], &ctx->lap[2], &ctx->take_idx};
-  for (bc_scratch* sc : all)
-    if (sc->p) (void)hipFree(sc->p);
+  for (bc_scratch* sc : all) bc_scratch_free(sc);
   if (ctx->proj_pinned) (void)hipHostFree(ctx->proj_pinned);
   if (ctx->vi_pinned) (void)hipHostFree(ctx->vi_pinned);
   if (ctx->vi_side) { (void)hipStreamSynchronize(ctx->vi_side); (void)hipStreamDestroy(ctx->vi_side); }

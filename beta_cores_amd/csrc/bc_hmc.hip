@@ -26,10 +26,10 @@
 #include "bc_internal.h"
 #include "bc_lr_terms.h"
 #include "bc_hmc_dev.h"
+#include "bc_slab.h"
 #include "../../include/beta_cores_hmc.h"
 #include <cmath>
 #include <cstring>
-#include <string>
 
 typedef double bc_d4 __attribute__((ext_vector_type(4)));
 
@@ -229,24 +229,19 @@ __global__ __launch_bounds__(BC_HMC_BLOCK) void k_hmc_last(HmcState s, const int
 
 // ------------------------------------------------------------------ host side
 struct bc_hmc {
-  double* dev = nullptr;          // the chains' state (HmcState) | inverse mass | flag
-  size_t dev_cap = 0;
-  double* part = nullptr;         // the rows pass's partials
-  size_t part_cap = 0;
-  double* stage_dev = nullptr;    // a chunk's draws: normals [k][c][d] | log-uniforms [k][c]
-  double* stage_pin = nullptr;
-  size_t stage_cap = 0;
-  double* out_dev = nullptr;      // a chunk's results: samples [k][c][d] | log-joints [k][c] | accept flags [k][c] (ints)
-  size_t out_cap = 0;
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  bc_scratch dev;                 // the chains' state (HmcState) | inverse mass | flag
+  bc_scratch part;                // the rows pass's partials
+  bc_stage stage;                 // a chunk's draws: normals [k][c][d] | log-uniforms [k][c]
+  bc_scratch out;                 // a chunk's results: samples [k][c][d] | log-joints [k][c] | accept flags [k][c] (ints)
+  bc_run_clock clock;
   bool active = false, chunk_pending = false, failed = false;
   const bc_data* data = nullptr;
   const bc_data* w = nullptr;
   HmcState st;
   int* d_flag = nullptr;
   int32_t n_leapfrog = 0, pending_k = 0;
+  size_t o_l = 0, o_a = 0;        // where the pending chunk's log-joints and accept flags begin in `out` (set by _chunk_begin)
   int64_t n_iter = 0, done = 0;
-  double dev_ms = 0.;
 };
 
 bool bc_hmc_active(const bc_ctx* ctx) { return ctx->hmc && ctx->hmc->active; }
@@ -254,43 +249,14 @@ bool bc_hmc_active(const bc_ctx* ctx) { return ctx->hmc && ctx->hmc->active; }
 void bc_hmc_free(bc_ctx* ctx) {
   bc_hmc* h = ctx->hmc;
   if (!h) return;
-  if (h->dev) (void)hipFree(h->dev);
-  if (h->part) (void)hipFree(h->part);
-  if (h->stage_dev) (void)hipFree(h->stage_dev);
-  if (h->stage_pin) (void)hipHostFree(h->stage_pin);
-  if (h->out_dev) (void)hipFree(h->out_dev);
-  for (auto& e : h->ev)
-    if (e) (void)hipEventDestroy(e);
+  bc_scratch_free(&h->dev);
+  bc_scratch_free(&h->part);
+  bc_stage_free(&h->stage);
+  bc_scratch_free(&h->out);
+  h->clock.free();
   delete h;
   ctx->hmc = nullptr;
 }
-
-// grow-only; only called while nothing of this module is enqueued on the buffer
-static int grow_dev(bc_ctx* ctx, double** p, size_t* cap, size_t need) {
-  if (need <= *cap) return BC_OK;
-  BC_HIP(hipStreamSynchronize(ctx->stream));
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const size_t want = need + need / 2;
-  BC_HIP(hipMalloc((void**)p, want * sizeof(double)));
-  *cap = want;
-  return BC_OK;
-}
-
-static int grow_pin(bc_ctx* ctx, double** p, size_t* cap, size_t need) {
-  if (need <= *cap) return BC_OK;
-  BC_HIP(hipStreamSynchronize(ctx->stream));
-  if (*p) (void)hipHostFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const size_t want = need + need / 2;
-  BC_HIP(hipHostMalloc((void**)p, want * sizeof(double), hipHostMallocDefault));
-  *cap = want;
-  return BC_OK;
-}
-
-static size_t even(size_t n) { return (n + 1) & ~(size_t)1; }
 
 static int nkb_of(int d) { return d <= 16 ? 1 : d <= 32 ? 2 : d <= 64 ? 4 : d <= 128 ? 8 : 16; }
 static int waves_of(int nkb) { return BC_MC_WAVES(nkb); }
@@ -383,29 +349,32 @@ static int check_problem(bc_ctx* ctx, const bc_data* data, const bc_data* w, int
 // lays the state slab out for c chains of d coordinates (growing it if need be) and points h->st into it
 static int layout_state(bc_ctx* ctx, bc_hmc* h, const bc_data* data, int c) {
   const int d = data->dz;
-  const size_t cd = even((size_t)c * d), cc = even((size_t)c);
-  const size_t total = 5 * cd + 3 * cc + even((size_t)c * (1 + d)) + even((size_t)d) + 2;
-  int rc = grow_dev(ctx, &h->dev, &h->dev_cap, total);
+  const size_t cd = (size_t)c * d;
+  bc_slab sl;
+  const size_t o_theta = sl.take(cd), o_thp = sl.take(cd), o_r = sl.take(cd), o_g = sl.take(cd), o_gp = sl.take(cd);
+  const size_t o_lj = sl.take(c), o_ljp = sl.take(c), o_h0 = sl.take(c), o_red = sl.take((size_t)c * (1 + d)), o_im = sl.take(d);
+  const size_t o_flag = sl.take(2);      // (two doubles: the flag ints)
+  int rc = bc_scratch_grow(ctx, &h->dev, sl.total);
   long long rpr = 0;
   const long long ranges = data->n_rows > 0 ? ranges_of(ctx, data->n_rows, &rpr) : 0;
-  if (!rc) rc = grow_dev(ctx, &h->part, &h->part_cap, (size_t)ranges * c * (1 + d) + 2);
+  if (!rc) rc = bc_scratch_grow(ctx, &h->part, (size_t)ranges * c * (1 + d) + 2);
   if (rc) return rc;
   HmcState& s = h->st;
   s.c = c;
   s.d = d;
   s.half_d_log_2pi = 0.5 * d * log(2. * M_PI);
-  double* p = h->dev;
-  s.theta = p; p += cd;
-  s.thp = p; p += cd;
-  s.r = p; p += cd;
-  s.g = p; p += cd;
-  s.gp = p; p += cd;
-  s.lj = p; p += cc;
-  s.ljp = p; p += cc;
-  s.h0 = p; p += cc;
-  s.red = p; p += even((size_t)c * (1 + d));
-  s.im = p; p += even((size_t)d);
-  h->d_flag = reinterpret_cast<int*>(p);
+  double* p = h->dev.p;
+  s.theta = p + o_theta;
+  s.thp = p + o_thp;
+  s.r = p + o_r;
+  s.g = p + o_g;
+  s.gp = p + o_gp;
+  s.lj = p + o_lj;
+  s.ljp = p + o_ljp;
+  s.h0 = p + o_h0;
+  s.red = p + o_red;
+  s.im = p + o_im;
+  h->d_flag = reinterpret_cast<int*>(p + o_flag);
   return BC_OK;
 }
 
@@ -422,8 +391,8 @@ extern "C" int bc_logistic_logjoint_batch(bc_ctx* ctx, const bc_data* data, cons
   }
   int rc = check_problem(ctx, data, w, c, "bc_logistic_logjoint_batch");
   if (rc) return rc;
-  if (bc_hmc_active(ctx)) { bc_set_error("bc_logistic_logjoint_batch: a bc_hmc run is open on this context (call bc_hmc_end first)"); return BC_INVALID_ARGUMENT; }
-  if (bc_hmc_small_active(ctx)) { bc_set_error("bc_logistic_logjoint_batch: a bc_hmc_small run is open on this context (call bc_hmc_small_end first)"); return BC_INVALID_ARGUMENT; }
+  rc = bc_ctx_refuse_busy(ctx, "bc_logistic_logjoint_batch", BC_HOLD_HMC | BC_HOLD_HMC_SMALL);
+  if (rc) return rc;
   BC_HIP(hipSetDevice(ctx->device));
   bc_hmc* h = hmc_of(ctx);
   rc = layout_state(ctx, h, data, c);
@@ -432,7 +401,7 @@ extern "C" int bc_logistic_logjoint_batch(bc_ctx* ctx, const bc_data* data, cons
   const size_t n_th = (size_t)c * d;
   BC_HIP(hipMemcpyAsync(h->st.theta, theta, n_th * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   BC_HIP(hipMemsetAsync(h->d_flag, 0, 2 * sizeof(int), ctx->stream));
-  rc = rows_pass(ctx, data, w, h->st.theta, c, out_value != nullptr, h->part, h->st.red);
+  rc = rows_pass(ctx, data, w, h->st.theta, c, out_value != nullptr, h->part.p, h->st.red);
   if (rc) return rc;
   hipLaunchKernelGGL(k_hmc_init, dim3((unsigned)c), dim3(BC_HMC_BLOCK), 0, ctx->stream, h->st, h->d_flag);
   BC_HIP(hipGetLastError());
@@ -464,22 +433,19 @@ extern "C" int bc_hmc_begin(bc_ctx* ctx, const bc_data* data, const bc_data* w, 
       bc_set_error("bc_hmc_begin: inv_mass[%d] = %g is not finite and positive", k, inv_mass[k]);
       return BC_INVALID_ARGUMENT;
     }
-  if (ctx->vi_pending_m > 0) { bc_set_error("bc_hmc_begin: a bc_vi_gradient is pending on this context"); return BC_INVALID_ARGUMENT; }
-  if (bc_viopt_active(ctx)) { bc_set_error("bc_hmc_begin: a bc_vi_optimize run is open on this context (call bc_vi_optimize_end first)"); return BC_INVALID_ARGUMENT; }
-  if (bc_hmc_active(ctx)) { bc_set_error("bc_hmc_begin: a run is already open on this context (call bc_hmc_end first)"); return BC_INVALID_ARGUMENT; }
-  if (bc_hmc_small_active(ctx)) { bc_set_error("bc_hmc_begin: a bc_hmc_small run is open on this context (call bc_hmc_small_end first)"); return BC_INVALID_ARGUMENT; }
+  rc = bc_ctx_refuse_busy(ctx, "bc_hmc_begin", BC_HOLD_ALL, BC_HOLD_HMC);
+  if (rc) return rc;
   BC_HIP(hipSetDevice(ctx->device));
   bc_hmc* h = hmc_of(ctx);
-  for (auto& e : h->ev)
-    if (!e) BC_HIP(hipEventCreate(&e));
-  rc = layout_state(ctx, h, data, c);
+  rc = h->clock.create();
+  if (!rc) rc = layout_state(ctx, h, data, c);
   if (rc) return rc;
   BC_HIP(hipStreamSynchronize(ctx->stream));
   // (pageable sources: the copies below have read them when they return)
   BC_HIP(hipMemcpyAsync(h->st.theta, start, (size_t)c * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   BC_HIP(hipMemcpyAsync(const_cast<double*>(h->st.im), inv_mass, (size_t)d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   BC_HIP(hipMemsetAsync(h->d_flag, 0, 2 * sizeof(int), ctx->stream));
-  rc = rows_pass(ctx, data, w, h->st.theta, c, true, h->part, h->st.red);
+  rc = rows_pass(ctx, data, w, h->st.theta, c, true, h->part.p, h->st.red);
   if (rc) return rc;
   hipLaunchKernelGGL(k_hmc_init, dim3((unsigned)c), dim3(BC_HMC_BLOCK), 0, ctx->stream, h->st, h->d_flag);
   BC_HIP(hipGetLastError());
@@ -488,7 +454,7 @@ extern "C" int bc_hmc_begin(bc_ctx* ctx, const bc_data* data, const bc_data* w, 
   h->n_leapfrog = n_leapfrog;
   h->n_iter = n_iter;
   h->done = 0;
-  h->dev_ms = 0.;
+  h->clock.ms = 0.;
   h->pending_k = 0;
   h->active = true;
   h->chunk_pending = false;
@@ -510,34 +476,33 @@ extern "C" int bc_hmc_chunk_begin(bc_ctx* ctx, const double* normals, const doub
   BC_HIP(hipSetDevice(ctx->device));
   const HmcState& s = h->st;
   const size_t cd = (size_t)s.c * s.d, n_e = (size_t)k * cd, n_u = (size_t)k * s.c;
-  const size_t need = even(n_e) + even(n_u);
-  if (need > h->stage_cap) {
-    size_t c1 = h->stage_cap, c2 = h->stage_cap;
-    int rc = grow_dev(ctx, &h->stage_dev, &c1, need);
-    if (!rc) rc = grow_pin(ctx, &h->stage_pin, &c2, need);
-    if (rc) { h->stage_cap = 0; return rc; }
-    h->stage_cap = c1 < c2 ? c1 : c2;
-  }
-  const size_t need_out = even(n_e) + even(n_u) + even((n_u + 1) / 2);
-  int rc = grow_dev(ctx, &h->out_dev, &h->out_cap, need_out);
+  bc_slab st, out;
+  st.take(n_e);
+  const size_t o_u = st.take(n_u);
+  out.take(n_e);
+  h->o_l = out.take(n_u);
+  h->o_a = out.take((n_u + 1) / 2);      // (ints)
+  int rc = bc_stage_reserve(ctx, &h->stage, st.total);
+  if (!rc) rc = bc_scratch_grow(ctx, &h->out, out.total);
   if (rc) return rc;
-  memcpy(h->stage_pin, normals, n_e * sizeof(double));
-  memcpy(h->stage_pin + even(n_e), log_u, n_u * sizeof(double));
-  BC_HIP(hipMemcpyAsync(h->stage_dev, h->stage_pin, need * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  BC_HIP(hipEventRecord(h->ev[0], ctx->stream));
+  memcpy(h->stage.pin.p, normals, n_e * sizeof(double));
+  memcpy(h->stage.pin.p + o_u, log_u, n_u * sizeof(double));
+  BC_HIP(hipMemcpyAsync(h->stage.dev.p, h->stage.pin.p, st.total * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  rc = h->clock.start(ctx->stream);
+  if (rc) return rc;
   h->chunk_pending = true;      // from here on something is enqueued: _chunk_end must wait even if a launch below fails
   h->pending_k = k;
-  const double* d_e = h->stage_dev;
-  const double* d_u = h->stage_dev + even(n_e);
-  double* o_s = h->out_dev;
-  double* o_l = h->out_dev + even(n_e);
-  int* o_a = reinterpret_cast<int*>(h->out_dev + even(n_e) + even(n_u));
+  const double* d_e = h->stage.dev.p;
+  const double* d_u = h->stage.dev.p + o_u;
+  double* o_s = h->out.p;
+  double* o_l = h->out.p + h->o_l;
+  int* o_a = reinterpret_cast<int*>(h->out.p + h->o_a);
   for (int t = 0; t < k; ++t) {
     hipLaunchKernelGGL(k_hmc_start, dim3((unsigned)s.c), dim3(BC_HMC_BLOCK), 0, ctx->stream, s, h->d_flag, d_e + (size_t)t * cd, step_size);
     BC_HIP(hipGetLastError());
     for (int l = 1; l <= h->n_leapfrog; ++l) {
       const bool last = l == h->n_leapfrog;
-      rc = rows_pass(ctx, h->data, h->w, s.thp, s.c, last, h->part, s.red);
+      rc = rows_pass(ctx, h->data, h->w, s.thp, s.c, last, h->part.p, s.red);
       if (rc) return rc;
       if (!last) hipLaunchKernelGGL(k_hmc_inner, dim3((unsigned)s.c), dim3(BC_HMC_BLOCK), 0, ctx->stream, s, h->d_flag, step_size);
       else
@@ -546,7 +511,8 @@ extern "C" int bc_hmc_chunk_begin(bc_ctx* ctx, const double* normals, const doub
       BC_HIP(hipGetLastError());
     }
   }
-  BC_HIP(hipEventRecord(h->ev[1], ctx->stream));
+  rc = h->clock.stop(ctx->stream);
+  if (rc) return rc;
   h->done += k;
   return BC_OK;
 }
@@ -561,18 +527,17 @@ extern "C" int bc_hmc_chunk_end(bc_ctx* ctx, double* out_samples, double* out_lo
   int flag = 0;
   BC_HIP(hipStreamSynchronize(ctx->stream));
   BC_HIP(hipMemcpy(&flag, h->d_flag, sizeof(int), hipMemcpyDeviceToHost));
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess) h->dev_ms += ms;
+  h->clock.collect();
   if (flag != 0) {
     h->failed = true;
     bc_set_error("bc_hmc: the log-joint or its gradient at a chain's start is not finite (a weight or a start point that is not finite)");
     return BC_NUMERICAL_PRECISION;
   }
   const HmcState& s = h->st;
-  const size_t n_e = (size_t)h->pending_k * s.c * s.d, n_u = (size_t)h->pending_k * s.c;
-  BC_HIP(hipMemcpy(out_samples, h->out_dev, n_e * sizeof(double), hipMemcpyDeviceToHost));
-  BC_HIP(hipMemcpy(out_logjoint, h->out_dev + even(n_e), n_u * sizeof(double), hipMemcpyDeviceToHost));
-  BC_HIP(hipMemcpy(out_accept, h->out_dev + even(n_e) + even(n_u), n_u * sizeof(int32_t), hipMemcpyDeviceToHost));
+  const size_t n_u = (size_t)h->pending_k * s.c;
+  BC_HIP(hipMemcpy(out_samples, h->out.p, n_u * s.d * sizeof(double), hipMemcpyDeviceToHost));
+  BC_HIP(hipMemcpy(out_logjoint, h->out.p + h->o_l, n_u * sizeof(double), hipMemcpyDeviceToHost));
+  BC_HIP(hipMemcpy(out_accept, h->out.p + h->o_a, n_u * sizeof(int32_t), hipMemcpyDeviceToHost));
   return BC_OK;
 }
 
@@ -591,7 +556,7 @@ extern "C" int bc_hmc_end(bc_ctx* ctx) {
 
 extern "C" int bc_hmc_device_ms(bc_ctx* ctx, double* out_ms) {
   if (!ctx || !out_ms) { bc_set_error("bc_hmc_device_ms: bad argument"); return BC_INVALID_ARGUMENT; }
-  *out_ms = ctx->hmc ? ctx->hmc->dev_ms : 0.;
+  *out_ms = ctx->hmc ? ctx->hmc->clock.ms : 0.;
   return BC_OK;
 }
 
@@ -611,11 +576,6 @@ extern "C" int bc_hmc_logistic(bc_ctx* ctx, const bc_data* data, const bc_data* 
       if (!rc) rc = rc2;
     }
   }
-  if (rc) {
-    const std::string msg = bc_last_error();      // (closing the run must not replace the message of what failed)
-    (void)bc_hmc_end(ctx);
-    bc_set_error("%s", msg.c_str());
-    return rc;
-  }
+  if (rc) return bc_close_failed_run(rc, [&] { return bc_hmc_end(ctx); });
   return bc_hmc_end(ctx);
 }

@@ -29,6 +29,7 @@
 #include "bc_internal.h"
 #include "bc_hmc_dev.h"
 #include "bc_hmc_small_dev.h"
+#include "bc_slab.h"
 #include "../../include/beta_cores_hmc_small.h"
 #include <cmath>
 #include <cstdlib>
@@ -146,23 +147,18 @@ __global__ __launch_bounds__(CPB * BC_SM_BLOCK) void k_hmc_small(SmArgs a) {
 
 // ------------------------------------------------------------------ host side
 struct bc_hmc_small {
-  double* prob = nullptr;         // rows | w | row_ptr (int64)
-  size_t prob_cap = 0;
-  double* state = nullptr;        // theta | g | lj | inverse masses | flags (ints)
-  size_t state_cap = 0;
-  double* stage_dev = nullptr;    // a chunk's draws and steps: normals | log-uniforms | step [P]
-  double* stage_pin = nullptr;
-  size_t stage_cap = 0;
-  double* out_dev = nullptr;      // a chunk's results: samples | log-joints | accept flags (ints)
-  size_t out_cap = 0;
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  bc_scratch prob;                // rows | w | row_ptr (int64)
+  bc_scratch state;               // theta | g | lj | inverse masses | flags (ints)
+  bc_stage stage;                 // a chunk's draws and steps: normals | log-uniforms | step [P]
+  bc_scratch out;                 // a chunk's results: samples | log-joints | accept flags (ints)
+  bc_run_clock clock;
   bool active = false, chunk_pending = false;
   SmArgs a;
   size_t lds = 0;
   int cpb = 1;                    // chains per block of the run's launches
   int32_t n_problems = 0, pending_k = 0;
+  size_t o_l = 0, o_a = 0;        // where the pending chunk's log-joints and accept flags begin in `out` (set by _chunk_begin)
   int64_t n_iter = 0, done = 0;
-  double dev_ms = 0.;
 };
 
 bool bc_hmc_small_active(const bc_ctx* ctx) { return ctx->hmc_small && ctx->hmc_small->active; }
@@ -170,43 +166,14 @@ bool bc_hmc_small_active(const bc_ctx* ctx) { return ctx->hmc_small && ctx->hmc_
 void bc_hmc_small_free(bc_ctx* ctx) {
   bc_hmc_small* h = ctx->hmc_small;
   if (!h) return;
-  if (h->prob) (void)hipFree(h->prob);
-  if (h->state) (void)hipFree(h->state);
-  if (h->stage_dev) (void)hipFree(h->stage_dev);
-  if (h->stage_pin) (void)hipHostFree(h->stage_pin);
-  if (h->out_dev) (void)hipFree(h->out_dev);
-  for (auto& e : h->ev)
-    if (e) (void)hipEventDestroy(e);
+  bc_scratch_free(&h->prob);
+  bc_scratch_free(&h->state);
+  bc_stage_free(&h->stage);
+  bc_scratch_free(&h->out);
+  h->clock.free();
   delete h;
   ctx->hmc_small = nullptr;
 }
-
-// grow-only; only called while nothing of this module is enqueued on the buffer
-static int grow_dev(bc_ctx* ctx, double** p, size_t* cap, size_t need) {
-  if (need <= *cap) return BC_OK;
-  BC_HIP(hipStreamSynchronize(ctx->stream));
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const size_t want = need + need / 2;
-  BC_HIP(hipMalloc((void**)p, want * sizeof(double)));
-  *cap = want;
-  return BC_OK;
-}
-
-static int grow_pin(bc_ctx* ctx, double** p, size_t* cap, size_t need) {
-  if (need <= *cap) return BC_OK;
-  BC_HIP(hipStreamSynchronize(ctx->stream));
-  if (*p) (void)hipHostFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const size_t want = need + need / 2;
-  BC_HIP(hipHostMalloc((void**)p, want * sizeof(double), hipHostMallocDefault));
-  *cap = want;
-  return BC_OK;
-}
-
-static size_t even(size_t n) { return (n + 1) & ~(size_t)1; }
 
 // the doubles of LDS a block of cpb chains needs for a problem of n rows and d columns; with cpb = 1: the capacity rule
 static size_t lds_doubles(int64_t n, int d, int cpb = 1) {
@@ -285,41 +252,38 @@ static int check_batch(bc_ctx* ctx, const int64_t* row_ptr, int32_t n_problems, 
   return BC_OK;
 }
 
-static int check_idle(bc_ctx* ctx, const char* who) {
-  if (ctx->vi_pending_m > 0) { bc_set_error("%s: a fused gradient is pending on this context", who); return BC_INVALID_ARGUMENT; }
-  if (bc_viopt_active(ctx)) { bc_set_error("%s: a weight-optimisation run is open on this context", who); return BC_INVALID_ARGUMENT; }
-  if (bc_hmc_small_active(ctx)) { bc_set_error("%s: a bc_hmc_small run is already open on this context (call bc_hmc_small_end first)", who); return BC_INVALID_ARGUMENT; }
-  if (bc_hmc_active(ctx)) { bc_set_error("%s: a bc_hmc run is open on this context (call bc_hmc_end first)", who); return BC_INVALID_ARGUMENT; }
-  return BC_OK;
-}
-
 // uploads the batch and the C x D vectors per problem, lays the state out and fills h->a except the chunk's fields; enqueued only
 static int stage_batch(bc_ctx* ctx, bc_hmc_small* h, const double* rows, const double* w, const int64_t* row_ptr, int32_t P, int32_t d,
                        const double* theta, int32_t c, const double* inv_mass, int64_t max_n) {
   const size_t n_all = (size_t)row_ptr[P];
-  const size_t o_w = even(n_all * d), o_ptr = o_w + even(n_all);
-  int rc = grow_dev(ctx, &h->prob, &h->prob_cap, o_ptr + (size_t)P + 2);
-  const size_t pc = (size_t)P * c, cd = even(pc * d), cc = even(pc), pd = even((size_t)P * d);
-  if (!rc) rc = grow_dev(ctx, &h->state, &h->state_cap, 2 * cd + cc + pd + even(((size_t)P + 1) / 2) + 2);
+  bc_slab pr, st;
+  const size_t o_rows = pr.take(n_all * d), o_w = pr.take(n_all), o_ptr = pr.take_unpadded((size_t)P + 2);      // (row_ptr: P + 1 int64)
+  int rc = bc_scratch_grow(ctx, &h->prob, pr.total);
+  const size_t pc = (size_t)P * c;
+  const size_t o_theta = st.take(pc * d), o_g = st.take(pc * d), o_lj = st.take(pc), o_im = st.take((size_t)P * d);
+  const size_t o_flag = st.take(((size_t)P + 1) / 2);      // (P + 1 ints)
+  st.take(2);
+  if (!rc) rc = bc_scratch_grow(ctx, &h->state, st.total);
   if (rc) return rc;
   // (per device, and cheap beside the uploads below: set at every begin instead of remembering where it was set)
   for (int cpb = 1; cpb <= 4; cpb <<= 1) BC_HIP(hipFuncSetAttribute(kernel_of(cpb), hipFuncAttributeMaxDynamicSharedMemorySize, ctx->max_lds));
   BC_HIP(hipStreamSynchronize(ctx->stream));
   // (pageable sources: the copies below have read them when they return)
-  BC_HIP(hipMemcpyAsync(h->prob, rows, n_all * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  BC_HIP(hipMemcpyAsync(h->prob + o_w, w, n_all * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  BC_HIP(hipMemcpyAsync(h->prob + o_ptr, row_ptr, ((size_t)P + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+  double* prob = h->prob.p;
+  BC_HIP(hipMemcpyAsync(prob + o_rows, rows, n_all * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  BC_HIP(hipMemcpyAsync(prob + o_w, w, n_all * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  BC_HIP(hipMemcpyAsync(prob + o_ptr, row_ptr, ((size_t)P + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
   SmArgs& a = h->a;
   memset(&a, 0, sizeof(a));
-  a.rows = h->prob;
-  a.w = h->prob + o_w;
-  a.row_ptr = reinterpret_cast<const long long*>(h->prob + o_ptr);
-  double* s = h->state;
-  a.theta = s; s += cd;
-  a.g = s; s += cd;
-  a.lj = s; s += cc;
-  a.im = s; s += pd;
-  a.flag = reinterpret_cast<int*>(s);
+  a.rows = prob + o_rows;
+  a.w = prob + o_w;
+  a.row_ptr = reinterpret_cast<const long long*>(prob + o_ptr);
+  double* s = h->state.p;
+  a.theta = s + o_theta;
+  a.g = s + o_g;
+  a.lj = s + o_lj;
+  a.im = s + o_im;
+  a.flag = reinterpret_cast<int*>(s + o_flag);
   BC_HIP(hipMemcpyAsync(a.theta, theta, pc * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   if (inv_mass) BC_HIP(hipMemcpyAsync(const_cast<double*>(a.im), inv_mass, (size_t)P * d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   BC_HIP(hipMemsetAsync(a.flag, 0, ((size_t)P + 1) * sizeof(int), ctx->stream));
@@ -349,7 +313,7 @@ extern "C" int bc_hmc_small_logjoint(bc_ctx* ctx, const double* rows, const doub
   }
   int64_t max_n = 0;
   int rc = check_batch(ctx, row_ptr, n_problems, d, c, "bc_hmc_small_logjoint", &max_n);
-  if (!rc) rc = check_idle(ctx, "bc_hmc_small_logjoint");
+  if (!rc) rc = bc_ctx_refuse_busy(ctx, "bc_hmc_small_logjoint", BC_HOLD_ALL, BC_HOLD_HMC_SMALL);
   if (rc) return rc;
   BC_HIP(hipSetDevice(ctx->device));
   bc_hmc_small* h = small_of(ctx);
@@ -385,13 +349,12 @@ extern "C" int bc_hmc_small_begin(bc_ctx* ctx, const double* rows, const double*
       bc_set_error("bc_hmc_small_begin: inv_mass[%zu][%zu] = %g is not finite and positive", k / d, k % d, inv_mass[k]);
       return BC_INVALID_ARGUMENT;
     }
-  rc = check_idle(ctx, "bc_hmc_small_begin");
+  rc = bc_ctx_refuse_busy(ctx, "bc_hmc_small_begin", BC_HOLD_ALL, BC_HOLD_HMC_SMALL);
   if (rc) return rc;
   BC_HIP(hipSetDevice(ctx->device));
   bc_hmc_small* h = small_of(ctx);
-  for (auto& e : h->ev)
-    if (!e) BC_HIP(hipEventCreate(&e));
-  rc = stage_batch(ctx, h, rows, w, row_ptr, n_problems, d, start, c, inv_mass, max_n);
+  rc = h->clock.create();
+  if (!rc) rc = stage_batch(ctx, h, rows, w, row_ptr, n_problems, d, start, c, inv_mass, max_n);
   if (rc) return rc;
   SmArgs a = h->a;
   a.mode = BC_SM_INIT;
@@ -401,7 +364,7 @@ extern "C" int bc_hmc_small_begin(bc_ctx* ctx, const double* rows, const double*
   h->a.n_leapfrog = n_leapfrog;
   h->n_iter = n_iter;
   h->done = 0;
-  h->dev_ms = 0.;
+  h->clock.ms = 0.;
   h->pending_k = 0;
   h->active = true;
   h->chunk_pending = false;
@@ -432,40 +395,40 @@ extern "C" int bc_hmc_small_chunk_begin(bc_ctx* ctx, const double* normals, cons
   BC_HIP(hipSetDevice(ctx->device));
   const bool shared = problem_stride == 0;
   const size_t n_e = shared ? kcd : P * kcd, n_u = shared ? kc : P * kc;
-  const size_t o_u = even(n_e), o_st = o_u + even(n_u), need = o_st + even(P);
-  if (need > h->stage_cap) {
-    size_t c1 = h->stage_cap, c2 = h->stage_cap;
-    int rc = grow_dev(ctx, &h->stage_dev, &c1, need);
-    if (!rc) rc = grow_pin(ctx, &h->stage_pin, &c2, need);
-    if (rc) { h->stage_cap = 0; return rc; }
-    h->stage_cap = c1 < c2 ? c1 : c2;
-  }
-  const size_t o_e = P * kcd, o_l = even(o_e), o_a = o_l + even(P * kc);
-  int rc = grow_dev(ctx, &h->out_dev, &h->out_cap, o_a + even((P * kc + 1) / 2));
+  bc_slab st, out;
+  st.take(n_e);
+  const size_t o_u = st.take(n_u), o_st = st.take(P), need = st.total;
+  out.take(P * kcd);
+  h->o_l = out.take(P * kc);
+  h->o_a = out.take((P * kc + 1) / 2);      // (ints)
+  int rc = bc_stage_reserve(ctx, &h->stage, need);
+  if (!rc) rc = bc_scratch_grow(ctx, &h->out, out.total);
   if (rc) return rc;
-  if (shared) memcpy(h->stage_pin, normals, kcd * sizeof(double));
+  double* pin = h->stage.pin.p;
+  const double* dev = h->stage.dev.p;
+  if (shared) memcpy(pin, normals, kcd * sizeof(double));
   else
-    for (size_t p = 0; p < P; ++p) memcpy(h->stage_pin + p * kcd, normals + p * (size_t)problem_stride, kcd * sizeof(double));
-  memcpy(h->stage_pin + o_u, log_u, n_u * sizeof(double));
-  memcpy(h->stage_pin + o_st, step, P * sizeof(double));
-  BC_HIP(hipMemcpyAsync(h->stage_dev, h->stage_pin, need * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    for (size_t p = 0; p < P; ++p) memcpy(pin + p * kcd, normals + p * (size_t)problem_stride, kcd * sizeof(double));
+  memcpy(pin + o_u, log_u, n_u * sizeof(double));
+  memcpy(pin + o_st, step, P * sizeof(double));
+  BC_HIP(hipMemcpyAsync(h->stage.dev.p, pin, need * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   h->chunk_pending = true;      // from here on something is enqueued: _chunk_end must wait even if the launch below fails
   h->pending_k = k;
   SmArgs a = h->a;
   a.mode = BC_SM_CHUNK;
   a.k = k;
-  a.e = h->stage_dev;
-  a.logu = h->stage_dev + o_u;
-  a.step = h->stage_dev + o_st;
+  a.e = dev;
+  a.logu = dev + o_u;
+  a.step = dev + o_st;
   a.e_stride = shared ? 0 : (long long)kcd;
   a.u_stride = shared ? 0 : (long long)kc;
-  a.out_s = h->out_dev;
-  a.out_l = h->out_dev + o_l;
-  a.out_a = reinterpret_cast<int*>(h->out_dev + o_a);
-  BC_HIP(hipEventRecord(h->ev[0], ctx->stream));
-  rc = launch(ctx, h, a);
+  a.out_s = h->out.p;
+  a.out_l = h->out.p + h->o_l;
+  a.out_a = reinterpret_cast<int*>(h->out.p + h->o_a);
+  rc = h->clock.start(ctx->stream);
+  if (!rc) rc = launch(ctx, h, a);
+  if (!rc) rc = h->clock.stop(ctx->stream);
   if (rc) return rc;
-  BC_HIP(hipEventRecord(h->ev[1], ctx->stream));
   h->done += k;
   return BC_OK;
 }
@@ -481,11 +444,9 @@ extern "C" int bc_hmc_small_chunk_end(bc_ctx* ctx, double* out_samples, double* 
   const size_t P = (size_t)h->n_problems, c = (size_t)h->a.c, d = (size_t)h->a.d;
   std::vector<int> flag(P);
   BC_HIP(hipMemcpy(flag.data(), h->a.flag, P * sizeof(int), hipMemcpyDeviceToHost));
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess) h->dev_ms += ms;
+  h->clock.collect();
   const size_t kc = (size_t)h->pending_k * c, kcd = kc * d;
-  const size_t o_l = even(P * kcd), o_a = o_l + even(P * kc);
-  const int* acc_dev = reinterpret_cast<const int*>(h->out_dev + o_a);
+  const int* acc_dev = reinterpret_cast<const int*>(h->out.p + h->o_a);
   // runs of consecutive unmarked problems are copied together (one run of all P when nothing is marked)
   size_t p = 0;
   while (p < P) {
@@ -495,8 +456,8 @@ extern "C" int bc_hmc_small_chunk_end(bc_ctx* ctx, double* out_samples, double* 
     }
     size_t q = p;
     while (q < P && flag[q] == 0) out_status[q++] = BC_OK;
-    BC_HIP(hipMemcpy(out_samples + p * kcd, h->out_dev + p * kcd, (q - p) * kcd * sizeof(double), hipMemcpyDeviceToHost));
-    BC_HIP(hipMemcpy(out_logjoint + p * kc, h->out_dev + o_l + p * kc, (q - p) * kc * sizeof(double), hipMemcpyDeviceToHost));
+    BC_HIP(hipMemcpy(out_samples + p * kcd, h->out.p + p * kcd, (q - p) * kcd * sizeof(double), hipMemcpyDeviceToHost));
+    BC_HIP(hipMemcpy(out_logjoint + p * kc, h->out.p + h->o_l + p * kc, (q - p) * kc * sizeof(double), hipMemcpyDeviceToHost));
     BC_HIP(hipMemcpy(out_accept + p * kc, acc_dev + p * kc, (q - p) * kc * sizeof(int32_t), hipMemcpyDeviceToHost));
     p = q;
   }
@@ -516,6 +477,6 @@ extern "C" int bc_hmc_small_end(bc_ctx* ctx) {
 
 extern "C" int bc_hmc_small_device_ms(bc_ctx* ctx, double* out_ms) {
   if (!ctx || !out_ms) { bc_set_error("bc_hmc_small_device_ms: bad argument"); return BC_INVALID_ARGUMENT; }
-  *out_ms = ctx->hmc_small ? ctx->hmc_small->dev_ms : 0.;
+  *out_ms = ctx->hmc_small ? ctx->hmc_small->clock.ms : 0.;
   return BC_OK;
 }

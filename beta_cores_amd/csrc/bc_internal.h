@@ -37,6 +37,29 @@ struct bc_scratch {
   size_t cap = 0;                // doubles
 };
 
+// ---- what the chunked device runs share (bc_viopt.hip, bc_hmc.hip, bc_hmc_small.hip; the functions are in bc_core.hip)
+// the pinned twin of bc_scratch: grow-only host memory, contents not kept when it grows
+struct bc_pinned {
+  double* p = nullptr;
+  size_t cap = 0;                // doubles
+};
+// a chunk's staging pair: filled on the host in `pin`, sent to `dev` in one transfer.  A half that failed to grow is left
+// with capacity 0 (and no memory), so the next bc_stage_reserve grows it again.
+struct bc_stage {
+  bc_scratch dev;
+  bc_pinned pin;
+};
+// the device time of a run's chunks: two events around each chunk's launches, folded into `ms` once the chunk has been waited for
+struct bc_run_clock {
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  double ms = 0.;
+  int create();                  // the events, where they do not exist yet
+  int start(hipStream_t s);
+  int stop(hipStream_t s);
+  void collect();                // after the stream has been synchronised; an elapsed time that cannot be read is left out
+  void free();
+};
+
 // phases of bc_vi_gradient, timed with HIP events when the context's timing is on (bc_ctx_phase_times)
 #define BC_VI_PHASES 5           // upload (Theta, coreset rows, w) | K1 of the coreset rows | K1 over the data rows (store-free) |
                                  // column-sum reduction (+ rank-order sum over ranks) | M x S algebra + download
@@ -108,11 +131,22 @@ int64_t bc_upload_default_chunk_rows(int64_t n_rows, size_t row_bytes);
 void bc_uploader_free(bc_ctx* ctx);
 void bc_take_free(bc_ctx* ctx);      // bc_take.hip: the two pinned index staging areas and their events
 void bc_viopt_free(bc_ctx* ctx);     // bc_viopt.hip
-bool bc_viopt_active(const bc_ctx* ctx);   // a bc_vi_optimize run is open on the context
+bool bc_viopt_active(const bc_ctx* ctx);   // the context holds an open bc_vi_optimize run
 void bc_hmc_free(bc_ctx* ctx);       // bc_hmc.hip
-bool bc_hmc_active(const bc_ctx* ctx);     // a bc_hmc run is open on the context
+bool bc_hmc_active(const bc_ctx* ctx);     // the context holds an open bc_hmc run
 void bc_hmc_small_free(bc_ctx* ctx); // bc_hmc_small.hip
-bool bc_hmc_small_active(const bc_ctx* ctx);   // a bc_hmc_small run is open on the context
+bool bc_hmc_small_active(const bc_ctx* ctx);   // the context holds an open bc_hmc_small run
+// What may hold a context, and the one place that says who is refused while it does (the table is beside the function in
+// bc_core.hip).  `holders`: the BC_HOLD_* that refuse the caller `who`; `own`: the caller's own kind, if it is a holder.
+#define BC_HOLD_GRADIENT 1u          // a fused gradient is pending (bc_vi_gradient_begin and its kin)
+#define BC_HOLD_VIOPT 2u             // an open bc_vi_optimize run
+#define BC_HOLD_HMC 4u               // an open bc_hmc run
+#define BC_HOLD_HMC_SMALL 8u         // an open bc_hmc_small run
+#define BC_HOLD_ALL 15u
+int bc_ctx_refuse_busy(const bc_ctx* ctx, const char* who, unsigned holders, unsigned own = 0);
+const char* bc_vi_kind_name(int kind);     // the entry point's name of a BC_VI_KIND_*
+// the tail of the one-call drivers: closes a run that failed with `end`, keeps the message of what failed, and returns rc
+int bc_close_failed_run(int rc, const std::function<int()>& end);
 // bc_take.hip: dst[j, :] = src[idx_dev[j], :] for indices that are already on the device and already checked; enqueued only
 int bc_take_rows_dev(bc_ctx* ctx, const bc_data* src, const long long* idx_dev, int64_t m, void* dst_z);
 // bc_project.hip: one gradient's projections and algebra for a Theta that is already on the device (bc_viopt.hip)
@@ -132,6 +166,11 @@ int bc_psvi_point_grad_launch(bc_ctx* ctx, int model, const double* pts_dev, con
                               const double* resid_dev, double* out_dev);
 
 int bc_scratch_grow(bc_ctx* ctx, bc_scratch* s, size_t doubles);   // contents are NOT kept when it grows
+int bc_pinned_grow(bc_ctx* ctx, bc_pinned* s, size_t doubles);     // the same for pinned host memory
+int bc_stage_reserve(bc_ctx* ctx, bc_stage* st, size_t doubles);   // both halves hold `doubles`; contents are NOT kept
+void bc_scratch_free(bc_scratch* s);
+void bc_pinned_free(bc_pinned* s);
+void bc_stage_free(bc_stage* st);
 
 int bc_timer_begin(bc_ctx* ctx, int which);
 int bc_gram_no_y(bc_ctx* ctx, const bc_data* data, const double* w_dev, double** out_dev);   // bc_gram.hip

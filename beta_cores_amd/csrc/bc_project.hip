@@ -858,10 +858,6 @@ static int core_phi_for(bc_ctx* ctx, bc_phi** slot, int64_t m, int32_t s, bc_phi
   return BC_OK;
 }
 
-static const char* vi_kind_name(int kind) {
-  return kind == BC_VI_KIND_BETA ? "bc_vi_beta_gradient" : kind == BC_VI_KIND_PSVI ? "bc_psvi_gradient" : "bc_vi_gradient";
-}
-
 // the three kinds of gradient.  BC_VI_KIND_PLAIN: bc_vi_gradient.  BC_VI_KIND_BETA (bc_vi_beta_gradient): the coreset rows are
 // projected a second time, with grad_model, and the algebra also leaves beta_dots behind grad and resid.  BC_VI_KIND_PSVI
 // (bc_psvi_gradient): k_psvi_point_grad runs behind the algebra and leaves the M x dz point-gradient behind grad and resid.
@@ -870,7 +866,7 @@ static int vi_gradient_begin(bc_ctx* ctx, const bc_data* data, const double* cor
                              double sum_scaling, bc_comm* comm, int kind = -1) {
   if (kind < 0) kind = grad_model >= 0 ? BC_VI_KIND_BETA : BC_VI_KIND_PLAIN;
   const bool with_beta = kind == BC_VI_KIND_BETA, psvi = kind == BC_VI_KIND_PSVI;
-  int rc = project_check(ctx, data, model, theta, s, params, n_params, vi_kind_name(kind));
+  int rc = project_check(ctx, data, model, theta, s, params, n_params, bc_vi_kind_name(kind));
   if (rc) return rc;
   if (psvi && bc_psvi_kind(model) < 0) {
     bc_set_error("bc_psvi_gradient: model %d has no x-gradient in the reference", model);
@@ -891,12 +887,8 @@ static int vi_gradient_begin(bc_ctx* ctx, const bc_data* data, const double* cor
   }
   // grad | resid [| beta_dots] [| grad_p]
   const size_t n_core = (size_t)m * dz, n_down = (with_beta ? 2 : 1) * (size_t)m + (size_t)s + (psvi ? n_core : 0);
-  if (ctx->vi_pending_m > 0) {
-    bc_set_error("%s_begin: a gradient is already pending on this context (call %s_end first)", who, vi_kind_name(ctx->vi_pending_kind));
-    return BC_INVALID_ARGUMENT;
-  }
-  if (bc_hmc_active(ctx)) { bc_set_error("%s_begin: a bc_hmc run is open on this context (call bc_hmc_end first)", who); return BC_INVALID_ARGUMENT; }
-  if (bc_hmc_small_active(ctx)) { bc_set_error("%s_begin: a bc_hmc_small run is open on this context (call bc_hmc_small_end first)", who); return BC_INVALID_ARGUMENT; }
+  rc = bc_ctx_refuse_busy(ctx, (std::string(who) + "_begin").c_str(), BC_HOLD_GRADIENT | BC_HOLD_HMC | BC_HOLD_HMC_SMALL, BC_HOLD_GRADIENT);
+  if (rc) return rc;
   if (n_down > ctx->pinned_doubles) {
     bc_set_error("%s: coreset of %lld rows x %d exceeds the staging area", who, (long long)m, dz);
     return BC_INVALID_ARGUMENT;
@@ -1054,11 +1046,11 @@ extern "C" int bc_vi_beta_gradient_begin(bc_ctx* ctx, const bc_data* data, const
 // out_extra: beta_dots [m] (BC_VI_KIND_BETA) or grad_p [m][dz] (BC_VI_KIND_PSVI)
 static int vi_gradient_end(bc_ctx* ctx, double* out_grad, double* out_extra, double* out_resid, int kind) {
   char who[40];
-  snprintf(who, sizeof(who), "%s_end", vi_kind_name(kind));
+  snprintf(who, sizeof(who), "%s_end", bc_vi_kind_name(kind));
   if (!ctx || !out_grad || (kind != BC_VI_KIND_PLAIN && !out_extra)) { bc_set_error("%s: bad argument", who); return BC_INVALID_ARGUMENT; }
   if (ctx->vi_pending_m <= 0) { bc_set_error("%s: no gradient is pending on this context", who); return BC_INVALID_ARGUMENT; }
   if (ctx->vi_pending_kind != kind) {       // the pending gradient stays pending
-    bc_set_error("%s: the pending gradient was begun by %s_begin", who, vi_kind_name(ctx->vi_pending_kind));
+    bc_set_error("%s: the pending gradient was begun by %s_begin", who, bc_vi_kind_name(ctx->vi_pending_kind));
     return BC_INVALID_ARGUMENT;
   }
   const int64_t m = ctx->vi_pending_m;

@@ -8,6 +8,7 @@
 #include "bc_internal.h"
 #include "bc_vi_sampler_dev.h"
 #include "bc_vi_laplace_dev.h"
+#include "bc_slab.h"
 #include "../../include/beta_cores_viopt.h"
 #include "../../include/beta_cores_vilaplace.h"
 #include <cmath>
@@ -48,16 +49,11 @@ __global__ __launch_bounds__(256) void k_vi_adam(const int* __restrict__ flag, c
 }
 
 struct bc_viopt {
-  double* dev = nullptr;          // one slab: what _begin uploads, then the run's device-only state
-  size_t dev_cap = 0;             // doubles
-  double* pin = nullptr;          // pinned mirror of the uploaded head; later the landing area of w | trace | flag
-  size_t pin_cap = 0;
-  double* stage_dev = nullptr;    // a chunk's draws: normals [k][S][D], then indices [k][n_sub]
-  double* stage_pin = nullptr;
-  size_t stage_cap = 0;           // doubles (an index takes one)
-  void* sub = nullptr;            // the step's sub-sample of the data rows
-  size_t sub_cap = 0;             // bytes
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  bc_scratch dev;                 // one slab: what _begin uploads, then the run's device-only state
+  bc_pinned pin;                  // pinned mirror of the uploaded head; later the landing area of w | trace | flag
+  bc_stage stage;                 // a chunk's draws: normals [k][S][D], then indices [k][n_sub] (an index takes one double)
+  bc_scratch sub;                 // the step's sub-sample of the data rows (their bytes rounded up to whole doubles)
+  bc_run_clock clock;
   bc_vi_plan* plan = nullptr;
   // the run in progress
   bool active = false, chunk_pending = false, failed = false, lds_set = false;
@@ -71,7 +67,7 @@ struct bc_viopt {
   int64_t m = 0, n_sub = 0;
   int32_t s = 0, itrs = 0, done = 0;
   int d = 0, dz = 0;
-  double scale = 1., dev_ms = 0.;
+  double scale = 1.;
   double *d_w = nullptr, *d_mom1 = nullptr, *d_mom2 = nullptr, *d_grad = nullptr, *d_resid = nullptr, *d_step = nullptr, *d_trace = nullptr;
   int* d_flag = nullptr;
 };
@@ -81,13 +77,11 @@ bool bc_viopt_active(const bc_ctx* ctx) { return ctx->viopt && ctx->viopt->activ
 void bc_viopt_free(bc_ctx* ctx) {
   bc_viopt* v = ctx->viopt;
   if (!v) return;
-  if (v->dev) (void)hipFree(v->dev);
-  if (v->pin) (void)hipHostFree(v->pin);
-  if (v->stage_dev) (void)hipFree(v->stage_dev);
-  if (v->stage_pin) (void)hipHostFree(v->stage_pin);
-  if (v->sub) (void)hipFree(v->sub);
-  for (auto& e : v->ev)
-    if (e) (void)hipEventDestroy(e);
+  bc_scratch_free(&v->dev);
+  bc_pinned_free(&v->pin);
+  bc_stage_free(&v->stage);
+  bc_scratch_free(&v->sub);
+  v->clock.free();
   bc_vi_plan_destroy(v->plan);
   delete v;
   ctx->viopt = nullptr;
@@ -99,33 +93,6 @@ extern "C" int bc_vi_optimize_auto_chunk(int32_t s, int32_t d, int64_t n_sub) {
   const double k = floor((double)BC_VI_STAGE_BYTES / per_step);
   return k < 1. ? 1 : k > 1048576. ? 1048576 : (int)k;
 }
-
-// grow-only pairs; only called while nothing of this module is enqueued
-static int grow_dev(bc_ctx* ctx, double** p, size_t* cap, size_t need) {
-  if (need <= *cap) return BC_OK;
-  BC_HIP(hipStreamSynchronize(ctx->stream));
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const size_t want = need + need / 2;
-  BC_HIP(hipMalloc((void**)p, want * sizeof(double)));
-  *cap = want;
-  return BC_OK;
-}
-
-static int grow_pin(bc_ctx* ctx, double** p, size_t* cap, size_t need) {
-  if (need <= *cap) return BC_OK;
-  BC_HIP(hipStreamSynchronize(ctx->stream));
-  if (*p) (void)hipHostFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const size_t want = need + need / 2;
-  BC_HIP(hipHostMalloc((void**)p, want * sizeof(double), hipHostMallocDefault));
-  *cap = want;
-  return BC_OK;
-}
-
-static size_t even(size_t n) { return (n + 1) & ~(size_t)1; }      // 16-byte aligned pieces
 
 extern "C" int bc_vi_optimize_begin(bc_ctx* ctx, const bc_data* data, const double* core_rows, int64_t m, int model, const double* params,
                                     int32_t n_params, int sampler_kind, const double* sampler_params, int32_t s, const double* w0,
@@ -149,9 +116,6 @@ extern "C" int bc_vi_optimize_begin(bc_ctx* ctx, const bc_data* data, const doub
                         : logistic ? (model == BC_MODEL_LOGISTIC_LL || model == BC_MODEL_LOGISTIC_BETA)
                                    : (model == BC_MODEL_LINREG_LL || model == BC_MODEL_LINREG_BETA);
   if (!model_ok) { bc_set_error("bc_vi_optimize_begin: model %d does not go with sampler kind %d", model, sampler_kind); return BC_INVALID_ARGUMENT; }
-  if (ctx->vi_pending_m > 0) { bc_set_error("bc_vi_optimize_begin: a bc_vi_gradient is pending on this context"); return BC_INVALID_ARGUMENT; }
-  if (bc_hmc_active(ctx)) { bc_set_error("bc_vi_optimize_begin: a bc_hmc run is open on this context (call bc_hmc_end first)"); return BC_INVALID_ARGUMENT; }
-  if (bc_hmc_small_active(ctx)) { bc_set_error("bc_vi_optimize_begin: a bc_hmc_small run is open on this context (call bc_hmc_small_end first)"); return BC_INVALID_ARGUMENT; }
   const int dz = data->dz;
   int d = 0, dk = 0, nrsel = 0, ntsel = 0;
   if (bc_vi_plan_layout(model, s, dz, &d, &dk, &nrsel, &ntsel) != BC_OK || d > BC_VI_MAX_DIM) {
@@ -171,35 +135,43 @@ extern "C" int bc_vi_optimize_begin(bc_ctx* ctx, const bc_data* data, const doub
     bc_set_error("bc_vi_optimize_begin: D = %d needs %zu bytes of LDS, the device offers %d", d, lds, ctx->max_lds);
     return BC_INVALID_ARGUMENT;
   }
+  int rc = bc_ctx_refuse_busy(ctx, "bc_vi_optimize_begin", BC_HOLD_ALL, BC_HOLD_VIOPT);
+  if (rc) return rc;
   bc_viopt* v = ctx->viopt;
   if (!v) v = ctx->viopt = new bc_viopt();
-  if (v->active) { bc_set_error("bc_vi_optimize_begin: a run is already open on this context (call bc_vi_optimize_end first)"); return BC_INVALID_ARGUMENT; }
   BC_HIP(hipSetDevice(ctx->device));
   if (!v->lds_set) {
     BC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vi_sampler), hipFuncAttributeMaxDynamicSharedMemorySize, ctx->max_lds));
     BC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vi_laplace), hipFuncAttributeMaxDynamicSharedMemorySize, ctx->max_lds));
     v->lds_set = true;
   }
-  for (auto& e : v->ev)
-    if (!e) BC_HIP(hipEventCreate(&e));
+  rc = v->clock.create();
+  if (rc) return rc;
   v->laid_out = false;      // (the slab may move below)
   // ---- the slab: [uploaded head] core | w | step | Sig0inv | b0 | Siginv   [device-only] mom1 | mom2 | grad | resid | Theta, saux |
   //      raw | trace | flag
   //      logistic kind: Sig0inv and b0 are the start point [d + 1] (then the run's mode) and nothing; behind the trace: the row
   //      scratch of k_vi_laplace [3 m] | its counts (4 ints), then the flag
   const size_t dd = logistic ? (size_t)d + 1 : (size_t)d * d;
-  const size_t o_core = 0, o_w = o_core + even((size_t)m * dz), o_step = o_w + even((size_t)m), o_s0 = o_step + even(3 * (size_t)opt_itrs);
-  const size_t o_b0 = o_s0 + even(dd), o_sg = o_b0 + (logistic ? 0 : even((size_t)d)), head = o_sg + (gauss ? even(dd) : 0);
-  const size_t o_m1 = head, o_m2 = o_m1 + even((size_t)m), o_g = o_m2 + even((size_t)m), o_r = o_g + even((size_t)m);
-  const size_t o_th = o_r + even((size_t)s), o_raw = o_th + even((size_t)nrsel * dk + nrsel), o_tr = o_raw + even((size_t)s * d);
-  const size_t o_rowc = o_tr + (want_trace ? even((size_t)opt_itrs * m) : 0), o_cnt = o_rowc + (logistic ? even(BC_VIL_ROW_DOUBLES(m)) : 0);
-  const size_t o_flag = o_cnt + (logistic ? 2 : 0), total = o_flag + 2;
-  int rc = grow_dev(ctx, &v->dev, &v->dev_cap, total);
-  const size_t down = even((size_t)m) + (want_trace ? even((size_t)opt_itrs * m) : 0) + 2;
-  if (!rc) rc = grow_pin(ctx, &v->pin, &v->pin_cap, head > down ? head : down);
+  //      (a piece that the run's kind does not have takes nothing: the piece behind it starts at the same offset)
+  const size_t n_trace = want_trace ? (size_t)opt_itrs * m : 0;
+  bc_slab sl;
+  const size_t o_core = sl.take((size_t)m * dz), o_w = sl.take(m), o_step = sl.take(3 * (size_t)opt_itrs), o_s0 = sl.take(dd);
+  const size_t o_b0 = sl.take(logistic ? 0 : d), o_sg = sl.take(gauss ? dd : 0), head = sl.total;
+  const size_t o_m1 = sl.take(m), o_m2 = sl.take(m), o_g = sl.take(m), o_r = sl.take(s);
+  const size_t o_th = sl.take((size_t)nrsel * dk + nrsel), o_raw = sl.take((size_t)s * d), o_tr = sl.take(n_trace);
+  const size_t o_rowc = sl.take(logistic ? BC_VIL_ROW_DOUBLES(m) : 0), o_cnt = sl.take(logistic ? 2 : 0), o_flag = sl.take(2);
+  const size_t total = sl.total;
+  rc = bc_scratch_grow(ctx, &v->dev, total);
+  bc_slab dn;      // what _end brings down: w | trace, and the flag's two doubles
+  dn.take(m);
+  dn.take(n_trace);
+  dn.take(2);
+  if (!rc) rc = bc_pinned_grow(ctx, &v->pin, head > dn.total ? head : dn.total);
   if (rc) return rc;
   BC_HIP(hipStreamSynchronize(ctx->stream));      // nothing enqueued earlier still reads the slab or the pinned area
-  double* h = v->pin;
+  double* h = v->pin.p;
+  double* dev = v->dev.p;
   memset(h, 0, head * sizeof(double));
   memcpy(h + o_core, core_rows, (size_t)m * dz * sizeof(double));
   memcpy(h + o_w, w0, (size_t)m * sizeof(double));
@@ -215,34 +187,26 @@ extern "C" int bc_vi_optimize_begin(bc_ctx* ctx, const bc_data* data, const doub
     if (gauss) memcpy(h + o_sg, sampler_params + d + dd, dd * sizeof(double));
     else sigsq = sampler_params[d + dd];
   }
-  BC_HIP(hipMemcpyAsync(v->dev, h, head * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  BC_HIP(hipMemsetAsync(v->dev + head, 0, (total - head) * sizeof(double), ctx->stream));
+  BC_HIP(hipMemcpyAsync(dev, h, head * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  BC_HIP(hipMemsetAsync(dev + head, 0, (total - head) * sizeof(double), ctx->stream));
   bc_vi_plan_destroy(v->plan);
   v->plan = nullptr;
-  rc = bc_vi_plan_create(ctx, model, params, n_params, dz, s, v->dev + o_th, gauss ? v->dev + o_sg : nullptr, &v->plan);
+  rc = bc_vi_plan_create(ctx, model, params, n_params, dz, s, dev + o_th, gauss ? dev + o_sg : nullptr, &v->plan);
   if (rc) return rc;
-  if (n_sub > 0) {
-    const size_t need = (size_t)n_sub * dz * data->elem;
-    if (need > v->sub_cap) {
-      if (v->sub) (void)hipFree(v->sub);
-      v->sub = nullptr;
-      v->sub_cap = 0;
-      BC_HIP(hipMalloc(&v->sub, need + need / 2));
-      v->sub_cap = need + need / 2;
-    }
-  }
+  rc = bc_scratch_grow(ctx, &v->sub, ((size_t)n_sub * dz * data->elem + 7) / 8);
+  if (rc) return rc;
   v->data = data;
   v->core_view = bc_data();
   v->core_view.ctx = ctx;
   v->core_view.n_rows = m;
   v->core_view.dz = dz;
-  v->core_view.z = v->dev + o_core;
+  v->core_view.z = dev + o_core;
   v->core_view.owned = false;
   v->sub_view = bc_data();
   v->sub_view.ctx = ctx;
   v->sub_view.n_rows = n_sub;
   v->sub_view.dz = dz;
-  v->sub_view.z = reinterpret_cast<double*>(v->sub);
+  v->sub_view.z = v->sub.p;
   v->sub_view.owned = false;
   v->sub_view.elem = data->elem;
   VisArgs& a = v->va;
@@ -252,16 +216,16 @@ extern "C" int bc_vi_optimize_begin(bc_ctx* ctx, const bc_data* data, const doub
   a.dz = dz;
   a.s = s;
   a.dk = dk;
-  a.core = v->dev + o_core;
-  a.w = v->dev + o_w;
-  a.sig0inv = v->dev + o_s0;
-  a.b0 = v->dev + o_b0;
-  a.siginv = gauss ? v->dev + o_sg : nullptr;
+  a.core = dev + o_core;
+  a.w = dev + o_w;
+  a.sig0inv = dev + o_s0;
+  a.b0 = dev + o_b0;
+  a.siginv = gauss ? dev + o_sg : nullptr;
   a.sigsq = sigsq;
   a.E = nullptr;
-  a.theta = v->dev + o_th;
-  a.saux = v->dev + o_th + (size_t)nrsel * dk;
-  a.raw = v->dev + o_raw;
+  a.theta = dev + o_th;
+  a.saux = dev + o_th + (size_t)nrsel * dk;
+  a.raw = dev + o_raw;
   VilArgs& l = v->la;
   l.d = d;
   l.m = (int)m;
@@ -273,9 +237,9 @@ extern "C" int bc_vi_optimize_begin(bc_ctx* ctx, const bc_data* data, const doub
   l.w = a.w;
   l.E = nullptr;
   l.theta = a.theta;
-  l.mode = v->dev + o_s0;
-  l.rowc = v->dev + o_rowc;
-  l.counts = reinterpret_cast<int*>(v->dev + o_cnt);
+  l.mode = dev + o_s0;
+  l.rowc = dev + o_rowc;
+  l.counts = reinterpret_cast<int*>(dev + o_cnt);
   v->kind = sampler_kind;
   v->m = m;
   v->n_sub = n_sub;
@@ -287,15 +251,15 @@ extern "C" int bc_vi_optimize_begin(bc_ctx* ctx, const bc_data* data, const doub
   v->nrsel = nrsel;
   v->laid_out = true;
   v->scale = sum_scaling;
-  v->dev_ms = 0.;
-  v->d_w = v->dev + o_w;
-  v->d_step = v->dev + o_step;
-  v->d_mom1 = v->dev + o_m1;
-  v->d_mom2 = v->dev + o_m2;
-  v->d_grad = v->dev + o_g;
-  v->d_resid = v->dev + o_r;
-  v->d_trace = want_trace ? v->dev + o_tr : nullptr;
-  v->d_flag = reinterpret_cast<int*>(v->dev + o_flag);
+  v->clock.ms = 0.;
+  v->d_w = dev + o_w;
+  v->d_step = dev + o_step;
+  v->d_mom1 = dev + o_m1;
+  v->d_mom2 = dev + o_m2;
+  v->d_grad = dev + o_g;
+  v->d_resid = dev + o_r;
+  v->d_trace = want_trace ? dev + o_tr : nullptr;
+  v->d_flag = reinterpret_cast<int*>(dev + o_flag);
   v->active = true;
   v->chunk_pending = false;
   v->failed = false;
@@ -322,20 +286,20 @@ extern "C" int bc_vi_optimize_chunk_begin(bc_ctx* ctx, const double* normals, co
     }
   // ---- nothing of this chunk has been enqueued up to here
   BC_HIP(hipSetDevice(ctx->device));
-  const size_t need = even(n_e) + n_idx;
-  if (need > v->stage_cap) {
-    size_t c1 = v->stage_cap, c2 = v->stage_cap;
-    int rc = grow_dev(ctx, &v->stage_dev, &c1, need);
-    if (!rc) rc = grow_pin(ctx, &v->stage_pin, &c2, need);
-    if (rc) { v->stage_cap = 0; return rc; }
-    v->stage_cap = c1 < c2 ? c1 : c2;
-  }
-  memcpy(v->stage_pin, normals, n_e * sizeof(double));
-  long long* hidx = reinterpret_cast<long long*>(v->stage_pin + even(n_e));
+  bc_slab sl;
+  sl.take(n_e);
+  const size_t o_idx = sl.take_unpadded(n_idx), need = sl.total;      // (the indices are the last piece: not rounded)
+  int rc = bc_stage_reserve(ctx, &v->stage, need);
+  if (rc) return rc;
+  double* pin = v->stage.pin.p;
+  const double* stage_dev = v->stage.dev.p;
+  memcpy(pin, normals, n_e * sizeof(double));
+  long long* hidx = reinterpret_cast<long long*>(pin + o_idx);
   for (size_t j = 0; j < n_idx; ++j) hidx[j] = (long long)sub_idx[j];
-  BC_HIP(hipMemcpyAsync(v->stage_dev, v->stage_pin, need * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  const long long* didx = reinterpret_cast<const long long*>(v->stage_dev + even(n_e));
-  BC_HIP(hipEventRecord(v->ev[0], ctx->stream));
+  BC_HIP(hipMemcpyAsync(v->stage.dev.p, pin, need * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  const long long* didx = reinterpret_cast<const long long*>(stage_dev + o_idx);
+  rc = v->clock.start(ctx->stream);
+  if (rc) return rc;
   v->chunk_pending = true;      // from here on something is enqueued: _chunk_end must wait even if a launch below fails
   const double b1 = 0.9, b2 = 0.999, eps = 1e-8;
   const bool logistic = v->kind == BC_VI_SAMPLER_LOGISTIC;
@@ -345,27 +309,28 @@ extern "C" int bc_vi_optimize_chunk_begin(bc_ctx* ctx, const double* normals, co
     const int i = v->done + t;
     if (logistic) {
       VilArgs a = v->la;
-      a.E = v->stage_dev + (size_t)t * v->s * v->d;
+      a.E = stage_dev + (size_t)t * v->s * v->d;
       hipLaunchKernelGGL(k_vi_laplace, dim3(1), dim3(BC_VIL_BLOCK), lds, ctx->stream, a, v->d_flag, i);
     } else {
       VisArgs a = v->va;
-      a.E = v->stage_dev + (size_t)t * v->s * v->d;
+      a.E = stage_dev + (size_t)t * v->s * v->d;
       hipLaunchKernelGGL(k_vi_sampler, dim3(1), dim3(BC_VIS_BLOCK), lds, ctx->stream, a, v->d_flag, i);
     }
     BC_HIP(hipGetLastError());
     const bc_data* rows = v->data;
     if (n_sub > 0) {
-      int rc = bc_take_rows_dev(ctx, v->data, didx + (size_t)t * n_sub, n_sub, v->sub);
+      rc = bc_take_rows_dev(ctx, v->data, didx + (size_t)t * n_sub, n_sub, v->sub.p);
       if (rc) return rc;
       rows = &v->sub_view;
     }
-    int rc = bc_vi_plan_step(ctx, v->plan, &v->core_view, rows, v->d_w, v->scale, v->d_resid, v->d_grad);
+    rc = bc_vi_plan_step(ctx, v->plan, &v->core_view, rows, v->d_w, v->scale, v->d_resid, v->d_grad);
     if (rc) return rc;
     hipLaunchKernelGGL(k_vi_adam, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, v->d_flag, v->d_grad, v->d_w, v->d_mom1,
                        v->d_mom2, m, v->d_step, (int)v->itrs, i, b1, 1. - b1, b2, 1. - b2, eps, v->d_trace);
     BC_HIP(hipGetLastError());
   }
-  BC_HIP(hipEventRecord(v->ev[1], ctx->stream));
+  rc = v->clock.stop(ctx->stream);
+  if (rc) return rc;
   v->done += k;
   return BC_OK;
 }
@@ -375,11 +340,10 @@ extern "C" int bc_vi_optimize_chunk_end(bc_ctx* ctx) {
   if (!v || !v->active || !v->chunk_pending) { bc_set_error("bc_vi_optimize_chunk_end: no chunk is pending"); return BC_INVALID_ARGUMENT; }
   v->chunk_pending = false;
   BC_HIP(hipSetDevice(ctx->device));
-  int* hflag = reinterpret_cast<int*>(v->pin + v->pin_cap - 2);
+  int* hflag = reinterpret_cast<int*>(v->pin.p + v->pin.cap - 2);
   BC_HIP(hipMemcpyAsync(hflag, v->d_flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   BC_HIP(hipStreamSynchronize(ctx->stream));
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, v->ev[0], v->ev[1]) == hipSuccess) v->dev_ms += ms;
+  v->clock.collect();
   if (*hflag != 0) {
     v->failed = true;
     if (v->kind == BC_VI_SAMPLER_LOGISTIC)
@@ -409,11 +373,12 @@ extern "C" int bc_vi_optimize_end(bc_ctx* ctx, double* out_w, double* out_trace)
   }
   if (out_trace && !v->d_trace) { bc_set_error("bc_vi_optimize_end: the run was begun without a trace"); return BC_INVALID_ARGUMENT; }
   const size_t m = (size_t)v->m;
-  BC_HIP(hipMemcpyAsync(v->pin, v->d_w, m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (out_trace) BC_HIP(hipMemcpyAsync(v->pin + even(m), v->d_trace, (size_t)v->itrs * m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  double* down = v->pin.p;      // w | trace, as _begin sized it
+  BC_HIP(hipMemcpyAsync(down, v->d_w, m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (out_trace) BC_HIP(hipMemcpyAsync(down + bc_even(m), v->d_trace, (size_t)v->itrs * m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   BC_HIP(hipStreamSynchronize(ctx->stream));
-  memcpy(out_w, v->pin, m * sizeof(double));
-  if (out_trace) memcpy(out_trace, v->pin + even(m), (size_t)v->itrs * m * sizeof(double));
+  memcpy(out_w, down, m * sizeof(double));
+  if (out_trace) memcpy(out_trace, down + bc_even(m), (size_t)v->itrs * m * sizeof(double));
   return BC_OK;
 }
 
@@ -472,7 +437,7 @@ extern "C" int bc_vi_laplace_last_mode(bc_ctx* ctx, int32_t d, double* out_mu, i
 
 extern "C" int bc_vi_optimize_device_ms(bc_ctx* ctx, double* out_ms) {
   if (!ctx || !out_ms) { bc_set_error("bc_vi_optimize_device_ms: bad argument"); return BC_INVALID_ARGUMENT; }
-  *out_ms = ctx->viopt ? ctx->viopt->dev_ms : 0.;
+  *out_ms = ctx->viopt ? ctx->viopt->clock.ms : 0.;
   return BC_OK;
 }
 
@@ -502,11 +467,6 @@ extern "C" int bc_vi_optimize(bc_ctx* ctx, const bc_data* data, const double* co
       if (!rc) rc = rc2;
     }
   }
-  if (rc) {
-    const std::string msg = bc_last_error();      // (closing the run must not replace the message of what failed)
-    (void)bc_vi_optimize_end(ctx, nullptr, nullptr);
-    bc_set_error("%s", msg.c_str());
-    return rc;
-  }
+  if (rc) return bc_close_failed_run(rc, [&] { return bc_vi_optimize_end(ctx, nullptr, nullptr); });
   return bc_vi_optimize_end(ctx, out_w, out_trace);
 }

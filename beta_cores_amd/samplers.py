@@ -465,7 +465,6 @@ def logistic_hmc(Z, wts=None, n_samples=1000, n_chains=16, step_size=0.1, n_leap
         if wts.shape != (n,):
             raise ValueError('wts must have one weight per row of Z (%d), got shape %r' % (n, wts.shape))
     randn = np.random.randn if rng is None else rng.randn
-    rand = np.random.rand if rng is None else rng.rand
     mode = None
     if start is None or (isinstance(inv_mass, str) and inv_mass == 'laplace'):
         if engine is not None:
@@ -488,29 +487,12 @@ def logistic_hmc(Z, wts=None, n_samples=1000, n_chains=16, step_size=0.1, n_leap
         chunk = eng.auto_chunk(c, d)
     if chunk < 1:
         raise ValueError('chunk must be >= 1')
-    step = float(step_size)
-    warm_steps = []
-    out_s, out_l, out_a = np.empty((n_samples, c, d)), np.empty((n_samples, c)), np.empty((n_samples, c), dtype=bool)
-    eng.begin(start, inv_mass, int(n_leapfrog), int(warmup) + int(n_samples))
-    try:
-        left = int(warmup)
-        while left > 0:
-            k = min(left, int(adapt_every))
-            e, u = randn(k, c, d), np.log(rand(k, c))
-            _, _, acc = eng.chunk(np.ascontiguousarray(e), np.ascontiguousarray(u), step)
-            warm_steps.append(step)
-            step = hmc_warmup_step(step, float(np.mean(acc != 0)), adapt_rate)
-            left -= k
-        i0 = 0
-        while i0 < n_samples:
-            k = min(n_samples - i0, int(chunk))
-            e, u = randn(k, c, d), np.log(rand(k, c))
-            s, lj, acc = eng.chunk(np.ascontiguousarray(e), np.ascontiguousarray(u), step)
-            out_s[i0:i0 + k], out_l[i0:i0 + k], out_a[i0:i0 + k] = s, lj, acc != 0
-            i0 += k
-    finally:
-        ms = eng.end()
-    return HMCResult(out_s, out_l, out_a, step, np.array(warm_steps), start, inv_mass, ms)
+    # the loop is _run_hmc_group's, for a batch of one on shared draws; a start that is not finite raises from the engine's chunk
+    res, _, ms = _run_hmc_group(_SingleAsBatch(eng, swallow=False), [0], start[None], inv_mass[None], [float(step_size)],
+                                _ManyDraws(rng, True, 1, c, d, keep=False), c, d, int(n_samples), n_leapfrog, warmup, adapt_every,
+                                adapt_rate, chunk)
+    out_s, out_l, out_a, step, warm_steps = res[0]
+    return HMCResult(out_s, out_l, out_a, step, warm_steps, start, inv_mass, ms)
 
 
 # ---- the same for MANY small problems at once: the weighted coresets of an evaluation curve (include/beta_cores_hmc_small.h)
@@ -526,10 +508,12 @@ class HMCManyResult(list):
 
 
 class _SingleAsBatch:
-    """One logistic_hmc engine (begin / auto_chunk / chunk / end) behind the batched protocol of _run_hmc_group, as a batch of one."""
+    """One logistic_hmc engine (begin / auto_chunk / chunk / end) behind the batched protocol of _run_hmc_group, as a batch of one.
+    swallow: a NumericalPrecisionError of the engine's chunk becomes the problem's status (logistic_hmc_many's marked problems);
+    False lets it through as it is (logistic_hmc)."""
 
-    def __init__(self, eng):
-        self.eng = eng
+    def __init__(self, eng, swallow=True):
+        self.eng, self.swallow = eng, swallow
 
     def begin(self, starts, inv_mass, n_leapfrog, n_iter):
         self.eng.begin(np.ascontiguousarray(starts[0]), np.ascontiguousarray(inv_mass[0]), n_leapfrog, n_iter)
@@ -542,6 +526,8 @@ class _SingleAsBatch:
         try:
             s, lj, acc = self.eng.chunk(np.ascontiguousarray(e), np.ascontiguousarray(u), float(steps[0]))
         except N.NumericalPrecisionError:
+            if not self.swallow:
+                raise
             return None, None, None, np.array([N.BC_NUMERICAL_PRECISION], dtype=np.int32)
         return s[None], lj[None], acc[None], np.zeros(1, dtype=np.int32)
 
@@ -611,8 +597,8 @@ class _ManyDraws:
 
 
 def _run_hmc_group(eng, idx, starts, ims, steps0, draws, c, d, n_samples, n_leapfrog, warmup, adapt_every, adapt_rate, chunk):
-    """logistic_hmc's loop -- warm-up chunks with hmc_warmup_step per problem, then the kept chunks at frozen steps -- for the
-    problems `idx` of one engine.  Returns ({p: (samples, logjoint, accept, step, warm_steps)}, marked indices, device ms)."""
+    """The loop of logistic_hmc and logistic_hmc_many -- warm-up chunks with hmc_warmup_step per problem, then the kept chunks at
+    frozen steps -- for the problems `idx` of one engine.  Returns ({p: (samples, logjoint, accept, step, warm_steps)}, marked indices, device ms)."""
     G = len(idx)
     step = [float(steps0[p]) for p in idx]
     warm = [[] for _ in idx]

@@ -39,7 +39,8 @@ extern "C" {
 /* The rows pass on its own, prior included: out_value[c] = logjoint(theta_c), out_grad[c] = its gradient, c < C.
  *   data: rows z = y * x, float64 or float32.   w: n x 1 float64 rows, or NULL (all ones).   theta: host, C x D.
  *   out_value: C, or NULL: the gradient-only pass the inner leapfrog steps run (no log1p per element).
- * Refused while an HMC run is open on the context. */
+ * Refused while a run of this header or of beta_cores_hmc_small.h is open on the context; a pending fused gradient and an open
+ * weight-optimisation run do not refuse it. */
 int bc_logistic_logjoint_batch(bc_ctx* ctx, const bc_data* data, const bc_data* w, const double* theta, int32_t c,
                                double* out_value, double* out_grad);
 
@@ -63,7 +64,9 @@ int bc_hmc_auto_chunk(int32_t c, int32_t d);
  * every later kernel of the run returns at once, _chunk_end returns BC_NUMERICAL_PRECISION and copies nothing.
  * _end closes the run; call it after a failure too.
  * A run cannot begin while a fused gradient (any kind: the _gradient_begin / _end pairs) is pending or a weight-optimisation run
- * (beta_cores_viopt.h) is open on the context, and those cannot begin while an HMC run is open: BC_INVALID_ARGUMENT. */
+ * (beta_cores_viopt.h), another run of this header or a run of beta_cores_hmc_small.h is open on the context, and none of those
+ * can begin while an HMC run is open: BC_INVALID_ARGUMENT.  (The whole table -- who is refused while what is held -- is beside
+ * bc_ctx_refuse_busy in csrc/bc_core.hip.) */
 int bc_hmc_begin(bc_ctx* ctx, const bc_data* data, const bc_data* w, const double* start, int32_t c, const double* inv_mass,
                  int32_t n_leapfrog, int64_t n_iter);
 int bc_hmc_chunk_begin(bc_ctx* ctx, const double* normals, const double* log_u, int32_t k, double step_size);

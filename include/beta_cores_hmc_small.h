@@ -44,7 +44,8 @@ int bc_hmc_small_fits(bc_ctx* ctx, int64_t n, int32_t d);
 
 /* The in-LDS pass on its own, prior included: out_value[p][c] = logjoint_p(theta[p][c]), out_grad[p][c] = its gradient.
  *   theta: host, P x C x D.   out_value: P x C, or NULL: the gradient-only pass of the inner leapfrog steps (no log1p).
- *   out_grad: P x C x D.   Refused while a run of any kind is open on the context. */
+ *   out_grad: P x C x D.   Refused, as _begin is, while a fused gradient is pending or a run of any
+ *   kind (weight optimisation, beta_cores_hmc.h, this header) is open on the context. */
 int bc_hmc_small_logjoint(bc_ctx* ctx, const double* rows, const double* w, const int64_t* row_ptr, int32_t n_problems, int32_t d,
                           const double* theta, int32_t c, double* out_value, double* out_grad);
 
@@ -66,7 +67,8 @@ int bc_hmc_small_logjoint(bc_ctx* ctx, const double* rows, const double* w, cons
  * out_status = BC_OK.  _chunk_end returns BC_OK whenever the call itself worked.
  * _end closes the run; call it after a failure too.
  * A run cannot begin while a fused gradient is pending, or a weight-optimisation run (beta_cores_viopt.h) or a run of
- * beta_cores_hmc.h is open on the context, and none of those can begin while a run of this header is open. */
+ * beta_cores_hmc.h or of this header is open on the context, and none of those (nor bc_logistic_logjoint_batch) can begin while
+ * a run of this header is open.  (The whole table is beside bc_ctx_refuse_busy in csrc/bc_core.hip.) */
 int bc_hmc_small_begin(bc_ctx* ctx, const double* rows, const double* w, const int64_t* row_ptr, int32_t n_problems, int32_t d,
                        const double* start, int32_t c, const double* inv_mass, int32_t n_leapfrog, int64_t n_iter);
 int bc_hmc_small_chunk_begin(bc_ctx* ctx, const double* normals, const double* log_u, int64_t problem_stride, int32_t k,
