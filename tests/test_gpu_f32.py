@@ -113,7 +113,7 @@ def assert_same(got, want, what, equal_nan=False):
 
 # ------------------------------------------------------------------ K1
 @pytest.mark.parametrize('n,dz,s', [(1, 3, 5), (127, 7, 16), (129, 33, 97), (5000, 129, 100), (129, 7, 112), (127, 33, 300),
-                                    (5000, 3, 100), (129, 129, 16), (1, 129, 100), (127, 3, 300)])
+                                    (5000, 3, 100), (129, 129, 16), (1, 129, 100), (127, 3, 300), (129, 17, 200), (127, 9, 256)])
 def test_k1_is_bit_identical_on_float32_rows(bc, n, dz, s):
     """All seven model ids, odd row widths, ragged row counts, every sample-tile variant of the staged kernel and the
     multi-pass mode of S > 256: float32 rows against the same rows widened on the host."""
