@@ -211,6 +211,14 @@ _HMC_SMALL_SIGNATURES = {
 }
 HMC_SMALL_EXPORTS = sorted(_HMC_SMALL_SIGNATURES)
 
+# entry points of the extension header include/beta_cores_prefdiag.h (test aids: the pre-filter's mirrors and per-row bounds)
+_PREFDIAG_SIGNATURES = {
+    'bc_snnls_prefdiag_info': [vp, c_i64p],
+    'bc_snnls_prefdiag_copy': [vp, C.c_char_p, vp, C.c_int64, c_i64p],
+    'bc_snnls_prefdiag_sweep': [vp, C.c_int32, vp, C.c_double, C.c_int32, vp, vp, vp, C.c_int64, C.c_int32, c_i32p],
+}
+PREFDIAG_EXPORTS = sorted(_PREFDIAG_SIGNATURES)
+
 _lib = None
 
 
@@ -245,7 +253,7 @@ def load():
     for name, argtypes in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_F32_SIGNATURES.items()) + list(_NNLS_SIGNATURES.items()) \
             + list(_TAKE_SIGNATURES.items()) + list(_BETAGRAD_SIGNATURES.items()) + list(_ENCODE_SIGNATURES.items()) \
             + list(_VIOPT_SIGNATURES.items()) + list(_PSVI_SIGNATURES.items()) + list(_VILAPLACE_SIGNATURES.items()) \
-            + list(_HMC_SIGNATURES.items()) + list(_HMC_SMALL_SIGNATURES.items()):
+            + list(_HMC_SIGNATURES.items()) + list(_HMC_SMALL_SIGNATURES.items()) + list(_PREFDIAG_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int

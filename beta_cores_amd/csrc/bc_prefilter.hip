@@ -27,6 +27,7 @@
 // FMA) and double-buffers its loads in registers; its planes are padded with zeros to a multiple of BC_HU and
 // the sweep vectors carry a zero tail (BC_V_PAD, bc_snnls.hip), so there is no remainder loop.
 #include "bc_rescore_dev.h"
+#include "../../include/beta_cores_prefdiag.h"
 #include <cstdlib>
 #include <cstring>
 
@@ -753,4 +754,149 @@ int bc_pref_launch(bc_pref* p, int mode, const double* v_dev, const double* v_no
   else hipLaunchKernelGGL(k_rescore<1>, dim3(1), dim3(BC_RESCORE_THREADS), 0, p->ctx->stream, r, (long long)p->phi->n_rows);
   BC_HIP(hipGetLastError());
   return bc_timer_end(p->ctx, 3);
+}
+
+// ------------------------------------------------------------------ diagnostic seam (include/beta_cores_prefdiag.h)
+// Test aids: nothing below is called by the product.  bc_snnls.hip owns the entry points and the solver's side of them.
+void bc_pref_diag_info(const bc_pref* p, bool qv_set, int64_t* out) {
+  out[BC_PREFDIAG_PREC] = p->prec;
+  out[BC_PREFDIAG_PTILE] = p->ptile;
+  out[BC_PREFDIAG_PTILES] = p->ptiles;
+  out[BC_PREFDIAG_SP] = p->sp;
+  out[BC_PREFDIAG_SP4] = p->sp4;
+  out[BC_PREFDIAG_SP8] = p->sp8;
+  out[BC_PREFDIAG_G4] = p->g4;
+  out[BC_PREFDIAG_RB] = p->rb;
+  out[BC_PREFDIAG_I4_U] = p->two ? p->i4_u : 0;
+  out[BC_PREFDIAG_GRID] = p->grid;
+  out[BC_PREFDIAG_GRID1] = p->two ? p->grid1 : 0;
+  out[BC_PREFDIAG_TWO] = p->two ? 1 : 0;
+  out[BC_PREFDIAG_TWO_ACTIVE] = (p->two && p->two_active) ? 1 : 0;
+  out[BC_PREFDIAG_IFLUSH] = BC_IFLUSH;
+  out[BC_PREFDIAG_BLK_NC] = BC_BLK_NC;
+  out[BC_PREFDIAG_NEXT_FORM] = p->bb ? 2 : ((p->two && p->two_active && p->qv && p->qv4 && p->sweeps_launched > 0) ? 3 : 1);
+  out[BC_PREFDIAG_QV] = (qv_set && p->qv) ? 1 : 0;
+  out[BC_PREFDIAG_SEEDS] = BC_I4_SEEDS;
+  out[BC_PREFDIAG_HOT] = BC_I4_HOT;
+  out[BC_PREFDIAG_SPILL_CAP] = 4096;
+}
+
+// 0: found (*dev, *bytes); 1: no such name; 2: this form of the pre-filter has no such buffer
+int bc_pref_diag_buffer(const bc_pref* p, const char* which, const void** dev, size_t* bytes) {
+  const size_t rows = (size_t)p->ptiles * p->ptile;
+  struct Ent { const char* name; const void* ptr; size_t bytes; };
+  const Ent tab[] = {
+      {"u32", p->u32, (size_t)p->ptiles * p->sp * BC_PTILE * sizeof(float)},
+      {"u16", p->u16, (size_t)p->ptiles * p->sp * BC_HTILE * sizeof(_Float16)},
+      {"live", p->live, (size_t)p->ptiles * 64},
+      {"u8", p->u8, bc_lay_i8_words(p->ptiles, p->sp4) * sizeof(int)},
+      {"rowq", p->rowq, rows * sizeof(bc_hq2)},
+      {"u4", p->u4, bc_lay_i4_words(p->ptiles, p->sp8) * sizeof(int)},
+      {"rowq4", p->rowq4, rows * sizeof(unsigned short)},
+      {"r8", p->r8, rows * (size_t)p->rb},
+      {"ub", p->ub, rows * sizeof(float)},
+      {"tile_u", p->tile_u, (size_t)p->ptiles * sizeof(float)},
+      {"tile_cand", p->tile_cand, (size_t)p->ptiles * 4 * sizeof(float2)},
+      {"tile_ncand", p->tile_ncand, (size_t)p->ptiles * sizeof(int)},
+      {"blk_l", p->blk_l, (size_t)p->grid * sizeof(double)},
+      {"blk_u", p->blk_u, (size_t)p->grid * sizeof(float)},
+      {"l2_blk_l", p->l2_blk_l, (size_t)p->grid1 * sizeof(double)},
+      {"l2_blk_u", p->l2_blk_u, (size_t)p->grid1 * sizeof(float)},
+      {"l2_blk_cand", p->l2_blk_cand, (size_t)p->grid1 * BC_BLK_NC * sizeof(int2)},
+      {"l2_blk_nc", p->l2_blk_nc, (size_t)p->grid1 * sizeof(int)},
+      {"spill", p->spill, (size_t)4096 * sizeof(int2)},
+      {"hot", p->hot, (size_t)(BC_I4_SEEDS + BC_I4_HOT) * sizeof(long long)},
+      {"ctrl", p->ctrl, 256},
+  };
+  for (const Ent& e : tab)
+    if (strcmp(which, e.name) == 0) {
+      if (!e.ptr) return 2;
+      *dev = e.ptr;
+      *bytes = e.bytes;
+      return 0;
+    }
+  return 1;
+}
+
+// bytes of device scratch bc_pref_diag_sweep needs to put the seeds and the control block aside
+size_t bc_pref_diag_save_bytes(void) { return (BC_I4_SEEDS + BC_I4_HOT) * sizeof(long long) + 256; }
+
+// One sweep of the form the next production sweep would take (two-level, else the one-level int8 sweep) through the DUMP
+// instances of the sweep kernels: no rescoring, no skip flag, none of the host-side counters touched; the seeds and the control
+// block are put aside in `save_dev` and restored.  qv / qv4: the digit records to sweep with (qv == nullptr: the int8 sweep
+// quantises v in its prologue).  *form_run = 3 / 1.
+int bc_pref_diag_sweep(bc_pref* p, int mode, const double* v_dev, const double* v_norm_dev, const int* qv, const int* qv4,
+                       double post_div, float2* dump1, float2* dump2, float* theta0, void* save_dev, int* form_run) {
+  bc_ctx* ctx = p->ctx;
+  bc_phi* phi = p->phi;
+  const bool two = p->two && p->two_active && qv != nullptr && qv4 != nullptr && p->sweeps_launched > 0;
+  *form_run = two ? 3 : 1;
+  if (two) {
+    const size_t hot_bytes = (BC_I4_SEEDS + BC_I4_HOT) * sizeof(long long);
+    BC_HIP(hipMemcpyAsync(save_dev, p->hot, hot_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    BC_HIP(hipMemcpyAsync((char*)save_dev + hot_bytes, p->ctrl, 256, hipMemcpyDeviceToDevice, ctx->stream));
+    BC_HIP(hipMemsetAsync(dump2, 0xff, (size_t)p->ptiles * BC_ITILE * sizeof(float2), ctx->stream));      // NaN: not re-bounded
+    I4DumpArgs fa;
+    fa.u4 = p->u4;
+    fa.rowq4 = p->rowq4;
+    fa.qv4 = qv4;
+    fa.qv8 = qv;
+    fa.r8 = p->r8;
+    fa.hot = p->hot;
+    fa.skip_flag = nullptr;
+    fa.blk_l = p->l2_blk_l;
+    fa.blk_u = p->l2_blk_u;
+    fa.blk_cand = p->l2_blk_cand;
+    fa.blk_nc = p->l2_blk_nc;
+    fa.ctrl = p->ctrl;
+    fa.spill = p->spill;
+    fa.spill_cap = 4096;
+    fa.ptiles = p->ptiles;
+    fa.post_div = post_div;
+    fa.s = phi->s;
+    fa.sp8 = p->sp8;
+    fa.sp4 = p->sp4;
+    fa.g4 = p->g4;
+    fa.rb = p->rb;
+    fa.dump1 = dump1;
+    fa.dump2 = dump2;
+    fa.theta0 = theta0;
+#define BC_I4_DUMP(MODE, UU) hipLaunchKernelGGL((k_sweep_i4<MODE, UU, true>), dim3(p->grid1), dim3(256), 0, ctx->stream, fa)
+#define BC_I4_DUMP_BY_U(MODE)                                                                     \
+    switch (p->i4_u) {                                                                            \
+      case 13: BC_I4_DUMP(MODE, 13); break;                                                       \
+      case 8: BC_I4_DUMP(MODE, 8); break;                                                         \
+      case 7: BC_I4_DUMP(MODE, 7); break;                                                         \
+      case 6: BC_I4_DUMP(MODE, 6); break;                                                         \
+      default: BC_I4_DUMP(MODE, 5); break;                                                        \
+    }
+    if (mode == 0) { BC_I4_DUMP_BY_U(0) } else { BC_I4_DUMP_BY_U(1) }
+    BC_HIP(hipGetLastError());
+    BC_HIP(hipMemcpyAsync(p->hot, save_dev, hot_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    BC_HIP(hipMemcpyAsync(p->ctrl, (char*)save_dev + hot_bytes, 256, hipMemcpyDeviceToDevice, ctx->stream));
+    return BC_OK;
+  }
+  I8DumpArgs ia;
+  ia.u8 = p->u8;
+  ia.rowq = p->rowq;
+  ia.v = v_dev;
+  ia.qv = qv;
+  ia.skip_flag = nullptr;
+  ia.v_norm = v_norm_dev;
+  ia.tile_u = p->tile_u;
+  ia.tile_cand = p->tile_cand;
+  ia.tile_ncand = p->tile_ncand;
+  ia.blk_l = p->blk_l;
+  ia.blk_u = p->blk_u;
+  ia.blk_cand = p->blk_cand;
+  ia.blk_nc = p->blk_nc;
+  ia.ptiles = p->ptiles;
+  ia.post_div = post_div;
+  ia.s = phi->s;
+  ia.sp4 = p->sp4;
+  ia.dump = dump1;
+  if (mode == 0) hipLaunchKernelGGL((k_sweep_i8<0, true>), dim3(p->grid), dim3(256), 0, ctx->stream, ia);
+  else hipLaunchKernelGGL((k_sweep_i8<1, true>), dim3(p->grid), dim3(256), 0, ctx->stream, ia);
+  BC_HIP(hipGetLastError());
+  return BC_OK;
 }

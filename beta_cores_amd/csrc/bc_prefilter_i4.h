@@ -27,6 +27,7 @@
 // Bytes per row and sweep: 4 * SP8 + 2 (S = 100: 54 against the int8 mirror's 104).
 #pragma once
 
+#include <type_traits>
 #include "bc_layout.h"
 #include "bc_i4_quant.h"
 #include "bc_i8_quant.h"
@@ -59,6 +60,13 @@ struct I4Args {
   long long ptiles;
   double post_div;
   int s, sp8, sp4, g4, rb;       // sp4: k-groups of the int8 digit record; g4 = ceil(S / 4); rb: bytes of an int8 record
+};
+
+// the diagnostic instance's arguments (DUMP = true, include/beta_cores_prefdiag.h): the production block and three outputs behind it
+struct I4DumpArgs : I4Args {
+  float2* dump1;                 // [ptiles*256] level 1's (U, L) of every row
+  float2* dump2;                 // [ptiles*256] level 2's (U8, L8) of the rows it re-bounded (the caller fills the rest)
+  float* theta0;                 // [grid] the seeds' bound as the block evaluated it
 };
 
 __device__ __forceinline__ int bc_f32_ord(float f) {        // order-preserving map float -> int (for LDS atomicMax)
@@ -241,8 +249,10 @@ extern "C" int bc_debug_i4_stamps(unsigned long long* out) {
 #endif
 
 // ------------------------------------------------------------------ levels 1 + 2
-template <int MODE, int U>
-__global__ __launch_bounds__(256) void k_sweep_i4(I4Args a) {
+// DUMP: the test aid of include/beta_cores_prefdiag.h -- the same kernel also stores both levels' per-row intervals and theta0.
+// The solver launches the DUMP = false instances only, whose code the switch leaves as it was (profiles/pref_bounds_notes.md).
+template <int MODE, int U, bool DUMP = false>
+__global__ __launch_bounds__(256) void k_sweep_i4(typename std::conditional<DUMP, I4DumpArgs, I4Args>::type a) {
   constexpr int NV = (MODE == 0) ? 4 : 2;           // (vector, digit): v0 d0, v0 d1 [, v1 d0, v1 d1]
   __shared__ __attribute__((aligned(16))) int dig4[BC_I4_MAXG][4];
   __shared__ __attribute__((aligned(16))) int dig8[BC_I4_MAXG8][4];
@@ -320,6 +330,9 @@ __global__ __launch_bounds__(256) void k_sweep_i4(I4Args a) {
   }
   __syncthreads();
   const float theta0 = fmaxf(fmaxf(sl[0], sl[1]), fmaxf(sl[2], sl[3]));
+  if constexpr (DUMP) {
+    if (threadIdx.x == 0) a.theta0[blockIdx.x] = theta0;
+  }
   I4STAMP(1);
 
   float wave_l = -INFINITY;                            // best 4-bit lower bound of the tiles this wave has finished
@@ -333,6 +346,7 @@ __global__ __launch_bounds__(256) void k_sweep_i4(I4Args a) {
         const int row = park[wave][base + lane];
         float U8, L8;
         bc_r8_interval<MODE>(a.r8 + (size_t)row * a.rb, dig8, hdr8, a.g4, a.rb, fpd, U8, L8);
+        if constexpr (DUMP) a.dump2[row] = make_float2(U8, L8);
         if (U8 != -INFINITY) {                         // (a dead row cannot have been passed on; kept for symmetry)
           // key: the lower bound in an unsigned order (-inf -> 0x007fffff > 0: an all-uncertain block still names a row)
           const unsigned long long key = ((unsigned long long)((unsigned)bc_f32_ord(L8) ^ 0x80000000u) << 32) | (unsigned)row;
@@ -375,6 +389,7 @@ __global__ __launch_bounds__(256) void k_sweep_i4(I4Args a) {
       Uj = dead ? -INFINITY : (unc ? INFINITY : Uj);
       Lj = (dead || unc) ? -INFINITY : Lj;
       Ub[j] = Uj;
+      if constexpr (DUMP) a.dump1[tt * BC_ITILE + 4 * lane + j] = make_float2(Uj, Lj);
       tl = fmaxf(tl, Lj);
       any |= Uj >= theta;                              // (-inf >= theta only when theta is -inf: filtered below)
     }

@@ -27,6 +27,7 @@
 // a tile with more than four such rows hands over all of its rows.
 #pragma once
 
+#include <type_traits>
 #include "bc_layout.h"
 #include "bc_i8_quant.h"
 #define BC_ITILE 256      /* == BC_LAY_ITILE (bc_layout.h) */
@@ -60,6 +61,10 @@ struct I8Args {
   int s, sp4;
 };
 #define BC_BLK_NC 8
+// the diagnostic instance's arguments (DUMP = true, include/beta_cores_prefdiag.h): the production block and one output behind it
+struct I8DumpArgs : I8Args {
+  float2* dump;             // [ptiles*256] (U, L) of every row, as the sweep evaluated them
+};
 
 // The interval of bc_score_interval evaluated in fp32.  The int8 mirror's delta is ~1e-2, five orders of magnitude
 // above fp32 rounding, so single precision costs nothing in selectivity; every fp32 evaluation error is covered
@@ -240,8 +245,10 @@ __global__ __launch_bounds__(256) void k_build_i8_r(const double* __restrict__ t
   rowq[r] = rq;
 }
 
-template <int MODE>
-__global__ __launch_bounds__(256) void k_sweep_i8(I8Args a) {
+// DUMP: the test aid of include/beta_cores_prefdiag.h -- the same kernel also stores every row's (U, L).  The solver launches the
+// DUMP = false instances only, whose code the switch leaves as it was (profiles/pref_bounds_notes.md).
+template <int MODE, bool DUMP = false>
+__global__ __launch_bounds__(256) void k_sweep_i8(typename std::conditional<DUMP, I8DumpArgs, I8Args>::type a) {
   constexpr int NV = (MODE == 0) ? 3 : 2;           // (vector, digit) combinations: v0 d0, v0 d1 [, v1 single digit]
   __shared__ __attribute__((aligned(16))) int dig[BC_IMAXG][4];   // packed digits of k-group g: [v0 d0, v0 d1, v1 d, 0]
   __shared__ double vmx[2][4];
@@ -417,6 +424,10 @@ __global__ __launch_bounds__(256) void k_sweep_i8(I8Args a) {
           tl = fmaxf(tl, Lb[j]);
           tmax = fmaxf(tmax, Ub[j]);
         }
+      }
+      if constexpr (DUMP) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) a.dump[t * BC_ITILE + 4 * lane + j] = make_float2(Ub[j], Lb[j]);
       }
       tl = bc_wave_max_f32_all(tl);                    // (DPP row rotations + v_readlane: the ds_bpermute tree of
       tmax = bc_wave_max_f32_all(tmax);                //  __shfl_xor was a dozen dependent LDS round trips per tile)

@@ -25,7 +25,8 @@ def zero(t):
 
 
 swept = 0
-for name, argtypes in sorted(N._SIGNATURES.items()):
+# (and the test aids of include/beta_cores_prefdiag.h, which take a solver handle like the diagnostics beside them)
+for name, argtypes in sorted(list(N._SIGNATURES.items()) + list(N._PREFDIAG_SIGNATURES.items())):
     fn = getattr(lib, name)
     rc = fn(*[zero(t) for t in argtypes])
     if rc == 0 and name not in MAY_SUCCEED:
