@@ -21,10 +21,11 @@ from .coreset import (Coreset, HilbertCoreset, BetaCoreset, SparseVICoreset, Bat
 from . import likelihoods
 from . import samplers
 from . import encoders
+from . import valuation
 from .posterior import weighted_gram, weighted_post, weighted_post_corrected, gaussian_weighted_post, logistic_newton_pass
 from .dist import ShardComm, shard_bounds
 
-__all__ = ['util', 'snnls', 'likelihoods', 'samplers', 'encoders', 'NumericalPrecisionError', 'Context', 'DeviceData', 'DevicePhi',
+__all__ = ['util', 'snnls', 'likelihoods', 'samplers', 'encoders', 'valuation', 'NumericalPrecisionError', 'Context', 'DeviceData', 'DevicePhi',
            'default_context', 'set_default_context', 'Coreset', 'HilbertCoreset', 'BetaCoreset', 'SparseVICoreset',
            'BatchPSVICoreset', 'UniformSamplingCoreset',
            'Projector', 'BlackBoxProjector', 'BetaBlackBoxProjector', 'DeviceProjector', 'DeviceBetaProjector',

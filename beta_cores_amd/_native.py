@@ -211,6 +211,14 @@ _HMC_SMALL_SIGNATURES = {
 }
 HMC_SMALL_EXPORTS = sorted(_HMC_SMALL_SIGNATURES)
 
+# entry points of the extension header include/beta_cores_score.h (held-out accuracy counts and log-likelihoods of many thetas at once)
+_SCORE_SIGNATURES = {
+    'bc_lr_score': [vp, vp, vp, vp, C.c_int64, vp, vp],
+    'bc_score_chunk': [vp, vp, vp],
+    'bc_score_chunk_end': [vp, vp, vp, vp, vp, vp, vp],
+}
+SCORE_EXPORTS = sorted(_SCORE_SIGNATURES)
+
 # entry points of the extension header include/beta_cores_prefdiag.h (test aids: the pre-filter's mirrors and per-row bounds)
 _PREFDIAG_SIGNATURES = {
     'bc_snnls_prefdiag_info': [vp, c_i64p],
@@ -253,7 +261,8 @@ def load():
     for name, argtypes in list(_SIGNATURES.items()) + list(_EXT_SIGNATURES.items()) + list(_F32_SIGNATURES.items()) + list(_NNLS_SIGNATURES.items()) \
             + list(_TAKE_SIGNATURES.items()) + list(_BETAGRAD_SIGNATURES.items()) + list(_ENCODE_SIGNATURES.items()) \
             + list(_VIOPT_SIGNATURES.items()) + list(_PSVI_SIGNATURES.items()) + list(_VILAPLACE_SIGNATURES.items()) \
-            + list(_HMC_SIGNATURES.items()) + list(_HMC_SMALL_SIGNATURES.items()) + list(_PREFDIAG_SIGNATURES.items()):
+            + list(_HMC_SIGNATURES.items()) + list(_HMC_SMALL_SIGNATURES.items()) + list(_SCORE_SIGNATURES.items()) \
+            + list(_PREFDIAG_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int

@@ -124,6 +124,7 @@ const char* bc_vi_kind_name(int kind) {
 //   bc_hmc_begin                                                             refuse   refuse   refuse   refuse
 //   bc_logistic_logjoint_batch                                               allow    allow    refuse   refuse
 //   bc_hmc_small_begin, bc_hmc_small_logjoint                                refuse   refuse   refuse   refuse
+//   bc_lr_score                                                              allow    allow    refuse   refuse
 //
 // An entrant passes the holders of its row that refuse it; they are looked at in the order G, V, H, S, and the first one found
 // is named.  Nothing is enqueued, allocated or changed by a refusal.
@@ -176,6 +177,7 @@ extern "C" int bc_ctx_destroy(bc_ctx* ctx) {
   bc_viopt_free(ctx);
   bc_hmc_free(ctx);
   bc_hmc_small_free(ctx);
+  bc_scratch_free(&ctx->score);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
   return BC_OK;

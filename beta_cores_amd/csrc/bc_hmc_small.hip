@@ -31,6 +31,7 @@
 #include "bc_hmc_small_dev.h"
 #include "bc_slab.h"
 #include "../../include/beta_cores_hmc_small.h"
+#include "../../include/beta_cores_score.h"
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -151,8 +152,10 @@ struct bc_hmc_small {
   bc_scratch state;               // theta | g | lj | inverse masses | flags (ints)
   bc_stage stage;                 // a chunk's draws and steps: normals | log-uniforms | step [P]
   bc_scratch out;                 // a chunk's results: samples | log-joints | accept flags (ints)
+  bc_scratch score;               // a chunk's held-out scores (bc_score_chunk): ll [P k C] | correct [P k C] (ints)
   bc_run_clock clock;
   bool active = false, chunk_pending = false;
+  bool scored = false;            // bc_score_chunk has enqueued the pending chunk's scores
   SmArgs a;
   size_t lds = 0;
   int cpb = 1;                    // chains per block of the run's launches
@@ -170,6 +173,7 @@ void bc_hmc_small_free(bc_ctx* ctx) {
   bc_scratch_free(&h->state);
   bc_stage_free(&h->stage);
   bc_scratch_free(&h->out);
+  bc_scratch_free(&h->score);
   h->clock.free();
   delete h;
   ctx->hmc_small = nullptr;
@@ -413,6 +417,7 @@ extern "C" int bc_hmc_small_chunk_begin(bc_ctx* ctx, const double* normals, cons
   memcpy(pin + o_st, step, P * sizeof(double));
   BC_HIP(hipMemcpyAsync(h->stage.dev.p, pin, need * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   h->chunk_pending = true;      // from here on something is enqueued: _chunk_end must wait even if the launch below fails
+  h->scored = false;
   h->pending_k = k;
   SmArgs a = h->a;
   a.mode = BC_SM_CHUNK;
@@ -433,12 +438,11 @@ extern "C" int bc_hmc_small_chunk_begin(bc_ctx* ctx, const double* normals, cons
   return BC_OK;
 }
 
-extern "C" int bc_hmc_small_chunk_end(bc_ctx* ctx, double* out_samples, double* out_logjoint, int32_t* out_accept, int32_t* out_status) {
-  bc_hmc_small* h = ctx ? ctx->hmc_small : nullptr;
-  if (!h || !h->active || !h->chunk_pending) { bc_set_error("bc_hmc_small_chunk_end: no chunk is pending"); return BC_INVALID_ARGUMENT; }
-  // (checked first: the chunk stays pending, a second call with the outputs can still fetch it)
-  if (!out_samples || !out_logjoint || !out_accept || !out_status) { bc_set_error("bc_hmc_small_chunk_end: the four outputs are required"); return BC_INVALID_ARGUMENT; }
+// the chunk end behind both headers.  out_samples may be null only for `who` = bc_score_chunk_end; out_correct / out_ll: both or neither
+static int chunk_end(bc_ctx* ctx, bc_hmc_small* h, double* out_samples, double* out_logjoint, int32_t* out_accept, int32_t* out_status,
+                     int32_t* out_correct, double* out_ll) {
   h->chunk_pending = false;
+  h->scored = false;
   BC_HIP(hipSetDevice(ctx->device));
   BC_HIP(hipStreamSynchronize(ctx->stream));
   const size_t P = (size_t)h->n_problems, c = (size_t)h->a.c, d = (size_t)h->a.d;
@@ -447,6 +451,7 @@ extern "C" int bc_hmc_small_chunk_end(bc_ctx* ctx, double* out_samples, double* 
   h->clock.collect();
   const size_t kc = (size_t)h->pending_k * c, kcd = kc * d;
   const int* acc_dev = reinterpret_cast<const int*>(h->out.p + h->o_a);
+  const int* cor_dev = out_ll ? reinterpret_cast<const int*>(h->score.p + bc_even(P * kc)) : nullptr;
   // runs of consecutive unmarked problems are copied together (one run of all P when nothing is marked)
   size_t p = 0;
   while (p < P) {
@@ -456,12 +461,52 @@ extern "C" int bc_hmc_small_chunk_end(bc_ctx* ctx, double* out_samples, double* 
     }
     size_t q = p;
     while (q < P && flag[q] == 0) out_status[q++] = BC_OK;
-    BC_HIP(hipMemcpy(out_samples + p * kcd, h->out.p + p * kcd, (q - p) * kcd * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_samples) BC_HIP(hipMemcpy(out_samples + p * kcd, h->out.p + p * kcd, (q - p) * kcd * sizeof(double), hipMemcpyDeviceToHost));
     BC_HIP(hipMemcpy(out_logjoint + p * kc, h->out.p + h->o_l + p * kc, (q - p) * kc * sizeof(double), hipMemcpyDeviceToHost));
     BC_HIP(hipMemcpy(out_accept + p * kc, acc_dev + p * kc, (q - p) * kc * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (out_ll) {
+      BC_HIP(hipMemcpy(out_ll + p * kc, h->score.p + p * kc, (q - p) * kc * sizeof(double), hipMemcpyDeviceToHost));
+      BC_HIP(hipMemcpy(out_correct + p * kc, cor_dev + p * kc, (q - p) * kc * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
     p = q;
   }
   return BC_OK;
+}
+
+extern "C" int bc_hmc_small_chunk_end(bc_ctx* ctx, double* out_samples, double* out_logjoint, int32_t* out_accept, int32_t* out_status) {
+  bc_hmc_small* h = ctx ? ctx->hmc_small : nullptr;
+  if (!h || !h->active || !h->chunk_pending) { bc_set_error("bc_hmc_small_chunk_end: no chunk is pending"); return BC_INVALID_ARGUMENT; }
+  // (checked first: the chunk stays pending, a second call with the outputs can still fetch it)
+  if (!out_samples || !out_logjoint || !out_accept || !out_status) { bc_set_error("bc_hmc_small_chunk_end: the four outputs are required"); return BC_INVALID_ARGUMENT; }
+  return chunk_end(ctx, h, out_samples, out_logjoint, out_accept, out_status, nullptr, nullptr);
+}
+
+// ---- include/beta_cores_score.h: the held-out scores of the pending chunk, computed where its samples lie (k_lr_score, bc_score.hip)
+extern "C" int bc_score_chunk(bc_ctx* ctx, const bc_data* zt, const bc_data* yt) {
+  bc_hmc_small* h = ctx ? ctx->hmc_small : nullptr;
+  if (!h || !h->active || !h->chunk_pending) { bc_set_error("bc_score_chunk: no chunk of a batched small-problem run is pending"); return BC_INVALID_ARGUMENT; }
+  const int64_t t = (int64_t)h->n_problems * h->pending_k * h->a.c;
+  int rc = bc_score_check(ctx, zt, yt, t, h->a.d, "bc_score_chunk");
+  if (rc) return rc;
+  BC_HIP(hipSetDevice(ctx->device));
+  rc = bc_scratch_grow(ctx, &h->score, bc_even((size_t)t) + ((size_t)t + 1) / 2);
+  if (rc) return rc;
+  // (the stream orders this behind the chunk's launch; a marked problem's slice holds no samples: its scores are never copied)
+  rc = bc_score_launch(ctx, zt, yt, h->out.p, t, reinterpret_cast<int*>(h->score.p + bc_even((size_t)t)), h->score.p);
+  if (rc) return rc;
+  h->scored = true;
+  return BC_OK;
+}
+
+extern "C" int bc_score_chunk_end(bc_ctx* ctx, double* out_samples, double* out_logjoint, int32_t* out_accept, int32_t* out_status,
+                                  int32_t* out_correct, double* out_ll) {
+  bc_hmc_small* h = ctx ? ctx->hmc_small : nullptr;
+  if (!h || !h->active || !h->chunk_pending) { bc_set_error("bc_score_chunk_end: no chunk is pending"); return BC_INVALID_ARGUMENT; }
+  // (checked first: the chunk stays pending, a second call -- of either chunk end -- can still fetch it)
+  if (!out_logjoint || !out_accept || !out_status) { bc_set_error("bc_score_chunk_end: log-joints, accept flags and status are required"); return BC_INVALID_ARGUMENT; }
+  if ((out_correct == nullptr) != (out_ll == nullptr)) { bc_set_error("bc_score_chunk_end: out_correct and out_ll are given together or not at all"); return BC_INVALID_ARGUMENT; }
+  if (out_ll && !h->scored) { bc_set_error("bc_score_chunk_end: no score was enqueued for this chunk (call bc_score_chunk first)"); return BC_INVALID_ARGUMENT; }
+  return chunk_end(ctx, h, out_samples, out_logjoint, out_accept, out_status, out_correct, out_ll);
 }
 
 extern "C" int bc_hmc_small_end(bc_ctx* ctx) {
@@ -471,6 +516,7 @@ extern "C" int bc_hmc_small_end(bc_ctx* ctx) {
   const bool pending = h->chunk_pending;
   h->active = false;
   h->chunk_pending = false;
+  h->scored = false;
   if (pending) BC_HIP(hipStreamSynchronize(ctx->stream));      // abandoned mid-chunk: nothing may outlive the run's buffers
   return BC_OK;
 }

@@ -75,7 +75,7 @@ struct bc_ctx {
   int timing = 0;                // 0 = off, n >= 1: every n-th launch of each kernel class is timed
   unsigned timing_mask = 0x7;    // which classes (bit = class): the step stages 3-5 only on request (bc_ctx_timing_classes)
   bc_timer timers[7];            // 0 K3 sweep | 1 K1 projection | 2 K4 Gram + reduce | 3 rescoring / local winner |
-                                 // 4 candidate all-gather (RCCL) | 5 step finish | 6 logistic rows pass + reduce (K5)
+                                 // 4 candidate all-gather (RCCL) | 5 step finish | 6 logistic rows pass + reduce (K5), k_lr_score
   int n_cu = 256;
   int max_lds = 64 * 1024;       // hipDeviceAttributeMaxSharedMemoryPerBlock (160 KiB on gfx950)
   double* pinned = nullptr;      // small pinned staging area (host)
@@ -119,6 +119,7 @@ struct bc_ctx {
   struct bc_viopt* viopt = nullptr;    // bc_vi_optimize (bc_viopt.hip): the buffers and the state of the run in progress
   struct bc_hmc* hmc = nullptr;        // bc_hmc_* (bc_hmc.hip): the buffers and the state of the HMC run in progress
   struct bc_hmc_small* hmc_small = nullptr;   // bc_hmc_small_* (bc_hmc_small.hip): the same for the batched small-problem run
+  bc_scratch score;              // bc_lr_score (bc_score.hip): theta | ll | correct (ints)
 };
 
 // bc_upload.hip: rows of a host array -> dst_dev through pinned staging and several copy threads; the hook (optional) is
@@ -136,6 +137,11 @@ void bc_hmc_free(bc_ctx* ctx);       // bc_hmc.hip
 bool bc_hmc_active(const bc_ctx* ctx);     // the context holds an open bc_hmc run
 void bc_hmc_small_free(bc_ctx* ctx); // bc_hmc_small.hip
 bool bc_hmc_small_active(const bc_ctx* ctx);   // the context holds an open bc_hmc_small run
+// bc_score.hip: the checks of the held-out pair (d_run > 0: the columns the rows must have), and k_lr_score over t thetas that are
+// already on the device; enqueued only
+int bc_score_check(const bc_ctx* ctx, const struct bc_data* zt, const struct bc_data* yt, int64_t t, int32_t d_run, const char* who);
+int bc_score_launch(bc_ctx* ctx, const struct bc_data* zt, const struct bc_data* yt, const double* theta_dev, int64_t t, int* correct_dev,
+                    double* ll_dev);
 // What may hold a context, and the one place that says who is refused while it does (the table is beside the function in
 // bc_core.hip).  `holders`: the BC_HOLD_* that refuse the caller `who`; `own`: the caller's own kind, if it is a holder.
 #define BC_HOLD_GRADIENT 1u          // a fused gradient is pending (bc_vi_gradient_begin and its kin)

@@ -22,7 +22,7 @@ from scipy.optimize import minimize
 
 from . import _native as N
 from .device import DeviceData, _ptr
-from .posterior import check_hmc_problem, gaussian_weighted_post, logistic_newton_pass, small_lapack_scope, weighted_post, _weights_on_device
+from .posterior import HMC_MAX_DIM, check_hmc_problem, gaussian_weighted_post, logistic_newton_pass, small_lapack_scope, weighted_post, _weights_on_device
 
 
 class _PosteriorSampler:
@@ -380,7 +380,12 @@ class HMCResult:
     """What logistic_hmc returns.  samples: n_samples x n_chains x D (the position of every chain after every kept iteration);
     logjoint: n_samples x n_chains; accept: n_samples x n_chains (bool); accept_rate: per chain, over the kept iterations;
     step_size: the step the kept iterations ran with (frozen after warm-up); warmup_steps: the step of every warm-up chunk;
-    start, inv_mass: what the run began with; device_ms: GPU milliseconds of the run's chunks (None from a stand-in engine)."""
+    start, inv_mass: what the run began with; device_ms: GPU milliseconds of the run's chunks (None from a stand-in engine).
+    From logistic_hmc_many(score=held) also: correct (n_samples x n_chains: held-out rows predicted correctly by every kept
+    position), test_ll (n_samples x n_chains: its summed held-out log-likelihood) and accuracy (held.accuracy(correct)); None
+    otherwise.  samples is None from a run with keep_samples=False."""
+
+    correct = test_ll = accuracy = None
 
     def __init__(self, samples, logjoint, accept, step_size, warmup_steps, start, inv_mass, device_ms):
         self.samples, self.logjoint, self.accept = samples, logjoint, accept
@@ -495,6 +500,54 @@ def logistic_hmc(Z, wts=None, n_samples=1000, n_chains=16, step_size=0.1, n_leap
     return HMCResult(out_s, out_l, out_a, step, warm_steps, start, inv_mass, ms)
 
 
+# ---- held-out scores of many thetas at once (include/beta_cores_score.h)
+class HeldOut:
+    """Held-out data of the logistic drivers, resident on the device for logistic_score and logistic_hmc_many(score=...):
+    Xt (Nt x D, the intercept as a column where the model has one) and the labels Yt in {-1, +1}.  Kept: Z = Yt[:, None] * Xt
+    (float64; dtype=np.float32 takes a float32 Xt and keeps the product, which is exact, as float32) and Yt (Nt x 1)."""
+
+    def __init__(self, Xt, Yt, ctx=None, dtype=None):
+        Xt = np.asarray(Xt)
+        Yt = np.asarray(Yt, dtype=np.float64).ravel()
+        if Xt.ndim != 2 or Xt.shape[0] < 1 or Xt.shape[1] < 1:
+            raise ValueError('Xt must be Nt x D with Nt >= 1 and D >= 1, got shape %r' % (Xt.shape,))
+        if Yt.shape[0] != Xt.shape[0]:
+            raise ValueError('Yt must have one label per row of Xt (%d), got %d' % (Xt.shape[0], Yt.shape[0]))
+        if not np.all((Yt == 1.) | (Yt == -1.)):
+            raise ValueError('Yt must hold labels -1 and +1 only')
+        if dtype is not None and np.dtype(dtype) == np.float32:
+            if Xt.dtype != np.float32:
+                raise ValueError('dtype=float32 takes a float32 Xt (got %s): the library never rounds the caller\'s data' % Xt.dtype)
+            Z = np.ascontiguousarray(Yt.astype(np.float32)[:, None] * Xt)
+        else:
+            Z = Yt[:, None] * np.asarray(Xt, dtype=np.float64)
+        if not 1 <= Z.shape[1] <= HMC_MAX_DIM:
+            raise ValueError('the rows must have 1 .. %d columns, got %d' % (HMC_MAX_DIM, Z.shape[1]))
+        self.Z = DeviceData(Z, ctx=ctx, dtype=dtype)
+        self.ctx = self.Z.ctx
+        self.Y = DeviceData(np.ascontiguousarray(Yt[:, None]), ctx=self.ctx)
+        self.shape = self.Z.shape
+
+    def accuracy(self, correct):
+        """correct.sum() / (T * Nt): the reference's compute_accuracy over the thetas `correct` was counted for."""
+        correct = np.asarray(correct)
+        return float(correct.sum()) / (correct.size * self.shape[0])
+
+
+def logistic_score(held, thetas):
+    """(correct [T] int64, ll [T]) of T parameter vectors against the held-out data `held`: correct[t] counts the rows theta_t
+    predicts as the reference does (model_lr.py:32-42: -1 iff log_likelihood(-x, theta) > log_likelihood(x, theta), +1 on a tie;
+    in terms of s = y x . theta: correct iff (y = +1 and s >= 0) or (y = -1 and s > 0)), ll[t] = sum_n log_likelihood(z_n, theta_t).
+    One kernel (k_lr_score, the contraction on the fp64 matrix cores); the bits of a theta's scores do not depend on the others in
+    the batch.  thetas: T x D, finite.  No CPU fallback."""
+    th = np.ascontiguousarray(np.atleast_2d(np.asarray(thetas, dtype=np.float64)))
+    if th.ndim != 2 or th.shape[0] < 1 or th.shape[1] != held.shape[1]:
+        raise ValueError('thetas must be T x %d with T >= 1, got shape %r' % (held.shape[1], th.shape))
+    cor, ll = np.empty(th.shape[0], dtype=np.int32), np.empty(th.shape[0])
+    N.call('bc_lr_score', held.ctx.h, held.Z.h, held.Y.h, _ptr(th), int(th.shape[0]), _ptr(cor), _ptr(ll))
+    return cor.astype(np.int64), ll
+
+
 # ---- the same for MANY small problems at once: the weighted coresets of an evaluation curve (include/beta_cores_hmc_small.h)
 class HMCManyResult(list):
     """What logistic_hmc_many returns: a list with one HMCResult per problem (None for a marked problem under strict=False).
@@ -553,15 +606,34 @@ class _DeviceHMCMany:
     def auto_chunk(self, c, d):
         return int(N.load().bc_hmc_auto_chunk(int(c), int(d)))
 
-    def chunk(self, normals, log_u, steps, shared):
+    def _begin_chunk(self, normals, log_u, steps, shared):
         k = normals.shape[0] if shared else normals.shape[1]
         normals, log_u = np.ascontiguousarray(normals), np.ascontiguousarray(log_u)
         steps = np.ascontiguousarray(steps, dtype=np.float64)
         N.call('bc_hmc_small_chunk_begin', self.ctx.h, _ptr(normals), _ptr(log_u), 0 if shared else k * self.c * self.d, int(k), _ptr(steps))
-        s, lj = np.empty((self.P, k, self.c, self.d)), np.empty((self.P, k, self.c))
+        lj = np.empty((self.P, k, self.c))
         acc, status = np.zeros((self.P, k, self.c), dtype=np.int32), np.empty(self.P, dtype=np.int32)
+        return k, lj, acc, status
+
+    def chunk(self, normals, log_u, steps, shared):
+        k, lj, acc, status = self._begin_chunk(normals, log_u, steps, shared)
+        s = np.empty((self.P, k, self.c, self.d))
         N.call('bc_hmc_small_chunk_end', self.ctx.h, _ptr(s), _ptr(lj), _ptr(acc), _ptr(status))
         return s, lj, acc, status
+
+    def chunk_scored(self, normals, log_u, steps, shared, held, keep_samples):
+        """chunk() with the held-out scores of every position, computed on the device where the chunk's samples lie (k_lr_score):
+        (samples or None, logjoint, accept, status, correct, test_ll).  held=None: a warm-up chunk -- nothing is scored and no
+        samples are copied (None for samples, correct and test_ll)."""
+        k, lj, acc, status = self._begin_chunk(normals, log_u, steps, shared)
+        s = np.empty((self.P, k, self.c, self.d)) if keep_samples and held is not None else None
+        cor = tll = None
+        if held is not None:
+            N.call('bc_score_chunk', self.ctx.h, held.Z.h, held.Y.h)
+            cor, tll = np.zeros((self.P, k, self.c), dtype=np.int32), np.zeros((self.P, k, self.c))
+        N.call('bc_score_chunk_end', self.ctx.h, _ptr(s) if s is not None else None, _ptr(lj), _ptr(acc), _ptr(status),
+               _ptr(cor) if cor is not None else None, _ptr(tll) if tll is not None else None)
+        return s, lj, acc, status, cor, tll
 
     def end(self):
         N.load().bc_hmc_small_end(self.ctx.h)      # (status ignored: also called to close a failed run)
@@ -596,13 +668,19 @@ class _ManyDraws:
         return (e, u) if self.shared else (e[idx], u[idx])
 
 
-def _run_hmc_group(eng, idx, starts, ims, steps0, draws, c, d, n_samples, n_leapfrog, warmup, adapt_every, adapt_rate, chunk):
+def _run_hmc_group(eng, idx, starts, ims, steps0, draws, c, d, n_samples, n_leapfrog, warmup, adapt_every, adapt_rate, chunk, held=None,
+                   keep_samples=True):
     """The loop of logistic_hmc and logistic_hmc_many -- warm-up chunks with hmc_warmup_step per problem, then the kept chunks at
-    frozen steps -- for the problems `idx` of one engine.  Returns ({p: (samples, logjoint, accept, step, warm_steps)}, marked indices, device ms)."""
+    frozen steps -- for the problems `idx` of one engine.  Returns ({p: (samples, logjoint, accept, step, warm_steps)}, marked indices, device ms).
+    held (with an engine that has chunk_scored): the kept chunks are scored on the device, warm-up chunks are neither scored nor
+    copied, keep_samples=False copies no samples at all (samples is None); the result tuples end with (correct, test_ll)."""
     G = len(idx)
     step = [float(steps0[p]) for p in idx]
     warm = [[] for _ in idx]
-    out = [(np.empty((n_samples, c, d)), np.empty((n_samples, c)), np.empty((n_samples, c), dtype=bool)) for _ in idx]
+    in_run = held is not None and hasattr(eng, 'chunk_scored')
+    keep = keep_samples or not in_run
+    out = [(np.empty((n_samples, c, d)) if keep else None, np.empty((n_samples, c)), np.empty((n_samples, c), dtype=bool)) for _ in idx]
+    sc = [(np.empty((n_samples, c), dtype=np.int64), np.empty((n_samples, c))) for _ in idx] if in_run else None
     bad = np.zeros(G, dtype=bool)
     eng.begin(np.ascontiguousarray(starts[idx]), np.ascontiguousarray(ims[idx]), int(n_leapfrog), int(warmup) + int(n_samples))
     try:
@@ -610,7 +688,10 @@ def _run_hmc_group(eng, idx, starts, ims, steps0, draws, c, d, n_samples, n_leap
         while left > 0 and not bad.all():
             k = min(left, int(adapt_every))
             e, u = draws.get(ci, k, idx)
-            _, _, acc, status = eng.chunk(e, u, np.array(step), draws.shared)
+            if in_run:
+                acc, status = eng.chunk_scored(e, u, np.array(step), draws.shared, None, False)[2:4]
+            else:
+                _, _, acc, status = eng.chunk(e, u, np.array(step), draws.shared)
             bad |= status != 0
             for j in range(G):
                 if not bad[j]:
@@ -622,16 +703,23 @@ def _run_hmc_group(eng, idx, starts, ims, steps0, draws, c, d, n_samples, n_leap
         while i0 < n_samples and not bad.all():
             k = min(n_samples - i0, int(chunk))
             e, u = draws.get(ci, k, idx)
-            s, lj, acc, status = eng.chunk(e, u, np.array(step), draws.shared)
+            if in_run:
+                s, lj, acc, status, cor, tll = eng.chunk_scored(e, u, np.array(step), draws.shared, held, keep)
+            else:
+                s, lj, acc, status = eng.chunk(e, u, np.array(step), draws.shared)
             bad |= status != 0
             for j in range(G):
                 if not bad[j]:
-                    out[j][0][i0:i0 + k], out[j][1][i0:i0 + k], out[j][2][i0:i0 + k] = s[j], lj[j], acc[j] != 0
+                    out[j][1][i0:i0 + k], out[j][2][i0:i0 + k] = lj[j], acc[j] != 0
+                    if keep:
+                        out[j][0][i0:i0 + k] = s[j]
+                    if in_run:
+                        sc[j][0][i0:i0 + k], sc[j][1][i0:i0 + k] = cor[j], tll[j]
             i0 += k
             ci += 1
     finally:
         ms = eng.end()
-    res = {p: out[j] + (step[j], np.array(warm[j])) for j, p in enumerate(idx) if not bad[j]}
+    res = {p: out[j] + (step[j], np.array(warm[j])) + (sc[j] if in_run else ()) for j, p in enumerate(idx) if not bad[j]}
     return res, [p for j, p in enumerate(idx) if bad[j]], ms
 
 
@@ -646,7 +734,8 @@ def _per_problem(x, P, shape, what):
 
 
 def logistic_hmc_many(problems, n_samples=1000, n_chains=16, step_size=0.1, n_leapfrog=8, inv_mass=None, start=None, warmup=0, rng=None,
-                      draws='shared', adapt_every=25, adapt_rate=1.0, chunk=None, strict=True, ctx=None, engine=None):
+                      draws='shared', adapt_every=25, adapt_rate=1.0, chunk=None, strict=True, ctx=None, engine=None, score=None,
+                      keep_samples=True, scorer=None):
     """logistic_hmc for MANY small problems in one batched run: the posteriors of the weighted coresets of an evaluation curve
     (`for m in range(M + 1): sample the coreset of size m` in the logistic drivers).  One thread block per problem and group of
     up to four chains holds the problem's rows in LDS and runs whole chunks of iterations there (k_hmc_small); a chunk is one
@@ -670,8 +759,20 @@ def logistic_hmc_many(problems, n_samples=1000, n_chains=16, step_size=0.1, n_le
       has `.route`.
     A problem whose start is not finite (a non-finite weight shows there) is marked on the device and costs the others nothing:
       strict=True raises NumericalPrecisionError naming the indices after the run is closed, strict=False leaves None there.
-    engine: a stand-in `engine(Z_p, wts_p)` per problem with logistic_hmc's engine protocol (CPU tests).
+    score: a HeldOut.  Every HMCResult then carries `correct` and `test_ll` (n_samples x C: the held-out rows predicted correctly
+      by every kept position and its summed held-out log-likelihood) and `accuracy` = score.accuracy(correct), the reference's
+      compute_accuracy over the pooled samples.  On the 'small' route the kept chunks are scored on the device where their
+      samples lie, before anything is copied; warm-up chunks are neither scored nor copied.  A problem on the 'single' route is
+      scored by logistic_score on its returned samples after the run.  Both give the bits of
+      logistic_score(score, result.pooled()).  None: nothing changes.
+    keep_samples=False (with score): `samples` is None and no chunk's samples are copied -- the largest transfer of a chunk.
+    engine: a stand-in `engine(Z_p, wts_p)` per problem with logistic_hmc's engine protocol (CPU tests); scorer: a stand-in
+      `scorer(held, thetas) -> (correct, ll)` for logistic_score (CPU tests).
     Limits: 1 <= n_chains <= 64, D <= 256, one device.  Returns an HMCManyResult."""
+    if not keep_samples and score is None:
+        raise ValueError('keep_samples=False needs score: nothing would be returned')
+    if scorer is None:
+        scorer = logistic_score
     if draws not in ('shared', 'independent'):
         raise ValueError("draws must be 'shared' or 'independent'")
     probs, d = [], None
@@ -711,6 +812,8 @@ def logistic_hmc_many(problems, n_samples=1000, n_chains=16, step_size=0.1, n_le
     if engine is None:
         from .device import default_context
         ctx = default_context() if ctx is None else ctx
+        if score is not None and (score.ctx is not ctx or score.shape[1] != d):
+            raise ValueError('score must hold rows of %d columns on the context of the run' % d)
     fits = [True] * P if engine is not None else [bool(N.load().bc_hmc_small_fits(ctx.h, int(z.shape[0]), int(d))) for z, _ in probs]
     resident = {}
 
@@ -752,10 +855,20 @@ def logistic_hmc_many(problems, n_samples=1000, n_chains=16, step_size=0.1, n_le
     done, marked, ms_small = {}, [], None
     for eng, idx in groups:
         res, bad, ms = _run_hmc_group(eng, idx, starts, ims, steps0, stream, c, d, int(n_samples), n_leapfrog, warmup, adapt_every,
-                                      adapt_rate, chunk)
-        for p, (s, lj, acc, step, warm) in res.items():
+                                      adapt_rate, chunk, held=score, keep_samples=keep_samples)
+        for p, r in res.items():
+            s, lj, acc, step, warm = r[:5]
             done[p] = HMCResult(s, lj, acc, step, warm, starts[p], ims[p], ms)
             done[p].route = 'small' if fits[p] else 'single'
+            if score is not None:
+                if len(r) > 5:
+                    cor, tll = r[5:]
+                else:
+                    cor, tll = scorer(score, done[p].pooled())
+                    cor, tll = np.asarray(cor, dtype=np.int64).reshape(lj.shape), np.asarray(tll, dtype=np.float64).reshape(lj.shape)
+                    if not keep_samples:
+                        done[p].samples = None
+                done[p].correct, done[p].test_ll, done[p].accuracy = cor, tll, score.accuracy(cor)
         marked += bad
         if isinstance(eng, _DeviceHMCMany):
             ms_small = ms
