@@ -86,7 +86,7 @@ class BetaBlackBoxProjector(Projector):
         self.samples = self.sampler(self.projection_dimension, wts, pts)
 
 
-# limits of the native gradient entry points (bc_vi_gradient, bc_vi_optimize: csrc/bc_project.hip, csrc/bc_viopt.hip)
+# limits of the native gradient entry points (bc_vi_gradient, bc_vi_optimize: csrc/bc_vigrad.hip, csrc/bc_viopt.hip)
 VI_MAX_SAMPLES = 256           # one pass of the store-free K1
 VI_MAX_CORE_DOUBLES = 60000    # m * (dz + 1): the coreset rows and their weights fit the native staging area
 PSVI_MAX_ROW_DOUBLES = 3840    # bc_psvi_gradient: widest point row (csrc/bc_psvi_dev.h: BC_PSVI_MAX_DZ, the kernel's LDS work space)

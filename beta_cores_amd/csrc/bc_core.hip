@@ -111,10 +111,6 @@ void bc_run_clock::free() {
     if (e) (void)hipEventDestroy(e);
 }
 
-const char* bc_vi_kind_name(int kind) {
-  return kind == BC_VI_KIND_BETA ? "bc_vi_beta_gradient" : kind == BC_VI_KIND_PSVI ? "bc_psvi_gradient" : "bc_vi_gradient";
-}
-
 // Who is refused while what is held on a context.  G: a fused gradient is pending; V, H, S: a bc_vi_optimize / bc_hmc /
 // bc_hmc_small run is open.
 //
@@ -129,9 +125,10 @@ const char* bc_vi_kind_name(int kind) {
 // An entrant passes the holders of its row that refuse it; they are looked at in the order G, V, H, S, and the first one found
 // is named.  Nothing is enqueued, allocated or changed by a refusal.
 int bc_ctx_refuse_busy(const bc_ctx* ctx, const char* who, unsigned holders, unsigned own) {
-  if ((holders & BC_HOLD_GRADIENT) && ctx->vi_pending_m > 0) {
+  int kind = 0;
+  if ((holders & BC_HOLD_GRADIENT) && bc_vigrad_pending(ctx, &kind)) {
     bc_set_error("%s: a gradient is %spending on this context (call %s_end first)", who, (own & BC_HOLD_GRADIENT) ? "already " : "",
-                 bc_vi_kind_name(ctx->vi_pending_kind));
+                 bc_vi_kind_name(kind));
     return BC_INVALID_ARGUMENT;
   }
   const struct { unsigned bit; bool open; const char* kind; } runs[3] = {{BC_HOLD_VIOPT, bc_viopt_active(ctx), "bc_vi_optimize"},
@@ -157,20 +154,13 @@ extern "C" int bc_ctx_destroy(bc_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
   for (auto& t : ctx->timers) timer_free(t);
-  for (auto& ev : ctx->vi_ev)
-    if (ev) (void)hipEventDestroy(ev);
+  bc_vigrad_free(ctx);      // before anything below: it joins a stream of its own whose launches read proj_theta and proj_rowaux
   if (ctx->colsum_phi) bc_phi_destroy(ctx->colsum_phi);
-  if (ctx->core_phi) bc_phi_destroy(ctx->core_phi);
-  if (ctx->core_gphi) bc_phi_destroy(ctx->core_gphi);
-  bc_scratch* all[] = {&ctx->proj_theta, &ctx->proj_rowaux, &ctx->proj_rowaux2, &ctx->gradx, &ctx->vi_buf, &ctx->const_rows,
+  bc_scratch* all[] = {&ctx->proj_theta, &ctx->proj_rowaux, &ctx->proj_rowaux2, &ctx->gradx, &ctx->const_rows,
                        &ctx->gram[0], &ctx->gram[1], &ctx->gram[2], &ctx->gram[3], &ctx->gram[4],
                        &ctx->lap[0], &ctx->lap[1], &ctx->lap[2], &ctx->take_idx};
   for (bc_scratch* sc : all) bc_scratch_free(sc);
   if (ctx->proj_pinned) (void)hipHostFree(ctx->proj_pinned);
-  if (ctx->vi_pinned) (void)hipHostFree(ctx->vi_pinned);
-  if (ctx->vi_side) { (void)hipStreamSynchronize(ctx->vi_side); (void)hipStreamDestroy(ctx->vi_side); }
-  if (ctx->vi_ev_staged) (void)hipEventDestroy(ctx->vi_ev_staged);
-  if (ctx->vi_ev_core) (void)hipEventDestroy(ctx->vi_ev_core);
   if (ctx->pinned) (void)hipHostFree(ctx->pinned);
   bc_uploader_free(ctx);
   bc_take_free(ctx);

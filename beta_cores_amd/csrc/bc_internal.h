@@ -88,20 +88,7 @@ struct bc_ctx {
   bc_scratch gram[5];            // K4: partial, partial_y, out, out_y, w
   bc_scratch lap[3];             // K5 (bc_laplace.hip): theta | reduced terms, per-block partials, curvature weights
   bc_phi* colsum_phi = nullptr;  // store-free K1: a Phi with the per-tile column partials but no tiles / norms
-  bc_phi* core_phi = nullptr;    // bc_vi_gradient: the projection of the <= M coreset rows
-  bc_phi* core_gphi = nullptr;   // bc_vi_beta_gradient: their beta-gradient's projection
-  bc_scratch vi_buf;             // bc_vi_gradient: grad | resid
-  hipEvent_t vi_ev[BC_VI_PHASES + 1] = {};
-  double vi_phase_ms[BC_VI_PHASES] = {};
-  int64_t vi_calls_timed = 0;
-  int64_t vi_pending_m = 0;      // bc_vi_gradient_begin enqueued a gradient of this many rows (bc_vi_gradient_end fetches it)
-  int32_t vi_pending_s = 0;
-  bool vi_pending_timed = false;
-  int vi_pending_kind = 0;       // BC_VI_KIND_*: what the pending gradient left in vi_pinned
-  int32_t vi_pending_dz = 0;     // (BC_VI_KIND_PSVI: the width of the rows of grad_p)
-  double* vi_pinned = nullptr;   // pinned landing area of the pending gradient
-  hipStream_t vi_side = nullptr;  // bc_vi_gradient: the coreset rows' K1 runs here, beside the data rows' launch on `stream`
-  hipEvent_t vi_ev_staged = nullptr, vi_ev_core = nullptr;
+  struct bc_vigrad* vigrad = nullptr;  // the fused VI gradients (bc_vigrad.hip): cached Phis, result buffers, side stream, what is pending
   struct bc_uploader* upl = nullptr;   // pipelined host -> HBM uploads (bc_upload.hip): copy streams, pinned staging, events
   // host-evaluated constants of constant rows (bc_ctx_set_constant_row_values): sorted keys, then values, on the device
   bc_scratch const_rows;
@@ -131,6 +118,8 @@ int bc_upload_rows(bc_ctx* ctx, const void* src, void* dst_dev, int64_t n_rows, 
 int64_t bc_upload_default_chunk_rows(int64_t n_rows, size_t row_bytes);
 void bc_uploader_free(bc_ctx* ctx);
 void bc_take_free(bc_ctx* ctx);      // bc_take.hip: the two pinned index staging areas and their events
+void bc_vigrad_free(bc_ctx* ctx);    // bc_vigrad.hip: joins the gradient's side stream, then frees what it kept
+bool bc_vigrad_pending(const bc_ctx* ctx, int* kind);   // a fused gradient is pending (*kind, optional: its BC_VI_KIND_*)
 void bc_viopt_free(bc_ctx* ctx);     // bc_viopt.hip
 bool bc_viopt_active(const bc_ctx* ctx);   // the context holds an open bc_vi_optimize run
 void bc_hmc_free(bc_ctx* ctx);       // bc_hmc.hip
@@ -150,12 +139,12 @@ int bc_score_launch(bc_ctx* ctx, const struct bc_data* zt, const struct bc_data*
 #define BC_HOLD_HMC_SMALL 8u         // an open bc_hmc_small run
 #define BC_HOLD_ALL 15u
 int bc_ctx_refuse_busy(const bc_ctx* ctx, const char* who, unsigned holders, unsigned own = 0);
-const char* bc_vi_kind_name(int kind);     // the entry point's name of a BC_VI_KIND_*
+const char* bc_vi_kind_name(int kind);     // the entry point's name of a BC_VI_KIND_* (bc_vigrad.hip)
 // the tail of the one-call drivers: closes a run that failed with `end`, keeps the message of what failed, and returns rc
 int bc_close_failed_run(int rc, const std::function<int()>& end);
 // bc_take.hip: dst[j, :] = src[idx_dev[j], :] for indices that are already on the device and already checked; enqueued only
 int bc_take_rows_dev(bc_ctx* ctx, const bc_data* src, const long long* idx_dev, int64_t m, void* dst_z);
-// bc_project.hip: one gradient's projections and algebra for a Theta that is already on the device (bc_viopt.hip)
+// bc_vigrad.hip: one gradient's projections and algebra for a Theta that is already on the device (bc_viopt.hip)
 struct bc_vi_plan;
 int bc_vi_plan_layout(int model, int32_t s, int dz, int* d, int* dk, int* nrsel, int* ntsel);
 int bc_vi_plan_create(bc_ctx* ctx, int model, const double* params, int32_t n_params, int dz, int32_t s, const double* theta_dev,

@@ -21,7 +21,6 @@
 #include "bc_k1_math.h"
 #include "../../include/beta_cores_f32.h"
 #include "../../include/beta_cores_betagrad.h"
-#include "../../include/beta_cores_psvi.h"
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -120,7 +119,7 @@ static int grow_pinned(bc_ctx* ctx, size_t need) {
 }
 
 // model constants, evaluated in the same expression order as the Python sources
-static int model_constants(int model, const double* p, int np, int d, double* c, const double** siginv) {
+int bc_proj_model_constants(int model, const double* p, int np, int d, double* c, const double** siginv) {
   const double pi = 3.141592653589793;
   *siginv = nullptr;
   memset(c, 0, 8 * sizeof(double));
@@ -216,8 +215,6 @@ static int model_constants(int model, const double* p, int np, int d, double* c,
   return BC_INVALID_ARGUMENT;
 }
 
-enum { PROJ_FULL = 0, PROJ_RAW = 1, PROJ_COLSUM = 2 };
-
 // rows [row0, row0 + rows) of `data` as the kernels' untyped base pointer
 static const void* data_rows_at(const bc_data* data, int64_t row0) {
   return reinterpret_cast<const char*>(data->z) + (size_t)row0 * data->dz * data->elem;
@@ -243,22 +240,14 @@ static int launch_quadform(bc_ctx* ctx, const bc_data* data, int64_t row0, int64
   return BC_OK;
 }
 
-// ---- a projection in two steps: the plan (model constants, Theta zero-padded and uploaded: once per Theta) and the
-// launches that use it (one per set of rows: bc_vi_gradient projects the data rows and the coreset rows with one plan)
-struct ProjPlan {
-  ProjArgs a;             // constants, theta, saux, d, dk, s, model filled in; the per-launch fields are set by plan_launch
-  int model = 0, s = 0, d = 0, ntsel = 0;
-  bool raw = false;
-  const double* siginv_dev = nullptr;      // Gaussian models: Siginv [d][d] on the device
-};
-
-static bool model_has_y(int model) { return model == BC_MODEL_LINREG_LL || model == BC_MODEL_LINREG_BETA || model == BC_MODEL_LINREG_BETA_GRAD; }
+// ---- a projection in two steps, the plan and the launches that use it: struct ProjPlan, bc_project_plan.h
+bool bc_proj_model_has_y(int model) { return model == BC_MODEL_LINREG_LL || model == BC_MODEL_LINREG_BETA || model == BC_MODEL_LINREG_BETA_GRAD; }
 // the beta-gradients of the regression models: materialising projections only (include/beta_cores_betagrad.h)
-static bool model_store_only(int model) { return model == BC_MODEL_LINREG_BETA_GRAD || model == BC_MODEL_LOGISTIC_BETA_GRAD; }
+bool bc_proj_model_store_only(int model) { return model == BC_MODEL_LINREG_BETA_GRAD || model == BC_MODEL_LOGISTIC_BETA_GRAD; }
 
 // the zero-padded Theta [NRsel][dk] (and saux [NRsel]) a single pass over s samples of dimension d reads, and the K1
 // instantiation (NTsel sample tiles) that reads it
-static void theta_layout(int s, int d, bool raw, int* NTsel_out, int* NRsel_out, int* dk_out) {
+void bc_proj_theta_layout(int s, int d, bool raw, int* NTsel_out, int* NRsel_out, int* dk_out) {
   const int nt = (s + 15) / 16;
   static const int no_tail = getenv("BC_K1_NOTAIL") ? atoi(getenv("BC_K1_NOTAIL")) : 0;
   const bool tail = !raw && s > 96 && s <= 100 && !no_tail;      // 6 MFMA tiles + one sample quad
@@ -272,8 +261,8 @@ static void theta_layout(int s, int d, bool raw, int* NTsel_out, int* NRsel_out,
 
 // the model's constants and, where the host has evaluated them for exactly this model and these parameters, the constants of
 // the all-zero-feature rows, into the launch arguments (every plan starts here: plan_stage, bc_vi_plan_create)
-static int plan_constants(bc_ctx* ctx, int model, const double* params, int32_t n_params, int d, ProjArgs* a, const double** siginv) {
-  if (model_constants(model, params, n_params, d, a->c, siginv) != BC_OK) {
+int bc_proj_plan_constants(bc_ctx* ctx, int model, const double* params, int32_t n_params, int d, ProjArgs* a, const double** siginv) {
+  if (bc_proj_model_constants(model, params, n_params, d, a->c, siginv) != BC_OK) {
     bc_set_error("bc_project: model %d expects a different number of parameters than %d (d = %d)", model, n_params, d);
     return BC_INVALID_ARGUMENT;
   }
@@ -287,7 +276,7 @@ static int plan_constants(bc_ctx* ctx, int model, const double* params, int32_t 
 }
 
 // where a plan's Theta is, and what a launch needs to know of it (the tail of every plan)
-static void plan_bind(ProjPlan* pl, int model, int32_t s, int d, int dk, int NTsel, int NRsel, bool raw, const double* theta_dev,
+void bc_proj_plan_bind(ProjPlan* pl, int model, int32_t s, int d, int dk, int NTsel, int NRsel, bool raw, const double* theta_dev,
                       const double* siginv_dev) {
   ProjArgs& a = pl->a;
   a.theta = theta_dev;
@@ -307,11 +296,11 @@ static void plan_bind(ProjPlan* pl, int model, int32_t s, int d, int dk, int NTs
 // `extra` (optional): further host arrays shipped in the same transfer (bc_vi_gradient: the coreset rows and their
 // weights); extra_dev[i] receives the device address of extra_src[i].  ONE pinned staging area, ONE device buffer, ONE
 // hipMemcpyAsync per plan: a copy call costs ~5 us of host time, a gradient step of the 1M-row configuration 350.
-static int plan_stage(bc_ctx* ctx, int model, const double* theta, int32_t s, const double* params, int32_t n_params,
-                      int dz, bool raw, ProjPlan* pl, int n_extra = 0, const double* const* extra_src = nullptr,
-                      const size_t* extra_n = nullptr, double** extra_dev = nullptr) {
+int bc_proj_plan_stage(bc_ctx* ctx, int model, const double* theta, int32_t s, const double* params, int32_t n_params,
+                      int dz, bool raw, ProjPlan* pl, int n_extra, const double* const* extra_src, const size_t* extra_n,
+                      double** extra_dev) {
   if (s <= 0 || s > 256) { bc_set_error("bc_project: internal: a single pass handles 1..256 samples"); return BC_INVALID_ARGUMENT; }
-  const int d = dz - (model_has_y(model) ? 1 : 0);
+  const int d = dz - (bc_proj_model_has_y(model) ? 1 : 0);
   if (d <= 0) { bc_set_error("bc_project: data rows too short for this model"); return BC_INVALID_ARGUMENT; }
   ProjArgs& a = pl->a;
   memset(&a, 0, sizeof(a));
@@ -319,9 +308,9 @@ static int plan_stage(bc_ctx* ctx, int model, const double* theta, int32_t s, co
   a.stamps = getenv("BC_K1_STAMP_PTR") ? (unsigned long long*)strtoull(getenv("BC_K1_STAMP_PTR"), nullptr, 10) : nullptr;
 #endif
   const double* siginv = nullptr;
-  if (plan_constants(ctx, model, params, n_params, d, &a, &siginv) != BC_OK) return BC_INVALID_ARGUMENT;
+  if (bc_proj_plan_constants(ctx, model, params, n_params, d, &a, &siginv) != BC_OK) return BC_INVALID_ARGUMENT;
   int NTsel, NRsel, dk;
-  theta_layout(s, d, raw, &NTsel, &NRsel, &dk);
+  bc_proj_theta_layout(s, d, raw, &NTsel, &NRsel, &dk);
   const size_t th_n = (size_t)NRsel * dk, sa_n = (size_t)NRsel, sg_n = siginv ? (size_t)d * d : 0;
   const size_t head_n = (th_n + sa_n + sg_n + 1) & ~(size_t)1;
   size_t total = head_n;
@@ -362,7 +351,7 @@ static int plan_stage(bc_ctx* ctx, int model, const double* theta, int32_t s, co
     off += (extra_n[i] + 1) & ~(size_t)1;
   }
   BC_HIP(hipMemcpyAsync(ctx->proj_theta.p, ctx->proj_pinned, total * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  plan_bind(pl, model, s, d, dk, NTsel, NRsel, raw, ctx->proj_theta.p, siginv ? ctx->proj_theta.p + th_n + sa_n : nullptr);      // (th_n = NRsel * dk)
+  bc_proj_plan_bind(pl, model, s, d, dk, NTsel, NRsel, raw, ctx->proj_theta.p, siginv ? ctx->proj_theta.p + th_n + sa_n : nullptr);      // (th_n = NRsel * dk)
   return BC_OK;
 }
 
@@ -378,7 +367,7 @@ static int project_r_grid(const bc_ctx* ctx, const ProjPlan& pl, const bc_phi* p
   // S in 101..112 with an exp in the epilogue: those three instantiations need 4-6 VGPRs more than the 256 a wave of a
   // 512-thread block may hold (they would spill): the staged kernel serves them
   // (the two regression beta-gradients have no resident instantiation there either: launch_project_r_nt)
-  if (pl.ntsel == 7 && (bc_model_has_np_exp_rt(pl.model) || model_store_only(pl.model))) return 0;
+  if (pl.ntsel == 7 && (bc_model_has_np_exp_rt(pl.model) || bc_proj_model_store_only(pl.model))) return 0;
   if (pl.model == BC_MODEL_LOGISTIC_BETA && !(env && atoi(env) < 0)) return 0;      // measured slower there (0.80 vs 0.74 ms at N = 1M, D = 128): four
                                                                                        // transcendental bodies per element; BC_K1_STAGED=-1 forces the resident kernel
   const int nr = pl.ntsel * 16 + (pl.ntsel == 6 ? 4 : 0);
@@ -391,7 +380,7 @@ static int project_r_grid(const bc_ctx* ctx, const ProjPlan& pl, const bc_phi* p
 // One launch of a staged projection over `data`'s rows.  mode PROJ_FULL: the whole of Phi (s == s_total <= 256),
 // centred, with norms and column partials.  PROJ_RAW: samples [s_off, s_off + s) of s_total, un-centred.
 // PROJ_COLSUM: `phi` is a stats-only Phi: column partials only.  rowaux: the scratch that receives x^T Siginv x.
-static int plan_launch(bc_ctx* ctx, const ProjPlan& pl, const bc_data* data, bc_phi* phi, int mode, int32_t s_total,
+int bc_proj_plan_launch(bc_ctx* ctx, const ProjPlan& pl, const bc_data* data, bc_phi* phi, int mode, int32_t s_total,
                        int32_t s_off, bc_scratch* rowaux) {
   ProjArgs a = pl.a;
   a.rowaux = nullptr;
@@ -430,7 +419,7 @@ static int plan_launch(bc_ctx* ctx, const ProjPlan& pl, const bc_data* data, bc_
   return rc;
 }
 
-static int project_check(bc_ctx* ctx, const bc_data* data, int model, const double* theta, int32_t s,
+int bc_proj_project_check(bc_ctx* ctx, const bc_data* data, int model, const double* theta, int32_t s,
                          const double* params, int32_t n_params, const char* who) {
   if (!ctx || !data || !theta || s <= 0 || (n_params > 0 && !params)) { bc_set_error("%s: bad argument", who); return BC_INVALID_ARGUMENT; }
   if (data->ctx != ctx) { bc_set_error("%s: data belongs to another context", who); return BC_INVALID_ARGUMENT; }
@@ -442,12 +431,12 @@ static int project_check(bc_ctx* ctx, const bc_data* data, int model, const doub
 static int project_impl(bc_ctx* ctx, const bc_data* data, int model, const double* theta, int32_t s,
                         const double* params, int32_t n_params, int64_t row_offset, bc_phi** inout,
                         int32_t s_total, int32_t s_off, bool raw) {
-  int rc = project_check(ctx, data, model, theta, s, params, n_params, "bc_project");
+  int rc = bc_proj_project_check(ctx, data, model, theta, s, params, n_params, "bc_project");
   if (rc) return rc;
   if (!inout) { bc_set_error("bc_project: bad argument"); return BC_INVALID_ARGUMENT; }
   BC_HIP(hipSetDevice(ctx->device));
   ProjPlan pl;
-  rc = plan_stage(ctx, model, theta, s, params, n_params, data->dz, raw, &pl);
+  rc = bc_proj_plan_stage(ctx, model, theta, s, params, n_params, data->dz, raw, &pl);
   if (rc) return rc;
   // output handle: reuse buffers when the shape matches
   bc_phi* phi = *inout;
@@ -463,7 +452,7 @@ static int project_impl(bc_ctx* ctx, const bc_data* data, int model, const doubl
   }
   phi->row_offset = row_offset;
   phi->stats_valid = false;
-  rc = plan_launch(ctx, pl, data, phi, raw ? PROJ_RAW : PROJ_FULL, s_total, s_off, &ctx->proj_rowaux);
+  rc = bc_proj_plan_launch(ctx, pl, data, phi, raw ? PROJ_RAW : PROJ_FULL, s_total, s_off, &ctx->proj_rowaux);
   if (!rc && !raw) rc = bc_phi_finish_stats(phi);
   if (rc) { if (fresh) bc_phi_destroy(phi); return rc; }
   *inout = phi;
@@ -473,7 +462,7 @@ static int project_impl(bc_ctx* ctx, const bc_data* data, int model, const doubl
 // S > 256: passes of <= 256 samples write un-centred values, then one centring pass over Phi.
 static int bc_project_wide(bc_ctx* ctx, const bc_data* data, int model, const double* theta, int32_t s,
                            const double* params, int32_t n_params, int64_t row_offset, bc_phi** inout) {
-  const int d = data->dz - (model_has_y(model) ? 1 : 0);
+  const int d = data->dz - (bc_proj_model_has_y(model) ? 1 : 0);
   bc_phi* phi = *inout;
   const bool fresh = phi == nullptr;
   for (int s_off = 0; s_off < s; s_off += 256) {
@@ -495,17 +484,13 @@ static int bc_project_wide(bc_ctx* ctx, const bc_data* data, int model, const do
 
 extern "C" int bc_project(bc_ctx* ctx, const bc_data* data, int model, const double* theta, int32_t s,
                           const double* params, int32_t n_params, int64_t row_offset, bc_phi** inout) {
-  int rc = project_check(ctx, data, model, theta, s, params, n_params, "bc_project");
+  int rc = bc_proj_project_check(ctx, data, model, theta, s, params, n_params, "bc_project");
   if (rc) return rc;
   if (!inout) { bc_set_error("bc_project: bad argument"); return BC_INVALID_ARGUMENT; }
   if (s > 256) return bc_project_wide(ctx, data, model, theta, s, params, n_params, row_offset, inout);
   return project_impl(ctx, data, model, theta, s, params, n_params, row_offset, inout, s, 0, false);
 }
 
-// ---------------------------------------------------------------------------------------------
-// Host rows -> Phi, pipelined (hilbert.py:11-17 and bcores.py:44 hand the projector HOST arrays): the rows are uploaded in
-// chunks (bc_upload.hip) and K1 runs on chunk c behind the event that marks its arrival while chunks c+1.. are still on
-// the wire.  Rows are independent, so Phi and the norms are the resident path's bit for bit; the column sums too, because
 // ---- constant rows with the CALLER's bits (hosts whose NumPy does not evaluate np.exp with the SVML routine bc_np_exp.h
 // restates: the reference's own bits for a constant row's value are then NumPy's on THAT host).
 // A data row with all-zero features projects to S equal values that depend on its y alone (model_neurlinr.py:102-110 with
@@ -583,6 +568,10 @@ extern "C" int bc_ctx_set_constant_row_values(bc_ctx* ctx, int model, const doub
   return BC_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Host rows -> Phi, pipelined (hilbert.py:11-17 and bcores.py:44 hand the projector HOST arrays): the rows are uploaded in
+// chunks (bc_upload.hip) and K1 runs on chunk c behind the event that marks its arrival while chunks c+1.. are still on
+// the wire.  Rows are independent, so Phi and the norms are the resident path's bit for bit; the column sums too, because
 // the chunks keep the partial sums' association: the staged kernel writes one partial row per 128-row tile (chunks are
 // tile-aligned), the Theta-resident kernel's per-wave partials are CONTINUED from chunk to chunk (ProjArgs::part_init;
 // chunks start at multiples of 8 * n_cu groups = 65 536 rows, so every wave adds the same groups in the same order as in
@@ -654,7 +643,7 @@ static int project_from_host(bc_ctx* ctx, const void* z_host, int elem, const ch
     return BC_OK;
   }
   ProjPlan pl;
-  rc = plan_stage(ctx, model, theta, s, params, n_params, dz, false, &pl);
+  rc = bc_proj_plan_stage(ctx, model, theta, s, params, n_params, dz, false, &pl);
   if (rc) { drop_data(); return rc; }
   bc_phi* phi = *inout;
   if (phi && (phi->ctx != ctx || phi->s != s || !phi->tiles || bc_phi_set_rows(phi, n_rows) != 0)) {
@@ -709,17 +698,13 @@ extern "C" int bc_project_from_host_f32(bc_ctx* ctx, const float* z_host, int64_
 }
 
 // ---------------------------------------------------------------------------------------------
-// Store-free projection and the fused gradient of the greedy-VI weight optimisation.
-//
-// bcores.py:141-146 / sparsevi.py:129-134: every one of the opt_itrs ADAM steps of every build step evaluates
-//     vecs = project_f(data, beta) ; resid = sum_scaling * vecs.sum(axis=0) - w.dot(corevecs) ; grad = -corevecs.dot(resid) / S
-// i.e. of the N x S projection only its S column sums are used.  The materialising path writes 8*N*S bytes to read S
-// numbers back; here K1 keeps its per-tile column partials and stores nothing else (k_project<..., STORE = false>).
+// Store-free projection: the S column sums of the N x S projection and nothing else (why, and the fused gradient of the
+// greedy-VI weight optimisation that is built on it: bc_vigrad.hip).
 int bc_comm_sum_dev(bc_comm* c, const double* in_dev, int64_t count, const double** result_dev);   // bc_comm.hip
 bc_ctx* bc_comm_ctx(const bc_comm* c);
 
 // the context's stats-only Phi, sized for n_rows x s
-static int colsum_phi_for(bc_ctx* ctx, int64_t n_rows, int32_t s, bc_phi** out) {
+int bc_proj_colsum_phi_for(bc_ctx* ctx, int64_t n_rows, int32_t s, bc_phi** out) {
   bc_phi* p = ctx->colsum_phi;
   if (p && (p->s != s || bc_phi_set_rows(p, n_rows) != 0)) {
     BC_HIP(hipStreamSynchronize(ctx->stream));
@@ -738,10 +723,10 @@ static int colsum_phi_for(bc_ctx* ctx, int64_t n_rows, int32_t s, bc_phi** out) 
 
 extern "C" int bc_project_colsum(bc_ctx* ctx, const bc_data* data, int model, const double* theta, int32_t s,
                                  const double* params, int32_t n_params, bc_comm* comm, double* out_s) {
-  int rc = project_check(ctx, data, model, theta, s, params, n_params, "bc_project_colsum");
+  int rc = bc_proj_project_check(ctx, data, model, theta, s, params, n_params, "bc_project_colsum");
   if (rc) return rc;
   if (!out_s) { bc_set_error("bc_project_colsum: bad argument"); return BC_INVALID_ARGUMENT; }
-  if (model_store_only(model)) {
+  if (bc_proj_model_store_only(model)) {
     bc_set_error("bc_project_colsum: model %d (a beta-gradient) has no store-free form: project and take bc_phi_colsum", model);
     return BC_INVALID_ARGUMENT;
   }
@@ -749,11 +734,11 @@ extern "C" int bc_project_colsum(bc_ctx* ctx, const bc_data* data, int model, co
   if (s > 256) { bc_set_error("bc_project_colsum: at most 256 samples (S = %d): project and take bc_phi_colsum", s); return BC_INVALID_ARGUMENT; }
   BC_HIP(hipSetDevice(ctx->device));
   ProjPlan pl;
-  rc = plan_stage(ctx, model, theta, s, params, n_params, data->dz, false, &pl);
+  rc = bc_proj_plan_stage(ctx, model, theta, s, params, n_params, data->dz, false, &pl);
   if (rc) return rc;
   bc_phi* phi = nullptr;
-  rc = colsum_phi_for(ctx, data->n_rows, s, &phi);
-  if (!rc) rc = plan_launch(ctx, pl, data, phi, PROJ_COLSUM, s, 0, &ctx->proj_rowaux);
+  rc = bc_proj_colsum_phi_for(ctx, data->n_rows, s, &phi);
+  if (!rc) rc = bc_proj_plan_launch(ctx, pl, data, phi, PROJ_COLSUM, s, 0, &ctx->proj_rowaux);
   if (!rc) rc = bc_phi_reduce_colsum(phi);
   if (rc) return rc;
   const double* res = phi->colsum;
@@ -764,426 +749,5 @@ extern "C" int bc_project_colsum(bc_ctx* ctx, const bc_data* data, int model, co
   BC_HIP(hipMemcpyAsync(ctx->pinned, res, (size_t)s * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   BC_HIP(hipStreamSynchronize(ctx->stream));
   memcpy(out_s, ctx->pinned, (size_t)s * sizeof(double));
-  return BC_OK;
-}
-
-// resid[k] = scale * colsum[k] - sum_i w[i] * C[i, k]   (bcores.py:145: sum_scaling*vecs.sum(axis=0) - w.dot(corevecs))
-// grad[i]  = -(sum_k C[i, k] * resid[k]) / S            (bcores.py:146: -corevecs.dot(resid)/corevecs.shape[1])
-// C = the projected coreset rows in the tiled layout (row i, sample k at bc_tile_off(i, k, S)): neighbouring threads
-// read neighbouring rows, so both passes are coalesced.  One block; m is the coreset size (tens to a few thousand).
-__global__ __launch_bounds__(256) void k_vi_gradient(const double* __restrict__ colsum, const double* __restrict__ core,
-                                                    const double* __restrict__ w, int m, int s, double scale,
-                                                    double* __restrict__ resid_out, double* __restrict__ grad_out) {
-  extern __shared__ double rs[];      // [s]
-  for (int k = threadIdx.x; k < s; k += blockDim.x) {
-    double acc = 0.;
-    int i = 0;
-    for (; i + 8 <= m; i += 8) {           // same fma chain, eight loads in flight (one block, pure latency)
-      double c[8], ww[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) { c[u] = core[bc_tile_off(i + u, k, s)]; ww[u] = w[i + u]; }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) acc = fma(ww[u], c[u], acc);
-    }
-    for (; i < m; ++i) acc = fma(w[i], core[bc_tile_off(i, k, s)], acc);
-    const double r = scale * colsum[k] - acc;
-    rs[k] = r;
-    resid_out[k] = r;
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < m; i += blockDim.x) {
-    double acc = 0.;
-    int k = 0;
-    for (; k + 8 <= s; k += 8) {
-      double c[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) c[u] = core[bc_tile_off(i, k + u, s)];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) acc = fma(c[u], rs[k + u], acc);
-    }
-    for (; k < s; ++k) acc = fma(core[bc_tile_off(i, k, s)], rs[k], acc);
-    grad_out[i] = -acc / (double)s;
-  }
-}
-
-// learn_beta (bcores.py:134-137): beta_dots[i] = sum_k G[i, k] * resid[k] for G = the projected beta-gradient of the coreset
-// rows (tiled like C above) and the residual k_vi_gradient has just written.  A kernel of its own behind k_vi_gradient, so that
-// the latter -- and with it the bits of grad and resid -- is the same code with and without the beta part.
-__global__ __launch_bounds__(256) void k_vi_beta_dots(const double* __restrict__ bgrad, const double* __restrict__ resid, int m, int s,
-                                                     double* __restrict__ dots_out) {
-  extern __shared__ double rs[];      // [s]
-  for (int k = threadIdx.x; k < s; k += blockDim.x) rs[k] = resid[k];
-  __syncthreads();
-  for (int i = threadIdx.x; i < m; i += blockDim.x) {
-    double acc = 0.;
-    int k = 0;
-    for (; k + 8 <= s; k += 8) {
-      double c[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) c[u] = bgrad[bc_tile_off(i, k + u, s)];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) acc = fma(c[u], rs[k + u], acc);
-    }
-    for (; k < s; ++k) acc = fma(bgrad[bc_tile_off(i, k, s)], rs[k], acc);
-    dots_out[i] = acc;
-  }
-}
-
-extern "C" int bc_model_beta_grad(int beta_model) {
-  switch (beta_model) {
-    case BC_MODEL_LINREG_BETA: return BC_MODEL_LINREG_BETA_GRAD;
-    case BC_MODEL_LOGISTIC_BETA: return BC_MODEL_LOGISTIC_BETA_GRAD;
-    case BC_MODEL_GAUSS_BETA: return BC_MODEL_GAUSS_BETA_GRAD;
-    default: return -1;
-  }
-}
-
-// the Phi of the <= M coreset rows the gradient keeps in the context (*slot: core_phi, or core_gphi for the beta-gradient)
-static int core_phi_for(bc_ctx* ctx, bc_phi** slot, int64_t m, int32_t s, bc_phi** out) {
-  bc_phi* cphi = *slot;
-  if (cphi && (cphi->s != s || bc_phi_set_rows(cphi, m) != 0)) {
-    BC_HIP(hipStreamSynchronize(ctx->stream));
-    bc_phi_destroy(cphi);
-    *slot = cphi = nullptr;
-  }
-  if (!cphi) {
-    int64_t cap = 256;
-    while (cap < m) cap *= 2;
-    int rc = bc_phi_alloc(ctx, m, s, 0, &cphi, cap);
-    if (rc) return rc;
-    *slot = cphi;
-  }
-  cphi->stats_valid = false;
-  *out = cphi;
-  return BC_OK;
-}
-
-// the three kinds of gradient.  BC_VI_KIND_PLAIN: bc_vi_gradient.  BC_VI_KIND_BETA (bc_vi_beta_gradient): the coreset rows are
-// projected a second time, with grad_model, and the algebra also leaves beta_dots behind grad and resid.  BC_VI_KIND_PSVI
-// (bc_psvi_gradient): k_psvi_point_grad runs behind the algebra and leaves the M x dz point-gradient behind grad and resid.
-static int vi_gradient_begin(bc_ctx* ctx, const bc_data* data, const double* core_rows, int64_t m, int model, int grad_model,
-                             const double* theta, int32_t s, const double* params, int32_t n_params, const double* w,
-                             double sum_scaling, bc_comm* comm, int kind = -1) {
-  if (kind < 0) kind = grad_model >= 0 ? BC_VI_KIND_BETA : BC_VI_KIND_PLAIN;
-  const bool with_beta = kind == BC_VI_KIND_BETA, psvi = kind == BC_VI_KIND_PSVI;
-  int rc = project_check(ctx, data, model, theta, s, params, n_params, bc_vi_kind_name(kind));
-  if (rc) return rc;
-  if (psvi && bc_psvi_kind(model) < 0) {
-    bc_set_error("bc_psvi_gradient: model %d has no x-gradient in the reference", model);
-    return BC_INVALID_ARGUMENT;
-  }
-  if (model_store_only(model)) {
-    bc_set_error("bc_vi_gradient: model %d (a beta-gradient) has no store-free form for the data rows", model);
-    return BC_INVALID_ARGUMENT;
-  }
-  const char* who = psvi ? "bc_psvi_gradient" : "bc_vi_gradient";
-  if (m <= 0 || !core_rows || !w) { bc_set_error("%s: needs a non-empty coreset (m = %lld)", who, (long long)m); return BC_INVALID_ARGUMENT; }
-  if (s > 256) { bc_set_error("%s: at most 256 samples (S = %d)", who, s); return BC_INVALID_ARGUMENT; }
-  if (comm && bc_comm_ctx(comm) != ctx) { bc_set_error("bc_vi_gradient: the communicator belongs to another context"); return BC_INVALID_ARGUMENT; }
-  const int dz = data->dz;
-  if (psvi && dz > bc_psvi_max_dz()) {
-    bc_set_error("bc_psvi_gradient: rows of %d doubles do not fit the point-gradient's work space (at most %d)", dz, bc_psvi_max_dz());
-    return BC_INVALID_ARGUMENT;
-  }
-  // grad | resid [| beta_dots] [| grad_p]
-  const size_t n_core = (size_t)m * dz, n_down = (with_beta ? 2 : 1) * (size_t)m + (size_t)s + (psvi ? n_core : 0);
-  rc = bc_ctx_refuse_busy(ctx, (std::string(who) + "_begin").c_str(), BC_HOLD_GRADIENT | BC_HOLD_HMC | BC_HOLD_HMC_SMALL, BC_HOLD_GRADIENT);
-  if (rc) return rc;
-  if (n_down > ctx->pinned_doubles) {
-    bc_set_error("%s: coreset of %lld rows x %d exceeds the staging area", who, (long long)m, dz);
-    return BC_INVALID_ARGUMENT;
-  }
-  BC_HIP(hipSetDevice(ctx->device));
-  const bool timed = ctx->timing != 0;
-  if (timed)
-    for (auto& ev : ctx->vi_ev)
-      if (!ev) BC_HIP(hipEventCreate(&ev));
-  auto mark = [&](int i) -> int {
-    if (timed) BC_HIP(hipEventRecord(ctx->vi_ev[i], ctx->stream));
-    return BC_OK;
-  };
-  // --- stage Theta, the coreset rows and w: one pinned area, one transfer (plan_stage synchronises with the stream first)
-  ProjPlan pl;
-  rc = mark(0);
-  if (rc) return rc;
-  const double* esrc[2] = {core_rows, w};
-  const size_t en[2] = {n_core, (size_t)m};
-  double* edev[2] = {nullptr, nullptr};
-  rc = plan_stage(ctx, model, theta, s, params, n_params, dz, false, &pl, 2, esrc, en, edev);
-  if (rc) return rc;
-  bc_data core_view;                     // the coreset rows where the transfer put them (borrowed)
-  core_view.ctx = ctx;
-  core_view.n_rows = m;
-  core_view.dz = dz;
-  core_view.z = edev[0];
-  core_view.owned = false;
-  bc_data* cd = &core_view;
-  const double* d_w = edev[1];
-  rc = bc_scratch_grow(ctx, &ctx->vi_buf, n_down);
-  if (rc) return rc;
-  double* d_grad = ctx->vi_buf.p;
-  double* d_resid = d_grad + m;
-  double* d_bdots = d_resid + s;           // (with_beta)
-  double* d_gradp = d_resid + s;           // (psvi) [m][dz]
-  // the beta-gradient's plan: the value model's staged Theta, saux and Siginv (nothing is uploaded twice), its own constants
-  ProjPlan gpl = pl;
-  if (with_beta) {
-    const double* unused = nullptr;
-    if (model_constants(grad_model, params, n_params, pl.d, gpl.a.c, &unused) != BC_OK) {
-      bc_set_error("bc_vi_beta_gradient: model %d expects a different number of parameters than %d (d = %d)", grad_model, n_params, pl.d);
-      return BC_INVALID_ARGUMENT;
-    }
-    gpl.a.model = gpl.model = grad_model;
-    gpl.a.ck = gpl.a.cv = nullptr;         // host-evaluated constants belong to the value model
-    gpl.a.nck = 0;
-  }
-  rc = mark(1);
-  if (rc) return rc;
-  // --- the <= M coreset rows (materialised: the M x S algebra below reads them), then the data rows (store-free)
-  bc_phi *cphi = nullptr, *gphi = nullptr;
-  rc = core_phi_for(ctx, &ctx->core_phi, m, s, &cphi);
-  if (!rc && with_beta) rc = core_phi_for(ctx, &ctx->core_gphi, m, s, &gphi);
-  if (rc) return rc;
-  // The coreset rows' launch (one tile or a few: ~20 us of dependent latency, no work to speak of) runs on a side stream
-  // BESIDE the data rows' launch instead of in front of it; the algebra kernel waits for both (0.441 -> 0.427 ms per native
-  // call at N = 1M, D = 64).  The instrumented pass (timing on) keeps everything on one stream, so that its five phases stay a
-  // partition of the call.
-  const bool beside = !timed;
-  if (beside && !ctx->vi_side) {
-    BC_HIP(hipStreamCreateWithFlags(&ctx->vi_side, hipStreamNonBlocking));
-    BC_HIP(hipEventCreateWithFlags(&ctx->vi_ev_staged, hipEventDisableTiming));
-    BC_HIP(hipEventCreateWithFlags(&ctx->vi_ev_core, hipEventDisableTiming));
-  }
-  const int saved_timing = ctx->timing;
-  ctx->timing = 0;                      // the coreset rows' launch is not a K1 sample of the kernel timer
-  if (beside) {
-    BC_HIP(hipEventRecord(ctx->vi_ev_staged, ctx->stream));             // Theta, the coreset rows and w have landed
-    BC_HIP(hipStreamWaitEvent(ctx->vi_side, ctx->vi_ev_staged, 0));
-    hipStream_t main_stream = ctx->stream;
-    ctx->stream = ctx->vi_side;
-    rc = plan_launch(ctx, pl, cd, cphi, PROJ_FULL, s, 0, &ctx->proj_rowaux);
-    if (!rc && with_beta) rc = plan_launch(ctx, gpl, cd, gphi, PROJ_FULL, s, 0, &ctx->proj_rowaux);      // behind it, same stream
-    ctx->stream = main_stream;
-    if (!rc) {
-      const hipError_t e = hipEventRecord(ctx->vi_ev_core, ctx->vi_side);
-      if (e != hipSuccess) rc = bc_hip_fail(e, "hipEventRecord(vi_ev_core)", __FILE__, __LINE__);
-    }
-  } else {
-    rc = plan_launch(ctx, pl, cd, cphi, PROJ_FULL, s, 0, &ctx->proj_rowaux);
-    if (!rc && with_beta) rc = plan_launch(ctx, gpl, cd, gphi, PROJ_FULL, s, 0, &ctx->proj_rowaux);
-  }
-  ctx->timing = saved_timing;
-  // Everything after the side launch runs inside `rest`: on ANY failure in it the side stream is joined before the error
-  // leaves this function -- the next call's plan_stage / bc_scratch_grow synchronise ctx->stream only and would otherwise
-  // overwrite proj_theta / free core_phi under a coreset-row kernel that is still reading them.
-  auto rest = [&]() -> int {
-    int rc = mark(2);
-    bc_phi* phi = nullptr;
-    if (!rc) rc = colsum_phi_for(ctx, data->n_rows, s, &phi);
-    // (x^T Siginv x of the data rows, Gaussian models, goes to a scratch of its own: the coreset rows' is still in use)
-    if (!rc) rc = plan_launch(ctx, pl, data, phi, PROJ_COLSUM, s, 0, &ctx->proj_rowaux2);
-    if (!rc) rc = mark(3);
-    if (!rc) rc = bc_phi_reduce_colsum(phi);
-    if (rc) return rc;
-    const double* colsum = phi->colsum;
-    if (comm) {
-      rc = bc_comm_sum_dev(comm, phi->colsum, s, &colsum);
-      if (rc) return rc;
-    }
-    rc = mark(4);
-    if (rc) return rc;
-    if (beside) BC_HIP(hipStreamWaitEvent(ctx->stream, ctx->vi_ev_core, 0));
-    hipLaunchKernelGGL(k_vi_gradient, dim3(1), dim3(256), (size_t)s * sizeof(double), ctx->stream, colsum, cphi->tiles, d_w,
-                       (int)m, s, sum_scaling, d_resid, d_grad);
-    BC_HIP(hipGetLastError());
-    if (with_beta) {
-      hipLaunchKernelGGL(k_vi_beta_dots, dim3(1), dim3(256), (size_t)s * sizeof(double), ctx->stream, gphi->tiles, d_resid, (int)m, s, d_bdots);
-      BC_HIP(hipGetLastError());
-    }
-    if (psvi) {      // the points, their weights, Theta (Gaussian: Theta') and Siginv are where plan_stage has put them
-      rc = bc_psvi_point_grad_launch(ctx, model, edev[0], d_w, m, dz, pl.d, s, pl.a.theta, pl.a.dk, pl.siginv_dev,
-                                     model == BC_MODEL_LINREG_LL ? params[0] : 0., d_resid, d_gradp);
-      if (rc) return rc;
-    }
-    // the result lands in a pinned area of its own: whatever the host does between _begin and _end (it may well call into this
-    // library, whose other entry points stage through ctx->pinned) cannot overwrite it
-    if (!ctx->vi_pinned) BC_HIP(hipHostMalloc((void**)&ctx->vi_pinned, ctx->pinned_doubles * sizeof(double), hipHostMallocDefault));
-    BC_HIP(hipMemcpyAsync(ctx->vi_pinned, d_grad, n_down * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    return mark(5);
-  };
-  if (!rc) rc = rest();
-  if (rc) {
-    if (beside) (void)hipStreamSynchronize(ctx->vi_side);
-    return rc;
-  }
-  ctx->vi_pending_m = m;
-  ctx->vi_pending_s = s;
-  ctx->vi_pending_timed = timed;
-  ctx->vi_pending_kind = kind;
-  ctx->vi_pending_dz = dz;
-  return BC_OK;
-}
-
-extern "C" int bc_vi_gradient_begin(bc_ctx* ctx, const bc_data* data, const double* core_rows, int64_t m, int model,
-                                    const double* theta, int32_t s, const double* params, int32_t n_params, const double* w,
-                                    double sum_scaling, bc_comm* comm) {
-  return vi_gradient_begin(ctx, data, core_rows, m, model, -1, theta, s, params, n_params, w, sum_scaling, comm);
-}
-
-extern "C" int bc_vi_beta_gradient_begin(bc_ctx* ctx, const bc_data* data, const double* core_rows, int64_t m, int beta_model,
-                                         const double* theta, int32_t s, const double* params, int32_t n_params, const double* w,
-                                         double sum_scaling, bc_comm* comm) {
-  const int grad_model = bc_model_beta_grad(beta_model);
-  if (grad_model < 0) {
-    bc_set_error("bc_vi_beta_gradient: model %d is not a beta-likelihood with a beta-gradient", beta_model);
-    return BC_INVALID_ARGUMENT;
-  }
-  return vi_gradient_begin(ctx, data, core_rows, m, beta_model, grad_model, theta, s, params, n_params, w, sum_scaling, comm);
-}
-
-// second half: wait for the enqueued gradient and hand it out (whatever the host did meanwhile -- e.g. drawing the next
-// sample matrix's normals -- ran beside the GPU)
-// out_extra: beta_dots [m] (BC_VI_KIND_BETA) or grad_p [m][dz] (BC_VI_KIND_PSVI)
-static int vi_gradient_end(bc_ctx* ctx, double* out_grad, double* out_extra, double* out_resid, int kind) {
-  char who[40];
-  snprintf(who, sizeof(who), "%s_end", bc_vi_kind_name(kind));
-  if (!ctx || !out_grad || (kind != BC_VI_KIND_PLAIN && !out_extra)) { bc_set_error("%s: bad argument", who); return BC_INVALID_ARGUMENT; }
-  if (ctx->vi_pending_m <= 0) { bc_set_error("%s: no gradient is pending on this context", who); return BC_INVALID_ARGUMENT; }
-  if (ctx->vi_pending_kind != kind) {       // the pending gradient stays pending
-    bc_set_error("%s: the pending gradient was begun by %s_begin", who, bc_vi_kind_name(ctx->vi_pending_kind));
-    return BC_INVALID_ARGUMENT;
-  }
-  const int64_t m = ctx->vi_pending_m;
-  const int32_t s = ctx->vi_pending_s;
-  const bool timed = ctx->vi_pending_timed;
-  ctx->vi_pending_m = 0;
-  BC_HIP(hipSetDevice(ctx->device));
-  BC_HIP(hipStreamSynchronize(ctx->stream));
-  memcpy(out_grad, ctx->vi_pinned, (size_t)m * sizeof(double));
-  if (out_resid) memcpy(out_resid, ctx->vi_pinned + m, (size_t)s * sizeof(double));
-  if (kind == BC_VI_KIND_BETA) memcpy(out_extra, ctx->vi_pinned + m + s, (size_t)m * sizeof(double));
-  if (kind == BC_VI_KIND_PSVI) memcpy(out_extra, ctx->vi_pinned + m + s, (size_t)m * ctx->vi_pending_dz * sizeof(double));
-  if (timed) {
-    for (int i = 0; i < BC_VI_PHASES; ++i) {
-      float ms = 0.f;
-      BC_HIP(hipEventElapsedTime(&ms, ctx->vi_ev[i], ctx->vi_ev[i + 1]));
-      ctx->vi_phase_ms[i] += ms;
-    }
-    ctx->vi_calls_timed++;
-  }
-  return BC_OK;
-}
-
-extern "C" int bc_vi_gradient_end(bc_ctx* ctx, double* out_grad, double* out_resid) {
-  return vi_gradient_end(ctx, out_grad, nullptr, out_resid, BC_VI_KIND_PLAIN);
-}
-
-extern "C" int bc_vi_beta_gradient_end(bc_ctx* ctx, double* out_grad, double* out_beta_dots, double* out_resid) {
-  return vi_gradient_end(ctx, out_grad, out_beta_dots, out_resid, BC_VI_KIND_BETA);
-}
-
-// ---- include/beta_cores_psvi.h: BatchPSVICoreset's whole gradient.  The same staging, the same projections and the same
-// k_vi_gradient launch as bc_vi_gradient (grad_w and resid carry its bits), k_psvi_point_grad behind it, one download.
-extern "C" int bc_psvi_gradient_begin(bc_ctx* ctx, const bc_data* data, const double* points, int64_t m, int model,
-                                      const double* theta, int32_t s, const double* params, int32_t n_params, const double* w,
-                                      double sum_scaling) {
-  return vi_gradient_begin(ctx, data, points, m, model, -1, theta, s, params, n_params, w, sum_scaling, nullptr, BC_VI_KIND_PSVI);
-}
-
-extern "C" int bc_psvi_gradient_end(bc_ctx* ctx, double* out_grad_w, double* out_grad_p, double* out_resid) {
-  return vi_gradient_end(ctx, out_grad_w, out_grad_p, out_resid, BC_VI_KIND_PSVI);
-}
-
-extern "C" int bc_psvi_gradient(bc_ctx* ctx, const bc_data* data, const double* points, int64_t m, int model,
-                                const double* theta, int32_t s, const double* params, int32_t n_params, const double* w,
-                                double sum_scaling, double* out_grad_w, double* out_grad_p, double* out_resid) {
-  if (!out_grad_w || !out_grad_p) { bc_set_error("bc_psvi_gradient: bad argument"); return BC_INVALID_ARGUMENT; }
-  int rc = bc_psvi_gradient_begin(ctx, data, points, m, model, theta, s, params, n_params, w, sum_scaling);
-  if (rc) return rc;
-  return bc_psvi_gradient_end(ctx, out_grad_w, out_grad_p, out_resid);
-}
-
-extern "C" int bc_vi_beta_gradient(bc_ctx* ctx, const bc_data* data, const double* core_rows, int64_t m, int beta_model,
-                                   const double* theta, int32_t s, const double* params, int32_t n_params, const double* w,
-                                   double sum_scaling, bc_comm* comm, double* out_grad, double* out_beta_dots, double* out_resid) {
-  if (!out_grad || !out_beta_dots) { bc_set_error("bc_vi_beta_gradient: bad argument"); return BC_INVALID_ARGUMENT; }
-  int rc = bc_vi_beta_gradient_begin(ctx, data, core_rows, m, beta_model, theta, s, params, n_params, w, sum_scaling, comm);
-  if (rc) return rc;
-  return bc_vi_beta_gradient_end(ctx, out_grad, out_beta_dots, out_resid);
-}
-
-extern "C" int bc_vi_gradient(bc_ctx* ctx, const bc_data* data, const double* core_rows, int64_t m, int model,
-                              const double* theta, int32_t s, const double* params, int32_t n_params, const double* w,
-                              double sum_scaling, bc_comm* comm, double* out_grad, double* out_resid) {
-  if (!out_grad) { bc_set_error("bc_vi_gradient: bad argument"); return BC_INVALID_ARGUMENT; }
-  int rc = bc_vi_gradient_begin(ctx, data, core_rows, m, model, theta, s, params, n_params, w, sum_scaling, comm);
-  if (rc) return rc;
-  return bc_vi_gradient_end(ctx, out_grad, out_resid);
-}
-
-extern "C" int bc_ctx_phase_times(bc_ctx* ctx, double* out_ms, int32_t n, int64_t* calls, int reset) {
-  if (!ctx || (n > 0 && !out_ms)) { bc_set_error("bc_ctx_phase_times: bad argument"); return BC_INVALID_ARGUMENT; }
-  for (int i = 0; i < n; ++i) out_ms[i] = i < BC_VI_PHASES ? ctx->vi_phase_ms[i] : 0.;
-  if (calls) *calls = ctx->vi_calls_timed;
-  if (reset) {
-    for (auto& v : ctx->vi_phase_ms) v = 0.;
-    ctx->vi_calls_timed = 0;
-  }
-  return BC_OK;
-}
-
-// ------------------------------------------------------------------ bc_viopt.hip's way into the projection
-// The steps 2 and 4-6 of one gradient (include/beta_cores_viopt.h) for a Theta that is ALREADY on the device -- k_vi_sampler
-// has written it there in the zero-padded layout the plan describes -- enqueued on ctx->stream without any host wait.
-struct bc_vi_plan {
-  ProjPlan pl;
-};
-
-int bc_vi_plan_layout(int model, int32_t s, int dz, int* d, int* dk, int* nrsel, int* ntsel) {
-  *d = dz - (model_has_y(model) ? 1 : 0);
-  if (*d <= 0 || s <= 0 || s > 256) return BC_INVALID_ARGUMENT;
-  theta_layout(s, *d, false, ntsel, nrsel, dk);
-  return BC_OK;
-}
-
-// theta_dev: [nrsel][dk] | saux [nrsel], zero outside the s x d block the sampler writes.  siginv_dev: the Gaussian models' Siginv.
-int bc_vi_plan_create(bc_ctx* ctx, int model, const double* params, int32_t n_params, int dz, int32_t s, const double* theta_dev,
-                      const double* siginv_dev, bc_vi_plan** out) {
-  if (model < 0 || model > BC_MODEL_LOGISTIC_BETA_GRAD || model_store_only(model)) {
-    bc_set_error("bc_vi_optimize: model %d has no store-free projection", model);
-    return BC_INVALID_ARGUMENT;
-  }
-  int d, dk, nrsel, ntsel;
-  if (bc_vi_plan_layout(model, s, dz, &d, &dk, &nrsel, &ntsel) != BC_OK) { bc_set_error("bc_vi_optimize: bad shape (S = %d, dz = %d)", s, dz); return BC_INVALID_ARGUMENT; }
-  bc_vi_plan* p = new bc_vi_plan();
-  memset(&p->pl.a, 0, sizeof(p->pl.a));
-  const double* siginv = nullptr;
-  if (plan_constants(ctx, model, params, n_params, d, &p->pl.a, &siginv) != BC_OK) { delete p; return BC_INVALID_ARGUMENT; }
-  if ((siginv != nullptr) != (siginv_dev != nullptr)) { bc_set_error("bc_vi_optimize: internal: Siginv"); delete p; return BC_INVALID_ARGUMENT; }
-  plan_bind(&p->pl, model, s, d, dk, ntsel, nrsel, false, theta_dev, siginv_dev);
-  *out = p;
-  return BC_OK;
-}
-
-void bc_vi_plan_destroy(bc_vi_plan* p) { delete p; }
-
-// resid = scale * colsum(K1(rows)) - w . K1(core), grad = -K1(core) . resid / S: everything on ctx->stream, nothing waited for
-int bc_vi_plan_step(bc_ctx* ctx, const bc_vi_plan* p, const bc_data* core, const bc_data* rows, const double* w_dev, double scale,
-                    double* resid_dev, double* grad_dev) {
-  const ProjPlan& pl = p->pl;
-  const int32_t s = pl.s;
-  bc_phi *cphi = nullptr, *phi = nullptr;
-  int rc = core_phi_for(ctx, &ctx->core_phi, core->n_rows, s, &cphi);
-  if (!rc) rc = colsum_phi_for(ctx, rows->n_rows, s, &phi);
-  const int saved_timing = ctx->timing;
-  ctx->timing = 0;                      // (no K1 samples of the kernel timer from inside the loop)
-  if (!rc) rc = plan_launch(ctx, pl, core, cphi, PROJ_FULL, s, 0, &ctx->proj_rowaux);
-  if (!rc) rc = plan_launch(ctx, pl, rows, phi, PROJ_COLSUM, s, 0, &ctx->proj_rowaux2);
-  ctx->timing = saved_timing;
-  if (!rc) rc = bc_phi_reduce_colsum(phi);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_vi_gradient, dim3(1), dim3(256), (size_t)s * sizeof(double), ctx->stream, phi->colsum, cphi->tiles, w_dev,
-                     (int)core->n_rows, s, scale, resid_dev, grad_dev);
-  BC_HIP(hipGetLastError());
   return BC_OK;
 }

@@ -3,6 +3,7 @@
 // takes about a minute to compile, so they are built side by side.
 #pragma once
 #include "bc_internal.h"
+#include "bc_project_plan.h"
 #include "bc_np_exp.h"
 #include "bc_np_pow2.h"
 #include "bc_layout.h"
@@ -33,30 +34,7 @@ __device__ __forceinline__ void bc_store2(double* p, double x, double y) {
 __device__ __forceinline__ void bc_store2(double* p, double x, double y) { *reinterpret_cast<double2*>(p) = make_double2(x, y); }
 #endif
 
-struct ProjArgs {
-  const void* z;          // [n_rows][dz] of the kernel's ZT (double, or float: widened in registers, see k_project_r)
-  const double* theta;    // [nt*16][dk]  zero padded            (MFMA kernel)
-  const double* saux;     // [nt*16] per-sample extra (gauss: theta^T Siginv theta)
-  const double* rowaux;   // [n_rows] per-row extra (gauss: x^T Siginv x) or null
-  double* tiles;
-  double* norms;
-  double* tile_part;
-  long long n_rows;
-  int dz, d, dk, s, model;
-  int s_total, s_off;     // RAW passes (S > 256): this launch fills samples [s_off, s_off + s) of s_total, un-centred
-  long long ngroups;      // k_project_r: 32-row groups of this launch
-  int part_init;          // k_project_r: start the per-wave column partials from tile_part instead of 0 (a later chunk of
-                          // a chunked projection, bc_project_from_host: the same sums in the same order as ONE launch)
-  double c[8];            // model constants, see model_constants()
-  // constant rows whose model value the HOST evaluated (bc_ctx_set_constant_row_values: hosts whose NumPy does not take the
-  // SVML exp bc_np_exp.h restates): sorted keys (LINREG_BETA: the row's y), the values, how many; 0: none
-  const double* ck;
-  const double* cv;
-  int nck;
-#ifdef BC_K1_STAMPS       // diagnostic build: s_memtime of wave 0 at phase boundaries, 32 slots per tile
-  unsigned long long* stamps;
-#endif
-};
+// struct ProjArgs, which the kernels take by value: bc_project_plan.h
 #ifdef BC_K1_STAMPS
 #define KSTAMP(i) do { if (a.stamps && threadIdx.x == 0) { a.stamps[(size_t)blockIdx.x * 32 + (i)] = __builtin_amdgcn_s_memtime(); \
     if ((i) == 0 || (i) == 24) a.stamps[(size_t)blockIdx.x * 32 + ((i) == 0 ? 30 : 31)] = __builtin_amdgcn_s_memrealtime(); } } while (0)

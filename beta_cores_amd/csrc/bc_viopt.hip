@@ -1,7 +1,7 @@
 // The weight optimisation of the greedy variational coresets as runs of steps enqueued on the device
 // (include/beta_cores_viopt.h): k_vi_sampler (the posterior draw: bc_vi_sampler_dev.h), k_vi_laplace (the logistic Laplace
-// sampler: bc_vi_laplace_dev.h), k_vi_adam (util/opt.py's nn_opt), and the entry points that chain them with the projections of
-// bc_project.hip and the row gather of bc_take.hip.
+// sampler: bc_vi_laplace_dev.h), k_vi_adam (util/opt.py's nn_opt), and the entry points that chain them with one gradient's
+// projections and algebra (bc_vi_plan_step, bc_vigrad.hip) and the row gather of bc_take.hip.
 //
 // Nothing here waits for the device except bc_vi_optimize_chunk_end (once per chunk) and the buffer (re)allocations of a run's
 // first chunk.  The weights, both ADAM moments and the abort mark live in device memory for the whole run.

@@ -1,7 +1,7 @@
 """What may be open on a context at once, and the buffers the chunked device runs keep between runs, through the C ABI
 (bc_vi_optimize_*, bc_hmc_*, bc_hmc_small_*, the fused gradients' _begin / _end).
 
-1. The table of csrc/bc_core.hip (bc_ctx_refuse_busy): with a holder open -- G a pending gradient, V / H / S an open
+1. The table of csrc/bc_core.hip (bc_ctx_refuse_busy): with a holder open -- G a pending gradient (csrc/bc_vigrad.hip), V / H / S an open
    bc_vi_optimize / bc_hmc / bc_hmc_small run -- every entrant is refused with the holder named, or allowed and closed at once;
    the holder then finishes with the bits of the same run on an undisturbed context.
 2. Buffers that grow and are reused at a smaller size: small run, larger run in two chunks, small run again, on one context.
