@@ -2,6 +2,7 @@
 // sums / norms) and K3 (fused score + argmax sweep).  gfx950 only.
 #include "bc_internal.h"
 #include "bc_layout.h"
+#include "bc_sweep_plan.h"
 #include "../../include/beta_cores_f32.h"
 #include <cstdarg>
 #include <cstdio>
@@ -404,17 +405,9 @@ extern "C" int bc_data_destroy(bc_data* d) {
 
 // ------------------------------------------------------------------ Phi storage
 int bc_sweep_grid(const bc_phi* phi) {
-  // Memory-bound sweep, one wave per tile and a grid-stride loop.  FEWER resident waves stream better: at N = 10M, S = 100
-  // one 4-wave block per CU (each wave keeps 10 KiB in flight) reaches 0.886 of the HBM spec, two 0.873, four 0.857, eight
-  // 0.846 (profiles/r02_notes.md); a wave of a narrow Phi has fewer bytes per tile to keep in flight and needs company
-  // (S = 16: four blocks per CU are best, one loses 40 %).
-  long long per_cu = phi->s >= 64 ? 1 : (phi->s >= 24 ? 2 : 4);
+  // the arithmetic (and why fewer blocks per CU for a wide Phi): bc_sweep_plan.h
   const char* env = getenv("BC_SWEEP_BLOCKS_PER_CU");
-  if (env && atoi(env) > 0) per_cu = atoi(env);
-  long long want = (phi->ntiles + 3) / 4;
-  long long cap = (long long)phi->ctx->n_cu * per_cu;
-  long long g = want < cap ? want : cap;
-  return (int)(g < 1 ? 1 : g);
+  return bc_sweep_plan(phi->ntiles, phi->s, phi->ctx->n_cu, env ? atoi(env) : 0);
 }
 
 static int stat_blocks_for(int64_t ntiles) {

@@ -18,8 +18,8 @@
 template <int MODE>
 __global__ __launch_bounds__(256) void k_sweep(bc_sweep_args a, double* __restrict__ blk_val,
                                               long long* __restrict__ blk_idx) {
-  __shared__ double sv[4];
-  __shared__ long long si[4];
+  __shared__ double sv[BC_SWEEP_WAVES];
+  __shared__ long long si[BC_SWEEP_WAVES];
   const bool skip = a.skip_flag != nullptr && *a.skip_flag != 0;
   double best_v;
   long long best_i;

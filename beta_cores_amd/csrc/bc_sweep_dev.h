@@ -3,6 +3,7 @@
 // the per-block sweep body.
 #pragma once
 #include "bc_internal.h"
+#include "bc_sweep_plan.h"
 #include <climits>
 #include <cmath>
 
@@ -78,8 +79,8 @@ __device__ __forceinline__ void bc_emit_record(const double* __restrict__ blk_va
   for (int k = threadIdx.x; k < s; k += blockDim.x) rec[BC_REC_HDR + k] = (r >= 0) ? tiles[bc_tile_off(r, k, s)] : 0.0;
 }
 
-// One block's share of the sweep: tiles block*4+wave, +nblocks*4, ...  Leaves the block's best
-// (score, global row) in thread 0's best_v / best_i (sv/si: 4-entry shared scratch).
+// One block's share of the sweep: tiles block*W+wave, +nblocks*W, ... with W = BC_SWEEP_WAVES (bc_sweep_plan.h sizes the grid
+// by the same W).  Leaves the block's best (score, global row) in thread 0's best_v / best_i (sv/si: W-entry shared scratch).
 template <int MODE>
 __device__ __forceinline__ void bc_sweep_block(const bc_sweep_args& a, int block, int nblocks, bool skip, double* sv,
                                                long long* si, double& best_v, long long& best_i) {
@@ -90,7 +91,7 @@ __device__ __forceinline__ void bc_sweep_block(const bc_sweep_args& a, int block
     const int S = a.s;
     const double2* __restrict__ v2 = reinterpret_cast<const double2*>(a.v);
     const double* __restrict__ v1 = a.v;
-    for (long long t = (long long)block * 4 + wave; t < a.ntiles; t += (long long)nblocks * 4) {
+    for (long long t = (long long)block * BC_SWEEP_WAVES + wave; t < a.ntiles; t += (long long)nblocks * BC_SWEEP_WAVES) {
       const double2* __restrict__ p = reinterpret_cast<const double2*>(a.tiles + (size_t)t * S * BC_TILE) + lane;
       double a00 = 0., a01 = 0., a10 = 0., a11 = 0.;
       int k = 0;
@@ -149,6 +150,6 @@ __device__ __forceinline__ void bc_sweep_block(const bc_sweep_args& a, int block
   if (lane == 0) { sv[wave] = best_v; si[wave] = best_i; }
   __syncthreads();
   if (threadIdx.x == 0)
-    for (int w = 1; w < 4; ++w)
+    for (int w = 1; w < BC_SWEEP_WAVES; ++w)
       if (bc_better(sv[w], si[w], best_v, best_i)) { best_v = sv[w]; best_i = si[w]; }
 }

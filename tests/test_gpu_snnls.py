@@ -94,6 +94,7 @@ def test_k3_argmax_matches_numpy(bc, n, s):
     f, val = d.argmax(np.stack((c, x), axis=1), mode=0)
     if ok.any():
         assert f == int(np.argmax(full))
+        assert abs(val - full.max()) <= 1e-12 * abs(full.max())
 
 
 def test_k3_ties_take_lowest_index(bc):
