@@ -2,6 +2,7 @@
 // left behind -> the winner's candidate record.  Included by the fused step kernel (bc_snnls.hip) and by k_bb_winner
 // (bc_prefilter.hip) through bc_rescore_dev.h.
 #pragma once
+#include "bc_pref_ctrl.h"
 
 #define BC_BB_FLAG_OVF 1
 struct BbRec {
@@ -42,7 +43,7 @@ __device__ __forceinline__ BbPre bc_bb_prefetch(const BbArgs& a) {
 
 // Whole block (any size that is a multiple of 64, nblk <= BC_BB_PER * blockDim.x); `rec` may be LDS or global memory.
 // Returns 1 on overflow (block-uniform; no record then), else 0 with rec = [score, global row, norm, valid, column(S)].
-// ctrl: the pre-filter's counters ([1] last launch overflowed, [3] overflows, u64 [4..5] sweeps, [6..7] rows rescored).
+// ctrl: the pre-filter's control block (bc_pref_ctrl.h): last launch overflowed, overflows, sweeps, rows rescored.
 __device__ __forceinline__ int bc_bb_pick(const BbArgs& a, const BbPre& pre, int s, int* ctrl, double* __restrict__ rec) {
   __shared__ double sv[16], sn[16];
   __shared__ long long si[16];
@@ -80,11 +81,10 @@ __device__ __forceinline__ int bc_bb_pick(const BbArgs& a, const BbPre& pre, int
   int tot = 0, anyovf = 0;
   for (int w = 0; w < nw; ++w) { tot += sres[w]; anyovf |= sovf[w]; }
   if (threadIdx.x == blockDim.x - 1) {
-    ctrl[1] = anyovf ? 1 : 0;
-    if (anyovf) ctrl[3] += 1;
-    unsigned long long* st = reinterpret_cast<unsigned long long*>(ctrl + 4);
-    st[0] += 1;
-    st[1] += anyovf ? 0ull : (unsigned long long)tot;
+    ctrl[BC_PCTL_OVERFLOWED] = anyovf ? 1 : 0;
+    if (anyovf) ctrl[BC_PCTL_OVERFLOWS] += 1;
+    *reinterpret_cast<unsigned long long*>(ctrl + BC_PCTL_SWEEPS) += 1;
+    *reinterpret_cast<unsigned long long*>(ctrl + BC_PCTL_RESCORED) += anyovf ? 0ull : (unsigned long long)tot;
   }
   if (anyovf) return 1;
   if (threadIdx.x == 0) {

@@ -7,9 +7,11 @@
 #include <functional>
 #include <vector>
 #include "../../include/beta_cores.h"
+#include "bc_layout.h"
 
 #define BC_WAVE 64
-#define BC_TILE BC_TILE_ROWS          // rows per Phi tile
+#define BC_TILE BC_LAY_TILE           // rows per Phi tile: bc_layout.h's value, which the public header states to callers
+static_assert(BC_TILE_ROWS == BC_LAY_TILE, "include/beta_cores.h documents the tile's rows");
 #define BC_REC_HDR 4                  // candidate record header doubles: score, gidx(bits), norm, valid
 
 void bc_set_error(const char* fmt, ...);
@@ -227,6 +229,15 @@ int bc_phi_set_rows(bc_phi* phi, int64_t n_rows);   // 0 if n_rows fits the capa
 int bc_phi_finish_stats(bc_phi* phi);   // tile_part -> colsum, norm stats (device), then host copy
 int bc_phi_reduce_colsum(bc_phi* phi);  // tile_part -> colsum on the device only: no norm statistics, no host copy, no sync
 int bc_sweep_grid(const bc_phi* phi);
+// bc_sweep.hip: the exact fp64 K3 sweep with v_dev, enqueued only (rec_dev == nullptr: no record, the caller reduces
+// blk_val / blk_idx itself)
+int bc_launch_sweep(bc_phi* p, int mode, const double* v_dev, double post_div, const int* skip_flag, double* rec_dev);
+
+// bc_comm.hip, for the other units (a communicator's C ABI is include/beta_cores.h): enqueued on the context's stream, no
+// host synchronisation; *result_dev of the rank-order sum stays valid until the next sum through the communicator
+bc_ctx* bc_comm_ctx(const bc_comm* c);
+int bc_comm_all_gather_dev(bc_comm* c, const double* send_dev, double* recv_dev, size_t count);
+int bc_comm_sum_dev(bc_comm* c, const double* in_dev, int64_t count, const double** result_dev);
 
 // ------------------------------------------------------------------ device helpers
 #if defined(__HIPCC__)

@@ -22,10 +22,11 @@
 #define BC_LAY static inline
 #endif
 
-#define BC_LAY_TILE 128      /* == BC_TILE_ROWS */
-#define BC_LAY_ITILE 256     /* == BC_ITILE */
-#define BC_LAY_IU 5          /* == BC_IU */
-#define BC_LAY_IMAXG 320     /* == BC_IMAXG: k-groups the sweep's digit table holds */
+/* the one definition of each: bc_internal.h (BC_TILE) and bc_prefilter_i8.h (BC_ITILE, BC_IU, BC_IMAXG) alias them */
+#define BC_LAY_TILE 128      /* rows per Phi tile (BC_TILE_ROWS of include/beta_cores.h) */
+#define BC_LAY_ITILE 256     /* rows per tile of the int8 and 4-bit mirrors */
+#define BC_LAY_IU 5          /* k-groups per batch of the int8 sweep */
+#define BC_LAY_IMAXG 320     /* k-groups the int8 sweep's digit table holds */
 
 BC_LAY long long bc_lay_tiles(long long n_rows) { return (n_rows + BC_LAY_TILE - 1) / BC_LAY_TILE; }
 BC_LAY size_t bc_lay_phi_doubles(long long tiles, int S) { return (size_t)tiles * (size_t)S * BC_LAY_TILE; }

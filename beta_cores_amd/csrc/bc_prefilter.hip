@@ -25,8 +25,8 @@
 //
 // The fp16 kernel accumulates in fp32 (v_cvt_f32_f16 + v_pk_fma_f32: both dot products of a row in one packed
 // FMA) and double-buffers its loads in registers; its planes are padded with zeros to a multiple of BC_HU and
-// the sweep vectors carry a zero tail (BC_V_PAD, bc_snnls.hip), so there is no remainder loop.
-#include "bc_rescore_dev.h"
+// the sweep vectors carry a zero tail (BC_V_PAD, bc_rescore_dev.h), so there is no remainder loop.
+#include "bc_pref.h"
 #include "../../include/beta_cores_prefdiag.h"
 #include <cstdlib>
 #include <cstring>
@@ -87,10 +87,7 @@ struct bc_pref {
   int* l2_blk_nc = nullptr;
   int2* spill = nullptr;           // [cap] pairs of blocks with more than BC_BLK_NC rows in play
   long long* cand = nullptr;  // [cap] candidate LOCAL rows
-  int* ctrl = nullptr;        // [1] the last rescoring overflowed, [3] overflows so far,
-                              // [4..5] sweeps so far (u64), [6..7] candidates rescored so far (u64); two-level form: [9] position
-                              // in the seeds' ring, [12..13] rows passed on by the first level so far (u64), [14] pairs in the spill
-                              // list of the sweep in flight; branch-and-bound form: [16..17] its shared bound
+  int* ctrl = nullptr;        // [BC_PCTL_INTS] the control block, every field of it named in bc_pref_ctrl.h
   int cap = 4096;
   long long ptiles = 0;
   int grid = 1;
@@ -256,7 +253,7 @@ __global__ __launch_bounds__(256) void k_sweep_f16(PrefArgs a) {
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-          const int kk = k + u;        // planes S..SP-1 are zero and so is v's tail (BC_V_PAD in bc_snnls.hip)
+          const int kk = k + u;        // planes S..SP-1 are zero and so is v's tail (BC_V_PAD)
           if (MODE == 0) {
             const double2 vv = v2[kk];
             const float vx = (float)vv.x, vy = (float)vv.y;
@@ -383,8 +380,6 @@ int bc_pref_create(bc_phi* phi, int prec, bc_pref** out) {
   p->sp4 = bc_lay_i8_sp4(phi->s);
   p->ptiles = (phi->n_rows + p->ptile - 1) / p->ptile;
   if (p->ptiles < 1) p->ptiles = 1;
-  static_assert(BC_BLK_NC == BC_RS_BLK_NC, "bc_rescore_dev.h mirrors the block list length");
-  static_assert(BC_ITILE == BC_LAY_ITILE && BC_IU == BC_LAY_IU && BC_TILE == BC_LAY_TILE && BC_IMAXG == BC_LAY_IMAXG, "bc_layout.h mirrors these");
   // one wave per tile and a grid-stride loop: size the grid so that all its waves are resident at once
   // (4 per SIMD) and every wave walks the same number of tiles -- a 2x over-subscribed grid left waves with
   // 2 or 3 tiles each (79% balance at 10M rows)
@@ -434,7 +429,7 @@ int bc_pref_create(bc_phi* phi, int prec, bc_pref** out) {
   const size_t o_bl = take((size_t)p->grid * sizeof(double));
   const size_t o_bu = take((size_t)p->grid * sizeof(float));
   const size_t o_c = take((size_t)p->cap * sizeof(long long));
-  const size_t o_ctrl = take(256);
+  const size_t o_ctrl = take(BC_PCTL_BYTES);
   const size_t o_bc = take(p->prec == 8 ? (size_t)p->grid * BC_BLK_NC * sizeof(int2) : 0);
   const size_t o_bn = take(p->prec == 8 ? (size_t)p->grid * sizeof(int) : 0);
   const size_t o_bbr = take(p->bb ? (size_t)p->grid * sizeof(BbRec) : 0);
@@ -442,12 +437,12 @@ int bc_pref_create(bc_phi* phi, int prec, bc_pref** out) {
   const size_t o_u4 = take(p->two ? bc_lay_i4_words(p->ptiles, p->sp8) * sizeof(int) : 0);
   const size_t o_rq4 = take(p->two ? (size_t)p->ptiles * BC_ITILE * sizeof(unsigned short) : 0);
   const size_t o_r8 = take(p->two ? (size_t)p->ptiles * BC_ITILE * p->rb : 0);
-  const size_t o_hot = take(p->two ? (BC_I4_SEEDS + BC_I4_HOT) * sizeof(long long) : 0);
+  const size_t o_hot = take(p->two ? BC_I4_SEED_BYTES : 0);
   const size_t o_l2l = take(p->two ? (size_t)p->grid1 * sizeof(double) : 0);
   const size_t o_l2u = take(p->two ? (size_t)p->grid1 * sizeof(float) : 0);
   const size_t o_l2c = take(p->two ? (size_t)p->grid1 * BC_BLK_NC * sizeof(int2) : 0);
   const size_t o_l2n = take(p->two ? (size_t)p->grid1 * sizeof(int) : 0);
-  const size_t o_sp = take(p->two ? (size_t)4096 * sizeof(int2) : 0);
+  const size_t o_sp = take(p->two ? (size_t)BC_PREF_SPILL_CAP * sizeof(int2) : 0);
   hipError_t e = hipMalloc(&p->slab, off);
   if (e != hipSuccess) { delete p; return bc_hip_fail(e, "hipMalloc(prefilter)", __FILE__, __LINE__); }
   char* base = (char*)p->slab;
@@ -486,14 +481,13 @@ int bc_pref_create(bc_phi* phi, int prec, bc_pref** out) {
   p->cand = (long long*)(base + o_c);
   p->ctrl = (int*)(base + o_ctrl);
   if (p->bb) {
-    p->bb_theta = reinterpret_cast<unsigned long long*>(p->ctrl + 16);      // inside the zeroed control block (sequence 0 = "none")
+    p->bb_theta = reinterpret_cast<unsigned long long*>(p->ctrl + BC_PCTL_BB_THETA);      // inside the zeroed control block (sequence 0 = "none")
     p->bb_rec = (BbRec*)(base + o_bbr);
     p->bb_col = (double*)(base + o_bbc);
   }
-  e = hipMemsetAsync(p->ctrl, 0, 256, ctx->stream);
+  e = hipMemsetAsync(p->ctrl, 0, BC_PCTL_BYTES, ctx->stream);
   if (e == hipSuccess) {
-    if (p->prec == 8)
-    {
+    if (p->prec == 8) {
       const int two_pass = getenv("BC_BUILD_I8_TWO_PASS") ? atoi(getenv("BC_BUILD_I8_TWO_PASS")) : 0;   // (A/B and tests: read per call)
       if (phi->s <= 104 && !two_pass)        // (S <= 104 covers every BASELINE configuration; two-pass kernel for the rest)
         hipLaunchKernelGGL(k_build_i8_r<104>, dim3((unsigned)p->ptiles), dim3(256), 0, ctx->stream, phi->tiles, phi->norms,
@@ -501,16 +495,14 @@ int bc_pref_create(bc_phi* phi, int prec, bc_pref** out) {
       else
         hipLaunchKernelGGL(k_build_i8, dim3((unsigned)p->ptiles), dim3(256), 0, ctx->stream, phi->tiles, phi->norms,
                            (long long)phi->n_rows, phi->s, p->sp4, p->u8, p->rowq);
-    }
-    if (p->two && e == hipSuccess) {
-      e = hipMemsetAsync(p->hot, 0xff, (BC_I4_SEEDS + BC_I4_HOT) * sizeof(long long), ctx->stream);            // -1: no seeds yet
-      if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_build_i4, dim3((unsigned)p->ptiles), dim3(256), 0, ctx->stream, phi->tiles, phi->norms,
-                           (long long)phi->n_rows, phi->s, p->sp8, p->u8, p->rowq, p->sp4, p->g4, p->u4, p->rowq4);
-        hipLaunchKernelGGL(k_build_r8, dim3((unsigned)p->ptiles), dim3(256), 0, ctx->stream, p->u8, p->rowq, p->sp4, p->g4, p->rb, p->r8);
+      if (p->two) {                            // (only ever behind an int8 mirror)
+        e = hipMemsetAsync(p->hot, 0xff, BC_I4_SEED_BYTES, ctx->stream);            // -1: no seeds yet
+        if (e == hipSuccess) {
+          hipLaunchKernelGGL(k_build_i4, dim3((unsigned)p->ptiles), dim3(256), 0, ctx->stream, phi->tiles, phi->norms,
+                             (long long)phi->n_rows, phi->s, p->sp8, p->u8, p->rowq, p->sp4, p->g4, p->u4, p->rowq4);
+          hipLaunchKernelGGL(k_build_r8, dim3((unsigned)p->ptiles), dim3(256), 0, ctx->stream, p->u8, p->rowq, p->sp4, p->g4, p->rb, p->r8);
+        }
       }
-    }
-    if (p->prec == 8) {
     } else if (p->prec == 16)
       hipLaunchKernelGGL(k_build_u16, dim3((unsigned)p->ptiles), dim3(256), 0, ctx->stream, phi->tiles, phi->norms,
                          (long long)phi->n_rows, phi->s, p->sp, p->u16, p->live);
@@ -530,9 +522,92 @@ void bc_pref_destroy(bc_pref* p) {
   delete p;
 }
 
-const int* bc_pref_ctrl(const bc_pref* p) { return p->ctrl; }
+static long long pctl_u64(const int* ctrl, int word) {
+  unsigned long long v;
+  memcpy(&v, ctrl + word, sizeof(v));
+  return (long long)v;
+}
+
+int bc_pref_read_counters(const bc_pref* p, bc_pref_counters* out) {
+  int ctrl[BC_PCTL_INTS];
+  BC_HIP(hipMemcpyAsync(ctrl, p->ctrl, BC_PCTL_BYTES, hipMemcpyDeviceToHost, p->ctx->stream));
+  BC_HIP(hipStreamSynchronize(p->ctx->stream));
+  out->overflows = ctrl[BC_PCTL_OVERFLOWS];
+  out->sweeps = pctl_u64(ctrl, BC_PCTL_SWEEPS);
+  out->rescored = pctl_u64(ctrl, BC_PCTL_RESCORED);
+  out->l1_passed = pctl_u64(ctrl, BC_PCTL_L1_PASSED);
+  out->l1_seq = (long long)p->l1_seq;
+  return BC_OK;
+}
+
 void bc_pref_set_cap(bc_pref* p, int cap) { if (cap >= 1 && cap <= 4096) p->cap = cap; }
 int bc_pref_precision(const bc_pref* p) { return p->prec; }
+
+// Will a sweep with these digit records take the two-level form?  It needs both records (from the owner's step kernels) and
+// seeds from an earlier rescoring; the host's watch (bc_pref_adapt) may have put the form aside.
+static bool sweeps_two_level(const bc_pref* p, const int* qv, const int* qv4) {
+  return p->two && p->two_active && qv != nullptr && qv4 != nullptr && p->sweeps_launched > 0;
+}
+
+// the argument blocks of the two-level and of the one-level int8 sweep; the dump instances add their outputs behind them
+static void fill_i4_args(const bc_pref* p, const int* qv, const int* qv4, const int* skip_flag, double post_div, I4Args* fa) {
+  fa->u4 = p->u4;
+  fa->rowq4 = p->rowq4;
+  fa->qv4 = qv4;
+  fa->qv8 = qv;
+  fa->r8 = p->r8;
+  fa->hot = p->hot;
+  fa->skip_flag = skip_flag;
+  fa->blk_l = p->l2_blk_l;
+  fa->blk_u = p->l2_blk_u;
+  fa->blk_cand = p->l2_blk_cand;
+  fa->blk_nc = p->l2_blk_nc;
+  fa->ctrl = p->ctrl;
+  fa->spill = p->spill;
+  fa->spill_cap = BC_PREF_SPILL_CAP;
+  fa->ptiles = p->ptiles;
+  fa->post_div = post_div;
+  fa->s = p->phi->s;
+  fa->sp8 = p->sp8;
+  fa->sp4 = p->sp4;
+  fa->g4 = p->g4;
+  fa->rb = p->rb;
+}
+
+static void fill_i8_args(const bc_pref* p, const double* v_dev, const double* v_norm_dev, const int* qv, const int* skip_flag,
+                         double post_div, I8Args* ia) {
+  ia->u8 = p->u8;
+  ia->rowq = p->rowq;
+  ia->v = v_dev;
+  ia->qv = qv;
+  ia->skip_flag = skip_flag;
+  ia->v_norm = v_norm_dev;
+  ia->tile_u = p->tile_u;
+  ia->tile_cand = p->tile_cand;
+  ia->tile_ncand = p->tile_ncand;
+  ia->blk_l = p->blk_l;
+  ia->blk_u = p->blk_u;
+  ia->blk_cand = p->bb ? nullptr : p->blk_cand;      // (the branch-and-bound sweep keeps no block lists; it has no dump instance)
+  ia->blk_nc = p->bb ? nullptr : p->blk_nc;
+  ia->ptiles = p->ptiles;
+  ia->post_div = post_div;
+  ia->s = p->phi->s;
+  ia->sp4 = p->sp4;
+}
+
+// the instance of k_sweep_i4 for this pre-filter's batch size (bc_lay_i4_batch); Args: I4Args, or I4DumpArgs with DUMP
+template <int MODE, bool DUMP, typename Args>
+static void launch_sweep_i4(const bc_pref* p, const Args& fa) {
+  const dim3 grid(p->grid1), block(256);
+  hipStream_t st = p->ctx->stream;
+  switch (p->i4_u) {
+    case 13: hipLaunchKernelGGL((k_sweep_i4<MODE, 13, DUMP>), grid, block, 0, st, fa); break;
+    case 8: hipLaunchKernelGGL((k_sweep_i4<MODE, 8, DUMP>), grid, block, 0, st, fa); break;
+    case 7: hipLaunchKernelGGL((k_sweep_i4<MODE, 7, DUMP>), grid, block, 0, st, fa); break;
+    case 6: hipLaunchKernelGGL((k_sweep_i4<MODE, 6, DUMP>), grid, block, 0, st, fa); break;
+    default: hipLaunchKernelGGL((k_sweep_i4<MODE, 5, DUMP>), grid, block, 0, st, fa); break;
+  }
+}
 
 // pass A: the reduced-precision sweep (bounds per tile / block); fills the argument block of passes B + C
 int bc_pref_launch_sweep(bc_pref* p, int mode, const double* v_dev, const double* v_norm_dev, double post_div,
@@ -559,67 +634,18 @@ int bc_pref_launch_sweep(bc_pref* p, int mode, const double* v_dev, const double
   a.s = phi->s;
   int rc = bc_timer_begin(ctx, 0);
   if (rc) return rc;
-  // two-level form: needs both digit records from the owner's step kernels and seeds from an earlier rescoring
-  const bool two = p->two && p->two_active && p->qv != nullptr && p->qv4 != nullptr && p->sweeps_launched > 0;
+  const bool two = sweeps_two_level(p, p->qv, p->qv4);
   p->sweeps_launched += 1;
   if (p->two && !p->two_active) p->int8_since += 1;
   if (two) {
     I4Args fa;
-    fa.u4 = p->u4;
-    fa.rowq4 = p->rowq4;
-    fa.qv4 = p->qv4;
-    fa.qv8 = p->qv;
-    fa.r8 = p->r8;
-    fa.hot = p->hot;
-    fa.skip_flag = skip_flag;
-    fa.blk_l = p->l2_blk_l;
-    fa.blk_u = p->l2_blk_u;
-    fa.blk_cand = p->l2_blk_cand;
-    fa.blk_nc = p->l2_blk_nc;
-    fa.ctrl = p->ctrl;
-    fa.spill = p->spill;
-    fa.spill_cap = 4096;
-    fa.ptiles = p->ptiles;
-    fa.post_div = post_div;
+    fill_i4_args(p, p->qv, p->qv4, skip_flag, post_div, &fa);
     p->l1_seq += 1;
-    fa.s = phi->s;
-    fa.sp8 = p->sp8;
-    fa.sp4 = p->sp4;
-    fa.g4 = p->g4;
-    fa.rb = p->rb;
-#define BC_I4_LAUNCH(MODE, UU) hipLaunchKernelGGL((k_sweep_i4<MODE, UU>), dim3(p->grid1), dim3(256), 0, ctx->stream, fa)
-#define BC_I4_BY_U(MODE)                                                                          \
-    switch (p->i4_u) {                                                                            \
-      case 13: BC_I4_LAUNCH(MODE, 13); break;                                                     \
-      case 8: BC_I4_LAUNCH(MODE, 8); break;                                                       \
-      case 7: BC_I4_LAUNCH(MODE, 7); break;                                                       \
-      case 6: BC_I4_LAUNCH(MODE, 6); break;                                                       \
-      default: BC_I4_LAUNCH(MODE, 5); break;                                                      \
-    }
-    if (mode == 0) { BC_I4_BY_U(0) } else { BC_I4_BY_U(1) }
-    BC_HIP(hipGetLastError());
-    rc = bc_timer_end(ctx, 0);
-    if (rc) return rc;
-  } else
-  if (p->prec == 8) {
+    if (mode == 0) launch_sweep_i4<0, false>(p, fa);
+    else launch_sweep_i4<1, false>(p, fa);
+  } else if (p->prec == 8) {
     I8Args ia;
-    ia.u8 = p->u8;
-    ia.rowq = p->rowq;
-    ia.v = v_dev;
-    ia.qv = p->qv;
-    ia.skip_flag = skip_flag;
-    ia.v_norm = v_norm_dev;
-    ia.tile_u = p->tile_u;
-    ia.tile_cand = p->tile_cand;
-    ia.tile_ncand = p->tile_ncand;
-    ia.blk_l = p->blk_l;
-    ia.blk_u = p->blk_u;
-    ia.blk_cand = p->bb ? nullptr : p->blk_cand;
-    ia.blk_nc = p->bb ? nullptr : p->blk_nc;
-    ia.ptiles = p->ptiles;
-    ia.post_div = post_div;
-    ia.s = phi->s;
-    ia.sp4 = p->sp4;
+    fill_i8_args(p, v_dev, v_norm_dev, p->qv, skip_flag, post_div, &ia);
     if (p->bb) {
       I8BbArgs ba;
       ba.a = ia;
@@ -644,11 +670,9 @@ int bc_pref_launch_sweep(bc_pref* p, int mode, const double* v_dev, const double
     if (mode == 0) hipLaunchKernelGGL(k_sweep_f32<0>, dim3(p->grid), dim3(256), 0, ctx->stream, a);
     else hipLaunchKernelGGL(k_sweep_f32<1>, dim3(p->grid), dim3(256), 0, ctx->stream, a);
   }
-  if (!two) {
-    BC_HIP(hipGetLastError());
-    rc = bc_timer_end(ctx, 0);
-    if (rc) return rc;
-  }
+  BC_HIP(hipGetLastError());
+  rc = bc_timer_end(ctx, 0);
+  if (rc) return rc;
   RescoreArgs& r = *r_out;
   r.bb.rec = p->bb ? p->bb_rec : nullptr;
   r.bb.col = p->bb_col;
@@ -683,7 +707,7 @@ int bc_pref_launch_sweep(bc_pref* p, int mode, const double* v_dev, const double
   r.ptile = p->ptile;
   r.two_level = two ? 1 : 0;
   r.spill = p->spill;
-  r.spill_cap = 4096;
+  r.spill_cap = BC_PREF_SPILL_CAP;
   r.hot = p->two ? p->hot + BC_I4_SEEDS : nullptr;      // (the ring behind the sweep blocks' slots)
   if (two) {
     // the two-level sweep's block lists; there are no tiles behind them
@@ -716,7 +740,7 @@ int bc_pref_adapt(bc_pref* p) {
   const unsigned dl1 = p->l1_seq - p->chk_l1;
   if (!probe_due && !(p->two_active && dl1 >= 4)) return BC_OK;
   unsigned long long rows = 0;
-  BC_HIP(hipMemcpyAsync(&rows, p->ctrl + 12, sizeof(rows), hipMemcpyDeviceToHost, p->ctx->stream));
+  BC_HIP(hipMemcpyAsync(&rows, p->ctrl + BC_PCTL_L1_PASSED, sizeof(rows), hipMemcpyDeviceToHost, p->ctx->stream));
   BC_HIP(hipStreamSynchronize(p->ctx->stream));
   if (p->two_active) {
     const double share = (double)(rows - p->chk_rows) / ((double)dl1 * (double)(p->phi->n_rows > 0 ? p->phi->n_rows : 1));
@@ -737,7 +761,6 @@ int bc_pref_adapt(bc_pref* p) {
 }
 int bc_pref_two_level_active(const bc_pref* p) { return (p->two && p->two_active) ? 1 : 0; }
 
-long long bc_pref_l1_sweeps(const bc_pref* p) { return (long long)p->l1_seq; }     // (host count: includes sweeps the device skipped)
 int bc_pref_sp4(const bc_pref* p) { return p->sp4; }
 int bc_pref_bb(const bc_pref* p) { return p->bb ? 1 : 0; }
 
@@ -774,11 +797,11 @@ void bc_pref_diag_info(const bc_pref* p, bool qv_set, int64_t* out) {
   out[BC_PREFDIAG_TWO_ACTIVE] = (p->two && p->two_active) ? 1 : 0;
   out[BC_PREFDIAG_IFLUSH] = BC_IFLUSH;
   out[BC_PREFDIAG_BLK_NC] = BC_BLK_NC;
-  out[BC_PREFDIAG_NEXT_FORM] = p->bb ? 2 : ((p->two && p->two_active && p->qv && p->qv4 && p->sweeps_launched > 0) ? 3 : 1);
+  out[BC_PREFDIAG_NEXT_FORM] = p->bb ? 2 : (sweeps_two_level(p, p->qv, p->qv4) ? 3 : 1);
   out[BC_PREFDIAG_QV] = (qv_set && p->qv) ? 1 : 0;
   out[BC_PREFDIAG_SEEDS] = BC_I4_SEEDS;
   out[BC_PREFDIAG_HOT] = BC_I4_HOT;
-  out[BC_PREFDIAG_SPILL_CAP] = 4096;
+  out[BC_PREFDIAG_SPILL_CAP] = BC_PREF_SPILL_CAP;
 }
 
 // 0: found (*dev, *bytes); 1: no such name; 2: this form of the pre-filter has no such buffer
@@ -804,9 +827,9 @@ int bc_pref_diag_buffer(const bc_pref* p, const char* which, const void** dev, s
       {"l2_blk_u", p->l2_blk_u, (size_t)p->grid1 * sizeof(float)},
       {"l2_blk_cand", p->l2_blk_cand, (size_t)p->grid1 * BC_BLK_NC * sizeof(int2)},
       {"l2_blk_nc", p->l2_blk_nc, (size_t)p->grid1 * sizeof(int)},
-      {"spill", p->spill, (size_t)4096 * sizeof(int2)},
-      {"hot", p->hot, (size_t)(BC_I4_SEEDS + BC_I4_HOT) * sizeof(long long)},
-      {"ctrl", p->ctrl, 256},
+      {"spill", p->spill, (size_t)BC_PREF_SPILL_CAP * sizeof(int2)},
+      {"hot", p->hot, BC_I4_SEED_BYTES},
+      {"ctrl", p->ctrl, BC_PCTL_BYTES},
   };
   for (const Ent& e : tab)
     if (strcmp(which, e.name) == 0) {
@@ -819,7 +842,7 @@ int bc_pref_diag_buffer(const bc_pref* p, const char* which, const void** dev, s
 }
 
 // bytes of device scratch bc_pref_diag_sweep needs to put the seeds and the control block aside
-size_t bc_pref_diag_save_bytes(void) { return (BC_I4_SEEDS + BC_I4_HOT) * sizeof(long long) + 256; }
+size_t bc_pref_diag_save_bytes(void) { return BC_I4_SEED_BYTES + BC_PCTL_BYTES; }
 
 // One sweep of the form the next production sweep would take (two-level, else the one-level int8 sweep) through the DUMP
 // instances of the sweep kernels: no rescoring, no skip flag, none of the host-side counters touched; the seeds and the control
@@ -828,72 +851,27 @@ size_t bc_pref_diag_save_bytes(void) { return (BC_I4_SEEDS + BC_I4_HOT) * sizeof
 int bc_pref_diag_sweep(bc_pref* p, int mode, const double* v_dev, const double* v_norm_dev, const int* qv, const int* qv4,
                        double post_div, float2* dump1, float2* dump2, float* theta0, void* save_dev, int* form_run) {
   bc_ctx* ctx = p->ctx;
-  bc_phi* phi = p->phi;
-  const bool two = p->two && p->two_active && qv != nullptr && qv4 != nullptr && p->sweeps_launched > 0;
+  const bool two = sweeps_two_level(p, qv, qv4);
   *form_run = two ? 3 : 1;
   if (two) {
-    const size_t hot_bytes = (BC_I4_SEEDS + BC_I4_HOT) * sizeof(long long);
-    BC_HIP(hipMemcpyAsync(save_dev, p->hot, hot_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-    BC_HIP(hipMemcpyAsync((char*)save_dev + hot_bytes, p->ctrl, 256, hipMemcpyDeviceToDevice, ctx->stream));
+    char* const save_ctrl = (char*)save_dev + BC_I4_SEED_BYTES;
+    BC_HIP(hipMemcpyAsync(save_dev, p->hot, BC_I4_SEED_BYTES, hipMemcpyDeviceToDevice, ctx->stream));
+    BC_HIP(hipMemcpyAsync(save_ctrl, p->ctrl, BC_PCTL_BYTES, hipMemcpyDeviceToDevice, ctx->stream));
     BC_HIP(hipMemsetAsync(dump2, 0xff, (size_t)p->ptiles * BC_ITILE * sizeof(float2), ctx->stream));      // NaN: not re-bounded
     I4DumpArgs fa;
-    fa.u4 = p->u4;
-    fa.rowq4 = p->rowq4;
-    fa.qv4 = qv4;
-    fa.qv8 = qv;
-    fa.r8 = p->r8;
-    fa.hot = p->hot;
-    fa.skip_flag = nullptr;
-    fa.blk_l = p->l2_blk_l;
-    fa.blk_u = p->l2_blk_u;
-    fa.blk_cand = p->l2_blk_cand;
-    fa.blk_nc = p->l2_blk_nc;
-    fa.ctrl = p->ctrl;
-    fa.spill = p->spill;
-    fa.spill_cap = 4096;
-    fa.ptiles = p->ptiles;
-    fa.post_div = post_div;
-    fa.s = phi->s;
-    fa.sp8 = p->sp8;
-    fa.sp4 = p->sp4;
-    fa.g4 = p->g4;
-    fa.rb = p->rb;
+    fill_i4_args(p, qv, qv4, nullptr, post_div, &fa);
     fa.dump1 = dump1;
     fa.dump2 = dump2;
     fa.theta0 = theta0;
-#define BC_I4_DUMP(MODE, UU) hipLaunchKernelGGL((k_sweep_i4<MODE, UU, true>), dim3(p->grid1), dim3(256), 0, ctx->stream, fa)
-#define BC_I4_DUMP_BY_U(MODE)                                                                     \
-    switch (p->i4_u) {                                                                            \
-      case 13: BC_I4_DUMP(MODE, 13); break;                                                       \
-      case 8: BC_I4_DUMP(MODE, 8); break;                                                         \
-      case 7: BC_I4_DUMP(MODE, 7); break;                                                         \
-      case 6: BC_I4_DUMP(MODE, 6); break;                                                         \
-      default: BC_I4_DUMP(MODE, 5); break;                                                        \
-    }
-    if (mode == 0) { BC_I4_DUMP_BY_U(0) } else { BC_I4_DUMP_BY_U(1) }
+    if (mode == 0) launch_sweep_i4<0, true>(p, fa);
+    else launch_sweep_i4<1, true>(p, fa);
     BC_HIP(hipGetLastError());
-    BC_HIP(hipMemcpyAsync(p->hot, save_dev, hot_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-    BC_HIP(hipMemcpyAsync(p->ctrl, (char*)save_dev + hot_bytes, 256, hipMemcpyDeviceToDevice, ctx->stream));
+    BC_HIP(hipMemcpyAsync(p->hot, save_dev, BC_I4_SEED_BYTES, hipMemcpyDeviceToDevice, ctx->stream));
+    BC_HIP(hipMemcpyAsync(p->ctrl, save_ctrl, BC_PCTL_BYTES, hipMemcpyDeviceToDevice, ctx->stream));
     return BC_OK;
   }
   I8DumpArgs ia;
-  ia.u8 = p->u8;
-  ia.rowq = p->rowq;
-  ia.v = v_dev;
-  ia.qv = qv;
-  ia.skip_flag = nullptr;
-  ia.v_norm = v_norm_dev;
-  ia.tile_u = p->tile_u;
-  ia.tile_cand = p->tile_cand;
-  ia.tile_ncand = p->tile_ncand;
-  ia.blk_l = p->blk_l;
-  ia.blk_u = p->blk_u;
-  ia.blk_cand = p->blk_cand;
-  ia.blk_nc = p->blk_nc;
-  ia.ptiles = p->ptiles;
-  ia.post_div = post_div;
-  ia.s = phi->s;
-  ia.sp4 = p->sp4;
+  fill_i8_args(p, v_dev, v_norm_dev, qv, nullptr, post_div, &ia);
   ia.dump = dump1;
   if (mode == 0) hipLaunchKernelGGL((k_sweep_i8<0, true>), dim3(p->grid), dim3(256), 0, ctx->stream, ia);
   else hipLaunchKernelGGL((k_sweep_i8<1, true>), dim3(p->grid), dim3(256), 0, ctx->stream, ia);

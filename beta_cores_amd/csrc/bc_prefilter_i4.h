@@ -35,8 +35,9 @@
 #define BC_I4_MAXG 48        // k-groups of 8 the 4-bit digit table holds (S <= 256 plus padding)
 #define BC_I4_MAXG8 72       // k-groups of 4 of the int8 digit table (seeds, level 2): S <= 256 plus padding
 #define BC_I4_PARK 128       // rows a wave parks in LDS before it appends them to the global list
-#define BC_I4_HOT 32         // seeds: ring of rows that were in play lately (local row numbers, -1: empty) ...
-#define BC_I4_SEEDS 256      // ... behind one slot per sweep block (its strongest row; the last BC_I4_HOT slots are not read): hot[BC_I4_SEEDS + BC_I4_HOT]
+#define BC_I4_SEEDS 256      // seeds: one slot per sweep block (its strongest row; the last BC_I4_HOT slots are not read) in front
+                             // of the ring of BC_I4_HOT rows (bc_rescore_dev.h, which writes it): hot[BC_I4_SEEDS + BC_I4_HOT]
+#define BC_I4_SEED_BYTES ((size_t)(BC_I4_SEEDS + BC_I4_HOT) * sizeof(long long))
 #define BC_I4_DEAD 255       // delta code of a dead row (padding or zero norm)
 #define BC_I4_UNCERTAIN 254  // delta code of a row the bound cannot cover (NaN / inf in it, or delta too large for the code)
 #define BC_L2_LCAP 512       // rows in play a block can hold before it gives up (-> exact redo); rows that cannot reach the
@@ -54,7 +55,7 @@ struct I4Args {
   float* blk_u;
   int2* blk_cand;                // [grid][BC_BLK_NC]
   int* blk_nc;
-  int* ctrl;                     // [12..13] u64 total: rows passed on by level 1 and re-bounded by level 2; [14]: pairs in `spill`
+  int* ctrl;                     // bc_pref_ctrl.h: BC_PCTL_L1_PASSED, rows passed on by level 1 and re-bounded by level 2; BC_PCTL_SPILL_N
   int2* spill;                   // [spill_cap] a block with more than BC_BLK_NC rows in play appends ALL its pairs here (blk_nc = -1)
   int spill_cap;
   long long ptiles;
@@ -485,7 +486,7 @@ __global__ __launch_bounds__(256) void k_sweep_i4(typename std::conditional<DUMP
   if ((int)threadIdx.x < on && threadIdx.x < BC_BLK_NC) a.blk_cand[(size_t)blockIdx.x * BC_BLK_NC + threadIdx.x] = s_out[threadIdx.x];
   bool spilled = false;
   if (on > BC_BLK_NC && n <= BC_L2_LCAP) {             // (block-uniform, rare) too many for the block's own list: the spill list
-    if (threadIdx.x == 0) { s_refined_base = atomicAdd(&a.ctrl[14], on); s_on = 0; }
+    if (threadIdx.x == 0) { s_refined_base = atomicAdd(&a.ctrl[BC_PCTL_SPILL_N], on); s_on = 0; }
     __syncthreads();
     const int gb = s_refined_base;
     spilled = gb + on <= a.spill_cap;
@@ -498,7 +499,7 @@ __global__ __launch_bounds__(256) void k_sweep_i4(typename std::conditional<DUMP
     a.blk_u[blockIdx.x] = bc_ord_f32(s_umax);
     a.blk_nc[blockIdx.x] = (n > BC_L2_LCAP || (on > BC_BLK_NC && !spilled)) ? -2 : (on > BC_BLK_NC ? -1 : on);
     if (bk != 0ull && blockIdx.x < BC_I4_SEEDS) a.hot[blockIdx.x] = (long long)(unsigned)(bk & 0xffffffffull);
-    if (s_refined > 0) atomicAdd(reinterpret_cast<unsigned long long*>(a.ctrl + 12), (unsigned long long)s_refined);
+    if (s_refined > 0) atomicAdd(reinterpret_cast<unsigned long long*>(a.ctrl + BC_PCTL_L1_PASSED), (unsigned long long)s_refined);
   }
   I4STAMP(5);
 }

@@ -30,11 +30,9 @@
 #include <type_traits>
 #include "bc_layout.h"
 #include "bc_i8_quant.h"
-#define BC_ITILE 256      /* == BC_LAY_ITILE (bc_layout.h) */
-#ifndef BC_IU
-#define BC_IU 5          // k-groups per batch (5 KiB in flight per wave and buffer)
-#endif
-#define BC_IMAXG 320     // k-groups the digit table holds: S <= 1280
+#define BC_ITILE BC_LAY_ITILE      // rows per tile of the mirror; the values of these three are bc_layout.h's
+#define BC_IU BC_LAY_IU            // k-groups per batch (5 KiB in flight per wave and buffer)
+#define BC_IMAXG BC_LAY_IMAXG      // k-groups the digit table holds: S <= 1280
 #define BC_IFLUSH 32     // tiles a wave parks in LDS before it writes their results out
 #ifndef BC_I8_DEPTH
 #define BC_I8_DEPTH 1    // batches requested ahead of the one being consumed (2: tools/build_variant.sh experiment, S >= 37 only)
@@ -60,7 +58,6 @@ struct I8Args {
   double post_div;
   int s, sp4;
 };
-#define BC_BLK_NC 8
 // the diagnostic instance's arguments (DUMP = true, include/beta_cores_prefdiag.h): the production block and one output behind it
 struct I8DumpArgs : I8Args {
   float2* dump;             // [ptiles*256] (U, L) of every row, as the sweep evaluated them

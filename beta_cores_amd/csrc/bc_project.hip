@@ -700,8 +700,6 @@ extern "C" int bc_project_from_host_f32(bc_ctx* ctx, const float* z_host, int64_
 // ---------------------------------------------------------------------------------------------
 // Store-free projection: the S column sums of the N x S projection and nothing else (why, and the fused gradient of the
 // greedy-VI weight optimisation that is built on it: bc_vigrad.hip).
-int bc_comm_sum_dev(bc_comm* c, const double* in_dev, int64_t count, const double** result_dev);   // bc_comm.hip
-bc_ctx* bc_comm_ctx(const bc_comm* c);
 
 // the context's stats-only Phi, sized for n_rows x s
 int bc_proj_colsum_phi_for(bc_ctx* ctx, int64_t n_rows, int32_t s, bc_phi** out) {

@@ -13,10 +13,13 @@
 // helper blocks spinning on a flag; that needed all of them co-resident and could time out silently.
 #pragma once
 #include "bc_sweep_dev.h"
+#include "bc_pref_ctrl.h"
 
 #define BC_PREF_DELTA 6.2e-8
 #define BC_HTILE 512   // rows per fp16 tile
 #define BC_HU 10       // fp16 sample planes per batch; the stored plane count is padded to a multiple (zero planes)
+#define BC_V_PAD 16    // doubles of zero padding the solver keeps behind its sweep vector(s): k_sweep_f16 reads whole batches
+static_assert(BC_V_PAD >= BC_HU - 1, "the fp16 sweep reads up to BC_HU - 1 elements past the sweep vector's end");
 #define BC_RS_TILE_LIMIT16 64   // fp16 mode recomputes candidate tiles (~3 us each): past this the fp64 sweep is cheaper
 #define BC_REC_OVERFLOW (-1.0)  // rec[3] of a record that says "this rank's pre-filter overflowed: redo the step exactly"
 typedef _Float16 bc_h2 __attribute__((ext_vector_type(2)));
@@ -65,10 +68,10 @@ struct RescoreArgs {
   int sp;
   const float2* tile_cand;   // int8 mode: the sweep left up to 4 (upper bound, row) pairs per tile
   const int* tile_ncand;
-  const int2* blk_cand;      // int8 mode, round 5: ... and up to BC_RS_BLK_NC (upper bound bits, local row) pairs per BLOCK
+  const int2* blk_cand;      // int8 mode, round 5: ... and up to BC_BLK_NC (upper bound bits, local row) pairs per BLOCK
   const int* blk_nc;         //   (count; -1: walk the block's tiles); nullptr: no such lists
   long long* cand;
-  int* ctrl;
+  int* ctrl;                 // the pre-filter's control block (bc_pref_ctrl.h)
   double* rec;
   long long row_offset, ptiles;
   double post_div;
@@ -78,11 +81,11 @@ struct RescoreArgs {
   // block with more rows in play than its list holds left them in the spill list, one that could not keep them at all means
   // "redo the step exactly"
   int two_level;
-  const int2* spill;         // two-level form: pairs of the blocks whose list says -1 (count in ctrl[14], reset here)
+  const int2* spill;         // two-level form: pairs of the blocks whose list says -1 (count in BC_PCTL_SPILL_N, reset here)
   int spill_cap;
-  long long* hot;            // ring of BC_RS_HOT rows that were in play lately (the first level's seeds), position in ctrl[9]; or nullptr
+  long long* hot;            // ring of BC_I4_HOT rows that were in play lately (the first level's seeds), position in BC_PCTL_RING_POS; or nullptr
 };
-#define BC_RS_HOT 32         /* == BC_I4_HOT (bc_prefilter_i4.h) */
+#define BC_I4_HOT 32         // rows in that ring (local row numbers, -1: empty; a power of two): read by k_sweep_i4 (bc_prefilter_i4.h)
 
 #ifndef FSTAMP      // diagnostic builds define it before including this header (bc_snnls.hip, -DBC_FIN_STAMPS)
 #define FSTAMP(i) do { } while (0)
@@ -222,7 +225,7 @@ __device__ __forceinline__ void bc_rs_accumulate(bc_h2 x, const double* __restri
 // The sweep blocks' bounds a thread of the rescoring block looks at (threads 0..255, blocks t, t+256, ...): a caller
 // with other loads to wait for requests them in the same round (bc_rescore_prefetch) instead of paying a round trip
 // of their own at the start of the rescoring.
-#define BC_RS_BLK_NC 8      /* == BC_BLK_NC (bc_prefilter_i8.h) */
+#define BC_BLK_NC 8         // pairs a sweep block's own candidate list holds (written by k_sweep_i8 and k_sweep_i4)
 #define BC_RS_BLK_PER 2     // block lists a thread looks at: blocks t, t + blockDim (nblk <= 1024, blockDim >= 512)
 struct RescorePre {
   double l[4];
@@ -230,7 +233,7 @@ struct RescorePre {
   // the sweep blocks' own candidate lists (int8 mirror): thread t holds those of blocks t, t + blockDim
   int nc[BC_RS_BLK_PER];
   float bu[BC_RS_BLK_PER];
-  int2 c[BC_RS_BLK_PER][BC_RS_BLK_NC];
+  int2 c[BC_RS_BLK_PER][BC_BLK_NC];
 };
 
 __device__ __forceinline__ RescorePre bc_rescore_prefetch(const RescoreArgs& a) {
@@ -255,9 +258,9 @@ __device__ __forceinline__ RescorePre bc_rescore_prefetch(const RescoreArgs& a) 
     if (a.blk_nc != nullptr && i < a.nblk) {
       p.nc[q] = a.blk_nc[i];
       p.bu[q] = a.blk_u[i];
-      const int4* src = reinterpret_cast<const int4*>(a.blk_cand + (size_t)i * BC_RS_BLK_NC);
+      const int4* src = reinterpret_cast<const int4*>(a.blk_cand + (size_t)i * BC_BLK_NC);
 #pragma unroll
-      for (int e = 0; e < BC_RS_BLK_NC / 2; ++e) {      // loaded whatever the count says: no dependent second round
+      for (int e = 0; e < BC_BLK_NC / 2; ++e) {      // loaded whatever the count says: no dependent second round
         const int4 v = src[e];
         p.c[q][2 * e] = make_int2(v.x, v.y);
         p.c[q][2 * e + 1] = make_int2(v.z, v.w);
@@ -303,7 +306,7 @@ __device__ __forceinline__ int bc_rescore_block(const RescoreArgs& a, long long 
   // (usually one or two), then only the tiles those blocks walked
   if (lists) {
     // every row whose upper bound reaches Lmax is in its block's list (it reaches the block's best lower bound a fortiori);
-    // only a block that could not keep a list (-1: a tile with more than four pairs, more than BC_RS_BLK_NC rows, or tiles
+    // only a block that could not keep a list (-1: a tile with more than four pairs, more than BC_BLK_NC rows, or tiles
     // flushed out of LDS early) goes through the tile walk below
     // (almost every thread finds nothing: one branch-free pass decides whether it has anything to do at all)
     // (Tried and dropped: the thread that finds a candidate touching its fp64 row right away, to start the ~2 us TLB miss of
@@ -316,7 +319,7 @@ __device__ __forceinline__ int bc_rescore_block(const RescoreArgs& a, long long 
     for (int q = 0; q < BC_RS_BLK_PER; ++q) {
       any |= mine.nc[q] < 0 && mine.bu[q] != -INFINITY && mine.bu[q] >= lmf;
 #pragma unroll
-      for (int e = 0; e < BC_RS_BLK_NC; ++e) any |= e < mine.nc[q] && __int_as_float(mine.c[q][e].x) >= lmf;
+      for (int e = 0; e < BC_BLK_NC; ++e) any |= e < mine.nc[q] && __int_as_float(mine.c[q][e].x) >= lmf;
     }
     if (any) {
 #pragma unroll
@@ -329,7 +332,7 @@ __device__ __forceinline__ int bc_rescore_block(const RescoreArgs& a, long long 
           }
         } else {
 #pragma unroll
-          for (int e = 0; e < BC_RS_BLK_NC; ++e) {
+          for (int e = 0; e < BC_BLK_NC; ++e) {
             const float ub = __int_as_float(mine.c[q][e].x);
             if (e < mine.nc[q] && (double)ub >= lmax) {
               const int slot = atomicAdd(&cnt, 1);
@@ -460,7 +463,7 @@ __device__ __forceinline__ int bc_rescore_block(const RescoreArgs& a, long long 
   if (a.two_level) {
     overflow = overflow || ocnt > 0;
     if (!overflow && nbl > 0) {                // (block-uniform, rare) some block in play spilled: scan the spill list
-      const int ns = a.ctrl[14];
+      const int ns = a.ctrl[BC_PCTL_SPILL_N];
       overflow = ns > a.spill_cap;
       if (!overflow)
         for (int i = threadIdx.x; i < ns; i += blockDim.x) {
@@ -595,12 +598,11 @@ __device__ __forceinline__ int bc_rescore_block(const RescoreArgs& a, long long 
     overflow = cnt > a.cap;
   }
   if (threadIdx.x == blockDim.x - 1) {         // (the last wave scores no candidate: its read-modify-writes delay nobody)
-    if (a.two_level) a.ctrl[14] = 0;           // the spill list is consumed (or abandoned)
-    a.ctrl[1] = overflow ? 1 : 0;              // observable: the last launch overflowed
-    if (overflow) a.ctrl[3] += 1;              // ... and how often since creation
-    unsigned long long* st = reinterpret_cast<unsigned long long*>(a.ctrl + 4);   // diagnostics: sweeps, candidates rescored
-    st[0] += 1;
-    st[1] += overflow ? 0 : (unsigned long long)cnt;
+    if (a.two_level) a.ctrl[BC_PCTL_SPILL_N] = 0;           // the spill list is consumed (or abandoned)
+    a.ctrl[BC_PCTL_OVERFLOWED] = overflow ? 1 : 0;          // observable: the last launch overflowed
+    if (overflow) a.ctrl[BC_PCTL_OVERFLOWS] += 1;           // ... and how often since creation
+    *reinterpret_cast<unsigned long long*>(a.ctrl + BC_PCTL_SWEEPS) += 1;      // diagnostics: sweeps, candidates rescored
+    *reinterpret_cast<unsigned long long*>(a.ctrl + BC_PCTL_RESCORED) += overflow ? 0 : (unsigned long long)cnt;
   }
   if (overflow) return 1;
   FSTAMP(12);
@@ -608,10 +610,10 @@ __device__ __forceinline__ int bc_rescore_block(const RescoreArgs& a, long long 
   const int count = cnt;
   // seeds of the two-level form's next sweeps: the rows in play go into the ring (the last wave: it scores nothing)
   if (a.hot != nullptr && wave == nw - 1) {
-    const int pos = a.ctrl[9];
-    const int n = count < BC_RS_HOT ? count : BC_RS_HOT;
-    if (lane < n) a.hot[(pos + lane) & (BC_RS_HOT - 1)] = scand[lane];
-    if (lane == 0) a.ctrl[9] = (pos + n) & (BC_RS_HOT - 1);
+    const int pos = a.ctrl[BC_PCTL_RING_POS];
+    const int n = count < BC_I4_HOT ? count : BC_I4_HOT;
+    if (lane < n) a.hot[(pos + lane) & (BC_I4_HOT - 1)] = scand[lane];
+    if (lane == 0) a.ctrl[BC_PCTL_RING_POS] = (pos + n) & (BC_I4_HOT - 1);
   }
   double bv = -INFINITY, bnorm = 0.;
   long long bi = LLONG_MAX;

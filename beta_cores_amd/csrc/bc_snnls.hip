@@ -18,7 +18,7 @@ extern "C" int bc_debug_fin_stamps(unsigned long long* out) {
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fin_stamps), sizeof(g_fin_stamps)) == hipSuccess ? 0 : -1;
 }
 #endif
-#include "bc_rescore_dev.h"
+#include "bc_pref.h"
 #include "../../include/beta_cores_nnls.h"
 #include "../../include/beta_cores_prefdiag.h"
 #include "bc_layout.h"
@@ -29,30 +29,6 @@ extern "C" int bc_debug_fin_stamps(unsigned long long* out) {
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
-
-int bc_launch_sweep(bc_phi* p, int mode, const double* v_dev, double post_div, const int* skip_flag, double* rec_dev);
-#define BC_PREF_DEFAULT_PREC 8
-#define BC_V_PAD 16            // >= BC_HU - 1 (bc_prefilter.hip): doubles of zero padding after the sweep vector(s)
-struct bc_comm;
-int bc_comm_all_gather_dev(bc_comm* c, const double* send_dev, double* recv_dev, size_t count);
-extern "C" int bc_comm_info(const bc_comm* c, int32_t* rank, int32_t* world);
-struct bc_pref;
-int bc_pref_create(bc_phi* phi, int prec, bc_pref** out);
-int bc_pref_precision(const bc_pref* p);
-void bc_pref_destroy(bc_pref* p);
-void bc_pref_set_cap(bc_pref* p, int cap);
-const int* bc_pref_ctrl(const bc_pref* p);
-void bc_pref_set_qv(bc_pref* p, const int* qv_dev);
-int bc_pref_sp4(const bc_pref* p);
-void bc_pref_set_qv4(bc_pref* p, const int* qv4_dev);
-int bc_pref_sp8(const bc_pref* p);
-int bc_pref_two_level(const bc_pref* p);
-int bc_pref_adapt(bc_pref* p);
-int bc_pref_two_level_active(const bc_pref* p);
-int bc_pref_launch(bc_pref* p, int mode, const double* v_dev, const double* v_norm_dev, double post_div,
-                   const int* skip_flag, double* rec_dev);
-int bc_pref_launch_sweep(bc_pref* p, int mode, const double* v_dev, const double* v_norm_dev, double post_div,
-                         const int* skip_flag, double* rec_dev, RescoreArgs* r_out);
 
 struct SnnlsState {
   long long nnz;        // length of the (idx, val) list, selection order; val may be 0
@@ -1367,6 +1343,30 @@ static bool bc_want_two_level(int preq, long long n_rows, int s) {
   return n_rows >= min_rows;
 }
 
+// What the environment asks of a new solver's pre-filter, read once per bc_snnls_create (tests set it per solver).
+// BC_PREFILTER = 0 (off) / 1 (on, default precision) / 8 / 16 / 32 (on, that storage precision) / 4 (the int8 mirror behind a
+// 4-bit first level); unset: on from BC_PREF_MIN_ROWS rows, where it is worth its extra launches (measured break-even ~131k
+// rows at S = 100 with the int8 mirror, profiles/r01_notes.md).  BC_I8_QV=0: sweeps quantise in their own prologue (A/B, tests).
+#define BC_PREF_MIN_ROWS 163840
+struct PrefWish {
+  bool want;        // a pre-filter is created ...
+  int prec;         // ... with this precision asked of bc_pref_create (4: the two-level form)
+  bool keep_qv;     // the step kernels keep v's int8 digit record current from the start (the int8 sweep reads v as digits) ...
+  bool keep_qv4;    // ... and its 4-bit record, which only the two-level form reads
+};
+static PrefWish pref_wish(long long n_rows, int s) {
+  const char* env = getenv("BC_PREFILTER");
+  const int req = env ? atoi(env) : -1;
+  const char* qenv = getenv("BC_I8_QV");
+  const int prec = (req == 8 || req == 16 || req == 32) ? req : BC_PREF_DEFAULT_PREC;
+  PrefWish w;
+  w.want = (env ? req != 0 : n_rows >= BC_PREF_MIN_ROWS) && n_rows > 0;
+  w.keep_qv = w.want && prec == 8 && (s + 3) / 4 <= BC_LAY_IMAXG - BC_LAY_IU && !(qenv && atoi(qenv) == 0);
+  w.keep_qv4 = w.keep_qv && bc_want_two_level(req, n_rows, s);
+  w.prec = w.keep_qv4 ? 4 : prec;
+  return w;
+}
+
 #define LAUNCH1(kern, ...)                                                         \
   do {                                                                             \
     hipLaunchKernelGGL(kern, dim3(1), dim3(BC_FIN_THREADS), 0, h->ctx->stream, __VA_ARGS__);   \
@@ -1415,6 +1415,7 @@ extern "C" int bc_snnls_create(bc_ctx* ctx, bc_phi* phi, const double* b, int al
   d.norms = phi->norms;
   d.n_rows = phi->n_rows;
   d.row_offset = phi->row_offset;
+  const PrefWish pw = pref_wish(phi->n_rows, s);
   {
     // one slab (see bc_snnls::state_slab): st | b | bn | xw | xw_prev | xf | send record | v (zero tail: the fp16
     // sweep reads whole plane batches), every piece 256-byte aligned
@@ -1436,22 +1437,16 @@ extern "C" int bc_snnls_create(bc_ctx* ctx, bc_phi* phi, const double* b, int al
     d.xf = (double*)(slab + o_xf);
     h->cand_send = (double*)(slab + o_rec);
     d.v = (double*)(slab + o_v);
-    // the int8 pre-filter (created below, after k_reset has produced the first sweep vector) reads v as digits: the step
-    // kernels keep that record current from the start when such a pre-filter is going to exist
-    const char* penv = getenv("BC_PREFILTER");
-    const int preq = penv ? atoi(penv) : -1;
-    const bool pwant = penv ? preq != 0 : phi->n_rows >= 163840;
-    const int pprec = (preq == 8 || preq == 16 || preq == 32) ? preq : BC_PREF_DEFAULT_PREC;      // (4: the int8 mirror behind a 4-bit first level)
-    const bool ptwo = bc_want_two_level(preq, phi->n_rows, s);
     const char* fenv = getenv("BC_FINISH_NOPF");         // finish-kernel forms ruled out for this solver (tests, A/B)
     h->no_pf = fenv && atoi(fenv) != 0;
     fenv = getenv("BC_FINISH_NOFUSE");
     h->no_fuse = fenv && atoi(fenv) != 0;
-    const char* qenv = getenv("BC_I8_QV");               // =0: sweeps quantise in their own prologue (A/B, tests)
+    // the int8 pre-filter (created below, after k_reset has produced the first sweep vector) reads v as digits: the step
+    // kernels keep that record current from the start when such a pre-filter is going to exist
     d.sp4 = bc_lay_i8_sp4(s);
-    d.qv = (pwant && pprec == 8 && phi->n_rows > 0 && (s + 3) / 4 <= BC_LAY_IMAXG - BC_LAY_IU && !(qenv && atoi(qenv) == 0)) ? (int*)(slab + o_qv) : nullptr;
+    d.qv = pw.keep_qv ? (int*)(slab + o_qv) : nullptr;
     d.sp8 = bc_lay_i4_sp8(s, bc_lay_i4_batch(s));
-    d.qv4 = (d.qv && ptwo) ? (int*)(slab + o_qv4) : nullptr;
+    d.qv4 = pw.keep_qv4 ? (int*)(slab + o_qv4) : nullptr;
   }
   hipError_t e = hipSuccess;
   d.cand_all = h->cand_send;
@@ -1473,14 +1468,9 @@ extern "C" int bc_snnls_create(bc_ctx* ctx, bc_phi* phi, const double* b, int al
   }
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e != hipSuccess) { bc_snnls_destroy(h); return bc_hip_fail(e, "snnls init", __FILE__, __LINE__); }
-  // reduced-precision pre-filter: worth its extra launches once the sweep is long enough.
-  // BC_PREFILTER = 0 (off) / 1 (on, default precision) / 8 / 16 / 32 (on, that storage precision)
-  const char* env = getenv("BC_PREFILTER");
-  const int req = env ? atoi(env) : -1;
-  const bool want = env ? req != 0 : phi->n_rows >= 163840;   // measured break-even ~131k rows at S = 100 (int8 mirror, profiles/r01_notes.md)
-  if (want && phi->n_rows > 0) {
-    const int cprec = (req == 8 || req == 16 || req == 32) ? req : BC_PREF_DEFAULT_PREC;
-    rc = bc_pref_create(phi, (cprec == 8 && d.qv4) ? 4 : cprec, &h->pref);
+  // the reduced-precision pre-filter (pref_wish), now that k_reset has produced the first sweep vector
+  if (pw.want) {
+    rc = bc_pref_create(phi, pw.prec, &h->pref);
     if (rc) { bc_snnls_destroy(h); return rc; }
     const char* cap = getenv("BC_PREFILTER_CAP");
     if (cap) bc_pref_set_cap(h->pref, atoi(cap));
@@ -1497,7 +1487,6 @@ extern "C" int bc_snnls_prefilter_active(const bc_snnls* h, int* on) {
   return BC_OK;
 }
 
-int bc_pref_bb(const bc_pref* p);
 extern "C" int bc_snnls_prefilter_form(const bc_snnls* h, int* form) {
   if (!h || !form) { bc_set_error("bc_snnls_prefilter_form: bad argument"); return BC_INVALID_ARGUMENT; }
   *form = !h->pref ? 0 : (bc_pref_bb(h->pref) ? 2 : (bc_pref_two_level_active(h->pref) ? 3 : 1));      // (3 put aside by the watch: 1)
@@ -1514,10 +1503,10 @@ extern "C" int bc_snnls_prefilter_fallbacks(const bc_snnls* h, int64_t* n) {
   if (!h || !n) return BC_INVALID_ARGUMENT;
   *n = 0;
   if (!h->pref) return BC_OK;
-  int ctrl[4] = {0, 0, 0, 0};
-  BC_HIP(hipMemcpyAsync(ctrl, bc_pref_ctrl(h->pref), sizeof(ctrl), hipMemcpyDeviceToHost, h->ctx->stream));
-  BC_HIP(hipStreamSynchronize(h->ctx->stream));
-  *n = ctrl[3];
+  bc_pref_counters c;
+  const int rc = bc_pref_read_counters(h->pref, &c);
+  if (rc) return rc;
+  *n = c.overflows;
   return BC_OK;
 }
 
@@ -1527,43 +1516,32 @@ extern "C" int bc_snnls_prefilter_stats(const bc_snnls* h, int64_t* sweeps, int6
   if (candidates) *candidates = 0;
   if (fallbacks) *fallbacks = 0;
   if (!h->pref) return BC_OK;
-  int ctrl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  BC_HIP(hipMemcpyAsync(ctrl, bc_pref_ctrl(h->pref), sizeof(ctrl), hipMemcpyDeviceToHost, h->ctx->stream));
-  BC_HIP(hipStreamSynchronize(h->ctx->stream));
-  unsigned long long st[2];
-  memcpy(st, ctrl + 4, sizeof(st));
-  if (sweeps) *sweeps = (int64_t)st[0];
-  if (candidates) *candidates = (int64_t)st[1];
-  if (fallbacks) *fallbacks = ctrl[3];
+  bc_pref_counters c;
+  const int rc = bc_pref_read_counters(h->pref, &c);
+  if (rc) return rc;
+  if (sweeps) *sweeps = c.sweeps;
+  if (candidates) *candidates = c.rescored;
+  if (fallbacks) *fallbacks = c.overflows;
   return BC_OK;
 }
 
-long long bc_pref_l1_sweeps(const bc_pref* p);
 extern "C" int bc_snnls_prefilter_levels(const bc_snnls* h, int64_t* l1_sweeps, int64_t* listed, int64_t* refined) {
   if (!h) { bc_set_error("bc_snnls_prefilter_levels: bad argument"); return BC_INVALID_ARGUMENT; }
   if (l1_sweeps) *l1_sweeps = 0;
   if (listed) *listed = 0;
   if (refined) *refined = 0;
   if (!h->pref || !bc_pref_two_level(h->pref)) return BC_OK;
-  int ctrl[16];
-  BC_HIP(hipMemcpyAsync(ctrl, bc_pref_ctrl(h->pref), sizeof(ctrl), hipMemcpyDeviceToHost, h->ctx->stream));
-  BC_HIP(hipStreamSynchronize(h->ctx->stream));
-  unsigned long long st[2];
-  memcpy(st, ctrl + 10, sizeof(st));
-  if (l1_sweeps) *l1_sweeps = (int64_t)bc_pref_l1_sweeps(h->pref);
-  (void)st[0];
-  if (listed) *listed = (int64_t)st[1];            // (every row the first level passes on is re-bounded by the same wave)
-  if (refined) *refined = (int64_t)st[1];
+  bc_pref_counters c;
+  const int rc = bc_pref_read_counters(h->pref, &c);
+  if (rc) return rc;
+  if (l1_sweeps) *l1_sweeps = c.l1_seq;
+  if (listed) *listed = c.l1_passed;               // (every row the first level passes on is re-bounded by the same wave)
+  if (refined) *refined = c.l1_passed;
   return BC_OK;
 }
 
 // ------------------------------------------------------------------ diagnostic seam (include/beta_cores_prefdiag.h): test aids
 static int mode_of(const bc_snnls* h);
-void bc_pref_diag_info(const bc_pref* p, bool qv_set, int64_t* out);
-int bc_pref_diag_buffer(const bc_pref* p, const char* which, const void** dev, size_t* bytes);
-size_t bc_pref_diag_save_bytes(void);
-int bc_pref_diag_sweep(bc_pref* p, int mode, const double* v_dev, const double* v_norm_dev, const int* qv, const int* qv4,
-                       double post_div, float2* dump1, float2* dump2, float* theta0, void* save_dev, int* form_run);
 
 extern "C" int bc_snnls_prefdiag_info(const bc_snnls* h, int64_t* out) {
   if (!h || !out) { bc_set_error("bc_snnls_prefdiag_info: bad argument"); return BC_INVALID_ARGUMENT; }

@@ -16,9 +16,6 @@
 #include <cstring>
 #include <string>
 
-int bc_comm_sum_dev(bc_comm* c, const double* in_dev, int64_t count, const double** result_dev);   // bc_comm.hip
-bc_ctx* bc_comm_ctx(const bc_comm* c);
-
 // what the gradient keeps on a context between calls (ctx->vigrad, created on first use)
 struct bc_vigrad {
   bc_phi* core_phi = nullptr;    // bc_vi_gradient: the projection of the <= M coreset rows
