@@ -1,5 +1,5 @@
 // bc_i8_quant.h -- quantisation of the int8 pre-filter's sweep vector(s), shared by the two places that can do it:
-//   * the single-block step kernels (bc_snnls.hip: dev_prep), which PRODUCE the vectors of the next sweep and now also
+//   * the single-block step kernels (bc_snnls_dev.h: dev_prep), which PRODUCE the vectors of the next sweep and now also
 //     leave their digits behind -- once per step, 1.3 KB;
 //   * the prologue of k_sweep_i8 (bc_prefilter_i8.h), where every block of every sweep used to redo the job (two block
 //     reductions, two barriers, a few divisions before the first dot4): still the path of standalone argmax sweeps, whose

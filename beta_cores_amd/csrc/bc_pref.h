@@ -1,5 +1,5 @@
-// The pre-filter's internal interface: what a translation unit other than bc_prefilter.hip (the solver, bc_snnls.hip) needs in
-// order to own one and sweep with it.  No kernel in here.  Everything declared below is defined in bc_prefilter.hip, which
+// The pre-filter's internal interface: what a translation unit other than bc_prefilter.hip (the solver: bc_snnls.hip and
+// bc_snnls_diag.hip, through bc_snnls_state.h) needs in order to own one and sweep with it.  No kernel in here.  Everything declared below is defined in bc_prefilter.hip, which
 // includes this header itself; the control block the kernels and the host share is bc_pref_ctrl.h, and no other unit reads it.
 #pragma once
 #include "bc_rescore_dev.h"
@@ -39,7 +39,8 @@ struct bc_pref_counters {
 };
 int bc_pref_read_counters(const bc_pref* p, bc_pref_counters* out);
 
-// diagnostic seam (include/beta_cores_prefdiag.h): test aids, nothing here is called by the product
+// diagnostic seam (include/beta_cores_prefdiag.h): test aids, nothing here is called by the product; the one caller is
+// bc_snnls_diag.hip, which holds the entry points
 void bc_pref_diag_info(const bc_pref* p, bool qv_set, int64_t* out);
 int bc_pref_diag_buffer(const bc_pref* p, const char* which, const void** dev, size_t* bytes);
 size_t bc_pref_diag_save_bytes(void);

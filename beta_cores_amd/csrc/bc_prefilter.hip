@@ -724,7 +724,7 @@ int bc_pref_launch_sweep(bc_pref* p, int mode, const double* v_dev, const double
   return BC_OK;
 }
 
-// The owner's step kernels keep a quantised copy of v_dev up to date (bc_snnls.hip: dev_prep -> bc_i8q_wave): the sweep
+// The owner's step kernels keep a quantised copy of v_dev up to date (bc_snnls_dev.h: dev_prep -> bc_i8q_wave): the sweep
 // then skips its own quantisation prologue.  Only valid while EVERY launch of this pre-filter sweeps that same v.
 void bc_pref_set_qv(bc_pref* p, const int* qv_dev) { p->qv = (p->prec == 8) ? qv_dev : nullptr; }
 // ... and a 4-bit copy for the two-level form's first level (bc_i4_quant.h; sp8 must be bc_pref_sp8)
@@ -780,7 +780,7 @@ int bc_pref_launch(bc_pref* p, int mode, const double* v_dev, const double* v_no
 }
 
 // ------------------------------------------------------------------ diagnostic seam (include/beta_cores_prefdiag.h)
-// Test aids: nothing below is called by the product.  bc_snnls.hip owns the entry points and the solver's side of them.
+// Test aids: nothing below is called by the product.  bc_snnls_diag.hip owns the entry points and the solver's side of them.
 void bc_pref_diag_info(const bc_pref* p, bool qv_set, int64_t* out) {
   out[BC_PREFDIAG_PREC] = p->prec;
   out[BC_PREFDIAG_PTILE] = p->ptile;

@@ -9,6 +9,10 @@
 // (giga.py:20-30 / frankwolfe.py:16).  All replicated state (sparse w, selected
 // columns, xw = A.w) lives in device memory; every rank runs the identical finish
 // kernel on identical gathered records, so ranks stay bit-identical.
+//
+// This unit holds the kernels and the host side.  What the solver is (SnnlsState, SnnlsDev, struct bc_snnls) is
+// bc_snnls_state.h; the device functions the kernels are made of are bc_snnls_dev.h; the pre-filter's diagnostic
+// seam (test aids) is a unit of its own, bc_snnls_diag.hip, and nothing here knows of it.
 #ifdef BC_FIN_STAMPS          // diagnostic build: phase time stamps of the single-block step kernels
 #include <hip/hip_runtime.h>
 __device__ unsigned long long g_fin_stamps[64];
@@ -18,781 +22,14 @@ extern "C" int bc_debug_fin_stamps(unsigned long long* out) {
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fin_stamps), sizeof(g_fin_stamps)) == hipSuccess ? 0 : -1;
 }
 #endif
-#include "bc_pref.h"
+#include "bc_snnls_state.h"
+#include "bc_snnls_dev.h"          // takes FSTAMP from the block above, as bc_rescore_dev.h does
 #include "../../include/beta_cores_nnls.h"
-#include "../../include/beta_cores_prefdiag.h"
-#include "bc_layout.h"
-#include "bc_i8_quant.h"
-#include "bc_i4_quant.h"
 #include <climits>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
-
-struct SnnlsState {
-  long long nnz;        // length of the (idx, val) list, selection order; val may be 0
-  long long npos;       // count(val > 0)  == SparseNNLS.size()
-  long long iter;       // consumed iterations since reset (trace length)
-  long long sel_f;      // last picked global index, -1 if none
-  double sel_score;
-  double sel_norm;
-  double err_cur;       // ||A.w - b||_2 for the current w
-  double xw_sq;         // ||A.w||^2 for the current w
-  int skip;             // select_fail | reached_limit : makes the next sweep a no-op
-  int reached_limit;
-  int retried;
-  int select_fail;      // the reference's _select would raise (giga.py:28-29)
-  int sel_valid;
-  int last_status;      // status of the last step-wise call
-  int overflow;         // list capacity exceeded (host bug guard)
-  int pf_overflow;      // the pre-filter's candidate lists overflowed in this step: nothing was consumed, the host
-                        // re-runs the step with the exact fp64 sweep (sticky until it does; later launches are no-ops)
-  double v_norm;        // ||v|| of the dot-mode sweep vector (scales the pre-filter's error bound)
-};
-
-struct SnnlsDev {
-  SnnlsState* st;
-  long long* idx;
-  double* val;
-  double* prev_val;
-  double* cols;       // [cap][s]
-  double* colnorm;    // [cap]
-  long long cap;
-  double* b;
-  double* bn;
-  double* xw;
-  double* xw_prev;
-  double* v;          // sweep vectors: GIGA [s][2], else [s]
-  int* qv;            // the same, quantised for the int8 pre-filter's sweep (bc_i8_quant.h record) -- or nullptr
-  int sp4;            // k-groups of that record
-  int* qv4;           // two-level pre-filter: the same in 4-bit digits for its first level (bc_i4_quant.h record) -- or nullptr
-  int sp8;            // k-groups of that record
-  double* xf;         // picked column
-  const double* cand_all;
-  const double* tiles;
-  const double* norms;
-  long long n_rows, row_offset;
-  long long* tr_f;
-  int* tr_status;
-  double* tr_err;
-  long long tr_cap;
-  double bnorm, tol, norm_sum;
-  int s, world, rec_len;
-  // single-rank fast path: the finish kernel reduces the sweep's per-block candidates itself
-  const double* blk_val;
-  const long long* blk_idx;
-  int nblk;
-  int fuse_winner;
-  // device NNLS refit (bc_nnls_dev.h): Gram matrix of the list's cached columns [BC_NNLS_MAXP][BC_NNLS_MAXP], its right-hand
-  // side cols . b, and {refits, solves, rejected, covered}: the refit counters and the number of leading list entries the Gram
-  // state covers -- written by the kernels that extend it, lowered by every kernel that puts another column into a covered
-  // slot (dev_gram_touch).  nullptr until a refit entry point is first used
-  double* gram;
-  double* gram_c;
-  long long* nnls_stats;
-};
-
-struct bc_snnls {
-  bc_ctx* ctx = nullptr;
-  bc_phi* phi = nullptr;
-  int alg = 0;
-  SnnlsDev d;
-  // second buffer set for set_weights (swapped in after the rebuild kernel)
-  long long* idx2 = nullptr;
-  double* val2 = nullptr;
-  double* cols2 = nullptr;
-  double* colnorm2 = nullptr;
-  // The small state arrays (st, b, bn, xw, xw_prev, v, xf, the send record) live in ONE allocation and the active
-  // lists (both buffer sets) in another: the single-block step kernel starts every greedy step with cold TLBs (a 1 GB
-  // sweep ran in between), and its first round of loads paid one page-table walk per separately allocated array.
-  void* state_slab = nullptr;
-  void* list_slab = nullptr;
-  bc_pref* pref = nullptr;         // reduced-precision pre-filter of the sweep (large shards), see bc_prefilter.hip
-  double* cand_send = nullptr;     // this rank's candidate record (S + 4 doubles)
-  bool cand_send_owned = true;     // false once the host bound its own exchange buffers
-  bc_comm* comm = nullptr;         // native RCCL exchange (bc_comm.hip): the loop all-gathers by itself
-  double* cand_all_owned = nullptr;
-  long long nnz_upper = 0;   // host-side upper bound on the list length
-  long long iter_upper = 0;
-  RescoreArgs rs;                 // argument block of the rescoring stage for the step in flight (fused finish)
-  bool rs_pending = false;        // step_local ran the sweep only: step_finish must run the fused rescoring + finish
-  bool exact_step = false;        // the step in flight uses the exact fp64 sweep (redo after a pre-filter overflow)
-  bool pref_suspended = false;    // repeated overflows: the rest of this build call sweeps in fp64
-  int consec_overflow = 0;
-  bool dev_refit = false;         // bc_snnls_device_refit: an OrthoPursuit handle runs the fused loop with the device NNLS refit
-  void* nnls_slab = nullptr;      // gram | gram_c | nnls_stats
-  bool no_pf = false;             // BC_FINISH_NOPF / BC_FINISH_NOFUSE as the environment had them at creation: no one-round
-  bool no_fuse = false;           // finish kernel / no rescoring inside it (tests and A/B measurements choose the form with them)
-  int finish_form = 0;            // BC_FINISH_* of the last step_finish (bc_snnls_finish_form)
-};
-
-// ------------------------------------------------------------------ device building blocks (single block)
-// The S-vector algebra of a step (dot products, step sizes, the next sweep vectors) is done by WAVE 0 alone:
-// lane l owns elements l, l+64, ... of every vector and reductions are shuffle trees, so a step needs a handful
-// of block barriers instead of three per reduction.  Only the O(nnz*S) work -- rebuilding xw from the list,
-// scaling / searching the list -- uses the whole block.  Every kernel goes through the same helpers, so the
-// fused loop and the step-wise protocol produce the same bits.
-#define BC_FIN_THREADS 512
-
-// xw = sum_j val[j] * cols[j], err = ||xw - b||, ||xw||^2 and the positive count.  The list is split over
-// G = blockDim/S thread groups (fixed split => deterministic), partial vectors are combined in group order.
-#define BC_PF_NC 16     // list columns per thread requested up front by the _pf kernels (32 was measured: no gain)
-// PF: the first BC_PF_NC terms of every thread's share come from `c16` (cols prefetched at kernel start, slot u <->
-// list entry g + u*G) except the entry appended in this very step (`at_new`), whose column is P.xf.
-template <bool PF>
-__device__ void dev_xw_err_t(const SnnlsDev& P, SnnlsState& S, double* red, const double (&c16)[BC_PF_NC], long long at_new) {
-  __shared__ double part[BC_FIN_THREADS];
-  __shared__ int npos_sh;
-  const int s = P.s;
-  const long long nnz = S.nnz;
-  if (threadIdx.x == 0) npos_sh = 0;
-  __syncthreads();
-  int np = 0;
-  if (s <= (int)blockDim.x) {
-    const int G = blockDim.x / s;
-    const int g = threadIdx.x / s, k = threadIdx.x - g * s;
-    double acc = 0.0;
-    if (g < G) {
-      // 16 independent loads in flight per thread: the list lives in global memory (L2) and a dependent
-      // load per term would cost a full memory latency each.  The k == 0 thread of each group also counts
-      // the positive weights it walks over (every list slot belongs to exactly one group).
-      long long j = g;
-      if (PF) {
-#pragma unroll
-        for (int u = 0; u < BC_PF_NC; ++u) {
-          if (j < nnz) {
-            const double vj = P.val[j];
-            const double cv = (j == at_new) ? P.xf[k] : c16[u];
-            acc = fma(vj, cv, acc);
-            np += (vj > 0.) ? 1 : 0;
-            j += G;
-          }
-        }
-      }
-      for (; j + 15 * (long long)G < nnz; j += 16 * (long long)G) {
-        double v8[16], c8[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-          v8[u] = P.val[j + u * (long long)G];
-          c8[u] = P.cols[(size_t)(j + u * (long long)G) * s + k];
-        }
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-          acc = fma(v8[u], c8[u], acc);
-          np += (v8[u] > 0.) ? 1 : 0;
-        }
-      }
-      for (; j + 3 * (long long)G < nnz; j += 4 * (long long)G) {
-        double v4[4], c4[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          v4[u] = P.val[j + u * (long long)G];
-          c4[u] = P.cols[(size_t)(j + u * (long long)G) * s + k];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          acc = fma(v4[u], c4[u], acc);
-          np += (v4[u] > 0.) ? 1 : 0;
-        }
-      }
-      for (; j < nnz; j += G) {
-        const double vj = P.val[j];
-        acc = fma(vj, P.cols[(size_t)j * s + k], acc);
-        np += (vj > 0.) ? 1 : 0;
-      }
-      if (k == 0 && np) atomicAdd(&npos_sh, np);
-    }
-    part[threadIdx.x] = acc;
-    __syncthreads();
-    if (threadIdx.x < BC_WAVE) {
-      double e = 0.0, q = 0.0;
-      for (int kk = threadIdx.x; kk < s; kk += BC_WAVE) {
-        double t = part[kk];
-        for (int gg = 1; gg < G; ++gg) t += part[gg * s + kk];
-        P.xw[kk] = t;
-        const double d = t - P.b[kk];
-        e = fma(d, d, e);
-        q = fma(t, t, q);
-      }
-      e = bc_wave_sum(e);
-      q = bc_wave_sum(q);
-      if (threadIdx.x == 0) {
-        S.err_cur = sqrt(e);
-        S.xw_sq = q;
-        S.npos = npos_sh;
-      }
-    }
-  } else {
-    for (long long j = threadIdx.x; j < nnz; j += blockDim.x) np += (P.val[j] > 0.) ? 1 : 0;
-    if (np) atomicAdd(&npos_sh, np);
-    double e = 0.0, q = 0.0;
-    for (int k = threadIdx.x; k < s; k += blockDim.x) {
-      double acc = 0.0;
-      for (long long j = 0; j < nnz; ++j) acc = fma(P.val[j], P.cols[(size_t)j * s + k], acc);
-      P.xw[k] = acc;
-      const double d = acc - P.b[k];
-      e = fma(d, d, e);
-      q = fma(acc, acc, q);
-    }
-    double r2[2] = {e, q};
-    bc_block_sum_n<2>(r2, red);
-    if (threadIdx.x == 0) {
-      S.err_cur = sqrt(r2[0]);
-      S.xw_sq = r2[1];
-      S.npos = npos_sh;
-    }
-  }
-  __syncthreads();
-}
-
-__device__ void dev_xw_err(const SnnlsDev& P, SnnlsState& S, double* red) {
-  const double none[BC_PF_NC] = {0.};
-  dev_xw_err_t<false>(P, S, red, none, -1);
-}
-
-// vectors for the next sweep.  GIGA: giga.py:21-30 ; FW / OMP: residual b - A.w          (wave 0 + one barrier)
-// With an int8 pre-filter (P.qv) the same wave also leaves the vectors' int8 digits behind (bc_i8_quant.h): the maxima are
-// taken while the elements are in registers, and the digits' pass reads them back from a 4 KB LDS copy (S <= BC_VQ_MAX;
-// larger S re-reads v from global memory).
-#define BC_VQ_MAX 256
-#ifndef BC_QD_INTS
-#define BC_QD_INTS 512
-#endif
-template <int ALG>
-__device__ void dev_prep(const SnnlsDev& P, SnnlsState& S, double* red) {
-  __shared__ double vq[2 * BC_VQ_MAX];
-  __shared__ int qd[BC_QD_INTS];           // LDS image of the two digit records (S <= ~256)
-  const int s = P.s;
-  if (threadIdx.x < BC_WAVE) {
-    const int lane = threadIdx.x;
-    const bool quant = P.qv != nullptr;
-    const bool lds_copy = quant && s <= BC_VQ_MAX;
-    double vnorm = 1.;                  // ||v|| of the sweep vector (GIGA's are unit vectors)
-    double m0 = 0., m1 = 0.;            // this lane's max |v0|, |v1|
-    if (ALG == BC_ALG_GIGA) {
-      double nw = sqrt(S.xw_sq);
-      nw = (nw == 0.) ? 1. : nw;
-      double bd = 0.0;
-      for (int k = lane; k < s; k += BC_WAVE) {
-        const double xn = P.xw[k] / nw;
-        P.v[2 * k + 1] = xn;
-        if (lds_copy) vq[2 * k + 1] = xn;
-        m1 = bc_i8q_absmax(m1, xn);
-        bd = fma(P.bn[k], xn, bd);
-      }
-      bd = bc_wave_sum_all(bd);
-      double cn = 0.0;
-      for (int k = lane; k < s; k += BC_WAVE) {
-        const double c = P.bn[k] - bd * (P.xw[k] / nw);
-        cn = fma(c, c, cn);
-      }
-      cn = sqrt(bc_wave_sum_all(cn));
-      const bool fail = cn < P.tol;
-      for (int k = lane; k < s; k += BC_WAVE) {
-        const double c = P.bn[k] - bd * (P.xw[k] / nw);
-        const double v0 = fail ? c : c / cn;
-        P.v[2 * k] = v0;
-        if (lds_copy) vq[2 * k] = v0;
-        m0 = bc_i8q_absmax(m0, v0);
-      }
-      if (lane == 0) S.select_fail = fail ? 1 : 0;
-    } else {
-      double vn = 0.0;
-      for (int k = lane; k < s; k += BC_WAVE) {
-        const double r = P.b[k] - P.xw[k];
-        P.v[k] = r;
-        if (lds_copy) vq[k] = r;
-        m0 = bc_i8q_absmax(m0, r);
-        vn = fma(r, r, vn);
-      }
-      vn = bc_wave_sum(vn);
-      vnorm = sqrt(vn);
-      if (lane == 0) {
-        S.select_fail = 0;
-        S.v_norm = vnorm;
-      }
-    }
-    if (lane == 0) S.skip = S.select_fail | S.reached_limit | S.pf_overflow;
-    FSTAMP(15);
-    if (quant) {
-      // this wave wrote v (and its LDS copy) itself: a wave-level fence orders the digits' reads behind those stores
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      const double* vsrc = lds_copy ? vq : P.v;
-      m0 = bc_wave_max_all(m0);
-      m1 = bc_wave_max_all(m1);
-      if (4 * (P.sp4 + P.sp8) <= BC_QD_INTS) {
-        // one element per lane, both records in one pass (bc_i4_quant.h: bc_q_wave_both)
-        if (ALG == BC_ALG_GIGA) bc_q_wave_both<0>(vsrc, s, P.sp4, P.sp8, 1., P.qv, P.qv4, lane, m0, m1, qd);
-        else bc_q_wave_both<1>(vsrc, s, P.sp4, P.sp8, vnorm, P.qv, P.qv4, lane, m0, m1, qd);
-      } else {
-        if (ALG == BC_ALG_GIGA) bc_i8q_wave<0>(vsrc, s, P.sp4, 1., P.qv, lane, m0, m1);
-        else bc_i8q_wave<1>(vsrc, s, P.sp4, vnorm, P.qv, lane, m0, m1);
-        if (P.qv4 != nullptr) {
-          if (ALG == BC_ALG_GIGA) bc_i4q_wave<0>(vsrc, s, P.sp8, 1., P.qv4, lane, m0, m1);
-          else bc_i4q_wave<1>(vsrc, s, P.sp8, vnorm, P.qv4, lane, m0, m1);
-        }
-      }
-    }
-  }
-  __syncthreads();
-}
-
-// winner over the gathered candidate records: max score, lowest global index on ties.
-// OMP additionally weighs the active set's negative direction (orthopursuit.py:25-35).
-template <int ALG>
-__device__ void dev_pick(const SnnlsDev& P, SnnlsState& S, double* red) {
-  __shared__ int src_rec;
-  __shared__ long long src_list;
-  const int s = P.s;
-  if (P.world == 1 && ALG != BC_ALG_OMP) {
-    // one record: nothing to reduce (the shuffle argmax below costs ~3.5k cycles of ds_bpermute latency)
-    const double* rec = P.cand_all;
-    const bool valid = rec[3] != 0.0;
-    if (threadIdx.x == 0) {
-      S.sel_valid = valid ? 1 : 0;
-      S.sel_f = valid ? reinterpret_cast<const long long*>(rec)[1] : -1;
-      S.sel_score = valid ? rec[0] : -INFINITY;
-      if (valid) S.sel_norm = rec[2];
-    }
-    if (P.xf != rec + BC_REC_HDR) {                 // (block-uniform; the fused kernel aliases the two)
-      if (valid)
-        for (int k = threadIdx.x; k < s; k += blockDim.x) P.xf[k] = rec[BC_REC_HDR + k];
-    }
-    __syncthreads();
-    return;
-  }
-  if (threadIdx.x < BC_WAVE) {
-    // wave 0: one record header per lane (independent loads), shuffle argmax on (score, global index)
-    // carrying the record slot; the winner's column is copied straight from its record
-    const int lane = threadIdx.x;
-    double bv = -INFINITY;
-    long long bi = LLONG_MAX;
-    int br = -1;
-    for (int r = lane; r < P.world; r += BC_WAVE) {
-      const double* rec = P.cand_all + (size_t)r * P.rec_len;
-      const double sc = rec[0], ok = rec[3];
-      const long long gi = reinterpret_cast<const long long*>(rec)[1];
-      if (ok != 0.0 && bc_better(sc, gi, bv, bi)) { bv = sc; bi = gi; br = r; }
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-      const double ov = __shfl_down(bv, d, BC_WAVE);
-      const long long oi = bc_shfl_down_ll(bi, d);
-      const int orr = __shfl_down(br, d, BC_WAVE);
-      if (bc_better(ov, oi, bv, bi)) { bv = ov; bi = oi; br = orr; }
-    }
-    br = __shfl(br, 0, BC_WAVE);
-    const bool valid = br >= 0;
-    const double* win = P.cand_all + (size_t)(valid ? br : 0) * P.rec_len;
-    if (lane == 0) {
-      S.sel_valid = valid ? 1 : 0;
-      S.sel_f = valid ? bi : -1;
-      S.sel_score = bv;
-      if (valid) S.sel_norm = win[2];
-      src_rec = br;
-      src_list = -1;
-    }
-    if (ALG != BC_ALG_OMP && valid)
-      for (int k = lane; k < s; k += BC_WAVE) P.xf[k] = win[BC_REC_HDR + k];
-  }
-  __syncthreads();
-  if (ALG != BC_ALG_OMP) return;
-  if (ALG == BC_ALG_OMP && S.sel_valid && S.npos > 0) {
-    // neg = max over active j of -(An[:,j] . residual)
-    __shared__ double nv[16];
-    __shared__ long long ni[16], nj[16];
-    double bv = -INFINITY;
-    long long bi = LLONG_MAX, bj = -1;
-    for (long long j = threadIdx.x; j < S.nnz; j += blockDim.x) {
-      if (!(P.val[j] > 0.)) continue;
-      double acc = 0.0;
-      for (int k = 0; k < s; ++k) acc = fma(P.cols[(size_t)j * s + k], P.v[k], acc);
-      const double d = -(acc / P.colnorm[j]);
-      if (bc_better(d, P.idx[j], bv, bi)) { bv = d; bi = P.idx[j]; bj = j; }
-    }
-    // block argmax carrying the list slot
-    for (int dlt = 32; dlt >= 1; dlt >>= 1) {
-      const double ov = __shfl_down(bv, dlt, BC_WAVE);
-      const long long oi = bc_shfl_down_ll(bi, dlt), oj = bc_shfl_down_ll(bj, dlt);
-      if (bc_better(ov, oi, bv, bi)) { bv = ov; bi = oi; bj = oj; }
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { nv[wave] = bv; ni[wave] = bi; nj[wave] = bj; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const int nwv = (blockDim.x + 63) >> 6;
-      for (int w = 1; w < nwv; ++w)
-        if (bc_better(nv[w], ni[w], bv, bi)) { bv = nv[w]; bi = ni[w]; bj = nj[w]; }
-      if (!(S.sel_score >= bv)) {   // orthopursuit.py:31 `if pos >= neg` else take the active point
-        S.sel_f = bi;
-        S.sel_score = bv;
-        S.sel_norm = P.colnorm[bj];
-        src_rec = -1;
-        src_list = bj;
-      }
-    }
-    __syncthreads();
-  }
-  if (S.sel_valid) {
-    const double* src = (src_rec >= 0) ? P.cand_all + (size_t)src_rec * P.rec_len + BC_REC_HDR
-                                       : P.cols + (size_t)src_list * s;
-    for (int k = threadIdx.x; k < s; k += blockDim.x) P.xf[k] = src[k];
-  }
-  __syncthreads();
-}
-
-// single-rank variant of dev_pick: reduce the sweep's per-block candidates here (no record round trip)
-__device__ void dev_pick_blocks(const SnnlsDev& P, SnnlsState& S) {
-  __shared__ double sv[16];
-  __shared__ long long si[16];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  double bv = -INFINITY;
-  long long bi = LLONG_MAX;
-  for (int i = threadIdx.x; i < P.nblk; i += blockDim.x)
-    if (bc_better(P.blk_val[i], P.blk_idx[i], bv, bi)) { bv = P.blk_val[i]; bi = P.blk_idx[i]; }
-  bc_wave_argmax(bv, bi);
-  if (lane == 0) { sv[wave] = bv; si[wave] = bi; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int nwv = (blockDim.x + 63) >> 6;
-    for (int w = 1; w < nwv; ++w)
-      if (bc_better(sv[w], si[w], bv, bi)) { bv = sv[w]; bi = si[w]; }
-    const bool valid = bi != LLONG_MAX;
-    S.sel_valid = valid ? 1 : 0;
-    S.sel_f = valid ? bi : -1;
-    S.sel_score = bv;
-    S.sel_norm = valid ? P.norms[bi - P.row_offset] : 0.0;
-  }
-  __syncthreads();
-  if (S.sel_valid) {
-    const long long r = S.sel_f - P.row_offset;
-    for (int k = threadIdx.x; k < P.s; k += blockDim.x) P.xf[k] = P.tiles[bc_tile_off(r, k, P.s)];
-  }
-  __syncthreads();
-}
-
-// closed-form step sizes.  Returns 1 when the reference would raise NumericalPrecisionError
-// (w untouched), else 0 with (alpha, beta) set.                                    (wave 0 + one barrier)
-template <int ALG>
-__device__ int dev_step_sizes(const SnnlsDev& P, const SnnlsState& S, double* red, double& alpha, double& beta) {
-  __shared__ double ab[2];
-  __shared__ int ab_fail;
-  const int s = P.s;
-  if (threadIdx.x < BC_WAVE) {
-    const int lane = threadIdx.x;
-    int fail = 0;
-    double al = 0., be = 0.;
-    if (ALG == BC_ALG_GIGA) {   // giga.py:42-61
-      double nw = sqrt(S.xw_sq);
-      nw = (nw == 0.) ? 1. : nw;
-      double ff = 0.;
-      for (int k = lane; k < s; k += BC_WAVE) ff = fma(P.xf[k], P.xf[k], ff);
-      const double nf = sqrt(bc_wave_sum_all(ff));
-      double r0 = 0., r1 = 0., r2 = 0.;
-      for (int k = lane; k < s; k += BC_WAVE) {
-        const double fn = P.xf[k] / nf, wn = P.xw[k] / nw;
-        r0 = fma(P.bn[k], fn, r0);
-        r1 = fma(P.bn[k], wn, r1);
-        r2 = fma(wn, fn, r2);
-      }
-      const double bxf = bc_wave_sum_all(r0), bxw = bc_wave_sum_all(r1), xwxf = bc_wave_sum_all(r2);
-      const double gA = bxf - bxw * xwxf;
-      const double gB = bxw - bxf * xwxf;
-      if (gA <= 0. || gB < 0.) {
-        fail = 1;
-      } else {
-        const double a = gB / (gA + gB) / nw;
-        const double b = gA / (gA + gB) / nf;
-        double nx = 0.;
-        for (int k = lane; k < s; k += BC_WAVE) {
-          const double x = a * P.xw[k] + b * P.xf[k];
-          nx = fma(x, x, nx);
-        }
-        nx = sqrt(bc_wave_sum_all(nx));
-        double xb = 0.;
-        for (int k = lane; k < s; k += BC_WAVE) {
-          const double x = a * P.xw[k] + b * P.xf[k];
-          xb = fma(x / nx, P.bn[k], xb);
-        }
-        xb = bc_wave_sum_all(xb);
-        const double scale = P.bnorm / nx * xb;
-        al = a * scale;
-        be = b * scale;
-      }
-    } else {                    // frankwolfe.py:20-37
-      const double nf = S.sel_norm;
-      if (S.npos == 0) {
-        al = 0.;
-        be = P.norm_sum / nf;
-      } else {
-        const double c = P.norm_sum / nf;
-        double num = 0., den = 0.;
-        for (int k = lane; k < s; k += BC_WAVE) {
-          const double d = c * P.xf[k] - P.xw[k];
-          num = fma(d, P.b[k] - P.xw[k], num);
-          den = fma(d, d, den);
-        }
-        num = bc_wave_sum_all(num);
-        den = bc_wave_sum_all(den);
-        if (num < 0. || den == 0. || num > den) {
-          fail = 1;
-        } else {
-          al = 1. - num / den;
-          be = c * num / den;
-        }
-      }
-    }
-    if (lane == 0) {
-      ab[0] = al;
-      ab[1] = be;
-      ab_fail = fail;
-    }
-  }
-  __syncthreads();
-  alpha = ab[0];
-  beta = ab[1];
-  return ab_fail;
-}
-
-// list slot `at` is about to hold another column (thread 0): the Gram state of the device NNLS refit, if this solver has one,
-// no longer covers it
-__device__ __forceinline__ void dev_gram_touch(const SnnlsDev& P, long long at) {
-  if (P.nnls_stats != nullptr && P.nnls_stats[3] > at) P.nnls_stats[3] = at;
-}
-
-// w = alpha*w ; w[f] = max(0, w[f] + beta)   (giga.py:63-64, frankwolfe.py:39-40)
-__device__ void dev_apply(const SnnlsDev& P, SnnlsState& S, double alpha, double beta) {
-  __shared__ int slot;
-  const int s = P.s;
-  const long long f = S.sel_f;
-  if (threadIdx.x == 0) slot = INT_MAX;
-  __syncthreads();
-  for (long long j = threadIdx.x; j < S.nnz; j += blockDim.x) {
-    P.val[j] = alpha * P.val[j];
-    if (P.idx[j] == f) atomicMin(&slot, (int)j);
-  }
-  __syncthreads();
-  long long at = slot == INT_MAX ? -1 : slot;
-  if (at >= 0) {
-    if (threadIdx.x == 0) {
-      const double nv = P.val[at] + beta;
-      P.val[at] = nv > 0. ? nv : 0.;
-    }
-  } else {
-    const double nv = (0. + beta) > 0. ? (0. + beta) : 0.;
-    if (nv > 0.) {
-      if (S.nnz < P.cap) {
-        at = S.nnz;
-        for (int k = threadIdx.x; k < s; k += blockDim.x) P.cols[(size_t)at * s + k] = P.xf[k];
-        if (threadIdx.x == 0) {
-          P.idx[at] = f;
-          P.val[at] = nv;
-          P.colnorm[at] = S.sel_norm;
-          dev_gram_touch(P, at);
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) S.nnz = at + 1;
-      } else if (threadIdx.x == 0) {
-        S.overflow = 1;
-      }
-    }
-  }
-  __syncthreads();
-}
-
-__device__ __forceinline__ void dev_trace(const SnnlsDev& P, SnnlsState& S, long long f, int status) {
-  if (threadIdx.x == 0) {
-    if (S.iter < P.tr_cap) {
-      P.tr_f[S.iter] = f;
-      P.tr_status[S.iter] = status;
-      P.tr_err[S.iter] = S.err_cur;
-    }
-    S.iter += 1;
-  }
-}
-
-// any gathered record carrying the overflow marker?  (block-uniform; every rank sees the same records)
-__device__ bool dev_records_overflow(const double* cand_all, int world, int rec_len) {
-  __shared__ int ovf;
-  if (threadIdx.x == 0) ovf = 0;
-  __syncthreads();
-  for (int r = threadIdx.x; r < world; r += blockDim.x)
-    if (cand_all[(size_t)r * rec_len + 3] < 0.) ovf = 1;
-  __syncthreads();
-  return ovf != 0;
-}
-
-// ------------------------------------------------------------------ device NNLS refit (OrthoPursuit, optimize())
-#include "bc_nnls_dev.h"
-#define BC_ST_LIST_LIMIT 100      // last_status of k_refit: the list would outgrow BC_NNLS_MAXP (the host words the error)
-
-// would column f find a slot (dev_omp_place below): it is listed, or a slot has weight 0, or the list may grow
-__device__ bool dev_omp_room(const SnnlsDev& P, const SnnlsState& S, long long f, long long limit) {
-  __shared__ int room;
-  const long long nnz = S.nnz;
-  if (threadIdx.x == 0) room = nnz < limit ? 1 : 0;
-  __syncthreads();
-  for (long long j = threadIdx.x; j < nnz; j += blockDim.x)
-    if (P.idx[j] == f || !(P.val[j] > 0.)) room = 1;
-  __syncthreads();
-  return room != 0;
-}
-
-// orthopursuit.py:38 `w[f] = 1` on the sparse list: make sure the picked column (S.sel_f, in P.xf) has a slot -- with weight
-// 0 when it is new: the refit lets it enter.  A slot whose weight is 0 is reused before the list grows.  Returns the slot, or
-// -1 when the list is full; *fresh: the slot's column was (re)written, so its Gram row is stale (the callers go straight on to
-// dev_gram_update, which recomputes it).
-__device__ long long dev_omp_place(const SnnlsDev& P, SnnlsState& S, long long limit, int* fresh) {
-  __shared__ int hit, zero;
-  const int s = P.s;
-  const long long f = S.sel_f, nnz = S.nnz;
-  if (threadIdx.x == 0) { hit = INT_MAX; zero = INT_MAX; }
-  __syncthreads();
-  for (long long j = threadIdx.x; j < nnz; j += blockDim.x) {
-    if (P.idx[j] == f) atomicMin(&hit, (int)j);
-    else if (!(P.val[j] > 0.)) atomicMin(&zero, (int)j);
-  }
-  __syncthreads();
-  *fresh = 0;
-  if (hit != INT_MAX) return hit;
-  const long long at = zero != INT_MAX ? (long long)zero : nnz;
-  if (at == nnz && at >= limit) return -1;
-  for (int k = threadIdx.x; k < s; k += blockDim.x) P.cols[(size_t)at * s + k] = P.xf[k];
-  if (threadIdx.x == 0) {
-    P.idx[at] = f;
-    P.val[at] = 0.;
-    P.colnorm[at] = S.sel_norm;
-    if (at == nnz) S.nnz = at + 1;
-  }
-  __syncthreads();
-  *fresh = 1;
-  return at;
-}
-
-// bring the Gram state up to the list: entries [covered, n) are new to it (covered = P.nnls_stats[3], never trusted beyond
-// the list as it was when this kernel started), and so is a slot below them that was reused in this kernel
-__device__ void dev_gram_update(const SnnlsDev& P, long long nnz0, long long n, long long at, int fresh) {
-  const long long covered = P.nnls_stats[3];
-  const long long from = covered < nnz0 ? covered : nnz0;
-  __syncthreads();                 // every thread has read the mark before thread 0 moves it
-  if (from < n) bc_nnls_gram_rows(P.cols, P.s, P.b, P.gram, P.gram_c, (int)n, (int)from, (int)n);
-  if (fresh && at < from) bc_nnls_gram_rows(P.cols, P.s, P.b, P.gram, P.gram_c, (int)n, (int)at, (int)at + 1);
-  if (threadIdx.x == 0) P.nnls_stats[3] = n;
-}
-
-// ------------------------------------------------------------------ stages of one guarded greedy iteration (snnls.py:41-74)
-// Written once for the finish kernels below: the kernels differ in where the vectors and the list live and in the reweight in
-// the middle, not in the guard, the retry rule or the close -- which is what keeps the fused loop and its forms bit-identical.
-
-// the five S-vectors into dynamic LDS: P points there, b / bn / xw are copied in (the caller's barrier publishes them)
-__device__ __forceinline__ void fin_stage_vecs(SnnlsDev& P, const SnnlsDev& P0, double* vec_lds) {
-  const int s = P.s;
-  P.b = vec_lds;
-  P.bn = vec_lds + s;
-  P.xw = vec_lds + 2 * s;
-  P.xf = vec_lds + 3 * s;
-  P.xw_prev = vec_lds + 4 * s;
-  for (int k = threadIdx.x; k < s; k += blockDim.x) {
-    P.b[k] = P0.b[k];
-    P.bn[k] = P0.bn[k];
-    P.xw[k] = P0.xw[k];
-  }
-}
-
-// snnls.py:32-34 / :73-74: over the limit, or a pending exact redo: the step consumes nothing
-__device__ __forceinline__ bool fin_idle(const SnnlsState& S) { return S.reached_limit || S.pf_overflow; }
-
-// a pre-filter's candidate lists overflowed in this step: mark it (sticky until the host's exact redo) and consume nothing
-__device__ __forceinline__ void fin_refuse_overflow(SnnlsState& S, SnnlsState* st) {
-  if (threadIdx.x == 0) { S.pf_overflow = 1; S.skip = 1; *st = S; }
-}
-
-// the winner (column -> P.xf, index -> f); returns 1 when _select raised or nothing is selectable
-template <int ALG>
-__device__ __forceinline__ int fin_pick(const SnnlsDev& P, SnnlsState& S, double* red, long long& f) {
-  int fail = S.select_fail;                          // _select raised
-  f = -1;
-  if (!fail) {
-    if (ALG != BC_ALG_OMP && P.fuse_winner) dev_pick_blocks(P, S);
-    else dev_pick<ALG>(P, S, red);
-    if (!S.sel_valid) fail = 1;
-    f = S.sel_f;
-  }
-  return fail;
-}
-
-// what a revert puts back (snnls.py:46-47)
-struct FinSaved {
-  long long nnz0, npos0;
-  double err0, xwsq0;
-};
-__device__ __forceinline__ FinSaved fin_save(const SnnlsState& S) { return {S.nnz, S.npos, S.err_cur, S.xw_sq}; }
-
-// ... and the vectors: xw -> xw_prev, and val -> prev_val where the kernel reweights the global list in place (LIST).  (No
-// barrier needed: each thread later rewrites exactly the val[j] it saved, and xw is only overwritten behind dev_xw_err's barriers)
-template <bool LIST>
-__device__ __forceinline__ void fin_keep_prev(const SnnlsDev& P, long long nnz0) {
-  if (LIST)
-    for (long long j = threadIdx.x; j < nnz0; j += blockDim.x) P.prev_val[j] = P.val[j];
-  for (int k = threadIdx.x; k < P.s; k += blockDim.x) P.xw_prev[k] = P.xw[k];
-}
-
-// the monotone-error guard (snnls.py:58-62) behind a reweight: returns 1 after reverting a step that raised the error
-template <bool LIST>
-__device__ __forceinline__ int fin_guard(const SnnlsDev& P, SnnlsState& S, const FinSaved& sv, bool guard) {
-  int fail = 0;
-  if (guard) {
-    if (S.err_cur > sv.err0) {                       // snnls.py:58-61
-      if (LIST)
-        for (long long j = threadIdx.x; j < sv.nnz0; j += blockDim.x) P.val[j] = P.prev_val[j];
-      for (int k = threadIdx.x; k < P.s; k += blockDim.x) P.xw[k] = P.xw_prev[k];
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        S.nnz = sv.nnz0;
-        S.npos = sv.npos0;
-        S.err_cur = sv.err0;
-        S.xw_sq = sv.xwsq0;
-      }
-      fail = 1;
-    } else if (threadIdx.x == 0) {
-      S.retried = 0;                                 // snnls.py:62
-    }
-    __syncthreads();
-  }
-  return fail;
-}
-
-// retry-once-then-stop (snnls.py:63-72), the trace entry, the next sweep vectors, and xw back to global memory where it
-// lived in LDS
-template <int ALG>
-__device__ __forceinline__ void fin_close(const SnnlsDev& P, SnnlsState& S, double* red, int fail, long long f, double* xw_out) {
-  __shared__ int sh_fail;
-  if (threadIdx.x == 0) {
-    if (fail) {
-      if (S.retried) S.reached_limit = 1;
-      else S.retried = 1;
-    }
-    sh_fail = fail;
-  }
-  __syncthreads();
-  FSTAMP(7);
-  dev_trace(P, S, f, sh_fail);
-  __syncthreads();
-  dev_prep<ALG>(P, S, red);
-  FSTAMP(8);
-  if (xw_out)
-    for (int k = threadIdx.x; k < P.s; k += blockDim.x) xw_out[k] = P.xw[k];
-}
-
-// the picked column lived in LDS: a later step-wise reweight / refit must fetch it again
-__device__ __forceinline__ void fin_store_state(SnnlsState& S, SnnlsState* st) {
-  if (threadIdx.x == 0) {
-    S.sel_valid = 0;
-    *st = S;
-  }
-}
 
 // ------------------------------------------------------------------ kernels (grid = 1 block)
 template <int ALG>
@@ -874,8 +111,6 @@ __global__ __launch_bounds__(BC_FIN_THREADS) void k_step_finish(SnnlsDev P0, int
 // kernel above pays a memory latency per phase (state -> records -> column -> list -> columns ...), ~7 dependent
 // round trips; both produce the same bits (same device functions, same orders).  Used when the list and the records
 // fit the LDS budget (nnz_hint + 1 <= BC_PF_MAXNNZ, world * rec_len <= BC_PF_MAXREC, S <= blockDim).
-#define BC_PF_MAXNNZ 1024
-#define BC_PF_MAXREC 2048
 // RS: the pre-filter's rescoring stage (bc_rescore_dev.h) runs INSIDE this launch, between the up-front loads and
 // the step: its record goes straight into LDS (single rank, no exchange).  One launch per greedy step besides the
 // sweep instead of two (k_rescore 11.7 us + k_step_finish_pf 12.6 us in round 1).
@@ -1039,38 +274,6 @@ __global__ __launch_bounds__(BC_FIN_THREADS) void k_pick(SnnlsDev P) {
     S.last_status = S.select_fail ? BC_NUMERICAL_PRECISION : (S.sel_valid ? BC_OK : BC_INVALID_ARGUMENT);
     *P.st = S;
   }
-}
-
-// column f -> P.xf (and its norm -> S.sel_norm) for a step-wise reweight: it is the last pick, or sits in a gathered
-// record, or in the local shard.  Returns 0 (block-uniform) when this rank cannot supply it.
-__device__ int dev_fetch_column(const SnnlsDev& P, SnnlsState& S, long long f) {
-  __shared__ int found;
-  const int s = P.s;
-  if (threadIdx.x == 0) {
-    int fd = 0;   // 0: not found, 1: xf already holds it, 2+r: record r, -1: local shard
-    if (S.sel_valid && S.sel_f == f) fd = 1;
-    if (!fd)
-      for (int r = 0; r < P.world; ++r) {
-        const double* rec = P.cand_all + (size_t)r * P.rec_len;
-        if (rec[3] != 0.0 && reinterpret_cast<const long long*>(rec)[1] == f) { fd = 2 + r; break; }
-      }
-    if (!fd && f >= P.row_offset && f < P.row_offset + P.n_rows) fd = -1;
-    found = fd;
-  }
-  __syncthreads();
-  if (found == 0) return 0;
-  if (found >= 2) {
-    const double* rec = P.cand_all + (size_t)(found - 2) * P.rec_len;
-    for (int k = threadIdx.x; k < s; k += blockDim.x) P.xf[k] = rec[BC_REC_HDR + k];
-    if (threadIdx.x == 0) S.sel_norm = rec[2];
-  } else if (found == -1) {
-    const long long r = f - P.row_offset;
-    for (int k = threadIdx.x; k < s; k += blockDim.x) P.xf[k] = P.tiles[bc_tile_off(r, k, s)];
-    if (threadIdx.x == 0) S.sel_norm = P.norms[r];
-  }
-  if (threadIdx.x == 0) { S.sel_f = f; S.sel_valid = 1; }
-  __syncthreads();
-  return 1;
 }
 
 // step-wise _reweight(f): no guard here, the host loop owns it (snnls.py:53-61)
@@ -1237,19 +440,17 @@ __global__ __launch_bounds__(BC_FIN_THREADS) void k_refit(SnnlsDev P, long long 
   }
 }
 
-// ------------------------------------------------------------------ host side
-static int fetch_state(bc_snnls* h, SnnlsState* out) {
-  bc_ctx* ctx = h->ctx;
-  BC_HIP(hipMemcpyAsync(ctx->pinned, h->d.st, sizeof(SnnlsState), hipMemcpyDeviceToHost, ctx->stream));
-  BC_HIP(hipStreamSynchronize(ctx->stream));
-  memcpy(out, ctx->pinned, sizeof(SnnlsState));
-  if (out->overflow) {
-    bc_set_error("bc_snnls: active-list capacity exceeded on device (internal error)");
-    return BC_INVALID_ARGUMENT;
-  }
-  return BC_OK;
+__global__ void k_clear_pf_overflow(SnnlsState* st) {
+  st->pf_overflow = 0;
+  st->skip = st->select_fail | st->reached_limit;
 }
 
+__global__ void k_set_flag(SnnlsState* st, int reached) {
+  st->reached_limit = reached;
+  st->skip = st->select_fail | reached;
+}
+
+// ------------------------------------------------------------------ host side: handle lifetime and buffers
 static void free_lists(bc_snnls* h) {
   if (h->list_slab) (void)hipFree(h->list_slab);
   h->list_slab = nullptr;
@@ -1281,11 +482,12 @@ static int ensure_capacity(bc_snnls* h, long long need) {
   double* cn2 = (double*)(slab + 6 * n8 + ncols);
   double* cols2 = (double*)(slab + 7 * n8 + ncols);
   if (h->d.cap > 0) {
-    BC_HIP(hipStreamSynchronize(ctx->stream));
-    BC_HIP(hipMemcpy(idx, h->d.idx, h->d.cap * sizeof(long long), hipMemcpyDeviceToDevice));
-    BC_HIP(hipMemcpy(val, h->d.val, h->d.cap * sizeof(double), hipMemcpyDeviceToDevice));
-    BC_HIP(hipMemcpy(cn, h->d.colnorm, h->d.cap * sizeof(double), hipMemcpyDeviceToDevice));
-    BC_HIP(hipMemcpy(cols, h->d.cols, (size_t)h->d.cap * s * sizeof(double), hipMemcpyDeviceToDevice));
+    e = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = hipMemcpy(idx, h->d.idx, h->d.cap * sizeof(long long), hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipMemcpy(val, h->d.val, h->d.cap * sizeof(double), hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipMemcpy(cn, h->d.colnorm, h->d.cap * sizeof(double), hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipMemcpy(cols, h->d.cols, (size_t)h->d.cap * s * sizeof(double), hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) { (void)hipFree(slab); return bc_hip_fail(e, "hipMemcpy(active list)", __FILE__, __LINE__); }   // the old list stays
   }
   free_lists(h);
   h->list_slab = slab;
@@ -1303,14 +505,22 @@ static int ensure_trace(bc_snnls* h, long long need) {
   long long* f = nullptr;
   int* st = nullptr;
   double* er = nullptr;
-  BC_HIP(hipMalloc((void**)&f, ncap * sizeof(long long)));
-  BC_HIP(hipMalloc((void**)&st, ncap * sizeof(int)));
-  BC_HIP(hipMalloc((void**)&er, ncap * sizeof(double)));
+  hipError_t e = hipMalloc((void**)&f, ncap * sizeof(long long));
+  if (e == hipSuccess) e = hipMalloc((void**)&st, ncap * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc((void**)&er, ncap * sizeof(double));
+  if (e == hipSuccess && h->d.tr_cap > 0) {
+    e = hipStreamSynchronize(h->ctx->stream);
+    if (e == hipSuccess) e = hipMemcpy(f, h->d.tr_f, h->d.tr_cap * sizeof(long long), hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipMemcpy(st, h->d.tr_status, h->d.tr_cap * sizeof(int), hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipMemcpy(er, h->d.tr_err, h->d.tr_cap * sizeof(double), hipMemcpyDeviceToDevice);
+  }
+  if (e != hipSuccess) {                 // the old trace stays
+    void* fresh[] = {f, st, er};
+    for (void* p : fresh)
+      if (p) (void)hipFree(p);
+    return bc_hip_fail(e, "hipMalloc / hipMemcpy(trace)", __FILE__, __LINE__);
+  }
   if (h->d.tr_cap > 0) {
-    BC_HIP(hipStreamSynchronize(h->ctx->stream));
-    BC_HIP(hipMemcpy(f, h->d.tr_f, h->d.tr_cap * sizeof(long long), hipMemcpyDeviceToDevice));
-    BC_HIP(hipMemcpy(st, h->d.tr_status, h->d.tr_cap * sizeof(int), hipMemcpyDeviceToDevice));
-    BC_HIP(hipMemcpy(er, h->d.tr_err, h->d.tr_cap * sizeof(double), hipMemcpyDeviceToDevice));
     (void)hipFree(h->d.tr_f); (void)hipFree(h->d.tr_status); (void)hipFree(h->d.tr_err);
   }
   h->d.tr_f = f; h->d.tr_status = st; h->d.tr_err = er; h->d.tr_cap = ncap;
@@ -1330,6 +540,7 @@ extern "C" int bc_snnls_destroy(bc_snnls* h) {
   return BC_OK;
 }
 
+// ------------------------------------------------------------------ what the environment asks of the pre-filter (read by bc_snnls_create, below)
 // Two-level pre-filter (bc_prefilter_i4.h) wanted?  BC_PREFILTER=4 forces it, =8 keeps the one-level int8 sweep; by default it
 // is used from BC_TWO_LEVEL_MIN_ROWS rows: measured per step at S = 100 (tools/two_level_probe.py, us, two-level / one-level):
 // 1.25M rows 43.4 / 42.5, 2.5M 53.6 / 62, 5M 72.5 / 102, 10M 114 / 177.  S <= 256.
@@ -1366,19 +577,6 @@ static PrefWish pref_wish(long long n_rows, int s) {
   w.prec = w.keep_qv4 ? 4 : prec;
   return w;
 }
-
-#define LAUNCH1(kern, ...)                                                         \
-  do {                                                                             \
-    hipLaunchKernelGGL(kern, dim3(1), dim3(BC_FIN_THREADS), 0, h->ctx->stream, __VA_ARGS__);   \
-    BC_HIP(hipGetLastError());                                                     \
-  } while (0)
-
-#define BY_ALG(kern, ...)                                                          \
-  do {                                                                             \
-    if (h->alg == BC_ALG_GIGA) LAUNCH1(kern<BC_ALG_GIGA>, __VA_ARGS__);             \
-    else if (h->alg == BC_ALG_FW) LAUNCH1(kern<BC_ALG_FW>, __VA_ARGS__);            \
-    else LAUNCH1(kern<BC_ALG_OMP>, __VA_ARGS__);                                    \
-  } while (0)
 
 extern "C" int bc_snnls_create(bc_ctx* ctx, bc_phi* phi, const double* b, int alg, double norm_sum,
                                int allow_zero_rows, bc_snnls** out) {
@@ -1419,11 +617,10 @@ extern "C" int bc_snnls_create(bc_ctx* ctx, bc_phi* phi, const double* b, int al
   {
     // one slab (see bc_snnls::state_slab): st | b | bn | xw | xw_prev | xf | send record | v (zero tail: the fp16
     // sweep reads whole plane batches), every piece 256-byte aligned
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t o_st = 0, o_b = up(sizeof(SnnlsState)), o_bn = o_b + up(s * 8), o_xw = o_bn + up(s * 8), o_xwp = o_xw + up(s * 8),
-                 o_xf = o_xwp + up(s * 8), o_rec = o_xf + up(s * 8), o_v = o_rec + up(d.rec_len * 8),
-                 o_qv = o_v + up(2 * (s + BC_V_PAD) * 8), o_qv4 = o_qv + up((size_t)BC_I8Q_INTS(bc_lay_i8_sp4(s)) * sizeof(int)),
-                 total = o_qv4 + up((size_t)BC_I4Q_INTS(bc_lay_i4_sp8(s, bc_lay_i4_batch(s))) * sizeof(int));
+    const size_t o_st = 0, o_b = bc_up256(sizeof(SnnlsState)), o_bn = o_b + bc_up256(s * 8), o_xw = o_bn + bc_up256(s * 8), o_xwp = o_xw + bc_up256(s * 8),
+                 o_xf = o_xwp + bc_up256(s * 8), o_rec = o_xf + bc_up256(s * 8), o_v = o_rec + bc_up256(d.rec_len * 8),
+                 o_qv = o_v + bc_up256(2 * (s + BC_V_PAD) * 8), o_qv4 = o_qv + bc_up256((size_t)BC_I8Q_INTS(bc_lay_i8_sp4(s)) * sizeof(int)),
+                 total = o_qv4 + bc_up256((size_t)BC_I4Q_INTS(bc_lay_i4_sp8(s, bc_lay_i4_batch(s))) * sizeof(int));
     char* slab = nullptr;
     hipError_t e0 = hipMalloc((void**)&slab, total);
     if (e0 == hipSuccess) e0 = hipMemsetAsync(slab, 0, total, ctx->stream);
@@ -1478,6 +675,25 @@ extern "C" int bc_snnls_create(bc_ctx* ctx, bc_phi* phi, const double* b, int al
     if (d.qv4 && bc_pref_two_level(h->pref) && bc_pref_sp8(h->pref) == d.sp8) bc_pref_set_qv4(h->pref, d.qv4);
   }
   *out = h;
+  return BC_OK;
+}
+
+extern "C" int bc_snnls_set_tolerance(bc_snnls* h, double tol) {
+  if (!h) return BC_INVALID_ARGUMENT;
+  h->d.tol = tol;
+  return BC_OK;
+}
+
+// ------------------------------------------------------------------ readers and counters
+static int fetch_state(bc_snnls* h, SnnlsState* out) {
+  bc_ctx* ctx = h->ctx;
+  BC_HIP(hipMemcpyAsync(ctx->pinned, h->d.st, sizeof(SnnlsState), hipMemcpyDeviceToHost, ctx->stream));
+  BC_HIP(hipStreamSynchronize(ctx->stream));
+  memcpy(out, ctx->pinned, sizeof(SnnlsState));
+  if (out->overflow) {
+    bc_set_error("bc_snnls: active-list capacity exceeded on device (internal error)");
+    return BC_INVALID_ARGUMENT;
+  }
   return BC_OK;
 }
 
@@ -1540,169 +756,84 @@ extern "C" int bc_snnls_prefilter_levels(const bc_snnls* h, int64_t* l1_sweeps, 
   return BC_OK;
 }
 
-// ------------------------------------------------------------------ diagnostic seam (include/beta_cores_prefdiag.h): test aids
-static int mode_of(const bc_snnls* h);
-
-extern "C" int bc_snnls_prefdiag_info(const bc_snnls* h, int64_t* out) {
-  if (!h || !out) { bc_set_error("bc_snnls_prefdiag_info: bad argument"); return BC_INVALID_ARGUMENT; }
-  for (int i = 0; i < BC_PREFDIAG_INFO_N; ++i) out[i] = 0;
-  if (h->pref) bc_pref_diag_info(h->pref, h->d.qv != nullptr, out);
-  return BC_OK;
-}
-
-extern "C" int bc_snnls_prefdiag_copy(const bc_snnls* h, const char* which, void* out, int64_t cap_bytes, int64_t* bytes) {
-  if (!h || !which) { bc_set_error("bc_snnls_prefdiag_copy: bad argument"); return BC_INVALID_ARGUMENT; }
-  if (bytes) *bytes = 0;
-  if (!h->pref) { bc_set_error("bc_snnls_prefdiag_copy: this solver has no pre-filter"); return BC_INVALID_ARGUMENT; }
-  const void* dev = nullptr;
-  size_t n = 0;
-  const double one = 1.0;
-  const void* host = nullptr;
-  const int s = h->d.s;
-  if (strcmp(which, "v") == 0) { dev = h->d.v; n = (size_t)(h->alg == BC_ALG_GIGA ? 2 * s : s) * sizeof(double); }
-  else if (strcmp(which, "v_norm") == 0) { n = sizeof(double); if (h->alg == BC_ALG_GIGA) host = &one; else dev = &h->d.st->v_norm; }
-  else if (strcmp(which, "post_div") == 0) { n = sizeof(double); host = &one; }
-  else if (strcmp(which, "qv") == 0 || strcmp(which, "qv4") == 0) {
-    const bool four = which[2] == '4';
-    dev = four ? (const void*)h->d.qv4 : (const void*)h->d.qv;
-    n = (four ? (size_t)BC_I4Q_INTS(h->d.sp8) : (size_t)BC_I8Q_INTS(h->d.sp4)) * sizeof(int);
-    if (!dev) { bc_set_error("bc_snnls_prefdiag_copy: this solver keeps no \"%s\" record", which); return BC_INVALID_ARGUMENT; }
-  } else {
-    const int rc = bc_pref_diag_buffer(h->pref, which, &dev, &n);
-    if (rc == 1) { bc_set_error("bc_snnls_prefdiag_copy: unknown buffer \"%s\"", which); return BC_INVALID_ARGUMENT; }
-    if (rc == 2) { bc_set_error("bc_snnls_prefdiag_copy: this solver's pre-filter has no buffer \"%s\"", which); return BC_INVALID_ARGUMENT; }
-  }
-  if (bytes) *bytes = (int64_t)n;
-  if (!out || cap_bytes < (int64_t)n) {
-    bc_set_error("bc_snnls_prefdiag_copy: \"%s\" holds %zu bytes, the caller offers %lld", which, n, (long long)cap_bytes);
-    return BC_INVALID_ARGUMENT;
-  }
-  BC_HIP(hipStreamSynchronize(h->ctx->stream));
-  if (host) memcpy(out, host, n);
-  else BC_HIP(hipMemcpy(out, dev, n, hipMemcpyDeviceToHost));
-  return BC_OK;
-}
-
-// one wave: both digit records of a vector that did not come out of a step kernel, with the step kernels' functions
-template <int MODE>
-__global__ __launch_bounds__(64) void k_prefdiag_quant(const double* __restrict__ v, int s, int sp4, int sp8, int* __restrict__ qv,
-                                                       int* __restrict__ qv4, double* __restrict__ v_norm) {
-  const int lane = threadIdx.x;
-  double m0 = 0., m1 = 0., vn = 0.;
-  for (int k = lane; k < s; k += BC_WAVE) {
-    if (MODE == 0) {
-      m0 = bc_i8q_absmax(m0, v[2 * k]);
-      m1 = bc_i8q_absmax(m1, v[2 * k + 1]);
-    } else {
-      m0 = bc_i8q_absmax(m0, v[k]);
-      vn = fma(v[k], v[k], vn);
-    }
-  }
-  const double vnorm = (MODE == 0) ? 1. : sqrt(bc_wave_sum(vn));      // (as dev_prep: GIGA's are unit vectors)
-  if (lane == 0) *v_norm = vnorm;
-  bc_i8q_wave<MODE>(v, s, sp4, vnorm, qv, lane, m0, m1);
-  if (qv4 != nullptr) bc_i4q_wave<MODE>(v, s, sp8, vnorm, qv4, lane, bc_wave_max_all(m0), bc_wave_max_all(m1));
-}
-
-extern "C" int bc_snnls_prefdiag_sweep(bc_snnls* h, int32_t mode, const double* v, double post_div, int32_t self_quantise, float* out_ul,
-                                       float* out_ul8, float* out_theta0, int64_t rows_cap, int32_t blocks_cap, int32_t* form_run) {
-  if (!h || !out_ul || !form_run || mode < 0 || mode > 1) { bc_set_error("bc_snnls_prefdiag_sweep: bad argument"); return BC_INVALID_ARGUMENT; }
-  if (!h->pref) { bc_set_error("bc_snnls_prefdiag_sweep: this solver has no pre-filter"); return BC_INVALID_ARGUMENT; }
-  int64_t info[BC_PREFDIAG_INFO_N];
-  bc_pref_diag_info(h->pref, h->d.qv != nullptr, info);
-  if (info[BC_PREFDIAG_PREC] != 8 || info[BC_PREFDIAG_NEXT_FORM] == 2) {
-    bc_set_error("bc_snnls_prefdiag_sweep: only the one-level int8 sweep and the two-level form have a per-row output (this solver: "
-                 "precision %d, form %d)", (int)info[BC_PREFDIAG_PREC], (int)info[BC_PREFDIAG_NEXT_FORM]);
-    return BC_INVALID_ARGUMENT;
-  }
-  if (h->rs_pending) { bc_set_error("bc_snnls_prefdiag_sweep: a step is in flight"); return BC_INVALID_ARGUMENT; }
-  if (!(post_div == post_div) || post_div == 0. || fabs(post_div) > 1.7976931348623157e308) {
-    bc_set_error("bc_snnls_prefdiag_sweep: post_div must be finite and non-zero");
-    return BC_INVALID_ARGUMENT;
-  }
-  if (!v && mode != mode_of(h)) {
-    bc_set_error("bc_snnls_prefdiag_sweep: the solver's own vectors are those of mode %d", mode_of(h));
-    return BC_INVALID_ARGUMENT;
-  }
-  const int s = h->d.s;
-  if (v && mode == 0) {
-    double n0 = 0., n1 = 0.;
-    for (int k = 0; k < s; ++k) { n0 += v[2 * k] * v[2 * k]; n1 += v[2 * k + 1] * v[2 * k + 1]; }
-    n0 = sqrt(n0); n1 = sqrt(n1);
-    if (fabs(n0 - 1.) > 1e-9 || fabs(n1 - 1.) > 1e-9) {
-      bc_set_error("bc_snnls_prefdiag_sweep: the GIGA sweep takes unit vectors (norms %.12g, %.12g)", n0, n1);
-      return BC_INVALID_ARGUMENT;
-    }
-  }
-  // the digit records this sweep reads: the solver's own, or those of the uploaded vector
-  const bool own = v == nullptr;
-  const bool two = info[BC_PREFDIAG_NEXT_FORM] == 3 && (own ? h->d.qv4 != nullptr : true);
-  if (two && self_quantise) { bc_set_error("bc_snnls_prefdiag_sweep: the two-level form reads digit records (self_quantise)"); return BC_INVALID_ARGUMENT; }
-  const int64_t rows = info[BC_PREFDIAG_PTILES] * 256;
-  if (rows_cap < rows) { bc_set_error("bc_snnls_prefdiag_sweep: %lld rows of output, the caller offers %lld", (long long)rows, (long long)rows_cap); return BC_INVALID_ARGUMENT; }
-  if (two && (!out_ul8 || !out_theta0 || blocks_cap < info[BC_PREFDIAG_GRID1])) {
-    bc_set_error("bc_snnls_prefdiag_sweep: the two-level form needs out_ul8 and out_theta0[%d]", (int)info[BC_PREFDIAG_GRID1]);
-    return BC_INVALID_ARGUMENT;
-  }
-  BC_HIP(hipStreamSynchronize(h->ctx->stream));
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const int grid1 = (int)info[BC_PREFDIAG_GRID1];
-  const size_t o_d1 = 0, o_d2 = o_d1 + up((size_t)rows * sizeof(float2)), o_th = o_d2 + up(two ? (size_t)rows * sizeof(float2) : 0),
-               o_v = o_th + up((size_t)(grid1 > 0 ? grid1 : 1) * sizeof(float)), o_vn = o_v + up(2 * (size_t)(s + BC_V_PAD) * sizeof(double)),
-               o_qv = o_vn + up(sizeof(double)), o_qv4 = o_qv + up((size_t)BC_I8Q_INTS(h->d.sp4) * sizeof(int)),
-               o_save = o_qv4 + up((size_t)BC_I4Q_INTS(h->d.sp8) * sizeof(int)), total = o_save + up(bc_pref_diag_save_bytes());
-  char* sc = nullptr;
-  BC_HIP(hipMalloc((void**)&sc, total));
-  hipStream_t st = h->ctx->stream;
-  int rc = BC_OK, form = 0;
-  auto hip = [&](hipError_t e, const char* what) { if (e != hipSuccess && rc == BC_OK) rc = bc_hip_fail(e, what, __FILE__, __LINE__); };
-  hip(hipMemsetAsync(sc + o_v, 0, total - o_v, st), "hipMemsetAsync(prefdiag)");
-  const double* v_dev = h->d.v;
-  const double* vn_dev = &h->d.st->v_norm;
-  const int* qv = self_quantise ? nullptr : h->d.qv;
-  const int* qv4 = h->d.qv4;
-  if (!own && rc == BC_OK) {
-    hip(hipMemcpyAsync(sc + o_v, v, (size_t)(mode == 0 ? 2 * s : s) * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpyAsync(prefdiag v)");
-    v_dev = (const double*)(sc + o_v);
-    vn_dev = (const double*)(sc + o_vn);
-    int* q8 = (int*)(sc + o_qv);
-    int* q4 = two ? (int*)(sc + o_qv4) : nullptr;
-    if (rc == BC_OK) {
-      if (mode == 0) hipLaunchKernelGGL(k_prefdiag_quant<0>, dim3(1), dim3(64), 0, st, v_dev, s, h->d.sp4, h->d.sp8, q8, q4, (double*)(sc + o_vn));
-      else hipLaunchKernelGGL(k_prefdiag_quant<1>, dim3(1), dim3(64), 0, st, v_dev, s, h->d.sp4, h->d.sp8, q8, q4, (double*)(sc + o_vn));
-      hip(hipGetLastError(), "k_prefdiag_quant");
-    }
-    qv = self_quantise ? nullptr : q8;
-    qv4 = q4;
-  }
-  if (rc == BC_OK)
-    rc = bc_pref_diag_sweep(h->pref, mode, v_dev, vn_dev, qv, two ? qv4 : nullptr, post_div, (float2*)(sc + o_d1), (float2*)(sc + o_d2),
-                            (float*)(sc + o_th), sc + o_save, &form);
-  if (rc == BC_OK && (form == 3) != two) { bc_set_error("bc_snnls_prefdiag_sweep: internal: form %d", form); rc = BC_INVALID_ARGUMENT; }
-  if (rc == BC_OK) hip(hipMemcpyAsync(out_ul, sc + o_d1, (size_t)rows * sizeof(float2), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(prefdiag out)");
-  if (rc == BC_OK && two) {
-    hip(hipMemcpyAsync(out_ul8, sc + o_d2, (size_t)rows * sizeof(float2), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(prefdiag out8)");
-    hip(hipMemcpyAsync(out_theta0, sc + o_th, (size_t)grid1 * sizeof(float), hipMemcpyDeviceToHost, st), "hipMemcpyAsync(prefdiag theta0)");
-  }
-  const hipError_t es = hipStreamSynchronize(st);
-  hip(es, "hipStreamSynchronize(prefdiag)");
-  (void)hipFree(sc);
-  *form_run = form;
-  return rc;
-}
-
-extern "C" int bc_snnls_set_tolerance(bc_snnls* h, double tol) {
-  if (!h) return BC_INVALID_ARGUMENT;
-  h->d.tol = tol;
-  return BC_OK;
-}
-
 extern "C" int bc_snnls_record_doubles(const bc_snnls* h, int32_t* n) {
   if (!h || !n) return BC_INVALID_ARGUMENT;
   *n = h->d.rec_len;
   return BC_OK;
 }
 
+extern "C" int bc_snnls_error(bc_snnls* h, double* err) {
+  if (!h || !err) return BC_INVALID_ARGUMENT;
+  SnnlsState st;
+  int rc = fetch_state(h, &st);
+  if (rc) return rc;
+  *err = st.err_cur;
+  return BC_OK;
+}
+
+extern "C" int bc_snnls_size(bc_snnls* h, int64_t* n) {
+  if (!h || !n) return BC_INVALID_ARGUMENT;
+  SnnlsState st;
+  int rc = fetch_state(h, &st);
+  if (rc) return rc;
+  *n = st.npos;
+  return BC_OK;
+}
+
+extern "C" int bc_snnls_weights(bc_snnls* h, int64_t cap, int64_t* idx, double* val, int64_t* n) {
+  if (!h || !n) return BC_INVALID_ARGUMENT;
+  SnnlsState st;
+  int rc = fetch_state(h, &st);
+  if (rc) return rc;
+  *n = st.nnz;
+  if (st.nnz == 0 || (!idx && !val)) return BC_OK;
+  if (cap < st.nnz) { bc_set_error("bc_snnls_weights: capacity %lld < nnz %lld", (long long)cap, (long long)st.nnz); return BC_INVALID_ARGUMENT; }
+  if (idx) BC_HIP(hipMemcpyAsync(idx, h->d.idx, st.nnz * sizeof(long long), hipMemcpyDeviceToHost, h->ctx->stream));
+  if (val) BC_HIP(hipMemcpyAsync(val, h->d.val, st.nnz * sizeof(double), hipMemcpyDeviceToHost, h->ctx->stream));
+  BC_HIP(hipStreamSynchronize(h->ctx->stream));
+  return BC_OK;
+}
+
+extern "C" int bc_snnls_columns(bc_snnls* h, int64_t cap, double* cols, int64_t* n) {
+  if (!h || !n) return BC_INVALID_ARGUMENT;
+  SnnlsState st;
+  int rc = fetch_state(h, &st);
+  if (rc) return rc;
+  *n = st.nnz;
+  if (st.nnz == 0 || !cols) return BC_OK;
+  if (cap < st.nnz) { bc_set_error("bc_snnls_columns: capacity too small"); return BC_INVALID_ARGUMENT; }
+  BC_HIP(hipMemcpyAsync(cols, h->d.cols, (size_t)st.nnz * h->d.s * sizeof(double), hipMemcpyDeviceToHost, h->ctx->stream));
+  BC_HIP(hipStreamSynchronize(h->ctx->stream));
+  return BC_OK;
+}
+
+extern "C" int bc_snnls_get_flags(bc_snnls* h, int* reached_numeric_limit) {
+  if (!h) return BC_INVALID_ARGUMENT;
+  SnnlsState st;
+  int rc = fetch_state(h, &st);
+  if (rc) return rc;
+  if (reached_numeric_limit) *reached_numeric_limit = st.reached_limit;
+  return BC_OK;
+}
+
+extern "C" int bc_snnls_trace(bc_snnls* h, int64_t cap, int64_t* f, int32_t* status, double* err, int64_t* n) {
+  if (!h || !n) return BC_INVALID_ARGUMENT;
+  SnnlsState st;
+  int rc = fetch_state(h, &st);
+  if (rc) return rc;
+  long long m = std::min<long long>(st.iter, h->d.tr_cap);
+  *n = m;
+  if (m == 0 || (!f && !status && !err)) return BC_OK;
+  if (cap < m) { bc_set_error("bc_snnls_trace: capacity too small"); return BC_INVALID_ARGUMENT; }
+  hipStream_t sm = h->ctx->stream;
+  if (f) BC_HIP(hipMemcpyAsync(f, h->d.tr_f, m * sizeof(long long), hipMemcpyDeviceToHost, sm));
+  if (status) BC_HIP(hipMemcpyAsync(status, h->d.tr_status, m * sizeof(int), hipMemcpyDeviceToHost, sm));
+  if (err) BC_HIP(hipMemcpyAsync(err, h->d.tr_err, m * sizeof(double), hipMemcpyDeviceToHost, sm));
+  BC_HIP(hipStreamSynchronize(sm));
+  return BC_OK;
+}
+
+// ------------------------------------------------------------------ exchange binding
 extern "C" int bc_snnls_bind_exchange(bc_snnls* h, int world, void* cand_send_dev, void* cand_all_dev) {
   if (!h || world < 1 || (world > 1 && (!cand_send_dev || !cand_all_dev))) {
     bc_set_error("bc_snnls_bind_exchange: bad argument");
@@ -1744,7 +875,19 @@ static int exchange(bc_snnls* h) {
   return rc;
 }
 
-static int mode_of(const bc_snnls* h) { return h->alg == BC_ALG_GIGA ? 0 : 1; }
+// ------------------------------------------------------------------ launch helpers
+#define LAUNCH1(kern, ...)                                                         \
+  do {                                                                             \
+    hipLaunchKernelGGL(kern, dim3(1), dim3(BC_FIN_THREADS), 0, h->ctx->stream, __VA_ARGS__);   \
+    BC_HIP(hipGetLastError());                                                     \
+  } while (0)
+
+#define BY_ALG(kern, ...)                                                          \
+  do {                                                                             \
+    if (h->alg == BC_ALG_GIGA) LAUNCH1(kern<BC_ALG_GIGA>, __VA_ARGS__);             \
+    else if (h->alg == BC_ALG_FW) LAUNCH1(kern<BC_ALG_FW>, __VA_ARGS__);            \
+    else LAUNCH1(kern<BC_ALG_OMP>, __VA_ARGS__);                                    \
+  } while (0)
 
 static int launch_prep(bc_snnls* h, int reset_retry) {
   BY_ALG(k_prep, h->d, reset_retry);
@@ -1784,12 +927,7 @@ static int launch_sweep(bc_snnls* h, bool with_record, bool allow_fused) {
   return bc_launch_sweep(h->phi, mode_of(h), h->d.v, 1.0, &h->d.st->skip, rec ? h->cand_send : nullptr);
 }
 
-__global__ void k_clear_pf_overflow(SnnlsState* st) {
-  st->pf_overflow = 0;
-  st->skip = st->select_fail | st->reached_limit;
-}
-
-// ---- device NNLS refit: state and LDS budget
+// ------------------------------------------------------------------ device refit
 static size_t nnls_lds_bytes(int s_vecs) { return ((size_t)BC_NNLS_WS_DOUBLES + (size_t)5 * s_vecs) * sizeof(double); }
 
 // Gram state of the list and the refit counters (allocated on first use), and the kernels' dynamic-LDS allowance: the packed
@@ -1889,7 +1027,7 @@ extern "C" int bc_snnls_refit_stats(const bc_snnls* h, int64_t* refits, int64_t*
   return BC_OK;
 }
 
-// ---- fused loop
+// ------------------------------------------------------------------ fused loop
 extern "C" int bc_snnls_build_begin(bc_snnls* h, int itrs) {
   if (!h || itrs < 0) { bc_set_error("bc_snnls_build_begin: bad argument"); return BC_INVALID_ARGUMENT; }
   if (h->alg == BC_ALG_OMP && !h->dev_refit) {
@@ -2047,7 +1185,7 @@ extern "C" int bc_snnls_build(bc_snnls* h, int itrs, int* reached_numeric_limit)
   return BC_OK;
 }
 
-// ---- step-wise protocol
+// ------------------------------------------------------------------ step-wise protocol
 extern "C" int bc_snnls_select_local(bc_snnls* h) {
   if (!h) return BC_INVALID_ARGUMENT;
   int rc = launch_prep(h, 0);
@@ -2114,51 +1252,6 @@ extern "C" int bc_snnls_reweight(bc_snnls* h, int64_t f) {
   return st.last_status;
 }
 
-extern "C" int bc_snnls_error(bc_snnls* h, double* err) {
-  if (!h || !err) return BC_INVALID_ARGUMENT;
-  SnnlsState st;
-  int rc = fetch_state(h, &st);
-  if (rc) return rc;
-  *err = st.err_cur;
-  return BC_OK;
-}
-
-extern "C" int bc_snnls_size(bc_snnls* h, int64_t* n) {
-  if (!h || !n) return BC_INVALID_ARGUMENT;
-  SnnlsState st;
-  int rc = fetch_state(h, &st);
-  if (rc) return rc;
-  *n = st.npos;
-  return BC_OK;
-}
-
-extern "C" int bc_snnls_weights(bc_snnls* h, int64_t cap, int64_t* idx, double* val, int64_t* n) {
-  if (!h || !n) return BC_INVALID_ARGUMENT;
-  SnnlsState st;
-  int rc = fetch_state(h, &st);
-  if (rc) return rc;
-  *n = st.nnz;
-  if (st.nnz == 0 || (!idx && !val)) return BC_OK;
-  if (cap < st.nnz) { bc_set_error("bc_snnls_weights: capacity %lld < nnz %lld", (long long)cap, (long long)st.nnz); return BC_INVALID_ARGUMENT; }
-  if (idx) BC_HIP(hipMemcpyAsync(idx, h->d.idx, st.nnz * sizeof(long long), hipMemcpyDeviceToHost, h->ctx->stream));
-  if (val) BC_HIP(hipMemcpyAsync(val, h->d.val, st.nnz * sizeof(double), hipMemcpyDeviceToHost, h->ctx->stream));
-  BC_HIP(hipStreamSynchronize(h->ctx->stream));
-  return BC_OK;
-}
-
-extern "C" int bc_snnls_columns(bc_snnls* h, int64_t cap, double* cols, int64_t* n) {
-  if (!h || !n) return BC_INVALID_ARGUMENT;
-  SnnlsState st;
-  int rc = fetch_state(h, &st);
-  if (rc) return rc;
-  *n = st.nnz;
-  if (st.nnz == 0 || !cols) return BC_OK;
-  if (cap < st.nnz) { bc_set_error("bc_snnls_columns: capacity too small"); return BC_INVALID_ARGUMENT; }
-  BC_HIP(hipMemcpyAsync(cols, h->d.cols, (size_t)st.nnz * h->d.s * sizeof(double), hipMemcpyDeviceToHost, h->ctx->stream));
-  BC_HIP(hipStreamSynchronize(h->ctx->stream));
-  return BC_OK;
-}
-
 extern "C" int bc_snnls_set_weights(bc_snnls* h, int64_t n, const int64_t* idx, const double* val, const double* cols) {
   if (!h || n < 0 || (n > 0 && (!idx || !val))) { bc_set_error("bc_snnls_set_weights: bad argument"); return BC_INVALID_ARGUMENT; }
   bc_ctx* ctx = h->ctx;
@@ -2210,41 +1303,10 @@ extern "C" int bc_snnls_reset(bc_snnls* h) {
   return BC_OK;
 }
 
-extern "C" int bc_snnls_get_flags(bc_snnls* h, int* reached_numeric_limit) {
-  if (!h) return BC_INVALID_ARGUMENT;
-  SnnlsState st;
-  int rc = fetch_state(h, &st);
-  if (rc) return rc;
-  if (reached_numeric_limit) *reached_numeric_limit = st.reached_limit;
-  return BC_OK;
-}
-
-__global__ void k_set_flag(SnnlsState* st, int reached) {
-  st->reached_limit = reached;
-  st->skip = st->select_fail | reached;
-}
-
 extern "C" int bc_snnls_set_flags(bc_snnls* h, int reached_numeric_limit) {
   if (!h) return BC_INVALID_ARGUMENT;
   hipLaunchKernelGGL(k_set_flag, dim3(1), dim3(1), 0, h->ctx->stream, h->d.st, reached_numeric_limit ? 1 : 0);
   BC_HIP(hipGetLastError());
   BC_HIP(hipStreamSynchronize(h->ctx->stream));
-  return BC_OK;
-}
-
-extern "C" int bc_snnls_trace(bc_snnls* h, int64_t cap, int64_t* f, int32_t* status, double* err, int64_t* n) {
-  if (!h || !n) return BC_INVALID_ARGUMENT;
-  SnnlsState st;
-  int rc = fetch_state(h, &st);
-  if (rc) return rc;
-  long long m = std::min<long long>(st.iter, h->d.tr_cap);
-  *n = m;
-  if (m == 0 || (!f && !status && !err)) return BC_OK;
-  if (cap < m) { bc_set_error("bc_snnls_trace: capacity too small"); return BC_INVALID_ARGUMENT; }
-  hipStream_t sm = h->ctx->stream;
-  if (f) BC_HIP(hipMemcpyAsync(f, h->d.tr_f, m * sizeof(long long), hipMemcpyDeviceToHost, sm));
-  if (status) BC_HIP(hipMemcpyAsync(status, h->d.tr_status, m * sizeof(int), hipMemcpyDeviceToHost, sm));
-  if (err) BC_HIP(hipMemcpyAsync(err, h->d.tr_err, m * sizeof(double), hipMemcpyDeviceToHost, sm));
-  BC_HIP(hipStreamSynchronize(sm));
   return BC_OK;
 }

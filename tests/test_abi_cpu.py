@@ -51,6 +51,22 @@ def test_no_oracle_import_in_product():
                 assert 'fake_engine' not in txt
 
 
+def test_prefdiag_test_aids_live_in_their_own_unit():
+    """The solver's kernels and host side know nothing of the diagnostic seam; bc_snnls_diag.hip defines exactly its entries."""
+    csrc = os.path.join(ROOT, 'beta_cores_amd', 'csrc')
+    for f in ('bc_snnls.hip', 'bc_snnls_dev.h'):
+        assert 'prefdiag' not in open(os.path.join(csrc, f)).read(), f
+    hdr = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'beta_cores_prefdiag.h')).read(), flags=re.S)
+    declared = sorted(re.findall(r'\b(bc_snnls_prefdiag_[a-z0-9_]+)\s*\(', hdr))
+    assert len(declared) == 3 and len(set(declared)) == 3, declared
+    diag = open(os.path.join(csrc, 'bc_snnls_diag.hip')).read()
+    defined = sorted(re.findall(r'^extern "C" int (bc_snnls_prefdiag_[a-z0-9_]+)\s*\(', diag, flags=re.M))
+    assert defined == declared, (defined, declared)
+    assert diag.count('extern "C"') == 3          # ... and no other entry point
+    srcs = re.search(r'^SRCS\s*=\s*(.*)$', open(os.path.join(csrc, 'Makefile')).read(), flags=re.M).group(1).split()
+    assert 'bc_snnls_diag.hip' in srcs and 'bc_snnls.hip' in srcs, srcs
+
+
 @pytest.mark.skipif(have_gpu(), reason='checks the no-GPU failure mode')
 def test_product_path_fails_loudly_without_gpu():
     import beta_cores_amd as bc
