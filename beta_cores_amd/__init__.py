@@ -20,6 +20,7 @@ from .coreset import (Coreset, HilbertCoreset, BetaCoreset, SparseVICoreset, Bat
                       BetaBlackBoxProjector, DeviceProjector, DeviceBetaProjector)
 from . import likelihoods
 from . import samplers
+from .samplers import RegressionHeldOut, linreg_predictive
 from . import encoders
 from . import valuation
 from .posterior import weighted_gram, weighted_post, weighted_post_corrected, gaussian_weighted_post, logistic_newton_pass
@@ -30,4 +31,4 @@ __all__ = ['util', 'snnls', 'likelihoods', 'samplers', 'encoders', 'valuation', 
            'BatchPSVICoreset', 'UniformSamplingCoreset',
            'Projector', 'BlackBoxProjector', 'BetaBlackBoxProjector', 'DeviceProjector', 'DeviceBetaProjector',
            'ShardComm', 'shard_bounds', 'weighted_gram', 'weighted_post', 'weighted_post_corrected',
-           'gaussian_weighted_post', 'logistic_newton_pass']
+           'gaussian_weighted_post', 'logistic_newton_pass', 'RegressionHeldOut', 'linreg_predictive']

@@ -219,6 +219,12 @@ _SCORE_SIGNATURES = {
 }
 SCORE_EXPORTS = sorted(_SCORE_SIGNATURES)
 
+# entry points of the extension header include/beta_cores_predict.h (held-out Gaussian predictive scores of the linear-regression family)
+_PREDICT_SIGNATURES = {
+    'bc_linreg_predict': [vp, vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp],
+}
+PREDICT_EXPORTS = sorted(_PREDICT_SIGNATURES)
+
 # entry points of the extension header include/beta_cores_prefdiag.h (test aids: the pre-filter's mirrors and per-row bounds)
 _PREFDIAG_SIGNATURES = {
     'bc_snnls_prefdiag_info': [vp, c_i64p],
@@ -262,7 +268,7 @@ def load():
             + list(_TAKE_SIGNATURES.items()) + list(_BETAGRAD_SIGNATURES.items()) + list(_ENCODE_SIGNATURES.items()) \
             + list(_VIOPT_SIGNATURES.items()) + list(_PSVI_SIGNATURES.items()) + list(_VILAPLACE_SIGNATURES.items()) \
             + list(_HMC_SIGNATURES.items()) + list(_HMC_SMALL_SIGNATURES.items()) + list(_SCORE_SIGNATURES.items()) \
-            + list(_PREFDIAG_SIGNATURES.items()):
+            + list(_PREFDIAG_SIGNATURES.items()) + list(_PREDICT_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int

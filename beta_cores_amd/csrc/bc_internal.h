@@ -109,6 +109,7 @@ struct bc_ctx {
   struct bc_hmc* hmc = nullptr;        // bc_hmc_* (bc_hmc.hip): the buffers and the state of the HMC run in progress
   struct bc_hmc_small* hmc_small = nullptr;   // bc_hmc_small_* (bc_hmc_small.hip): the same for the batched small-problem run
   bc_scratch score;              // bc_lr_score (bc_score.hip): theta | ll | correct (ints)
+  bc_scratch predict;            // bc_linreg_predict (bc_predict.hip): mu | factor | packed factor | noise | scale | partials | ll | sse | mean | var
 };
 
 // bc_upload.hip: rows of a host array -> dst_dev through pinned staging and several copy threads; the hook (optional) is

@@ -548,6 +548,117 @@ def logistic_score(held, thetas):
     return cor.astype(np.int64), ll
 
 
+# ---- held-out Gaussian predictive scores of the linear-regression family (include/beta_cores_predict.h)
+PREDICT_MAX_DIM = 512
+
+
+class RegressionHeldOut:
+    """Held-out rows `[x, y]` of the linear-regression drivers, resident on the device for linreg_predictive.
+
+    Zt: an ndarray, a CUDA torch tensor (borrowed, see DeviceData.from_torch) or a DeviceData, Nt x (D + 1).  Kept once; `dtype`
+    as in DeviceData (float32 keeps a float32 array as it is).  With an `encoder` (encoders.MLPEncoder) Zt holds RAW rows
+    `[raw x, y]`: they stay resident beside a cache of the encoded rows, which is refilled by DeviceData.encode(..., out=cache)
+    whenever `encoder.version` has moved, in `encoded_dtype` -- float32 by default, the storage DeviceProjector(encoder=...) uses
+    for its encoded rows, so the scorer sees the features K1 saw.  `.shape` is (Nt, D + 1) of what the kernel reads."""
+
+    def __init__(self, Zt, encoder=None, ctx=None, dtype=None, encoded_dtype=np.float32):
+        if isinstance(Zt, DeviceData):
+            raw = Zt
+        elif hasattr(Zt, 'is_cuda') and hasattr(Zt, 'data_ptr'):
+            raw = DeviceData.from_torch(Zt, ctx=ctx)
+        else:
+            Zt = np.asarray(Zt)
+            if Zt.ndim != 2 or Zt.shape[0] < 1 or Zt.shape[1] < 2:
+                raise ValueError('Zt must be Nt x (D + 1) rows [x, y] with Nt >= 1 and D >= 1, got shape %r' % (Zt.shape,))
+            if encoder is None and Zt.shape[1] - 1 > PREDICT_MAX_DIM:
+                raise ValueError('the rows must have 1 .. %d features, got %d' % (PREDICT_MAX_DIM, Zt.shape[1] - 1))
+            raw = DeviceData(Zt, ctx=ctx, dtype=dtype)
+        if ctx is not None and raw.ctx is not ctx:
+            raise ValueError('the held-out rows live on another context')
+        self.ctx = raw.ctx
+        self.raw = raw
+        self.encoder = encoder
+        self.encoded_dtype = np.dtype(encoded_dtype)
+        self._cache, self._cache_version = None, None
+        if encoder is not None:
+            if encoder.ctx is not self.ctx:
+                raise ValueError('the encoder lives on another context than the held-out rows')
+            if raw.shape[1] != encoder.widths[0] + 1:
+                raise ValueError('the held-out rows have %d columns, the encoder takes %d + 1 (y)' % (raw.shape[1], encoder.widths[0]))
+            width = encoder.widths[-1]
+        else:
+            width = raw.shape[1] - 1
+        if raw.shape[0] < 1 or not 1 <= width <= PREDICT_MAX_DIM:
+            raise ValueError('the scored rows must be Nt >= 1 rows of 1 .. %d features and y, got %d x (%d + 1)' % (PREDICT_MAX_DIM, raw.shape[0], width))
+        self.shape = (raw.shape[0], width + 1)
+
+    def rows(self):
+        """The DeviceData the kernel reads: the resident rows, or with an encoder their encoded copy (re-encoded when
+        `encoder.version` has moved since the cache was filled)."""
+        if self.encoder is None:
+            return self.raw
+        if self._cache_version != self.encoder.version:
+            self._cache = self.raw.encode(self.encoder, pass_cols=1, dtype=self.encoded_dtype, out=self._cache)
+            self._cache_version = self.encoder.version
+        return self._cache
+
+
+class PredictiveScores:
+    """What linreg_predictive returns: `.ll` and `.sse` ([T]: the summed Gaussian predictive log density and the summed squared
+    error of each posterior over the Nt held-out rows), `.n` = Nt, and `.mean` / `.var` (T x Nt, or None without per_row)."""
+
+    def __init__(self, ll, sse, n, mean=None, var=None):
+        self.ll, self.sse, self.n, self.mean, self.var = ll, sse, int(n), mean, var
+
+    def nll(self):
+        """-ll / Nt: the neural-linear driver's average loss (the mean negative log density)."""
+        return -self.ll / self.n
+
+    def rmse(self, output_std=1.0):
+        """output_std * sqrt(sse / Nt): the reference's RMSE after un-normalising (the output mean cancels in the residual)."""
+        return output_std * np.sqrt(self.sse / self.n)
+
+
+def linreg_predictive(held, mu, factor, noise, scale=1.0, per_row=False):
+    """Held-out scores of T Gaussian posteriors N(mu_t, F_t F_t^T) of a linear head against a RegressionHeldOut:
+
+        m = phi . mu,   var = noise + scale * ||F^T phi||^2,   ll = sum_n log N(y_n; m_n, var_n),   sse = sum_n (y_n - m_n)^2
+
+    mu: D or T x D.  factor: D x D or T x D x D, ANY factor of the covariance (weighted_post's LSigp gives the covariance the
+    reference's samplers draw from, the TRANSPOSE of weighted_post_corrected's LSigp the true posterior, whose covariance is
+    LSigp^T LSigp); it enters as a factor so that the
+    variance cannot go negative.  noise (> 0), scale (>= 0): scalars or T-vectors; noise = sigma^2, scale = 1 is the reference's
+    BayesianRegressionDense, noise = scale = b / a the variance of its fully Bayesian head.  The density is Gaussian only.
+    One kernel (k_linreg_predict, the contraction on the fp64 matrix cores, rows split over blocks) and a fixed-order sum of the
+    block partials; a posterior's bits do not depend on its batch or on per_row.  D <= 512, one device.  No CPU fallback."""
+    if not isinstance(held, RegressionHeldOut):
+        raise TypeError('linreg_predictive wants a RegressionHeldOut, got %s' % type(held).__name__)
+    nt, d = held.shape[0], held.shape[1] - 1
+    mu = np.asarray(mu, dtype=np.float64)
+    factor = np.asarray(factor, dtype=np.float64)
+    if mu.ndim == 1:
+        mu = mu[None]
+    if factor.ndim == 2:
+        factor = factor[None]
+    if mu.ndim != 2 or mu.shape[0] < 1 or mu.shape[1] != d:
+        raise ValueError('mu must be %d or T x %d with T >= 1, got shape %r' % (d, d, mu.shape))
+    T = mu.shape[0]
+    if factor.shape != (T, d, d):
+        raise ValueError('factor must be %d x %d or %d x %d x %d, got shape %r' % (d, d, T, d, d, factor.shape))
+    vecs = []
+    for name, v in (('noise', noise), ('scale', scale)):
+        v = np.asarray(v, dtype=np.float64)
+        if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != T):
+            raise ValueError('%s must be a scalar or %d values, got shape %r' % (name, T, v.shape))
+        vecs.append(np.ascontiguousarray(np.broadcast_to(v, (T,))))
+    mu, factor = np.ascontiguousarray(mu), np.ascontiguousarray(factor)
+    ll, sse = np.empty(T), np.empty(T)
+    mean, var = (np.empty((T, nt)), np.empty((T, nt))) if per_row else (None, None)
+    N.call('bc_linreg_predict', held.ctx.h, held.rows().h, _ptr(mu), _ptr(factor), _ptr(vecs[0]), _ptr(vecs[1]), T, _ptr(ll), _ptr(sse),
+           _ptr(mean) if per_row else None, _ptr(var) if per_row else None)
+    return PredictiveScores(ll, sse, nt, mean, var)
+
+
 # ---- the same for MANY small problems at once: the weighted coresets of an evaluation curve (include/beta_cores_hmc_small.h)
 class HMCManyResult(list):
     """What logistic_hmc_many returns: a list with one HMCResult per problem (None for a marked problem under strict=False).

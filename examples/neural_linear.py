@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Batch coreset construction for a neural-linear model on RAW resident rows, the feature map on the device.
 
-    python examples/neural_linear.py [--n 200000] [--alg BCORES|SVI] [--batches 5] [--seed 1]
+    python examples/neural_linear.py [--n 200000] [--alg BCORES|SVI] [--batches 5] [--seed 1] [--held 20000]
 
 The loop of the reference's neural-linear driver (zellner_neural_linear/main.py) on synthetic data: a small torch network
 x -> 20 features (Linear -> BatchNorm1d -> ReLU, twice) with a Bayesian linear head; every batch acquires one group of 20
@@ -9,6 +9,11 @@ rows with BetaCoreset / SparseVICoreset (groups, an initial set, sub-sampled sel
 network on the weighted coreset and hands the new parameters to the device encoder (`enc.update_from_torch`).  The raw
 rows [x, y] stay resident as float32; the projector encodes between the gather and K1 (`DeviceProjector(encoder=enc)`),
 the sampler sees the device's features of the coreset points (`enc(pts)`), and `get()` returns raw rows.
+
+After every batch the Bayesian head is judged as the driver's `nl.test(...)` judges it: `--held` further rows, drawn from the same
+process with a stream of their own and never handed to the coreset, stay resident as raw float32 rows
+(`RegressionHeldOut(encoder=enc)` re-encodes them once per retrained network), the head's posteriors come from `weighted_post` and
+`weighted_post_corrected` on `enc(pts)`, and one `linreg_predictive` call returns for both the mean negative log density of its Gaussian predictive and the RMSE -- on the device.
 """
 import argparse
 import os
@@ -48,6 +53,7 @@ def main():
     ap.add_argument('--batches', type=int, default=5)
     ap.add_argument('--proj-dim', type=int, default=100)
     ap.add_argument('--seed', type=int, default=1)
+    ap.add_argument('--held', type=int, default=20000)
     a = ap.parse_args()
     np.random.seed(a.seed)
     out_features, group, init_size, sigsq = 20, 20, 20, 1.0
@@ -62,6 +68,10 @@ def main():
     train(net, head, np.ones(init_size), Z_init)
     enc = bc.encoders.MLPEncoder.from_torch(net)
     data = bc.DeviceData(Z, dtype=np.float32)      # the raw rows, uploaded once, 4 bytes an entry
+    hrng = np.random.RandomState(a.seed + 1)       # the held-out split: its own stream, so the draws above and below are unchanged
+    Xh = hrng.randn(a.held, a.d)
+    yh = np.tanh(Xh[:, 0]) + 0.5 * Xh[:, 1] * Xh[:, 2] + 0.1 * hrng.randn(a.held)
+    held = bc.RegressionHeldOut(np.hstack((Xh, yh[:, None])).astype(np.float32), encoder=enc, dtype=np.float32)
 
     Sig0inv = np.eye(out_features)
 
@@ -93,6 +103,14 @@ def main():
             rmse = float(torch.sqrt(torch.mean((head(net(torch.from_numpy(Z[:5000, :-1]))).squeeze(1) - torch.from_numpy(Z[:5000, -1])) ** 2)))
         print('batch %d: %d points, %d groups, rmse on 5000 rows %.4f, encoder version %d, bulk encodes so far %d'
               % (m, len(idcs), len(alg.selected_groups), rmse, enc.version, prj.encode_launches))
+        # two posteriors of the head in ONE call: weighted_post's (the covariance LSigp LSigp^T the reference's samplers draw
+        # from, its quirk included) and weighted_post_corrected's (the true posterior: covariance LSigp^T LSigp, so F = LSigp^T)
+        z = enc(pts)
+        mu_q, L_q, _ = bc.weighted_post(np.ones(out_features), Sig0inv, sigsq, z, wts)
+        mu_c, L_c, _ = bc.weighted_post_corrected(np.ones(out_features), Sig0inv, sigsq, z, wts)
+        scores = bc.linreg_predictive(held, np.array([mu_q, mu_c]), np.array([L_q, L_c.T]), sigsq)      # re-encodes the held-out rows once
+        print('         Bayesian head on %d held-out rows: nll %.4f, rmse %.4f (weighted_post); nll %.4f, rmse %.4f (true posterior)'
+              % (a.held, scores.nll()[0], scores.rmse()[0], scores.nll()[1], scores.rmse()[1]))
 
 
 if __name__ == '__main__':
