@@ -219,6 +219,14 @@ _SCORE_SIGNATURES = {
 }
 SCORE_EXPORTS = sorted(_SCORE_SIGNATURES)
 
+# entry points of the extension header include/beta_cores_laplace_small.h (many small logistic posteriors Laplace-fitted at once, one block each)
+_LAPLACE_SMALL_SIGNATURES = {
+    'bc_laplace_small': [vp, vp, vp, vp, C.c_int32, C.c_int32, vp, C.c_int32, vp, C.c_int64, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                         vp, vp],
+    'bc_laplace_small_device_ms': [vp, c_dp],
+}
+LAPLACE_SMALL_EXPORTS = sorted(_LAPLACE_SMALL_SIGNATURES)
+
 # entry points of the extension header include/beta_cores_predict.h (held-out Gaussian predictive scores of the linear-regression family)
 _PREDICT_SIGNATURES = {
     'bc_linreg_predict': [vp, vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp, vp],
@@ -268,7 +276,7 @@ def load():
             + list(_TAKE_SIGNATURES.items()) + list(_BETAGRAD_SIGNATURES.items()) + list(_ENCODE_SIGNATURES.items()) \
             + list(_VIOPT_SIGNATURES.items()) + list(_PSVI_SIGNATURES.items()) + list(_VILAPLACE_SIGNATURES.items()) \
             + list(_HMC_SIGNATURES.items()) + list(_HMC_SMALL_SIGNATURES.items()) + list(_SCORE_SIGNATURES.items()) \
-            + list(_PREFDIAG_SIGNATURES.items()) + list(_PREDICT_SIGNATURES.items()):
+            + list(_PREFDIAG_SIGNATURES.items()) + list(_PREDICT_SIGNATURES.items()) + list(_LAPLACE_SMALL_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int

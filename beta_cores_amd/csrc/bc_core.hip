@@ -123,6 +123,7 @@ void bc_run_clock::free() {
 //   bc_hmc_small_begin, bc_hmc_small_logjoint                                refuse   refuse   refuse   refuse
 //   bc_lr_score                                                              allow    allow    refuse   refuse
 //   bc_linreg_predict                                                        allow    allow    refuse   refuse
+//   bc_laplace_small (synchronous: holds nothing after it returns)           refuse   refuse   refuse   refuse
 //
 // An entrant passes the holders of its row that refuse it; they are looked at in the order G, V, H, S, and the first one found
 // is named.  Nothing is enqueued, allocated or changed by a refusal.
@@ -169,6 +170,7 @@ extern "C" int bc_ctx_destroy(bc_ctx* ctx) {
   bc_viopt_free(ctx);
   bc_hmc_free(ctx);
   bc_hmc_small_free(ctx);
+  bc_laplace_small_free(ctx);
   bc_scratch_free(&ctx->score);
   bc_scratch_free(&ctx->predict);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);

@@ -108,6 +108,7 @@ struct bc_ctx {
   struct bc_viopt* viopt = nullptr;    // bc_vi_optimize (bc_viopt.hip): the buffers and the state of the run in progress
   struct bc_hmc* hmc = nullptr;        // bc_hmc_* (bc_hmc.hip): the buffers and the state of the HMC run in progress
   struct bc_hmc_small* hmc_small = nullptr;   // bc_hmc_small_* (bc_hmc_small.hip): the same for the batched small-problem run
+  struct bc_lap_small* laplace_small = nullptr;   // bc_laplace_small (bc_laplace_small.hip): the buffers of the batched Laplace fit
   bc_scratch score;              // bc_lr_score (bc_score.hip): theta | ll | correct (ints)
   bc_scratch predict;            // bc_linreg_predict (bc_predict.hip): mu | factor | packed factor | noise | scale | partials | ll | sse | mean | var
 };
@@ -129,6 +130,7 @@ void bc_hmc_free(bc_ctx* ctx);       // bc_hmc.hip
 bool bc_hmc_active(const bc_ctx* ctx);     // the context holds an open bc_hmc run
 void bc_hmc_small_free(bc_ctx* ctx); // bc_hmc_small.hip
 bool bc_hmc_small_active(const bc_ctx* ctx);   // the context holds an open bc_hmc_small run
+void bc_laplace_small_free(bc_ctx* ctx);   // bc_laplace_small.hip (the call is synchronous: it never holds the context)
 // bc_score.hip: the checks of the held-out pair (d_run > 0: the columns the rows must have), and k_lr_score over t thetas that are
 // already on the device; enqueued only
 int bc_score_check(const bc_ctx* ctx, const struct bc_data* zt, const struct bc_data* yt, int64_t t, int32_t d_run, const char* who);

@@ -1,4 +1,5 @@
-// The logistic Laplace sampler of the greedy-VI weight optimisation, for one thread block (k_vi_laplace in bc_viopt.hip).
+// The logistic Laplace sampler of the greedy-VI weight optimisation, for one thread block (k_vi_laplace in bc_viopt.hip); the
+// same four stages, one block per problem, are the batched fit of many small posteriors (k_laplace_many in bc_laplace_small.hip).
 //
 //   mu = argmax_th  f(th) = -sum_n w_n softplus(-z_n . th) - D/2 log(2 pi) - th . th / 2          (rows z = y * x, prior N(0, I))
 //   Theta = mu + E . C^-T            with  C = chol(H(mu)),  H(th) = I + Z^T diag(w p (1 - p)) Z,  p_n = sigmoid(-z_n . th)
@@ -25,7 +26,7 @@
 //
 // Written the way bc_vi_sampler_dev.h is: the same text compiles for the host with tid = 0, nt = 1 and an empty barrier; what
 // the host cannot compile (MFMA, cross-lane moves) is under __HIPCC__ with a plain loop of the same mathematical result beside
-// it (tests/vi_laplace_harness.cpp).  On the device the block is BC_VIL_BLOCK threads.
+// it (tests/vi_laplace_harness.cpp, tests/laplace_many_harness.cpp).  On the device the block is BC_VIL_BLOCK threads.
 #pragma once
 #include <math.h>
 
@@ -273,19 +274,42 @@ BC_VIL_FN inline void bc_vil_backsolve(const double* A, const double* rdiag, int
 #endif
 }
 
-// Returns 1 (block-uniform) when the run must stop; nothing has been written to theta, mode or counts then.
-// ws: BC_VIL_WS_DOUBLES(d) doubles.
-BC_VIL_FN inline int bc_vi_laplace(const VilArgs& a, double* ws) {
+// ---- the four stages of a fit.  bc_vi_laplace() below runs them in order; k_laplace_many (bc_laplace_small.hip) runs the same
+// four and stores, between and after them, what bc_vi_laplace() computes but does not keep.
+struct VilWs {             // the pieces of the BC_VIL_WS_DOUBLES(d) doubles of work space
+  double* A;               // [H; g^T], then [C; y^T], packed: (i, k) at i (i + 1) / 2 + k
+  double* Li;              // C^-1, packed
+  double *mu, *stp, *cand;
+  double* rdiag;           // 1 / C[k][k]
+  double* red;             // [16]
+  double* part;
+};
+
+struct VilFit {            // what the mode search found besides mu (block-uniform)
+  double f;                // f(mu)
+  double dec;              // the decrement of the last Newton system solved
+  int steps, halvings, halvings_all;
+};
+
+BC_VIL_FN inline VilWs bc_vil_ws(double* ws, int d) {
+  VilWs W;
+  W.A = ws;
+  W.Li = W.A + BC_VIL_TRI(d + 1);
+  W.mu = W.Li + BC_VIL_TRI(d);
+  W.stp = W.mu + d;
+  W.cand = W.stp + d;
+  W.rdiag = W.cand + d;
+  W.red = W.rdiag + d;
+  W.part = W.red + 16;
+  return W;
+}
+
+// The mode search from the start point in a.mode: W.mu <- the mode; rowc keeps the m_n of the mode.  Returns 1 (block-uniform)
+// when the run must stop; writes nothing but the work space and rowc.
+BC_VIL_FN inline int bc_vil_mode(const VilArgs& a, const VilWs& W, VilFit* fit) {
   const int tid = BC_VIL_TID, nt = BC_VIL_NT;
   const int d = a.d, m = a.m;
-  double* A = ws;                               // [H; g^T], then [C; y^T], packed: (i, k) at i (i + 1) / 2 + k
-  double* Li = A + BC_VIL_TRI(d + 1);           // C^-1, packed
-  double* mu = Li + BC_VIL_TRI(d);
-  double* stp = mu + d;
-  double* cand = stp + d;
-  double* rdiag = cand + d;                     // 1 / C[k][k]
-  double* red = rdiag + d;                      // [16]
-  double* part = red + 16;
+  double *A = W.A, *mu = W.mu, *stp = W.stp, *cand = W.cand, *rdiag = W.rdiag, *red = W.red, *part = W.part;
   int grp = 1;                                  // lanes per row of the value pass
   while (grp < 16 && 2 * grp <= nt && (long)m * (2 * grp) <= nt && 2 * grp <= d) grp *= 2;
   for (int j = tid; j < d; j += nt) mu[j] = a.mode[j];
@@ -332,95 +356,137 @@ BC_VIL_FN inline int bc_vi_laplace(const VilArgs& a, double* ws) {
     // the host's rule: a FULL step whose decrement was at the rounding floor of f, or a step at the rounding floor of mu
     if ((t == 1. && dec <= 64. * 2.220446049250313e-16 * (1. + fabs(f))) || smax <= 1e-13 * (1. + mmax)) break;
   }
-  // ---- H at the mode (rowc holds the m_n of the last point evaluated, which is mu)
+  fit->f = f;
+  fit->dec = dec;
+  fit->steps = steps;
+  fit->halvings = halvings;
+  fit->halvings_all = halvings_all;
+  return 0;
+}
+
+// H at the mode into the packed triangle W.A (rowc holds the m_n of the last point evaluated, which is mu); ends with a barrier.
+BC_VIL_FN inline void bc_vil_hessian(const VilArgs& a, const VilWs& W) {
+  const int tid = BC_VIL_TID, nt = BC_VIL_NT;
   bc_vil_row_coefs(a, tid, nt);
   BC_VIL_SYNC();
-  bc_vil_gram(a, A, mu, part, tid, nt);
+  bc_vil_gram(a, W.A, W.mu, W.part, tid, nt);
   BC_VIL_SYNC();
-  const int total = a.s * d;
+}
+
+// The factor and its inverse: W.A <- C = chol(H), W.Li <- C^-1 (both packed); ends with a barrier.  The diagonal form only
+// looks at the diagonal of H.  Returns 1 (block-uniform) on a pivot that is not finite and positive.
+BC_VIL_FN inline int bc_vil_factor(const VilArgs& a, const VilWs& W) {
+  const int tid = BC_VIL_TID, nt = BC_VIL_NT;
+  const int d = a.d;
+  double *A = W.A, *Li = W.Li, *rdiag = W.rdiag;
   if (a.diag) {
     for (int j = 0; j < d; ++j) {
       const double h = A[bc_vil_tri(j, j)];
       if (!(h > 0. && h < INFINITY)) return 1;
     }
+    return 0;
+  }
+  if (bc_vil_chol(A, rdiag, d, d, tid, nt)) return 1;
+  // L = C^-1 by forward substitution on the identity, column by column, top to bottom
+#ifdef __HIPCC__
+  // four lanes per column: lane g takes the terms k = j + g, j + g + 4, ... of a row's sum, four at a time so that their LDS
+  // latencies overlap; a butterfly adds the four partial sums (the same bits in all four); element (i, j) is stored by the
+  // lane that will read it, so nobody reads what another lane wrote
+  for (int j = tid >> 2; j < d; j += nt >> 2) {
+    const int g = tid & 3;
+    if (g == 0) Li[bc_vil_tri(j, j)] = rdiag[j];
+    for (int i = j + 1; i < d; ++i) {
+      const double* ci = A + bc_vil_tri(i, 0);
+      double sum = 0.;
+      int k = j + g;
+      for (; k + 12 < i; k += 16) {
+        const double c0 = ci[k], c1 = ci[k + 4], c2 = ci[k + 8], c3 = ci[k + 12];
+        const double l0 = Li[bc_vil_tri(k, j)], l1 = Li[bc_vil_tri(k + 4, j)], l2 = Li[bc_vil_tri(k + 8, j)], l3 = Li[bc_vil_tri(k + 12, j)];
+        sum = fma(c3, l3, fma(c2, l2, fma(c1, l1, fma(c0, l0, sum))));
+      }
+      for (; k < i; k += 4) sum = fma(ci[k], Li[bc_vil_tri(k, j)], sum);
+      sum += __shfl_xor(sum, 1);
+      sum += __shfl_xor(sum, 2);
+      if (((i - j) & 3) == g) Li[bc_vil_tri(i, j)] = -sum * rdiag[i];
+    }
+  }
+#else
+  for (int j = tid; j < d; j += nt) {      // column j is one thread's (it reads what it wrote)
+    Li[bc_vil_tri(j, j)] = rdiag[j];
+    for (int i = j + 1; i < d; ++i) {
+      double sum = 0.;
+      const double* ci = A + bc_vil_tri(i, 0);
+      for (int k = j; k < i; ++k) sum = fma(ci[k], Li[bc_vil_tri(k, j)], sum);
+      Li[bc_vil_tri(i, j)] = -sum * rdiag[i];
+    }
+  }
+#endif
+  BC_VIL_SYNC();
+  return 0;
+}
+
+// The draw: a.theta <- mu + E . L^T, or with the diagonal form mu + E / sqrt(diag H) from the H bc_vil_hessian left.
+BC_VIL_FN inline void bc_vil_draw(const VilArgs& a, const VilWs& W) {
+  const int tid = BC_VIL_TID, nt = BC_VIL_NT;
+  const int d = a.d;
+  const double *A = W.A, *Li = W.Li, *mu = W.mu;
+  const int total = a.s * d;
+  if (a.diag) {
     for (int e = tid; e < total; e += nt) {
       const int q = e / d, c = e - q * d;
       a.theta[(size_t)q * a.dk + c] = mu[c] + a.E[e] / sqrt(A[bc_vil_tri(c, c)]);
     }
-  } else {
-    if (bc_vil_chol(A, rdiag, d, d, tid, nt)) return 1;
-    // L = C^-1 by forward substitution on the identity, column by column, top to bottom
-#ifdef __HIPCC__
-    // four lanes per column: lane g takes the terms k = j + g, j + g + 4, ... of a row's sum, four at a time so that their LDS
-    // latencies overlap; a butterfly adds the four partial sums (the same bits in all four); element (i, j) is stored by the
-    // lane that will read it, so nobody reads what another lane wrote
-    for (int j = tid >> 2; j < d; j += nt >> 2) {
-      const int g = tid & 3;
-      if (g == 0) Li[bc_vil_tri(j, j)] = rdiag[j];
-      for (int i = j + 1; i < d; ++i) {
-        const double* ci = A + bc_vil_tri(i, 0);
-        double sum = 0.;
-        int k = j + g;
-        for (; k + 12 < i; k += 16) {
-          const double c0 = ci[k], c1 = ci[k + 4], c2 = ci[k + 8], c3 = ci[k + 12];
-          const double l0 = Li[bc_vil_tri(k, j)], l1 = Li[bc_vil_tri(k + 4, j)], l2 = Li[bc_vil_tri(k + 8, j)], l3 = Li[bc_vil_tri(k + 12, j)];
-          sum = fma(c3, l3, fma(c2, l2, fma(c1, l1, fma(c0, l0, sum))));
-        }
-        for (; k < i; k += 4) sum = fma(ci[k], Li[bc_vil_tri(k, j)], sum);
-        sum += __shfl_xor(sum, 1);
-        sum += __shfl_xor(sum, 2);
-        if (((i - j) & 3) == g) Li[bc_vil_tri(i, j)] = -sum * rdiag[i];
-      }
-    }
-#else
-    for (int j = tid; j < d; j += nt) {      // column j is one thread's (it reads what it wrote)
-      Li[bc_vil_tri(j, j)] = rdiag[j];
-      for (int i = j + 1; i < d; ++i) {
-        double sum = 0.;
-        const double* ci = A + bc_vil_tri(i, 0);
-        for (int k = j; k < i; ++k) sum = fma(ci[k], Li[bc_vil_tri(k, j)], sum);
-        Li[bc_vil_tri(i, j)] = -sum * rdiag[i];
-      }
-    }
-#endif
-    BC_VIL_SYNC();
-    // Theta = mu + E . L^T
-#ifdef __HIPCC__
-    const int lane = tid & 63, wv = tid >> 6, nw = nt >> 6, r = lane & 15, kq = lane >> 4;
-    const int qt = (a.s + 15) >> 4, ct = (d + 15) >> 4;
-    for (int it = wv; it < qt * ct; it += nw) {
-      const int Q = it / ct, Cc = it - Q * ct, qa = Q * 16 + r, cb = Cc * 16 + r;
-      const int kend = (Cc + 1) * 16 < d ? (Cc + 1) * 16 : d;      // L is lower: k <= c
-      bc_vil_d4 acc = {0., 0., 0., 0.};
-      for (int k0 = 0; k0 < kend; k0 += 4) {
-        const int k = k0 + kq;
-        const double av = (qa < a.s && k < d) ? a.E[(size_t)qa * d + k] : 0.;
-        const double bv = (cb < d && k <= cb) ? Li[bc_vil_tri(cb, k)] : 0.;
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
-      }
-      for (int q4 = 0; q4 < 4; ++q4) {
-        const int q = Q * 16 + kq + 4 * q4;
-        if (q < a.s && cb < d) a.theta[(size_t)q * a.dk + cb] = mu[cb] + acc[q4];
-      }
-    }
-#else
-    for (int e = tid; e < total; e += nt) {
-      const int q = e / d, c = e - q * d;
-      const double* eq = a.E + (size_t)q * d;
-      const double* lc = Li + bc_vil_tri(c, 0);
-      double acc = 0.;
-      for (int k = 0; k <= c; ++k) acc = fma(eq[k], lc[k], acc);
-      a.theta[(size_t)q * a.dk + c] = mu[c] + acc;
-    }
-#endif
+    return;
   }
-  for (int j = tid; j < d; j += nt) a.mode[j] = mu[j];
+#ifdef __HIPCC__
+  (void)total;
+  const int lane = tid & 63, wv = tid >> 6, nw = nt >> 6, r = lane & 15, kq = lane >> 4;
+  const int qt = (a.s + 15) >> 4, ct = (d + 15) >> 4;
+  for (int it = wv; it < qt * ct; it += nw) {
+    const int Q = it / ct, Cc = it - Q * ct, qa = Q * 16 + r, cb = Cc * 16 + r;
+    const int kend = (Cc + 1) * 16 < d ? (Cc + 1) * 16 : d;      // L is lower: k <= c
+    bc_vil_d4 acc = {0., 0., 0., 0.};
+    for (int k0 = 0; k0 < kend; k0 += 4) {
+      const int k = k0 + kq;
+      const double av = (qa < a.s && k < d) ? a.E[(size_t)qa * d + k] : 0.;
+      const double bv = (cb < d && k <= cb) ? Li[bc_vil_tri(cb, k)] : 0.;
+      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
+    }
+    for (int q4 = 0; q4 < 4; ++q4) {
+      const int q = Q * 16 + kq + 4 * q4;
+      if (q < a.s && cb < d) a.theta[(size_t)q * a.dk + cb] = mu[cb] + acc[q4];
+    }
+  }
+#else
+  for (int e = tid; e < total; e += nt) {
+    const int q = e / d, c = e - q * d;
+    const double* eq = a.E + (size_t)q * d;
+    const double* lc = Li + bc_vil_tri(c, 0);
+    double acc = 0.;
+    for (int k = 0; k <= c; ++k) acc = fma(eq[k], lc[k], acc);
+    a.theta[(size_t)q * a.dk + c] = mu[c] + acc;
+  }
+#endif
+}
+
+// Returns 1 (block-uniform) when the run must stop; nothing has been written to theta, mode or counts then.
+// ws: BC_VIL_WS_DOUBLES(d) doubles.
+BC_VIL_FN inline int bc_vi_laplace(const VilArgs& a, double* ws) {
+  const int tid = BC_VIL_TID, nt = BC_VIL_NT;
+  const int d = a.d;
+  const VilWs W = bc_vil_ws(ws, d);
+  VilFit fit;
+  if (bc_vil_mode(a, W, &fit)) return 1;
+  bc_vil_hessian(a, W);
+  if (bc_vil_factor(a, W)) return 1;
+  bc_vil_draw(a, W);
+  for (int j = tid; j < d; j += nt) a.mode[j] = W.mu[j];
   if (tid == 0) {
-    a.mode[d] = dec;
-    a.counts[0] = steps;
-    a.counts[1] = halvings;
-    a.counts[2] += steps;
-    a.counts[3] = halvings_all;
+    a.mode[d] = fit.dec;
+    a.counts[0] = fit.steps;
+    a.counts[1] = fit.halvings;
+    a.counts[2] += fit.steps;
+    a.counts[3] = fit.halvings_all;
   }
   return 0;
 }

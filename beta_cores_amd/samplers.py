@@ -844,9 +844,152 @@ def _per_problem(x, P, shape, what):
     raise ValueError('%s must have shape %r (for all problems) or %r (one per problem), got %r' % (what, shape, (P,) + shape, a.shape))
 
 
+def _small_problems(problems):
+    """The problems of logistic_hmc_many / logistic_laplace_many as a list of (Z_p float64 n_p x D contiguous, w_p [n_p]) and D:
+    None weights are ones, an empty coreset is one zero row with weight 0, float32 rows are widened."""
+    probs, d = [], None
+    for p, pair in enumerate(problems):
+        Z, w = pair
+        Z = np.asarray(Z)
+        if Z.ndim != 2:
+            raise ValueError('problem %d: the rows must be n x D, got shape %r' % (p, Z.shape))
+        if d is None:
+            d = Z.shape[1]
+        if Z.shape[1] != d:
+            raise ValueError('problem %d: %d columns, the problems before it have %d' % (p, Z.shape[1], d))
+        Z = np.ascontiguousarray(Z, dtype=np.float64)
+        n = Z.shape[0]
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float64)
+            if w.shape != (n,):
+                raise ValueError('problem %d: wts must have one weight per row of Z (%d), got shape %r' % (p, n, w.shape))
+        if n == 0:
+            Z, w = np.zeros((1, d)), np.zeros(1)
+        probs.append((Z, np.ones(Z.shape[0]) if w is None else w))
+    if not probs:
+        raise ValueError('needs at least one problem')
+    return probs, d
+
+
+# ---- the Laplace fit of many small problems at once (include/beta_cores_laplace_small.h)
+LAPLACE_SMALL_MAX_DIM = 128
+LAPLACE_SMALL_MAX_DRAWS = 256
+
+
+class LaplaceFit:
+    """One problem's entry of logistic_laplace_many: mu, LSig (= C^-1) and LSigInv (= C = chol H(mu)) as logistic_laplace returns
+    them, hdiag = diag H(mu), value = the log-joint at mu, newton = the Newton steps taken, halvings = the halvings of the last
+    line search (halvings_all: of all of them), draws (S x D, or None); with score: correct, test_ll [S] and accuracy."""
+
+    def __init__(self, mu, LSig, LSigInv, hdiag, value, counts, draws):
+        self.mu, self.LSig, self.LSigInv, self.hdiag, self.value, self.draws = mu, LSig, LSigInv, hdiag, float(value), draws
+        self.newton, self.halvings, self.halvings_all = int(counts[0]), int(counts[1]), int(counts[2])
+        self.correct = self.test_ll = self.accuracy = None
+
+
+class LaplaceManyResult(list):
+    """What logistic_laplace_many returns: a list with one LaplaceFit per problem (None for a marked problem under strict=False).
+    marked: the indices the device refused; device_ms: GPU milliseconds of the call's launches."""
+
+    def __init__(self, fits, marked, device_ms):
+        super().__init__(fits)
+        self.marked, self.device_ms = list(marked), device_ms
+
+
+def logistic_laplace_many(problems, mu0=None, diag=False, n_draws=0, rng=None, draws='shared', score=None, keep_draws=True, strict=True,
+                          ctx=None):
+    """logistic_laplace(solver='newton') for MANY small problems in one native call: the Laplace posteriors of the weighted
+    coresets of an evaluation curve.  One thread block per problem finds the mode by damped Newton steps, factorises H(mu),
+    inverts the factor and draws (k_laplace_many: the device function of the weight optimisation loop's logistic sampler);
+    nothing crosses the host link before the end.  No CPU fallback.
+
+    problems: as logistic_hmc_many takes them -- a sequence of (Z_p, wts_p): rows z = y*x (n_p x D, D common; float32 rows are
+      widened) and one weight per row, or None = all ones.  An empty coreset (0 x D) is one zero row with weight 0: the prior.
+    mu0: D numbers or P x D: where the Newton iteration starts (not a prior mean: the prior is N(0, I)); None = zeros.
+    diag: the drivers' diagonal form: LSig / LSigInv are np.diag(1 / sqrt(hdiag)) / np.diag(sqrt(hdiag)), as logistic_laplace
+      returns them, and the draws are mu + E / sqrt(hdiag).
+    n_draws = S: entry p's `draws` are what LogisticLaplaceSampler would draw, mu_p + E.dot(LSig_p.T), computed on the device.
+      draws='shared': E = randn(S, D), drawn ONCE from rng (None: the global NumPy stream) and read by every problem;
+      draws='independent': randn(S, D) per problem, for p = 0 .. P - 1 in order.  S = 0 draws nothing from the stream.
+    score: a HeldOut.  Every entry then carries `correct` and `test_ll` (S each: the bits of logistic_score(score, draws)),
+      computed on the device where the draws lie, and `accuracy` = score.accuracy(correct).  Needs n_draws >= 1.
+    keep_draws=False (with score): `draws` is None and no draw is copied.
+    A problem with a weight, start, value, decrement or pivot that is not finite is marked on the device and costs the others
+      nothing: strict=True raises NumericalPrecisionError naming the indices after everything has been copied, strict=False
+      leaves None there.
+    Limits: D <= 128, S <= 256, one device, Newton only (the reference's BFGS search stays in logistic_laplace).  Returns a
+    LaplaceManyResult."""
+    if not keep_draws and score is None:
+        raise ValueError('keep_draws=False needs score: nothing of the draws would be returned')
+    if draws not in ('shared', 'independent'):
+        raise ValueError("draws must be 'shared' or 'independent'")
+    probs, d = _small_problems(problems)
+    P, s = len(probs), int(n_draws)
+    if not 1 <= d <= LAPLACE_SMALL_MAX_DIM:
+        raise ValueError('logistic_laplace_many serves 1 .. %d columns (one block\'s LDS holds the factor and its inverse), got %d; '
+                         'logistic_laplace has no such limit' % (LAPLACE_SMALL_MAX_DIM, d))
+    if not 0 <= s <= LAPLACE_SMALL_MAX_DRAWS:
+        raise ValueError('n_draws must be 0 .. %d, got %d' % (LAPLACE_SMALL_MAX_DRAWS, s))
+    if score is not None and s < 1:
+        raise ValueError('score needs n_draws >= 1')
+    start = None if mu0 is None else _per_problem(mu0, P, (d,), 'mu0')
+    from .device import default_context
+    ctx = default_context() if ctx is None else ctx
+    if score is not None and (score.ctx is not ctx or score.shape[1] != d):
+        raise ValueError('score must hold rows of %d columns on the context of the call' % d)
+    diag = bool(diag)
+    rows = np.ascontiguousarray(np.concatenate([z for z, _ in probs], axis=0))
+    w = np.ascontiguousarray(np.concatenate([ww for _, ww in probs]))
+    row_ptr = np.concatenate(([0], np.cumsum([z.shape[0] for z, _ in probs]))).astype(np.int64)
+    randn = np.random.randn if rng is None else rng.randn
+    E, stride = None, 0
+    if s > 0 and draws == 'shared':
+        E = randn(s, d)
+    elif s > 0:
+        E, stride = np.empty((P, s, d)), s * d
+        for p in range(P):
+            E[p] = randn(s, d)
+    mu, hd, val = np.zeros((P, d)), np.zeros((P, d)), np.zeros(P)
+    cnt, status = np.zeros((P, 3), dtype=np.int32), np.zeros(P, dtype=np.int32)
+    chol = inv = theta = cor = tll = None
+    if not diag:
+        chol, inv = np.zeros((P, d, d)), np.zeros((P, d, d))
+    if s > 0 and keep_draws:
+        theta = np.zeros((P, s, d))
+    if score is not None:
+        cor, tll = np.zeros((P, s), dtype=np.int32), np.zeros((P, s))
+
+    def opt(a):
+        return None if a is None else _ptr(a)
+    N.call('bc_laplace_small', ctx.h, _ptr(rows), _ptr(w), _ptr(row_ptr), P, d, opt(start), int(diag), opt(E), stride, s,
+           None if score is None else score.Z.h, None if score is None else score.Y.h, _ptr(mu), _ptr(hd), _ptr(val), _ptr(cnt),
+           _ptr(status), opt(chol), opt(inv), opt(theta), opt(cor), opt(tll))
+    ms = ctypes.c_double()
+    N.call('bc_laplace_small_device_ms', ctx.h, ctypes.byref(ms))
+    fits, marked = [], []
+    for p in range(P):
+        if status[p] != 0:
+            fits.append(None)
+            marked.append(p)
+            continue
+        if diag:
+            sq = np.sqrt(hd[p])
+            f = LaplaceFit(mu[p], np.diag(1. / sq), np.diag(sq), hd[p], val[p], cnt[p], None if theta is None else theta[p])
+        else:
+            f = LaplaceFit(mu[p], inv[p], chol[p], hd[p], val[p], cnt[p], None if theta is None else theta[p])
+        if score is not None:
+            f.correct, f.test_ll = cor[p].astype(np.int64), tll[p]
+            f.accuracy = score.accuracy(f.correct)
+        fits.append(f)
+    if marked and strict:
+        raise N.NumericalPrecisionError('logistic_laplace_many: problem(s) %s could not be fitted (a weight, start, value, decrement or '
+                                        'pivot that is not finite)' % ', '.join(str(p) for p in marked))
+    return LaplaceManyResult(fits, marked, ms.value)
+
+
 def logistic_hmc_many(problems, n_samples=1000, n_chains=16, step_size=0.1, n_leapfrog=8, inv_mass=None, start=None, warmup=0, rng=None,
                       draws='shared', adapt_every=25, adapt_rate=1.0, chunk=None, strict=True, ctx=None, engine=None, score=None,
-                      keep_samples=True, scorer=None):
+                      keep_samples=True, scorer=None, laplace='each'):
     """logistic_hmc for MANY small problems in one batched run: the posteriors of the weighted coresets of an evaluation curve
     (`for m in range(M + 1): sample the coreset of size m` in the logistic drivers).  One thread block per problem and group of
     up to four chains holds the problem's rows in LDS and runs whole chunks of iterations there (k_hmc_small); a chunk is one
@@ -857,6 +1000,10 @@ def logistic_hmc_many(problems, n_samples=1000, n_chains=16, step_size=0.1, n_le
     start, inv_mass, step_size: as logistic_hmc's, one for all problems or one per problem (start: C x D or P x C x D; inv_mass:
       D, P x D, None or 'laplace'; step_size: a number or P numbers).  start=None and 'laplace' use the device Laplace fit of each
       problem, as logistic_hmc does.
+    laplace='each' (default): those fits are made one problem at a time by logistic_laplace(solver='newton') on the problem's
+      resident rows.  'batched': all of them by ONE logistic_laplace_many call (D <= 128; a problem it cannot fit raises
+      NumericalPrecisionError before the run): start = mu_p + e0.dot(LSig_p.T), inv_mass = 1 / hdiag_p.  The two agree to the
+      rounding of the mode search, not bit for bit.
     draws='shared' (default): the draws are made ONCE, in logistic_hmc's order and chunking -- the start's normals randn(C, D)
       if start is None; then per chunk randn(k, C, D) followed by log(rand(k, C)); warm-up chunks of adapt_every iterations, kept
       chunks of `chunk` (None = bc_hmc_auto_chunk(C, D)) -- and every problem reads the same ones: entry p equals, to rounding,
@@ -886,28 +1033,10 @@ def logistic_hmc_many(problems, n_samples=1000, n_chains=16, step_size=0.1, n_le
         scorer = logistic_score
     if draws not in ('shared', 'independent'):
         raise ValueError("draws must be 'shared' or 'independent'")
-    probs, d = [], None
-    for p, pair in enumerate(problems):
-        Z, w = pair
-        Z = np.asarray(Z)
-        if Z.ndim != 2:
-            raise ValueError('problem %d: the rows must be n x D, got shape %r' % (p, Z.shape))
-        if d is None:
-            d = Z.shape[1]
-        if Z.shape[1] != d:
-            raise ValueError('problem %d: %d columns, the problems before it have %d' % (p, Z.shape[1], d))
-        Z = np.ascontiguousarray(Z, dtype=np.float64)
-        n = Z.shape[0]
-        if w is not None:
-            w = np.ascontiguousarray(w, dtype=np.float64)
-            if w.shape != (n,):
-                raise ValueError('problem %d: wts must have one weight per row of Z (%d), got shape %r' % (p, n, w.shape))
-        if n == 0:
-            Z, w = np.zeros((1, d)), np.zeros(1)
-        probs.append((Z, np.ones(Z.shape[0]) if w is None else w))
+    if laplace not in ('each', 'batched'):
+        raise ValueError("laplace must be 'each' or 'batched'")
+    probs, d = _small_problems(problems)
     P = len(probs)
-    if P == 0:
-        raise ValueError('needs at least one problem')
     c = int(n_chains)
     check_hmc_problem((1, d), c)
     if n_samples < 1 or warmup < 0 or n_leapfrog < 1 or adapt_every < 1:
@@ -935,8 +1064,14 @@ def logistic_hmc_many(problems, n_samples=1000, n_chains=16, step_size=0.1, n_le
     if start is None or want_laplace:
         if engine is not None:
             raise ValueError('a stand-in engine has no Laplace fit: pass start and inv_mass')
-        fit = [logistic_laplace(w, on_device(p), np.zeros(d), solver='newton')[:2] for p, (z, w) in enumerate(probs)]
-        if want_laplace:
+        if laplace == 'batched':
+            many = logistic_laplace_many(probs, ctx=ctx)
+            fit = [(r.mu, r.LSig) for r in many]
+            if want_laplace:
+                inv_mass = np.array([1. / r.hdiag for r in many])
+        else:
+            fit = [logistic_laplace(w, on_device(p), np.zeros(d), solver='newton')[:2] for p, (z, w) in enumerate(probs)]
+        if want_laplace and laplace != 'batched':
             inv_mass = np.array([1. / (1. + logistic_newton_pass(on_device(p), fit[p][0], np.where(w > 0, w, 0.), hessian=False, diag=True)[3])
                                  for p, (z, w) in enumerate(probs)])
     ims = _per_problem(np.ones(d) if inv_mass is None else inv_mass, P, (d,), 'inv_mass')

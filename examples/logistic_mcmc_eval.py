@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The logistic drivers' evaluation with exact-posterior samples drawn on the GPU.
 
-    python examples/logistic_mcmc_eval.py [--n 200000] [--d 10] [--m 200] [--samples 250] [--chains 16] [--seed 1] [--curve K]
+    python examples/logistic_mcmc_eval.py [--n 200000] [--d 10] [--m 200] [--samples 250] [--chains 16] [--seed 1] [--curve K [--laplace]]
 
 The reference's logistic drivers end by drawing ~1 000 posterior samples with MCMC -- of the full data as ground truth
 (examples/common/mcmc.py:21), of the weighted coreset as the thing to judge (zellner_logreg/main.py:225-230) -- and scoring them
@@ -20,6 +20,10 @@ ground truth's posterior standard deviations.
 --curve K (opt-in) adds the drivers' evaluation curve (zellner_logreg/main.py:219-230: `for m in range(M + 1)`): K nested coreset
 sizes between 0 and M -- the coresets after m greedy steps of the same construction -- sampled by ONE batched call,
 samplers.logistic_hmc_many, on common random numbers, and scored as above.
+
+--laplace (with --curve) prints the Laplace curve beside the HMC one: the same K coresets fitted, drawn and scored on the device
+by samplers.logistic_laplace_many(..., score=held, keep_draws=False) -- as many draws per coreset as the HMC leg keeps, in calls
+of at most 256 draws each (the call's limit); no draw is copied to the host.
 """
 import argparse
 import os
@@ -62,6 +66,7 @@ def main():
     ap.add_argument('--proj-dim', type=int, default=200)
     ap.add_argument('--seed', type=int, default=1)
     ap.add_argument('--curve', type=int, default=0, help='score this many nested coreset sizes 0 .. m from one batched call (0: off)')
+    ap.add_argument('--laplace', action='store_true', help='with --curve: the Laplace posteriors of the same coresets, fitted, drawn and scored on the device')
     a = ap.parse_args()
     rng = np.random.RandomState(a.seed)
     X = rng.randn(a.n + a.n_test, a.d)
@@ -113,11 +118,28 @@ def main():
         t_curve = time.perf_counter() - t0
         print('curve: %d coreset sizes in one batched call, %.2f s (%.1f ms on the GPU); through the single-problem engine: %s' %
               (len(nested), t_curve, curve.device_ms or 0., curve.fallback or 'none'))
-        for m, (p_m, w_m), res in zip(curve_at, nested, curve):
+        lap_curve = None
+        if a.laplace:
+            held = bc.samplers.HeldOut(Xt, Yt)
+            total = a.samples * a.chains
+            calls = -(-total // bc.samplers.LAPLACE_SMALL_MAX_DRAWS)
+            per = -(-total // calls)
+            t0 = time.perf_counter()
+            parts = [bc.samplers.logistic_laplace_many(nested, n_draws=per, rng=rng, score=held, keep_draws=False) for _ in range(calls)]
+            t_lap = time.perf_counter() - t0
+            lap_curve = [(held.accuracy(np.concatenate([q[k].correct for q in parts])), np.concatenate([q[k].test_ll for q in parts]).mean(),
+                          parts[0][k].mu, parts[0][k].newton) for k in range(len(nested))]
+            print('laplace curve: %d coreset sizes x %d draws fitted, drawn and scored in %d call(s), %.3f s (%.2f ms on the GPU)' %
+                  (len(nested), per * calls, calls, t_lap, sum(q.device_ms for q in parts)))
+        for k, (m, (p_m, w_m), res) in enumerate(zip(curve_at, nested, curve)):
             th = res.pooled()
             print('m = %-4d points %-4d accuracy %.4f   test log-likelihood %.3f   |mean - truth| / sd: max %.3f   step %.4g' %
                   (m, len(w_m), compute_accuracy(Xt, Yt, th), log_likelihood(Zt, th).sum(axis=0).mean(),
                    np.abs((th.mean(axis=0) - mu_t) / sd_t).max(), res.step_size))
+            if lap_curve:
+                acc, tll, mu_l, newton = lap_curve[k]
+                print('         laplace     accuracy %.4f   test log-likelihood %.3f   |mode - truth| / sd: max %.3f   Newton steps %d' %
+                      (acc, tll, np.abs((mu_l - mu_t) / sd_t).max(), newton))
 
 
 if __name__ == '__main__':
