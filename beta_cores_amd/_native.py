@@ -241,6 +241,19 @@ _PREFDIAG_SIGNATURES = {
 }
 PREFDIAG_EXPORTS = sorted(_PREFDIAG_SIGNATURES)
 
+# entry points of the extension header include/beta_cores_psvi_many.h (BatchPSVI pseudo-coresets of many sizes in one device run)
+_PSVI_MANY_SIGNATURES = {
+    'bc_psvi_many_work_doubles': [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32],      # returns an int64 count, not a status
+    'bc_psvi_many_auto_chunk': [C.c_int32, C.c_int32, C.c_int64],      # returns a step count, not a status
+    'bc_psvi_many_begin': [vp, vp, C.c_int, C.c_int, C.c_int32, vp, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, C.c_int64, C.c_double],
+    'bc_psvi_many_chunk_begin': [vp, vp, vp, C.c_int32],
+    'bc_psvi_many_chunk_end': [vp, vp],
+    'bc_psvi_many_end': [vp, vp, vp, vp, vp],
+    'bc_psvi_many_device_ms': [vp, c_dp],
+    'bc_psvi_many_last_step': [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [vp] * 16,
+}
+PSVI_MANY_EXPORTS = sorted(_PSVI_MANY_SIGNATURES)
+
 _lib = None
 
 
@@ -276,10 +289,12 @@ def load():
             + list(_TAKE_SIGNATURES.items()) + list(_BETAGRAD_SIGNATURES.items()) + list(_ENCODE_SIGNATURES.items()) \
             + list(_VIOPT_SIGNATURES.items()) + list(_PSVI_SIGNATURES.items()) + list(_VILAPLACE_SIGNATURES.items()) \
             + list(_HMC_SIGNATURES.items()) + list(_HMC_SMALL_SIGNATURES.items()) + list(_SCORE_SIGNATURES.items()) \
-            + list(_PREFDIAG_SIGNATURES.items()) + list(_PREDICT_SIGNATURES.items()) + list(_LAPLACE_SMALL_SIGNATURES.items()):
+            + list(_PREFDIAG_SIGNATURES.items()) + list(_PREDICT_SIGNATURES.items()) + list(_LAPLACE_SMALL_SIGNATURES.items()) \
+            + list(_PSVI_MANY_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int
+    lib.bc_psvi_many_work_doubles.restype = C.c_int64
     lib.bc_version.restype = C.c_int
     lib.bc_version.argtypes = []
     lib.bc_last_error.restype = C.c_char_p

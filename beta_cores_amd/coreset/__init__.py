@@ -3,6 +3,6 @@ from .coreset import Coreset
 from .hilbert import HilbertCoreset
 from .bcores import BetaCoreset
 from .sparsevi import SparseVICoreset
-from .bpsvi import BatchPSVICoreset
+from .bpsvi import BatchPSVICoreset, PSVICurve
 from .sampling import UniformSamplingCoreset
 from .projector import (Projector, BlackBoxProjector, BetaBlackBoxProjector, DeviceProjector, DeviceBetaProjector)

@@ -9,12 +9,113 @@ Every gradient needs (bpsvi.py:27-57)
     the optimiser (util/opt.py partial_nn_opt) updates them there.
 With a BlackBoxProjector the reference's NumPy expressions run on whatever the callables return and the N-row column
 sum still runs on the GPU."""
+import ctypes as C
+
 import numpy as np
 
-from ..device import DeviceData, DevicePhi
-from ..util.opt import partial_nn_opt
+from .. import _native as N
+from ..device import DeviceData, DevicePhi, _ptr
+from ..likelihoods import LogisticRegression
+from ..util.opt import adam_step_arrays, partial_nn_opt
 from .coreset import Coreset
-from .residency import keep_resident, sub_rows
+from .residency import keep_resident, pin_for, resident_copy_of_view, sub_rows
+
+# limits of the batched run (include/beta_cores_psvi_many.h)
+PSVI_MANY_MAX_DIM, PSVI_MANY_MAX_SAMPLES, PSVI_MANY_MAX_SUB = 128, 256, 262144
+PSVI_MANY_MAX_PROBLEMS, PSVI_MANY_MAX_POINTS, PSVI_MANY_MAX_WORK_DOUBLES = 4096, 4096, 1 << 27
+_SAMPLER_LOGISTIC = 2          # BC_VI_SAMPLER_LOGISTIC
+
+
+class PSVICurve(list):
+    """What BatchPSVICoreset.build_many returns: one `(wts, pts, idcs)` per size, as `get()` gives it after `build(1, m)` (None for
+    a marked size).  `route`: 'batched' or 'each'; `marked`: the positions in `sizes` whose problem met a weight, value, gradient
+    or pivot that is not finite (batched route); `device_ms`: GPU time of the run's steps (0.0 on the 'each' route)."""
+
+    def __init__(self, entries, route, marked=(), device_ms=0.):
+        super().__init__(entries)
+        self.route, self.marked, self.device_ms = route, list(marked), float(device_ms)
+
+
+def psvi_many_run(data, pts, wts, S, opt_itrs, steps, draw, n_sub, n_total=None, start=None, diag=False, chunk_steps=0,
+                  model_id=None, sampler_kind=_SAMPLER_LOGISTIC, on_chunk=None):
+    """The native batched run (bc_psvi_many_begin / _chunk_begin / _chunk_end / _end) on resident rows `data` (a DeviceData):
+    problem p starts at points `pts[p]` (m_p x D) with weights `wts[p]` and takes `opt_itrs` joint projected-ADAM steps of sizes
+    `steps[p]` (opt_itrs values); all problems share each step's draws.  `draw(k)` returns the next k steps' (normals k x S x D,
+    row numbers k x n_sub); it is called for chunk i + 1 while the device runs chunk i, and never past the last step.
+    `on_chunk(done)`: called after every chunk has been waited for (tests read the seam there).
+    Returns a dict: `w`, `pts` (lists; None for a marked problem), `modes` (P x D), `status` (P), `marked`, `device_ms`."""
+    lib = N.load()
+    P = len(pts)
+    if int(opt_itrs) < 1:
+        raise ValueError('psvi_many_run: opt_itrs must be at least 1, got %d' % opt_itrs)
+    D = int(data.shape[1])
+    row_ptr = np.zeros(P + 1, dtype=np.int64)
+    row_ptr[1:] = np.cumsum([np.atleast_2d(p).shape[0] for p in pts])
+    R = int(row_ptr[-1])
+    pk = np.ascontiguousarray(np.vstack([np.atleast_2d(p) for p in pts]) if P else np.zeros((0, D)), dtype=np.float64)
+    wk = np.ascontiguousarray(np.concatenate([np.atleast_1d(w) for w in wts]) if P else np.zeros(0), dtype=np.float64)
+    if pk.shape != (R, D) or wk.shape != (R,):
+        raise ValueError('points must have %d columns and one weight each' % D)
+    steps = np.ascontiguousarray(steps, dtype=np.float64)
+    if steps.shape != (P, int(opt_itrs)):
+        raise ValueError('steps must be P x opt_itrs')
+    moments = np.ascontiguousarray(adam_step_arrays(int(opt_itrs), lambda i: 0.)[1:])
+    st = None if start is None else np.ascontiguousarray(start, dtype=np.float64)
+    if st is not None and st.shape != (P, D):
+        raise ValueError('start must be P x D')
+    n_total = int(data.shape[0] if n_total is None else n_total)
+    model_id = LogisticRegression().model_id if model_id is None else model_id
+    ctx = data.ctx
+    N.call('bc_psvi_many_begin', ctx.h, data.h, int(model_id), int(sampler_kind), 1 if diag else 0, _ptr(pk), _ptr(wk), _ptr(row_ptr), P,
+           _ptr(st) if st is not None else None, int(S), int(opt_itrs), _ptr(steps), _ptr(moments), int(n_sub),
+           float(n_total) / n_sub if n_sub else 1.)
+    chunk = int(chunk_steps) if chunk_steps else int(lib.bc_psvi_many_auto_chunk(int(S), D, int(n_sub)))
+    try:
+        done = 0
+        nxt = draw(min(chunk, int(opt_itrs)))
+        while done < opt_itrs:
+            E, idx = nxt
+            E = np.ascontiguousarray(E, dtype=np.float64)
+            idx = np.ascontiguousarray(idx, dtype=np.int64)
+            k = int(E.shape[0])
+            if E.shape != (k, int(S), D) or idx.shape != (k, int(n_sub)):
+                raise ValueError('draw(k) must return k x S x D normals and k x n_sub row numbers')
+            N.call('bc_psvi_many_chunk_begin', ctx.h, _ptr(E), _ptr(idx), k)
+            done += k
+            try:
+                nxt = draw(min(chunk, int(opt_itrs) - done)) if done < opt_itrs else None      # beside the GPU
+            finally:
+                status = lib.bc_psvi_many_chunk_end(ctx.h, None)
+            N.check(status)
+            if on_chunk is not None:
+                on_chunk(done)
+        ow, op, om, ost = np.full(R, np.nan), np.full((R, D), np.nan), np.full((P, D), np.nan), np.zeros(P, dtype=np.int32)
+        N.call('bc_psvi_many_end', ctx.h, _ptr(ow), _ptr(op), _ptr(om), _ptr(ost))
+    except BaseException:
+        lib.bc_psvi_many_end(ctx.h, None, None, None, None)      # (closes the run; a no-op status if _end itself has closed it)
+        raise
+    ms = C.c_double()
+    N.call('bc_psvi_many_device_ms', ctx.h, C.byref(ms))
+    ok = ost == N.BC_OK
+    return dict(w=[ow[row_ptr[p]:row_ptr[p + 1]] if ok[p] else None for p in range(P)],
+                pts=[op[row_ptr[p]:row_ptr[p + 1]] if ok[p] else None for p in range(P)], modes=om, status=ost,
+                marked=[p for p in range(P) if not ok[p]], device_ms=ms.value)
+
+
+def psvi_many_last_step(ctx, sizes, D, S):
+    """What the last executed step of the most recent batched run on `ctx` left on the device (bc_psvi_many_last_step; a seam for
+    tests, nothing is launched): a dict of packed arrays -- `w_before`, `pts_before`, `mode`, `theta`, `target`, `resid`, `gw`,
+    `gp`, `w`, `pts`, `mom1_w`, `mom1_p`, `mom2_w`, `mom2_p`, `newton` (P x 2: Newton steps of the last fit | of the run), `flag`
+    (P) -- and `row_ptr`."""
+    P, R = len(sizes), int(np.sum(sizes))
+    row_ptr = np.concatenate(([0], np.cumsum(sizes))).astype(np.int64)
+    shapes = dict(w_before=(R,), pts_before=(R, D), mode=(P, D), theta=(P, S, D), target=(P, S), resid=(P, S), gw=(R,), gp=(R, D),
+                  w=(R,), pts=(R, D), mom1_w=(R,), mom1_p=(R, D), mom2_w=(R,), mom2_p=(R, D))
+    out = {k: np.empty(v) for k, v in shapes.items()}
+    out['newton'], out['flag'] = np.zeros((P, 2), dtype=np.int32), np.zeros(P, dtype=np.int32)
+    N.call('bc_psvi_many_last_step', ctx.h, R, P, int(D), int(S), *[_ptr(out[k]) for k in list(shapes) + ['newton', 'flag']])
+    out['row_ptr'] = row_ptr
+    return out
 
 
 class BatchPSVICoreset(Coreset):
@@ -106,6 +207,140 @@ class BatchPSVICoreset(Coreset):
         self._grad_calls = 0
         x = partial_nn_opt(x0, lambda v: self._gradient(v, sz, d), np.arange(sz), self.opt_itrs, step_sched=self.step_sched(sz))
         self.wts, self.pts = x[:sz].copy(), x[sz:].reshape(sz, d).copy()
+
+    # ---- the whole evaluation curve: every size of `sizes` built from ONE stream state (what forked workers of the reference
+    # drivers' Pool get: zellner_logreg/main.py:173-186)
+    def _uncovered(self):
+        """Why the batched native run does not cover this coreset's configuration (None: it does)."""
+        from .projector import DeviceProjector      # (projector.py imports this package's residency module)
+        prj = self.ll_projector
+        if not isinstance(prj, DeviceProjector):
+            return 'the projector is not a DeviceProjector'
+        if not isinstance(prj.model, LogisticRegression):
+            return 'the likelihood is %s, only LogisticRegression() is covered (the linear-regression and Gaussian-location ' \
+                   'kinds take the loop of single builds)' % type(prj.model).__name__
+        if prj.encoder is not None:
+            return 'the projector has a feature encoder'
+        spec = getattr(prj.sampler, 'device_spec', None)
+        spec = spec() if spec is not None else None
+        if spec is None or spec[0] != _SAMPLER_LOGISTIC:
+            return "the sampler is not a LogisticLaplaceSampler(solver='newton') (the reference's BFGS search stays on the host)"
+        if self.n_subsample_opt is None:
+            return 'n_subsample_opt is None (all rows every step, for every size its own Theta)'
+        if self.opt_itrs < 1:
+            return 'opt_itrs is not positive'
+        if not isinstance(self.data, (DeviceData, np.ndarray)) or (isinstance(self.data, DeviceData) and self.data._transient):
+            return 'the data rows are neither resident nor an array that can be uploaded once'
+        return None
+
+    def _over_limit(self, sizes):
+        """A documented limit of the native run this request exceeds (None: none) -- 'auto' then takes the loop."""
+        prj = self.ll_projector
+        D, S = int(self.data.shape[1]), int(prj.projection_dimension)
+        if not sizes:
+            return 'no sizes'
+        work = N.load().bc_psvi_many_work_doubles(int(np.sum(sizes)), len(sizes), D, S, int(self.n_subsample_opt), int(self.opt_itrs))
+        if work < 0 or work > PSVI_MANY_MAX_WORK_DOUBLES or max(sizes) > PSVI_MANY_MAX_POINTS:
+            return 'a limit of include/beta_cores_psvi_many.h is exceeded'
+        return None
+
+    def _stream_state(self):
+        smp = getattr(self.ll_projector, 'sampler', None)
+        rng = getattr(smp, '_rng', None)
+        return (np.random.get_state(), rng.get_state() if rng is not None else None,
+                [(k, getattr(smp, k)) for k in ('_ahead', '_shape', '_mode') if hasattr(smp, k)])
+
+    def _set_stream_state(self, st):
+        smp = getattr(self.ll_projector, 'sampler', None)
+        np.random.set_state(st[0])
+        if st[1] is not None:
+            smp._rng.set_state(st[1])
+        for k, v in st[2]:
+            setattr(smp, k, None if v is None else np.copy(v) if isinstance(v, np.ndarray) else v)
+
+    def build_many(self, sizes, route='auto'):
+        """The pseudo-coresets of every size in `sizes` as a PSVICurve.  Entry m is what `build(1, m)` gives when started from the
+        stream state at entry (the sampler's stream for the normals, np.random for the permutation and the row numbers); on
+        return the streams stand where ONE such build leaves them.  With NumPy's legacy stream `choice(n, m, replace=False)`
+        consumes the same amount for every m and its result is a prefix of a larger m's, so all sizes see the same permutation
+        and, step by step, the same S x D normals and the same sub-sample: common random numbers.
+        route='each': that definition as code, a loop of single builds.  route='batched': all sizes stepped in lock-step in one
+        device run (bc_psvi_many_*); needs a DeviceProjector with LogisticRegression(), a LogisticLaplaceSampler(solver='newton'),
+        n_subsample_opt and no encoder, and raises NotImplementedError naming the reason otherwise.  'auto': batched when
+        covered.  This object's own wts / pts / idcs are left as they were; so is the sampler's `_mode`."""
+        if route not in ('auto', 'batched', 'each'):
+            raise ValueError("route must be 'auto', 'batched' or 'each'")
+        sizes = [int(m) for m in sizes]
+        n = self.data.shape[0]
+        if any(m < 1 or m > n for m in sizes):
+            raise ValueError('every size must be within 1 .. %d' % n)
+        if route != 'each':
+            why = self._uncovered()
+            if route == 'batched' and why is not None:
+                raise NotImplementedError("build_many(route='batched'): " + why)
+            route = 'each' if (why is not None or (route == 'auto' and self._over_limit(sizes) is not None)) else 'batched'
+        if not sizes:
+            return PSVICurve([], route)
+        return self._many_each(sizes) if route == 'each' else self._many_batched(sizes)
+
+    def _many_each(self, sizes):
+        mine = (self.wts, self.pts, self.idcs, self.reached_numeric_limit)
+        st0, end, entries = self._stream_state(), None, []
+        try:
+            for m in sizes:
+                self._set_stream_state(st0)
+                self._clear()
+                self.build(1, m)
+                entries.append(self.get())
+                end = self._stream_state()
+        finally:
+            self.wts, self.pts, self.idcs, self.reached_numeric_limit = mine
+        mode0 = [kv for kv in st0[2] if kv[0] == '_mode']
+        self._set_stream_state((end[0], end[1], [kv for kv in end[2] if kv[0] != '_mode'] + mode0))      # (the sampler's _mode is left alone)
+        return PSVICurve(entries, 'each')
+
+    def _many_rows(self):
+        """The resident rows of the batched run: the caller's DeviceData, or this coreset's array uploaded once."""
+        if isinstance(self.data, DeviceData):
+            return self.data
+        if getattr(self, '_many_resident', None) is None:
+            if self._resident is not None:
+                self._many_resident = self._resident
+            elif self.data.base is not None:
+                self._many_resident = resident_copy_of_view(self.data, self.ll_projector, stacklevel=4)
+            else:
+                self._many_resident = pin_for(self, self.data, self.ll_projector)
+        return self._many_resident
+
+    def _many_batched(self, sizes):
+        prj = self.ll_projector
+        smp = prj.sampler
+        S, n, n_sub = int(prj.projection_dimension), int(self.data.shape[0]), int(self.n_subsample_opt)
+        rows = self._many_rows()
+        D = int(rows.shape[1])
+        if D != int(smp._dim()):
+            raise ValueError('data rows have %d columns, the sampler draws %d-dimensional samples' % (D, smp._dim()))
+        sp = np.asarray(smp.device_spec()[1], dtype=np.float64)
+        perm = np.random.choice(n, size=max(sizes), replace=False)      # (size m's choice is its first m entries)
+        base = np.asarray(self.data[perm], dtype=np.float64)
+        steps = np.array([[self.step_sched(m)(i) for i in range(self.opt_itrs)] for m in sizes], dtype=np.float64).reshape(len(sizes), self.opt_itrs)
+
+        def draw(k):
+            E, idx = np.empty((k, S, D)), np.empty((k, n_sub), dtype=np.int64)
+            for t in range(k):
+                E[t] = smp._normals(S, D)
+                idx[t] = np.random.randint(n, size=n_sub)
+            return E, idx
+        res = psvi_many_run(rows, [base[:m] for m in sizes], [np.full(m, n / m) for m in sizes], S, self.opt_itrs, steps, draw, n_sub,
+                            n_total=n, start=np.tile(sp[:D], (len(sizes), 1)), diag=bool(sp[D]))
+        entries = []
+        for p, m in enumerate(sizes):
+            if res['w'][p] is None:
+                entries.append(None)
+                continue
+            keep = res['w'][p] > 0
+            entries.append((res['w'][p][keep], res['pts'][p][keep, :], perm[:m][keep]))
+        return PSVICurve(entries, 'batched', res['marked'], res['device_ms'])
 
     def error(self):
         return 0.          # bpsvi.py:64-65 leaves the KL estimate unimplemented

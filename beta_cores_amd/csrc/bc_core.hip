@@ -112,20 +112,21 @@ void bc_run_clock::free() {
     if (e) (void)hipEventDestroy(e);
 }
 
-// Who is refused while what is held on a context.  G: a fused gradient is pending; V, H, S: a bc_vi_optimize / bc_hmc /
-// bc_hmc_small run is open.
+// Who is refused while what is held on a context.  G: a fused gradient is pending; V, H, S, B: a bc_vi_optimize / bc_hmc /
+// bc_hmc_small / bc_psvi_many run is open.
 //
-//   entrant                                                                  G        V        H        S
-//   bc_vi_gradient_begin, bc_vi_beta_gradient_begin, bc_psvi_gradient_begin  refuse   allow    refuse   refuse
-//   bc_vi_optimize_begin                                                     refuse   refuse   refuse   refuse
-//   bc_hmc_begin                                                             refuse   refuse   refuse   refuse
-//   bc_logistic_logjoint_batch                                               allow    allow    refuse   refuse
-//   bc_hmc_small_begin, bc_hmc_small_logjoint                                refuse   refuse   refuse   refuse
-//   bc_lr_score                                                              allow    allow    refuse   refuse
-//   bc_linreg_predict                                                        allow    allow    refuse   refuse
-//   bc_laplace_small (synchronous: holds nothing after it returns)           refuse   refuse   refuse   refuse
+//   entrant                                                                  G        V        H        S        B
+//   bc_vi_gradient_begin, bc_vi_beta_gradient_begin, bc_psvi_gradient_begin  refuse   allow    refuse   refuse   refuse
+//   bc_vi_optimize_begin                                                     refuse   refuse   refuse   refuse   refuse
+//   bc_hmc_begin                                                             refuse   refuse   refuse   refuse   refuse
+//   bc_logistic_logjoint_batch                                               allow    allow    refuse   refuse   allow
+//   bc_hmc_small_begin, bc_hmc_small_logjoint                                refuse   refuse   refuse   refuse   refuse
+//   bc_lr_score                                                              allow    allow    refuse   refuse   allow
+//   bc_linreg_predict                                                        allow    allow    refuse   refuse   allow
+//   bc_laplace_small (synchronous: holds nothing after it returns)           refuse   refuse   refuse   refuse   refuse
+//   bc_psvi_many_begin                                                       refuse   refuse   refuse   refuse   refuse
 //
-// An entrant passes the holders of its row that refuse it; they are looked at in the order G, V, H, S, and the first one found
+// An entrant passes the holders of its row that refuse it; they are looked at in the order G, V, H, S, B, and the first one found
 // is named.  Nothing is enqueued, allocated or changed by a refusal.
 int bc_ctx_refuse_busy(const bc_ctx* ctx, const char* who, unsigned holders, unsigned own) {
   int kind = 0;
@@ -134,9 +135,10 @@ int bc_ctx_refuse_busy(const bc_ctx* ctx, const char* who, unsigned holders, uns
                  bc_vi_kind_name(kind));
     return BC_INVALID_ARGUMENT;
   }
-  const struct { unsigned bit; bool open; const char* kind; } runs[3] = {{BC_HOLD_VIOPT, bc_viopt_active(ctx), "bc_vi_optimize"},
+  const struct { unsigned bit; bool open; const char* kind; } runs[4] = {{BC_HOLD_VIOPT, bc_viopt_active(ctx), "bc_vi_optimize"},
                                                                         {BC_HOLD_HMC, bc_hmc_active(ctx), "bc_hmc"},
-                                                                        {BC_HOLD_HMC_SMALL, bc_hmc_small_active(ctx), "bc_hmc_small"}};
+                                                                        {BC_HOLD_HMC_SMALL, bc_hmc_small_active(ctx), "bc_hmc_small"},
+                                                                        {BC_HOLD_PSVI_MANY, bc_psvi_many_active(ctx), "bc_psvi_many"}};
   for (const auto& r : runs)
     if ((holders & r.bit) && r.open) {
       bc_set_error("%s: a %s run is %sopen on this context (call %s_end first)", who, r.kind, (own & r.bit) ? "already " : "", r.kind);
@@ -171,6 +173,7 @@ extern "C" int bc_ctx_destroy(bc_ctx* ctx) {
   bc_hmc_free(ctx);
   bc_hmc_small_free(ctx);
   bc_laplace_small_free(ctx);
+  bc_psvi_many_free(ctx);
   bc_scratch_free(&ctx->score);
   bc_scratch_free(&ctx->predict);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);

@@ -109,6 +109,7 @@ struct bc_ctx {
   struct bc_hmc* hmc = nullptr;        // bc_hmc_* (bc_hmc.hip): the buffers and the state of the HMC run in progress
   struct bc_hmc_small* hmc_small = nullptr;   // bc_hmc_small_* (bc_hmc_small.hip): the same for the batched small-problem run
   struct bc_lap_small* laplace_small = nullptr;   // bc_laplace_small (bc_laplace_small.hip): the buffers of the batched Laplace fit
+  struct bc_psvi_many* psvi_many = nullptr;   // bc_psvi_many_* (bc_psvi_many.hip): the buffers and the state of the batched BatchPSVI run
   bc_scratch score;              // bc_lr_score (bc_score.hip): theta | ll | correct (ints)
   bc_scratch predict;            // bc_linreg_predict (bc_predict.hip): mu | factor | packed factor | noise | scale | partials | ll | sse | mean | var
 };
@@ -131,6 +132,8 @@ bool bc_hmc_active(const bc_ctx* ctx);     // the context holds an open bc_hmc r
 void bc_hmc_small_free(bc_ctx* ctx); // bc_hmc_small.hip
 bool bc_hmc_small_active(const bc_ctx* ctx);   // the context holds an open bc_hmc_small run
 void bc_laplace_small_free(bc_ctx* ctx);   // bc_laplace_small.hip (the call is synchronous: it never holds the context)
+void bc_psvi_many_free(bc_ctx* ctx); // bc_psvi_many.hip
+bool bc_psvi_many_active(const bc_ctx* ctx);   // the context holds an open bc_psvi_many run
 // bc_score.hip: the checks of the held-out pair (d_run > 0: the columns the rows must have), and k_lr_score over t thetas that are
 // already on the device; enqueued only
 int bc_score_check(const bc_ctx* ctx, const struct bc_data* zt, const struct bc_data* yt, int64_t t, int32_t d_run, const char* who);
@@ -142,7 +145,8 @@ int bc_score_launch(bc_ctx* ctx, const struct bc_data* zt, const struct bc_data*
 #define BC_HOLD_VIOPT 2u             // an open bc_vi_optimize run
 #define BC_HOLD_HMC 4u               // an open bc_hmc run
 #define BC_HOLD_HMC_SMALL 8u         // an open bc_hmc_small run
-#define BC_HOLD_ALL 15u
+#define BC_HOLD_PSVI_MANY 16u        // an open bc_psvi_many run
+#define BC_HOLD_ALL 31u
 int bc_ctx_refuse_busy(const bc_ctx* ctx, const char* who, unsigned holders, unsigned own = 0);
 const char* bc_vi_kind_name(int kind);     // the entry point's name of a BC_VI_KIND_* (bc_vigrad.hip)
 // the tail of the one-call drivers: closes a run that failed with `end`, keeps the message of what failed, and returns rc

@@ -187,7 +187,7 @@ static int vi_gradient_begin(bc_ctx* ctx, const bc_data* data, const double* cor
   }
   // grad | resid [| beta_dots] [| grad_p]
   const size_t n_core = (size_t)m * dz, n_down = (with_beta ? 2 : 1) * (size_t)m + (size_t)s + (psvi ? n_core : 0);
-  rc = bc_ctx_refuse_busy(ctx, (std::string(who) + "_begin").c_str(), BC_HOLD_GRADIENT | BC_HOLD_HMC | BC_HOLD_HMC_SMALL, BC_HOLD_GRADIENT);
+  rc = bc_ctx_refuse_busy(ctx, (std::string(who) + "_begin").c_str(), BC_HOLD_GRADIENT | BC_HOLD_HMC | BC_HOLD_HMC_SMALL | BC_HOLD_PSVI_MANY, BC_HOLD_GRADIENT);
   if (rc) return rc;
   if (n_down > ctx->pinned_doubles) {
     bc_set_error("%s: coreset of %lld rows x %d exceeds the staging area", who, (long long)m, dz);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The logistic drivers' evaluation with exact-posterior samples drawn on the GPU.
 
-    python examples/logistic_mcmc_eval.py [--n 200000] [--d 10] [--m 200] [--samples 250] [--chains 16] [--seed 1] [--curve K [--laplace]]
+    python examples/logistic_mcmc_eval.py [--n 200000] [--d 10] [--m 200] [--samples 250] [--chains 16] [--seed 1] [--curve K [--laplace]] [--bpsvi M]
 
 The reference's logistic drivers end by drawing ~1 000 posterior samples with MCMC -- of the full data as ground truth
 (examples/common/mcmc.py:21), of the weighted coreset as the thing to judge (zellner_logreg/main.py:225-230) -- and scoring them
@@ -24,6 +24,11 @@ samplers.logistic_hmc_many, on common random numbers, and scored as above.
 --laplace (with --curve) prints the Laplace curve beside the HMC one: the same K coresets fitted, drawn and scored on the device
 by samplers.logistic_laplace_many(..., score=held, keep_draws=False) -- as many draws per coreset as the HMC leg keeps, in calls
 of at most 256 draws each (the call's limit); no draw is copied to the host.
+
+--bpsvi M (opt-in) adds the drivers' BatchPSVI curve (zellner_logreg/main.py:173-186: `build_per_m` for m = 1 .. M over a Pool): the
+pseudo-coresets of all M sizes from ONE BatchPSVICoreset.build_many -- stepped in lock-step on the device, common random numbers --
+handed to the same two batched calls, samplers.logistic_laplace_many and samplers.logistic_hmc_many, each scoring where its
+samples lie (score=held).
 """
 import argparse
 import os
@@ -67,6 +72,8 @@ def main():
     ap.add_argument('--seed', type=int, default=1)
     ap.add_argument('--curve', type=int, default=0, help='score this many nested coreset sizes 0 .. m from one batched call (0: off)')
     ap.add_argument('--laplace', action='store_true', help='with --curve: the Laplace posteriors of the same coresets, fitted, drawn and scored on the device')
+    ap.add_argument('--bpsvi', type=int, default=0, help='the BatchPSVI pseudo-coresets of sizes 1 .. M from one build_many, Laplace-fitted and sampled in one call each (0: off)')
+    ap.add_argument('--bpsvi-itrs', type=int, default=100, help='with --bpsvi: joint ADAM steps on weights and points')
     a = ap.parse_args()
     rng = np.random.RandomState(a.seed)
     X = rng.randn(a.n + a.n_test, a.d)
@@ -140,6 +147,25 @@ def main():
                 acc, tll, mu_l, newton = lap_curve[k]
                 print('         laplace     accuracy %.4f   test log-likelihood %.3f   |mode - truth| / sd: max %.3f   Newton steps %d' %
                       (acc, tll, np.abs((mu_l - mu_t) / sd_t).max(), newton))
+    if a.bpsvi > 0:
+        sizes = list(range(1, a.bpsvi + 1))
+        smp_w = bc.samplers.LogisticLaplaceSampler(mu0, rng=rng, solver='newton')
+        psvi = bc.BatchPSVICoreset(dz, bc.DeviceProjector(smp_w, min(a.proj_dim, 256), bc.likelihoods.LogisticRegression()), opt_itrs=a.bpsvi_itrs,
+                                   n_subsample_opt=200, fused_gradient=True)
+        np.random.seed(a.seed)
+        t0 = time.perf_counter()
+        pcurve = psvi.build_many(sizes)
+        t_build = time.perf_counter() - t0
+        print('bpsvi: %d sizes x %d steps by route %r in %.2f s (%.1f ms on the GPU); marked: %s' %
+              (len(sizes), a.bpsvi_itrs, pcurve.route, t_build, pcurve.device_ms, pcurve.marked or 'none'))
+        kept = [(m, e) for m, e in zip(sizes, pcurve) if e is not None]
+        probs = [(np.asarray(p, dtype=np.float64), np.asarray(w, dtype=np.float64)) for _, (w, p, _) in kept]
+        held = bc.samplers.HeldOut(Xt, Yt)
+        laps = bc.samplers.logistic_laplace_many(probs, n_draws=min(a.samples, bc.samplers.LAPLACE_SMALL_MAX_DRAWS), rng=rng, score=held, keep_draws=False)
+        many = bc.samplers.logistic_hmc_many(probs, rng=rng, score=held, keep_samples=False, **hmc)
+        for (m, (w, _, _)), fit, res in zip(kept, laps, many):
+            print('m = %-4d points %-4d laplace: accuracy %.4f  test log-likelihood %.3f   hmc: accuracy %.4f  test log-likelihood %.3f' %
+                  (m, len(w), held.accuracy(fit.correct), fit.test_ll.mean(), held.accuracy(res.correct.ravel()), res.test_ll.mean()))
 
 
 if __name__ == '__main__':
