@@ -86,6 +86,8 @@ struct bc_pref {
   int2* l2_blk_cand = nullptr;
   int* l2_blk_nc = nullptr;
   int2* spill = nullptr;           // [cap] pairs of blocks with more than BC_BLK_NC rows in play
+  int* ctrl_swept = nullptr;       // test aid (bc_pref_diag_sweep, its own allocation on first use): the control block as the last
+                                   // diagnostic two-level sweep left it, before the restore
   long long* cand = nullptr;  // [cap] candidate LOCAL rows
   int* ctrl = nullptr;        // [BC_PCTL_INTS] the control block, every field of it named in bc_pref_ctrl.h
   int cap = 4096;
@@ -519,6 +521,7 @@ int bc_pref_create(bc_phi* phi, int prec, bc_pref** out) {
 void bc_pref_destroy(bc_pref* p) {
   if (!p) return;
   if (p->slab) (void)hipFree(p->slab);
+  if (p->ctrl_swept) (void)hipFree(p->ctrl_swept);
   delete p;
 }
 
@@ -830,6 +833,7 @@ int bc_pref_diag_buffer(const bc_pref* p, const char* which, const void** dev, s
       {"spill", p->spill, (size_t)BC_PREF_SPILL_CAP * sizeof(int2)},
       {"hot", p->hot, BC_I4_SEED_BYTES},
       {"ctrl", p->ctrl, BC_PCTL_BYTES},
+      {"ctrl_swept", p->ctrl_swept, BC_PCTL_BYTES},
   };
   for (const Ent& e : tab)
     if (strcmp(which, e.name) == 0) {
@@ -846,7 +850,8 @@ size_t bc_pref_diag_save_bytes(void) { return BC_I4_SEED_BYTES + BC_PCTL_BYTES; 
 
 // One sweep of the form the next production sweep would take (two-level, else the one-level int8 sweep) through the DUMP
 // instances of the sweep kernels: no rescoring, no skip flag, none of the host-side counters touched; the seeds and the control
-// block are put aside in `save_dev` and restored.  qv / qv4: the digit records to sweep with (qv == nullptr: the int8 sweep
+// block are put aside in `save_dev` and restored (the two-level form keeps a copy of the control block as the sweep left it:
+// "ctrl_swept").  qv / qv4: the digit records to sweep with (qv == nullptr: the int8 sweep
 // quantises v in its prologue).  *form_run = 3 / 1.
 int bc_pref_diag_sweep(bc_pref* p, int mode, const double* v_dev, const double* v_norm_dev, const int* qv, const int* qv4,
                        double post_div, float2* dump1, float2* dump2, float* theta0, void* save_dev, int* form_run) {
@@ -854,10 +859,14 @@ int bc_pref_diag_sweep(bc_pref* p, int mode, const double* v_dev, const double* 
   const bool two = sweeps_two_level(p, qv, qv4);
   *form_run = two ? 3 : 1;
   if (two) {
+    if (!p->ctrl_swept) BC_HIP(hipMalloc((void**)&p->ctrl_swept, BC_PCTL_BYTES));
     char* const save_ctrl = (char*)save_dev + BC_I4_SEED_BYTES;
     BC_HIP(hipMemcpyAsync(save_dev, p->hot, BC_I4_SEED_BYTES, hipMemcpyDeviceToDevice, ctx->stream));
     BC_HIP(hipMemcpyAsync(save_ctrl, p->ctrl, BC_PCTL_BYTES, hipMemcpyDeviceToDevice, ctx->stream));
     BC_HIP(hipMemsetAsync(dump2, 0xff, (size_t)p->ptiles * BC_ITILE * sizeof(float2), ctx->stream));      // NaN: not re-bounded
+    // every slot of the spill list that this sweep does not write reads (-1, -1) afterwards: a pair left out shows as such
+    // instead of as the pair an earlier sweep left there
+    BC_HIP(hipMemsetAsync(p->spill, 0xff, (size_t)BC_PREF_SPILL_CAP * sizeof(int2), ctx->stream));
     I4DumpArgs fa;
     fill_i4_args(p, qv, qv4, nullptr, post_div, &fa);
     fa.dump1 = dump1;
@@ -866,6 +875,7 @@ int bc_pref_diag_sweep(bc_pref* p, int mode, const double* v_dev, const double* 
     if (mode == 0) launch_sweep_i4<0, true>(p, fa);
     else launch_sweep_i4<1, true>(p, fa);
     BC_HIP(hipGetLastError());
+    BC_HIP(hipMemcpyAsync(p->ctrl_swept, p->ctrl, BC_PCTL_BYTES, hipMemcpyDeviceToDevice, ctx->stream));      // (BC_PCTL_SPILL_N: no rescoring resets it here)
     BC_HIP(hipMemcpyAsync(p->hot, save_dev, BC_I4_SEED_BYTES, hipMemcpyDeviceToDevice, ctx->stream));
     BC_HIP(hipMemcpyAsync(p->ctrl, save_ctrl, BC_PCTL_BYTES, hipMemcpyDeviceToDevice, ctx->stream));
     return BC_OK;

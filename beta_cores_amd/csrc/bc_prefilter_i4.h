@@ -263,6 +263,7 @@ __global__ __launch_bounds__(256) void k_sweep_i4(typename std::conditional<DUMP
   __shared__ float l_u[BC_L2_LCAP];                    // the block's rows in play: int8 upper bound, row
   __shared__ int l_row[BC_L2_LCAP];
   __shared__ int s_n, s_umax, s_on, s_refined, s_refined_base;
+  __shared__ int s_spill_n;                            // the spill loop's own cursor: s_on is written nowhere after every thread has read it
   __shared__ unsigned long long s_best;                // (ordered int8 lower bound << 32 | row): the block's strongest row
   __shared__ int2 s_out[BC_BLK_NC];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -313,7 +314,7 @@ __global__ __launch_bounds__(256) void k_sweep_i4(typename std::conditional<DUMP
   if ((int)threadIdx.x < SP8) *reinterpret_cast<bc_i4*>(&dig4[threadIdx.x][0]) = d4v;
   if ((int)threadIdx.x < a.sp4) *reinterpret_cast<bc_i4*>(&dig8[threadIdx.x][0]) = d8v;
   if (threadIdx.x < 8) hdr8[threadIdx.x] = h8v;
-  if (threadIdx.x == 0) { s_n = 0; s_best = 0ull; s_umax = bc_f32_ord(-INFINITY); s_on = 0; s_refined = 0; }
+  if (threadIdx.x == 0) { s_n = 0; s_best = 0ull; s_umax = bc_f32_ord(-INFINITY); s_on = 0; s_refined = 0; s_spill_n = 0; }
   const float fpd = (float)a.post_div;
   const float ifpd = __frcp_rn(fabsf(fpd)) * 1.000001f;
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");        // LDS-only barrier: the tiles stay in flight
@@ -486,13 +487,13 @@ __global__ __launch_bounds__(256) void k_sweep_i4(typename std::conditional<DUMP
   if ((int)threadIdx.x < on && threadIdx.x < BC_BLK_NC) a.blk_cand[(size_t)blockIdx.x * BC_BLK_NC + threadIdx.x] = s_out[threadIdx.x];
   bool spilled = false;
   if (on > BC_BLK_NC && n <= BC_L2_LCAP) {             // (block-uniform, rare) too many for the block's own list: the spill list
-    if (threadIdx.x == 0) { s_refined_base = atomicAdd(&a.ctrl[BC_PCTL_SPILL_N], on); s_on = 0; }
+    if (threadIdx.x == 0) s_refined_base = atomicAdd(&a.ctrl[BC_PCTL_SPILL_N], on);
     __syncthreads();
     const int gb = s_refined_base;
     spilled = gb + on <= a.spill_cap;
     if (spilled)
       for (int i = threadIdx.x; i < n; i += blockDim.x)
-        if (l_u[i] >= best) a.spill[gb + atomicAdd(&s_on, 1)] = make_int2(__builtin_bit_cast(int, l_u[i]), l_row[i]);
+        if (l_u[i] >= best) a.spill[gb + atomicAdd(&s_spill_n, 1)] = make_int2(__builtin_bit_cast(int, l_u[i]), l_row[i]);
   }
   if (threadIdx.x == 0) {
     a.blk_l[blockIdx.x] = (double)best;

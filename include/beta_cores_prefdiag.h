@@ -10,8 +10,8 @@
  * pre-filtered sweep selects what the fp64 sweep selects" can be checked link by link on the device
  * (tests/test_gpu_pref_bounds.py against the reference of tests/pref_cases.py): the mirrors the builders wrote, the digit
  * records of the sweep vectors, and the interval [L_i, U_i] the sweep kernels computed for EVERY row -- which the product never
- * stores.  Each call synchronises the context's stream; none may be made while a step is in flight (between
- * bc_snnls_step_local and bc_snnls_step_finish).
+ * stores.  Each call synchronises the context's stream; no sweep may be run while a step is in flight (between
+ * bc_snnls_step_local and bc_snnls_step_finish; bc_snnls_prefdiag_copy only reads and may be called there).
  */
 #ifndef BETA_CORES_PREFDIAG_H
 #define BETA_CORES_PREFDIAG_H
@@ -51,7 +51,12 @@ int bc_snnls_prefdiag_info(const bc_snnls* h, int64_t* out);
 /* Copies ONE named device buffer to the host, raw, in its device layout (csrc/bc_layout.h, the comments of the bc_pref struct).
  *   mirrors:                  "u32" "u16" "live" | "u8" "rowq" | "u4" "rowq4" "r8"
  *   the last sweep's outputs: "ub" "tile_u" "tile_cand" "tile_ncand" "blk_l" "blk_u" | "l2_blk_l" "l2_blk_u" "l2_blk_cand"
- *                             "l2_blk_nc" "spill" | "ctrl" (64 ints) "hot" (the two-level form's seeds)
+ *                             "l2_blk_nc" "spill" | "ctrl" (64 ints) "hot" (the two-level form's seeds) | "ctrl_swept" (64 ints:
+ *                             the control block as the last two-level bc_snnls_prefdiag_sweep left it, before that call
+ *                             restored "ctrl" -- word 14 is the number of pairs the sweep appended to "spill", which may
+ *                             exceed BC_PREFDIAG_SPILL_CAP: pairs past the cap are not stored; no buffer before the first
+ *                             such sweep).  Of a production sweep the same count stands in "ctrl" until the rescoring stage
+ *                             clears it: this one call may be made between bc_snnls_step_local and bc_snnls_step_finish.
  *   the solver's current sweep vectors: "v" (GIGA: S pairs (cdir, y^) interleaved; else S doubles), "v_norm" and "post_div"
  *                             (one double each; v_norm is 1 for GIGA), "qv" / "qv4": the int8 / 4-bit digit records
  *                             (csrc/bc_i8_quant.h, bc_i4_quant.h: 4 sp4 / 4 sp8 ints of digits, then 8 header floats)
@@ -75,7 +80,9 @@ int bc_snnls_prefdiag_copy(const bc_snnls* h, const char* which, void* out, int6
  *   *form_run: 3 or 1.
  * The solver's skip flag is not consulted.  The call leaves the solver as found: the seeds ("hot") and "ctrl" are put aside and
  * restored and no host-side counter moves, so a build continued afterwards has the trace, weights, prefilter_stats and
- * prefilter_levels of a run without the call.  The buffers listed under "the last sweep's outputs" hold this sweep's results. */
+ * prefilter_levels of a run without the call.  The buffers listed under "the last sweep's outputs" hold this sweep's results;
+ * the two-level form's "spill" is filled with 0xff bytes first, so a slot this sweep did not write reads (-1, -1), and
+ * "ctrl_swept" holds the control block as the sweep left it. */
 int bc_snnls_prefdiag_sweep(bc_snnls* h, int32_t mode, const double* v, double post_div, int32_t self_quantise, float* out_ul,
                             float* out_ul8, float* out_theta0, int64_t rows_cap, int32_t blocks_cap, int32_t* form_run);
 

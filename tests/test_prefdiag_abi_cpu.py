@@ -50,6 +50,18 @@ def test_header_compiles_as_c99_and_the_indices_are_dense(tmp_path):
     assert sorted(idx.values()) == list(range(n))
 
 
+def test_every_named_buffer_is_documented():
+    """The names bc_snnls_prefdiag_copy accepts (the table of bc_pref_diag_buffer and the solver's own in bc_snnls_diag.hip) are
+    those the header lists, "ctrl_swept" -- the control block as a diagnostic two-level sweep left it -- among them."""
+    csrc = os.path.join(ROOT, 'beta_cores_amd', 'csrc')
+    tab = re.findall(r'\{"([a-z0-9_]+)", p->[a-z0-9_]+, ', open(os.path.join(csrc, 'bc_prefilter.hip')).read())
+    own = re.findall(r'strcmp\(which, "([a-z0-9_]+)"\)', open(os.path.join(csrc, 'bc_snnls_diag.hip')).read())
+    assert 'ctrl' in tab and 'ctrl_swept' in tab and 'spill' in tab and 'v' in own
+    hdr = open(os.path.join(ROOT, 'include', 'beta_cores_prefdiag.h')).read()
+    doc = hdr[hdr.index('Copies ONE named device buffer'):hdr.index('int bc_snnls_prefdiag_copy')]
+    assert sorted(set(re.findall(r'"([a-z0-9_]+)"', doc))) == sorted(set(tab + own))
+
+
 def test_entry_points_refuse_null_arguments():
     lib = N.load()
     assert lib.bc_snnls_prefdiag_info(None, None) == N.BC_INVALID_ARGUMENT and b'bc_snnls_prefdiag_info' in lib.bc_last_error()
