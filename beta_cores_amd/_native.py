@@ -254,6 +254,15 @@ _PSVI_MANY_SIGNATURES = {
 }
 PSVI_MANY_EXPORTS = sorted(_PSVI_MANY_SIGNATURES)
 
+# include/beta_cores_psvi_curve.h: the batched BatchPSVI run begun with a kind (the Gaussian-location model); a table of its own,
+# the one above is left as it is
+_PSVI_CURVE_SIGNATURES = {
+    'bc_psvi_curve_work_doubles': [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int],      # returns an int64 count, not a status
+    'bc_psvi_curve_begin': [vp, vp, C.c_int, C.c_int, C.c_int32, vp, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, C.c_int64, C.c_double,
+                                vp, C.c_int32, vp, C.c_int32],
+}
+PSVI_CURVE_EXPORTS = sorted(_PSVI_CURVE_SIGNATURES)
+
 _lib = None
 
 
@@ -290,11 +299,12 @@ def load():
             + list(_VIOPT_SIGNATURES.items()) + list(_PSVI_SIGNATURES.items()) + list(_VILAPLACE_SIGNATURES.items()) \
             + list(_HMC_SIGNATURES.items()) + list(_HMC_SMALL_SIGNATURES.items()) + list(_SCORE_SIGNATURES.items()) \
             + list(_PREFDIAG_SIGNATURES.items()) + list(_PREDICT_SIGNATURES.items()) + list(_LAPLACE_SMALL_SIGNATURES.items()) \
-            + list(_PSVI_MANY_SIGNATURES.items()):
+            + list(_PSVI_MANY_SIGNATURES.items()) + list(_PSVI_CURVE_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int
     lib.bc_psvi_many_work_doubles.restype = C.c_int64
+    lib.bc_psvi_curve_work_doubles.restype = C.c_int64
     lib.bc_version.restype = C.c_int
     lib.bc_version.argtypes = []
     lib.bc_last_error.restype = C.c_char_p

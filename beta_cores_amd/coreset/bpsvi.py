@@ -15,7 +15,7 @@ import numpy as np
 
 from .. import _native as N
 from ..device import DeviceData, DevicePhi, _ptr
-from ..likelihoods import LogisticRegression
+from ..likelihoods import GaussianLocation, LogisticRegression
 from ..util.opt import adam_step_arrays, partial_nn_opt
 from .coreset import Coreset
 from .residency import keep_resident, pin_for, resident_copy_of_view, sub_rows
@@ -23,7 +23,7 @@ from .residency import keep_resident, pin_for, resident_copy_of_view, sub_rows
 # limits of the batched run (include/beta_cores_psvi_many.h)
 PSVI_MANY_MAX_DIM, PSVI_MANY_MAX_SAMPLES, PSVI_MANY_MAX_SUB = 128, 256, 262144
 PSVI_MANY_MAX_PROBLEMS, PSVI_MANY_MAX_POINTS, PSVI_MANY_MAX_WORK_DOUBLES = 4096, 4096, 1 << 27
-_SAMPLER_LOGISTIC = 2          # BC_VI_SAMPLER_LOGISTIC
+_SAMPLER_GAUSS, _SAMPLER_LOGISTIC = 1, 2          # BC_VI_SAMPLER_GAUSS, BC_VI_SAMPLER_LOGISTIC
 
 
 class PSVICurve(list):
@@ -37,12 +37,15 @@ class PSVICurve(list):
 
 
 def psvi_many_run(data, pts, wts, S, opt_itrs, steps, draw, n_sub, n_total=None, start=None, diag=False, chunk_steps=0,
-                  model_id=None, sampler_kind=_SAMPLER_LOGISTIC, on_chunk=None):
+                  model_id=None, sampler_kind=_SAMPLER_LOGISTIC, on_chunk=None, model_params=None, sampler_params=None):
     """The native batched run (bc_psvi_many_begin / _chunk_begin / _chunk_end / _end) on resident rows `data` (a DeviceData):
     problem p starts at points `pts[p]` (m_p x D) with weights `wts[p]` and takes `opt_itrs` joint projected-ADAM steps of sizes
     `steps[p]` (opt_itrs values); all problems share each step's draws.  `draw(k)` returns the next k steps' (normals k x S x D,
     row numbers k x n_sub); it is called for chunk i + 1 while the device runs chunk i, and never past the last step.
     `on_chunk(done)`: called after every chunk has been waited for (tests read the seam there).
+    The default is the logistic kind (N(0, I) prior, `start`, `diag`).  The Gaussian-location kind: `model_id` of
+    likelihoods.GaussianLocation, `sampler_kind=1`, `model_params` = the model's `params()` ({logdetSig, Siginv}) and
+    `sampler_params` = GaussianPosteriorSampler.device_spec()[1] (mu0 | Sig0inv | Siginv); no `start`, no `diag` (bc_psvi_curve_begin).
     Returns a dict: `w`, `pts` (lists; None for a marked problem), `modes` (P x D), `status` (P), `marked`, `device_ms`."""
     lib = N.load()
     P = len(pts)
@@ -66,9 +69,15 @@ def psvi_many_run(data, pts, wts, S, opt_itrs, steps, draw, n_sub, n_total=None,
     n_total = int(data.shape[0] if n_total is None else n_total)
     model_id = LogisticRegression().model_id if model_id is None else model_id
     ctx = data.ctx
-    N.call('bc_psvi_many_begin', ctx.h, data.h, int(model_id), int(sampler_kind), 1 if diag else 0, _ptr(pk), _ptr(wk), _ptr(row_ptr), P,
-           _ptr(st) if st is not None else None, int(S), int(opt_itrs), _ptr(steps), _ptr(moments), int(n_sub),
-           float(n_total) / n_sub if n_sub else 1.)
+    begin = (ctx.h, data.h, int(model_id), int(sampler_kind), 1 if diag else 0, _ptr(pk), _ptr(wk), _ptr(row_ptr), P,
+             _ptr(st) if st is not None else None, int(S), int(opt_itrs), _ptr(steps), _ptr(moments), int(n_sub),
+             float(n_total) / n_sub if n_sub else 1.)
+    if model_params is None and sampler_params is None and int(sampler_kind) == _SAMPLER_LOGISTIC:
+        N.call('bc_psvi_many_begin', *begin)
+    else:
+        mp = np.ascontiguousarray(np.zeros(0) if model_params is None else model_params, dtype=np.float64).ravel()
+        sp = np.ascontiguousarray(np.zeros(0) if sampler_params is None else sampler_params, dtype=np.float64).ravel()
+        N.call('bc_psvi_curve_begin', *begin, _ptr(mp) if mp.size else None, int(mp.size), _ptr(sp) if sp.size else None, int(sp.size))
     chunk = int(chunk_steps) if chunk_steps else int(lib.bc_psvi_many_auto_chunk(int(S), D, int(n_sub)))
     try:
         done = 0
@@ -106,7 +115,7 @@ def psvi_many_last_step(ctx, sizes, D, S):
     """What the last executed step of the most recent batched run on `ctx` left on the device (bc_psvi_many_last_step; a seam for
     tests, nothing is launched): a dict of packed arrays -- `w_before`, `pts_before`, `mode`, `theta`, `target`, `resid`, `gw`,
     `gp`, `w`, `pts`, `mom1_w`, `mom1_p`, `mom2_w`, `mom2_p`, `newton` (P x 2: Newton steps of the last fit | of the run), `flag`
-    (P) -- and `row_ptr`."""
+    (P) -- and `row_ptr`.  Gaussian kind: `mode` is the posterior mean, `theta` the draw itself (not Siginv-multiplied), `newton` 0."""
     P, R = len(sizes), int(np.sum(sizes))
     row_ptr = np.concatenate(([0], np.cumsum(sizes))).astype(np.int64)
     shapes = dict(w_before=(R,), pts_before=(R, D), mode=(P, D), theta=(P, S, D), target=(P, S), resid=(P, S), gw=(R,), gp=(R, D),
@@ -216,14 +225,20 @@ class BatchPSVICoreset(Coreset):
         prj = self.ll_projector
         if not isinstance(prj, DeviceProjector):
             return 'the projector is not a DeviceProjector'
-        if not isinstance(prj.model, LogisticRegression):
+        gauss = isinstance(prj.model, GaussianLocation)
+        if not gauss and not isinstance(prj.model, LogisticRegression):
             return 'the likelihood is %s, only LogisticRegression() is covered (the linear-regression and Gaussian-location ' \
                    'kinds take the loop of single builds)' % type(prj.model).__name__
         if prj.encoder is not None:
             return 'the projector has a feature encoder'
         spec = getattr(prj.sampler, 'device_spec', None)
         spec = spec() if spec is not None else None
-        if spec is None or spec[0] != _SAMPLER_LOGISTIC:
+        if gauss:
+            if spec is None or spec[0] != _SAMPLER_GAUSS:
+                return 'the sampler is not a GaussianPosteriorSampler (a plain closure cannot be evaluated on the device)'
+            if not np.array_equal(np.asarray(prj.sampler.Siginv, dtype=np.float64), prj.model.Siginv):
+                return "the sampler's Siginv is not the model's (GaussianLocation.Siginv)"
+        elif spec is None or spec[0] != _SAMPLER_LOGISTIC:
             return "the sampler is not a LogisticLaplaceSampler(solver='newton') (the reference's BFGS search stays on the host)"
         if self.n_subsample_opt is None:
             return 'n_subsample_opt is None (all rows every step, for every size its own Theta)'
@@ -239,7 +254,8 @@ class BatchPSVICoreset(Coreset):
         D, S = int(self.data.shape[1]), int(prj.projection_dimension)
         if not sizes:
             return 'no sizes'
-        work = N.load().bc_psvi_many_work_doubles(int(np.sum(sizes)), len(sizes), D, S, int(self.n_subsample_opt), int(self.opt_itrs))
+        kind = _SAMPLER_GAUSS if isinstance(prj.model, GaussianLocation) else _SAMPLER_LOGISTIC
+        work = N.load().bc_psvi_curve_work_doubles(int(np.sum(sizes)), len(sizes), D, S, int(self.n_subsample_opt), int(self.opt_itrs), kind)
         if work < 0 or work > PSVI_MANY_MAX_WORK_DOUBLES or max(sizes) > PSVI_MANY_MAX_POINTS:
             return 'a limit of include/beta_cores_psvi_many.h is exceeded'
         return None
@@ -265,9 +281,11 @@ class BatchPSVICoreset(Coreset):
         consumes the same amount for every m and its result is a prefix of a larger m's, so all sizes see the same permutation
         and, step by step, the same S x D normals and the same sub-sample: common random numbers.
         route='each': that definition as code, a loop of single builds.  route='batched': all sizes stepped in lock-step in one
-        device run (bc_psvi_many_*); needs a DeviceProjector with LogisticRegression(), a LogisticLaplaceSampler(solver='newton'),
-        n_subsample_opt and no encoder, and raises NotImplementedError naming the reason otherwise.  'auto': batched when
-        covered.  This object's own wts / pts / idcs are left as they were; so is the sampler's `_mode`."""
+        device run (bc_psvi_many_*); needs a DeviceProjector with either LogisticRegression() and a
+        LogisticLaplaceSampler(solver='newton'), or GaussianLocation and a GaussianPosteriorSampler whose Siginv equals the
+        model's (full covariance, D <= 128, S <= 256); n_subsample_opt, opt_itrs >= 1 and no encoder; raises NotImplementedError
+        naming the reason otherwise.  'auto': batched when covered and within the limits of include/beta_cores_psvi_many.h.
+        This object's own wts / pts / idcs are left as they were; so is the sampler's `_mode`."""
         if route not in ('auto', 'batched', 'each'):
             raise ValueError("route must be 'auto', 'batched' or 'each'")
         sizes = [int(m) for m in sizes]
@@ -320,7 +338,8 @@ class BatchPSVICoreset(Coreset):
         D = int(rows.shape[1])
         if D != int(smp._dim()):
             raise ValueError('data rows have %d columns, the sampler draws %d-dimensional samples' % (D, smp._dim()))
-        sp = np.asarray(smp.device_spec()[1], dtype=np.float64)
+        kind, sp = smp.device_spec()
+        sp = np.asarray(sp, dtype=np.float64)
         perm = np.random.choice(n, size=max(sizes), replace=False)      # (size m's choice is its first m entries)
         base = np.asarray(self.data[perm], dtype=np.float64)
         steps = np.array([[self.step_sched(m)(i) for i in range(self.opt_itrs)] for m in sizes], dtype=np.float64).reshape(len(sizes), self.opt_itrs)
@@ -331,8 +350,12 @@ class BatchPSVICoreset(Coreset):
                 E[t] = smp._normals(S, D)
                 idx[t] = np.random.randint(n, size=n_sub)
             return E, idx
+        if kind == _SAMPLER_GAUSS:
+            how = dict(model_id=prj.model.model_id, sampler_kind=_SAMPLER_GAUSS, model_params=prj.model.params(), sampler_params=sp)
+        else:
+            how = dict(start=np.tile(sp[:D], (len(sizes), 1)), diag=bool(sp[D]))
         res = psvi_many_run(rows, [base[:m] for m in sizes], [np.full(m, n / m) for m in sizes], S, self.opt_itrs, steps, draw, n_sub,
-                            n_total=n, start=np.tile(sp[:D], (len(sizes), 1)), diag=bool(sp[D]))
+                            n_total=n, **how)
         entries = []
         for p, m in enumerate(sizes):
             if res['w'][p] is None:

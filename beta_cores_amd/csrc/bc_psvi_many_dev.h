@@ -6,6 +6,11 @@
 //                   v_mfma_f64_16x16x4_f64, one 16 x 16 tile of (rows, samples) per wave in turn; the row mean is projector.py:48.
 //                   The caller either adds the tile's rows up per sample (a tile of the gathered data rows: one row of the
 //                   target's partial sums) or stores them (a tile of the problem's own points: its corevecs).
+//   bc_pm_gauss_tile  the same tile for the Gaussian location model (gaussian.py:7-15): ll = c0 - 1/2 ((ra_r + sa_q) - 2 p),
+//                   p = x_r . Theta'_q on the same MFMA, Theta' = (Siginv Theta^T)^T, sa_q = th_q^T Siginv th_q (both from
+//                   bc_vi_sampler) and ra_r = x_r^T Siginv x_r from bc_pm_rowaux_tile.  K1's expression for this model
+//                   (bc_model_value<BC_MODEL_GAUSS_LL>), the terms the centring removes kept: the values round like K1's.
+//   bc_pm_rowaux_tile ra of the 16 rows of one tile: k_row_quadform's expression (bc_project.hip), (x * (x . Siginv)).sum()
 //   bc_pm_resid     target = scale * (partials added in tile order);  resid = target - w . corevecs;  g_w = -corevecs . resid / S
 //   (the point-gradient is bc_psvi_dev.h's bc_psvi_point_grad on resid, one block per point)
 //   bc_pm_adam      one step of util/opt.py's partial_nn_opt on x = (w, points), operation for operation; max(., 0) on w only
@@ -71,11 +76,28 @@ struct PmTileArgs {
   const void* rows;        // [n][d] row-major; elem == 4: floats, widened as they are read
   int elem;
   int n, d, s;
-  const double* theta;     // [s][d]
+  const double* theta;     // [s][d]   (Gaussian kind: Theta')
+  const double* ra;        // Gaussian kind: [n] x^T Siginv x of the rows
+  const double* sa;        // Gaussian kind: [s] theta^T Siginv theta
+  double c0;               // Gaussian kind: -d/2 log(2 pi) - 1/2 logdet Sigma
 };
 
+#define BC_PM_LOGISTIC 0                                   // the kinds of a run: what the tile evaluates
+#define BC_PM_GAUSS 1
+#define BC_PM_ROWAUX_DOUBLES(d) (2 * (size_t)BC_PM_TILE * (size_t)(d))      // bc_pm_rowaux_tile's LDS
+
+// One element of the tile from the contraction p = row . theta_q.  Logistic: z = row, m = -p.  Gaussian: K1's expression.
+template <int KIND>
+BC_PM_FN inline double bc_pm_value(const PmTileArgs& a, double p, int row, int q) {
+  if (KIND == BC_PM_LOGISTIC) return bc_pm_ll(-p);
+  const double qf = (a.ra[row] + a.sa[q]) - 2. * p;
+  return a.c0 - 1. / 2. * qf;
+}
+
 // t[r * s + q], r < 16, q < s: the row-centred log-likelihoods of rows tile * 16 + r (rows >= n: zeros); ends with a barrier.
-BC_PM_FN inline void bc_pm_ll_tile(const PmTileArgs& a, int tile, double* t) {
+// KIND: BC_PM_LOGISTIC (bc_pm_ll_tile) or BC_PM_GAUSS (bc_pm_gauss_tile); nothing but the element's value differs.
+template <int KIND>
+BC_PM_FN inline void bc_pm_tile(const PmTileArgs& a, int tile, double* t) {
   const int tid = BC_PM_TID, nt = BC_PM_NT;
   const int d = a.d, s = a.s, n = a.n, row0 = tile * BC_PM_TILE;
 #ifdef __HIPCC__
@@ -92,7 +114,7 @@ BC_PM_FN inline void bc_pm_ll_tile(const PmTileArgs& a, int tile, double* t) {
     }
     for (int q4 = 0; q4 < 4; ++q4) {                       // result map: col = lane & 15, row = (lane >> 4) + 4 q4
       const int i = kq + 4 * q4;
-      if (qb < s) t[i * s + qb] = (row0 + i < n) ? bc_pm_ll(-acc[q4]) : 0.;
+      if (qb < s) t[i * s + qb] = (row0 + i < n) ? bc_pm_value<KIND>(a, acc[q4], row0 + i, qb) : 0.;
     }
   }
   BC_PM_SYNC();
@@ -112,7 +134,7 @@ BC_PM_FN inline void bc_pm_ll_tile(const PmTileArgs& a, int tile, double* t) {
       double acc = 0.;
       if (row0 + i < n)
         for (int k = 0; k < d; ++k) acc = fma(bc_pm_row_elem(a.rows, a.elem, (size_t)(row0 + i) * d + k), a.theta[(size_t)q * d + k], acc);
-      t[i * s + q] = (row0 + i < n) ? bc_pm_ll(-acc) : 0.;
+      t[i * s + q] = (row0 + i < n) ? bc_pm_value<KIND>(a, acc, row0 + i, q) : 0.;
       sum += t[i * s + q];
     }
     const double mean = sum / (double)s;
@@ -120,6 +142,140 @@ BC_PM_FN inline void bc_pm_ll_tile(const PmTileArgs& a, int tile, double* t) {
   }
 #endif
   BC_PM_SYNC();
+}
+
+BC_PM_FN inline void bc_pm_ll_tile(const PmTileArgs& a, int tile, double* t) { bc_pm_tile<BC_PM_LOGISTIC>(a, tile, t); }
+BC_PM_FN inline void bc_pm_gauss_tile(const PmTileArgs& a, int tile, double* t) { bc_pm_tile<BC_PM_GAUSS>(a, tile, t); }
+
+// ra[tile * 16 + r] = x_r^T Siginv x_r for the rows of one tile (rows >= n: untouched), in k_row_quadform's expression
+// (bc_project.hip; gaussian.py:10): t_a = the fma chain over b of x_b Siginv[b][a], then the products x_a t_a added in
+// ascending a.  The d chains of a row are spread over the block; one thread adds a row's products up.
+// ws: BC_PM_ROWAUX_DOUBLES(d) doubles; ends with a barrier.
+BC_PM_FN inline void bc_pm_rowaux_tile(const void* rows, int elem, int n, int d, const double* siginv, int tile, double* ws, double* ra) {
+  const int tid = BC_PM_TID, nt = BC_PM_NT, row0 = tile * BC_PM_TILE;
+  const int here = n - row0 < BC_PM_TILE ? n - row0 : BC_PM_TILE;
+  double* x = ws;                                          // [16][d] the rows, widened
+  double* u = ws + (size_t)BC_PM_TILE * d;                 // [16][d] x_a t_a
+  for (int e = tid; e < here * d; e += nt) x[e] = bc_pm_row_elem(rows, elem, (size_t)row0 * d + e);
+  BC_PM_SYNC();
+  for (int e = tid; e < here * d; e += nt) {
+    const int r = e / d, aa = e - r * d;
+    const double* xr = x + (size_t)r * d;
+    double acc = 0.;
+    for (int bb = 0; bb < d; ++bb) acc = fma(xr[bb], siginv[(size_t)bb * d + aa], acc);
+    u[e] = xr[aa] * acc;
+  }
+  BC_PM_SYNC();
+  for (int r = tid; r < here; r += nt) {
+    double tot = 0.;
+    for (int aa = 0; aa < d; ++aa) tot += u[(size_t)r * d + aa];
+    ra[row0 + r] = tot;
+  }
+  BC_PM_SYNC();
+}
+
+// The three S x d x d products of the Gaussian kind's posterior stage on the fp64 matrix cores, from the factor that
+// bc_vi_sampler (called with no samples) leaves in its work space:
+//   Theta[q][c]  = mu[c] + sum_{k <= c} E[q][k] L[c][k]            (L = C^-1, packed lower triangle: (i, k) at i (i + 1) / 2 + k)
+//   Theta'[q][c] = sum_b Siginv[c][b] Theta[q][b]
+//   sa[q]        = sum_c Theta[q][c] (sum_b Theta[q][b] Siginv[b][c])
+// the expressions of bc_vi_sampler's Gaussian tail with its per-thread chains replaced by v_mfma_f64_16x16x4_f64 tiles of
+// (16 samples, 16 coordinates): a wave takes a strip of 16 samples and walks the coordinate tiles in ascending order.  sa: each
+// lane adds the products of its own column tile by tile, a butterfly adds the 16 columns -- a fixed order that depends on d
+// alone.  Theta is written to device memory and re-read after a barrier, as bc_vi_sampler does.  Not bc_vi_sampler's bits; the
+// same bounds (tests/psvi_many_gauss_cases.py).  The block is a multiple of 64 threads.
+#define BC_PM_VIS_TRI(d) ((d) * ((d) + 1) / 2)
+#define BC_PM_VIS_LI(d) BC_PM_VIS_TRI(d)                       // bc_vi_sampler's work space: C | L | rhs | t | mu | sc[2]
+#define BC_PM_VIS_MU(d) (2 * BC_PM_VIS_TRI(d) + 2 * (d))
+#define BC_PM_VIS_DOUBLES(d) (2 * BC_PM_VIS_TRI(d) + 3 * (d) + 2)      // (the unit that includes both headers asserts == BC_VIS_WS_DOUBLES)
+
+struct PmPostArgs {
+  int d, s;
+  const double* E;         // [s][d] this step's normals
+  const double* Li;        // packed L (LDS)
+  const double* mu;        // [d] (LDS)
+  const double* siginv;    // [d][d]
+  double* raw;             // out [s][d] Theta
+  double* thp;             // out [s][d] Theta'
+  double* sa;              // out [s]
+};
+
+BC_PM_FN inline void bc_pm_post_products(const PmPostArgs& a) {
+  const int tid = BC_PM_TID, nt = BC_PM_NT, d = a.d, s = a.s;
+#ifdef __HIPCC__
+  const int lane = tid & 63, wv = tid >> 6, nw = nt >> 6, r = lane & 15, kq = lane >> 4;
+  const int qt = (s + 15) >> 4, ct = (d + 15) >> 4;
+  for (int Q = wv; Q < qt; Q += nw) {                      // (wave-uniform: every lane issues the MFMAs)
+    const int qa = Q * 16 + r;
+    for (int Ct = 0; Ct < ct; ++Ct) {
+      const int cb = Ct * 16 + r, kend = Ct * 16 + 16 < d ? Ct * 16 + 16 : d;      // L[c][k] = 0 for k > c
+      bc_pm_d4 acc = {0., 0., 0., 0.};
+      for (int k0 = 0; k0 < kend; k0 += 4) {               // operand maps: A[i = lane & 15][k = lane >> 4], B[k = lane >> 4][j = lane & 15]
+        const int k = k0 + kq;
+        const double av = (qa < s && k < d) ? a.E[(size_t)qa * d + k] : 0.;
+        const double bv = (cb < d && k <= cb) ? a.Li[cb * (cb + 1) / 2 + k] : 0.;
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
+      }
+      for (int q4 = 0; q4 < 4; ++q4) {                     // result map: col = lane & 15, row = (lane >> 4) + 4 q4
+        const int q = Q * 16 + kq + 4 * q4;
+        if (q < s && cb < d) a.raw[(size_t)q * d + cb] = a.mu[cb] + acc[q4];
+      }
+    }
+  }
+  BC_PM_SYNC();
+  for (int Q = wv; Q < qt; Q += nw) {
+    const int qa = Q * 16 + r;
+    double part[4] = {0., 0., 0., 0.};
+    for (int Ct = 0; Ct < ct; ++Ct) {
+      const int cb = Ct * 16 + r;
+      bc_pm_d4 acc1 = {0., 0., 0., 0.}, acc2 = {0., 0., 0., 0.};
+      for (int k0 = 0; k0 < d; k0 += 4) {
+        const int k = k0 + kq;
+        const bool in = cb < d && k < d;
+        const double av = (qa < s && k < d) ? a.raw[(size_t)qa * d + k] : 0.;
+        const double b1 = in ? a.siginv[(size_t)cb * d + k] : 0.;
+        const double b2 = in ? a.siginv[(size_t)k * d + cb] : 0.;
+        acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(av, b1, acc1, 0, 0, 0);
+        acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(av, b2, acc2, 0, 0, 0);
+      }
+      for (int q4 = 0; q4 < 4; ++q4) {
+        const int q = Q * 16 + kq + 4 * q4;
+        if (q < s && cb < d) {
+          a.thp[(size_t)q * d + cb] = acc1[q4];
+          part[q4] += a.raw[(size_t)q * d + cb] * acc2[q4];
+        }
+      }
+    }
+    for (int q4 = 0; q4 < 4; ++q4) {
+      double v = part[q4];
+      for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o);
+      const int q = Q * 16 + kq + 4 * q4;
+      if (r == 0 && q < s) a.sa[q] = v;
+    }
+  }
+#else
+  for (int e = tid; e < s * d; e += nt) {
+    const int q = e / d, c = e - q * d;
+    double acc = 0.;
+    for (int k = 0; k <= c; ++k) acc = fma(a.E[(size_t)q * d + k], a.Li[c * (c + 1) / 2 + k], acc);
+    a.raw[e] = a.mu[c] + acc;
+  }
+  BC_PM_SYNC();
+  for (int q = tid; q < s; q += nt) {
+    const double* th = a.raw + (size_t)q * d;
+    double tst = 0.;
+    for (int c = 0; c < d; ++c) {
+      double m1 = 0., m2 = 0.;
+      for (int b = 0; b < d; ++b) {
+        m1 = fma(a.siginv[(size_t)c * d + b], th[b], m1);
+        m2 = fma(th[b], a.siginv[(size_t)b * d + c], m2);
+      }
+      a.thp[(size_t)q * d + c] = m1;
+      tst += th[c] * m2;
+    }
+    a.sa[q] = tst;
+  }
+#endif
 }
 
 // A tile of the gathered data rows: part[q] = sum over the tile's rows, top to bottom.

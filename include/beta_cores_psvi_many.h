@@ -24,15 +24,32 @@
  *   5. ADAM      one step of util/opt.py's partial_nn_opt on x_p = (w_p, points_p): b1 = 0.9, b2 = 0.999, eps = 1e-8, max(., 0) on
  *                the m_p weights only
  *
- * Scope: model BC_MODEL_LOGISTIC_LL with sampler kind BC_VI_SAMPLER_LOGISTIC (Newton search), diag 0 or 1, rows z = y * x of
- * exactly D columns, prior N(0, I).  Refused with BC_INVALID_ARGUMENT and a message: every other model or sampler kind, n_sub = 0
+ * Scope: two kinds of run.
+ *   logistic   model BC_MODEL_LOGISTIC_LL with sampler kind BC_VI_SAMPLER_LOGISTIC (Newton search), diag 0 or 1, rows z = y * x of
+ *              exactly D columns, prior N(0, I): the steps above (bc_psvi_many_begin, or bc_psvi_curve_begin without parameters).
+ *   Gaussian   model BC_MODEL_GAUSS_LL (Gaussian location, rows x of D columns, known covariance) with sampler kind
+ *              BC_VI_SAMPLER_GAUSS, through bc_psvi_curve_begin.  Step 2 is a closed form instead of a search:
+ *                2a. row aux    ra_r = x_r^T Siginv x_r of the gathered rows, once for the whole batch, and of every problem's points
+ *                               (the expression of the projection's row quadratic form; float32 rows widened as they are read)
+ *                2b. posterior  A = Sig0inv + (sum w) Siginv, rhs = Sig0inv mu0 + Siginv sum_i w_i x_i, C = chol(A), L = C^-1,
+ *                               mu_p = L L^T rhs (the reference's expression), Theta_p = mu_p + E L^T,
+ *                               Theta'_p = (Siginv Theta_p^T)^T, sa_q = theta_q^T Siginv theta_q (A, C, L and mu by the
+ *                               block of k_vi_sampler, beta_cores_viopt.h, bit for bit; the three products on the fp64
+ *                               matrix cores in a fixed order of their own)
+ *              and step 3's log-likelihood is c0 - 1/2 ((ra + sa_q) - 2 x . Theta'_q), K1's expression for this model, x-only terms
+ *              kept.  Steps 4-5 are the same code; the point-gradient takes Theta'_p and Siginv.  out_modes is mu_p.  Full
+ *              covariance only (diag = 0), start = NULL, and the sampler's Siginv must be the model's, double for double.
+ * The two entries that take a kind, bc_psvi_curve_begin and bc_psvi_curve_work_doubles, are declared in beta_cores_psvi_curve.h;
+ * a run begun there continues with this header's chunk, end, timing and seam entries.
+ * Refused with BC_INVALID_ARGUMENT and a message: every other model or sampler kind (linear regression included), n_sub = 0
  * (all rows every step), data of another context.  Not offered at all: encoders, row shards or communicators, the reference's BFGS
  * search, a device random-number generator, per-problem independent draws.
  *
  * Limits, refused with BC_INVALID_ARGUMENT before anything is enqueued:
  *   1 <= D <= BC_VI_MAX_DIM, 1 <= S <= BC_PSVI_MANY_MAX_SAMPLES, 1 <= n_sub <= BC_PSVI_MANY_MAX_SUB, 1 <= opt_itrs,
  *   1 <= P <= BC_PSVI_MANY_MAX_PROBLEMS, 1 <= m_p <= BC_PSVI_MANY_MAX_POINTS, and the run's device work space
- *   (bc_psvi_many_work_doubles) at most BC_PSVI_MANY_MAX_WORK_DOUBLES.
+ *   (bc_psvi_many_work_doubles / bc_psvi_curve_work_doubles) at most BC_PSVI_MANY_MAX_WORK_DOUBLES.  The Gaussian kind's
+ *   posterior block takes 2 D (D + 1) / 2 + 3 D + 2 doubles of LDS (132 KiB at D = 128: one block per compute unit).
  *
  * Reproducibility: every loop has a fixed bound and every sum a fixed order.  The bits of a problem's results depend on its own
  * points, weights, start, steps and the shared draws only -- not on P, on its place in the batch or on the other problems.  Float32
@@ -61,7 +78,11 @@ extern "C" {
  *   R (5 D + 8 + S) + R / 2 + P (S D + D + T S + 2 S + opt_itrs + 2) + P / 2 + 2 opt_itrs + 1      (state, moments, gradients, the
  *   last step's snapshot, Theta, corevecs, partial sums, row scratch, step arrays, row_ptr and the ints), rounded up piece by
  *   piece to even counts.
- * Returns the count (not a status); -1 for arguments outside the limits above. */
+ * The Gaussian kind (sampler_kind BC_VI_SAMPLER_GAUSS) adds P (S D + S) + n_sub + R: the raw draws Theta_p and sa, and the row aux
+ *   of the gathered rows and of the points -- four more pieces, rounded up the same way.  Its constants (Sig0inv, Sig0inv mu0,
+ *   Siginv: 2 D^2 + D doubles) and, for both kinds, the gathered rows are small buffers of their own, not part of this count.
+ * Returns the count (not a status); -1 for arguments outside the limits above or a sampler kind that is not served.
+ * bc_psvi_many_work_doubles is the logistic kind's count. */
 int64_t bc_psvi_many_work_doubles(int64_t total_points, int32_t n_problems, int32_t d, int32_t s, int64_t n_sub, int32_t opt_itrs);
 
 /* Steps per chunk that keep a chunk's staged draws (normals + indices) under BC_VI_STAGE_BYTES (at least 1): a count, not a status. */
@@ -69,7 +90,7 @@ int bc_psvi_many_auto_chunk(int32_t s, int32_t d, int64_t n_sub);
 
 /* Validates everything but the indices and stages what is constant over the run; zeroes both moments; nothing runs yet.
  *   data: the resident rows, D columns, float64 or float32.
- *   model: BC_MODEL_LOGISTIC_LL.   sampler_kind: BC_VI_SAMPLER_LOGISTIC.   diag: 0 or 1.
+ *   model: BC_MODEL_LOGISTIC_LL.   sampler_kind: BC_VI_SAMPLER_LOGISTIC.   diag: 0 or 1.   (the Gaussian kind: beta_cores_psvi_curve.h)
  *   pts: host, (sum m_p) x D, the initial points.   w0: host, sum m_p.   row_ptr: host, P + 1.
  *   start: host, P x D, where each problem's first mode search begins; NULL: zeros.
  *   steps: host, [P][opt_itrs]: step_sched(m_p)(i).   moments: host, [2][opt_itrs]: 1 - b1^(i+1) | 1 - b2^(i+1).
@@ -99,6 +120,7 @@ int bc_psvi_many_device_ms(bc_ctx* ctx, double* out_ms);
  *   out_w_before: R.  out_pts_before: R x D.  out_mode: P x D.  out_theta: P x S x D.  out_target, out_resid: P x S.
  *   out_gw: R.  out_gp: R x D.  out_w, out_mom1_w, out_mom2_w: R.  out_pts, out_mom1_p, out_mom2_p: R x D.
  *   out_newton: P x 2: Newton steps of the last fit | of all fits of the run.   out_flag: P: 0, or 1 + the step that marked it.
+ * Gaussian kind: out_theta is the draw Theta_p (not Theta'_p), out_mode is mu_p, out_newton is zero.
  * A marked problem's slices hold what its last executed stage left. */
 int bc_psvi_many_last_step(bc_ctx* ctx, int64_t total_points, int32_t n_problems, int32_t d, int32_t s, double* out_w_before,
                            double* out_pts_before, double* out_mode, double* out_theta, double* out_target, double* out_resid,
