@@ -9,11 +9,10 @@ Every gradient needs (bpsvi.py:27-57)
     the optimiser (util/opt.py partial_nn_opt) updates them there.
 With a BlackBoxProjector the reference's NumPy expressions run on whatever the callables return and the N-row column
 sum still runs on the GPU."""
-import ctypes as C
-
 import numpy as np
 
 from .. import _native as N
+from .._runs import device_ms, pack_problems, run_chunks, step_draws
 from ..device import DeviceData, DevicePhi, _ptr
 from ..likelihoods import GaussianLocation, LogisticRegression
 from ..util.opt import adam_step_arrays, partial_nn_opt
@@ -52,11 +51,8 @@ def psvi_many_run(data, pts, wts, S, opt_itrs, steps, draw, n_sub, n_total=None,
     if int(opt_itrs) < 1:
         raise ValueError('psvi_many_run: opt_itrs must be at least 1, got %d' % opt_itrs)
     D = int(data.shape[1])
-    row_ptr = np.zeros(P + 1, dtype=np.int64)
-    row_ptr[1:] = np.cumsum([np.atleast_2d(p).shape[0] for p in pts])
+    pk, wk, row_ptr = pack_problems([(np.atleast_2d(p), np.atleast_1d(w)) for p, w in zip(pts, wts)], width=D)
     R = int(row_ptr[-1])
-    pk = np.ascontiguousarray(np.vstack([np.atleast_2d(p) for p in pts]) if P else np.zeros((0, D)), dtype=np.float64)
-    wk = np.ascontiguousarray(np.concatenate([np.atleast_1d(w) for w in wts]) if P else np.zeros(0), dtype=np.float64)
     if pk.shape != (R, D) or wk.shape != (R,):
         raise ValueError('points must have %d columns and one weight each' % D)
     steps = np.ascontiguousarray(steps, dtype=np.float64)
@@ -79,36 +75,23 @@ def psvi_many_run(data, pts, wts, S, opt_itrs, steps, draw, n_sub, n_total=None,
         sp = np.ascontiguousarray(np.zeros(0) if sampler_params is None else sampler_params, dtype=np.float64).ravel()
         N.call('bc_psvi_curve_begin', *begin, _ptr(mp) if mp.size else None, int(mp.size), _ptr(sp) if sp.size else None, int(sp.size))
     chunk = int(chunk_steps) if chunk_steps else int(lib.bc_psvi_many_auto_chunk(int(S), D, int(n_sub)))
-    try:
-        done = 0
-        nxt = draw(min(chunk, int(opt_itrs)))
-        while done < opt_itrs:
-            E, idx = nxt
-            E = np.ascontiguousarray(E, dtype=np.float64)
-            idx = np.ascontiguousarray(idx, dtype=np.int64)
-            k = int(E.shape[0])
-            if E.shape != (k, int(S), D) or idx.shape != (k, int(n_sub)):
-                raise ValueError('draw(k) must return k x S x D normals and k x n_sub row numbers')
-            N.call('bc_psvi_many_chunk_begin', ctx.h, _ptr(E), _ptr(idx), k)
-            done += k
-            try:
-                nxt = draw(min(chunk, int(opt_itrs) - done)) if done < opt_itrs else None      # beside the GPU
-            finally:
-                status = lib.bc_psvi_many_chunk_end(ctx.h, None)
-            N.check(status)
-            if on_chunk is not None:
-                on_chunk(done)
-        ow, op, om, ost = np.full(R, np.nan), np.full((R, D), np.nan), np.full((P, D), np.nan), np.zeros(P, dtype=np.int32)
-        N.call('bc_psvi_many_end', ctx.h, _ptr(ow), _ptr(op), _ptr(om), _ptr(ost))
-    except BaseException:
-        lib.bc_psvi_many_end(ctx.h, None, None, None, None)      # (closes the run; a no-op status if _end itself has closed it)
-        raise
-    ms = C.c_double()
-    N.call('bc_psvi_many_device_ms', ctx.h, C.byref(ms))
+    ow, op, om, ost = np.full(R, np.nan), np.full((R, D), np.nan), np.full((P, D), np.nan), np.zeros(P, dtype=np.int32)
+
+    def chunk_begin(drawn):
+        E = np.ascontiguousarray(drawn[0], dtype=np.float64)
+        idx = np.ascontiguousarray(drawn[1], dtype=np.int64)
+        k = int(E.shape[0])
+        if E.shape != (k, int(S), D) or idx.shape != (k, int(n_sub)):
+            raise ValueError('draw(k) must return k x S x D normals and k x n_sub row numbers')
+        N.call('bc_psvi_many_chunk_begin', ctx.h, _ptr(E), _ptr(idx), k)
+        return k
+    run_chunks(opt_itrs, chunk, draw, chunk_begin, lambda: lib.bc_psvi_many_chunk_end(ctx.h, None),
+               close=lambda: lib.bc_psvi_many_end(ctx.h, None, None, None, None),
+               finish=lambda: N.call('bc_psvi_many_end', ctx.h, _ptr(ow), _ptr(op), _ptr(om), _ptr(ost)), on_chunk=on_chunk)
     ok = ost == N.BC_OK
     return dict(w=[ow[row_ptr[p]:row_ptr[p + 1]] if ok[p] else None for p in range(P)],
                 pts=[op[row_ptr[p]:row_ptr[p + 1]] if ok[p] else None for p in range(P)], modes=om, status=ost,
-                marked=[p for p in range(P) if not ok[p]], device_ms=ms.value)
+                marked=[p for p in range(P) if not ok[p]], device_ms=device_ms('bc_psvi_many_device_ms', ctx))
 
 
 def psvi_many_last_step(ctx, sizes, D, S):
@@ -343,19 +326,12 @@ class BatchPSVICoreset(Coreset):
         perm = np.random.choice(n, size=max(sizes), replace=False)      # (size m's choice is its first m entries)
         base = np.asarray(self.data[perm], dtype=np.float64)
         steps = np.array([[self.step_sched(m)(i) for i in range(self.opt_itrs)] for m in sizes], dtype=np.float64).reshape(len(sizes), self.opt_itrs)
-
-        def draw(k):
-            E, idx = np.empty((k, S, D)), np.empty((k, n_sub), dtype=np.int64)
-            for t in range(k):
-                E[t] = smp._normals(S, D)
-                idx[t] = np.random.randint(n, size=n_sub)
-            return E, idx
         if kind == _SAMPLER_GAUSS:
             how = dict(model_id=prj.model.model_id, sampler_kind=_SAMPLER_GAUSS, model_params=prj.model.params(), sampler_params=sp)
         else:
             how = dict(start=np.tile(sp[:D], (len(sizes), 1)), diag=bool(sp[D]))
-        res = psvi_many_run(rows, [base[:m] for m in sizes], [np.full(m, n / m) for m in sizes], S, self.opt_itrs, steps, draw, n_sub,
-                            n_total=n, **how)
+        res = psvi_many_run(rows, [base[:m] for m in sizes], [np.full(m, n / m) for m in sizes], S, self.opt_itrs, steps,
+                            step_draws(smp, S, D, n, n_sub), n_sub, n_total=n, **how)
         entries = []
         for p, m in enumerate(sizes):
             if res['w'][p] is None:

@@ -11,11 +11,11 @@ Two families, one protocol (bayesiancoresets/coreset/projector.py:5-66:
   leaves HBM (a DevicePhi is returned).
 """
 import ctypes as C
-import time
 
 import numpy as np
 
 from .. import _native as N
+from .._runs import device_ms, run_chunks, step_draws
 from ..device import DeviceData, _as_rows, _ptr, default_context, upload_slot
 from ..likelihoods import GaussianLocation, LinearRegression, LogisticRegression
 from ..util import numpy_bits
@@ -415,45 +415,28 @@ class _DeviceProjectorBase(Projector):
         steps = np.ascontiguousarray(adam_step_arrays(int(opt_itrs), step_sched))
         lib = N.load()
         chunk = int(chunk_steps) if chunk_steps else int(lib.bc_vi_optimize_auto_chunk(S, D, n_sub))
-        draw_s = [0.]
-
-        def draw(k):
-            t0 = time.perf_counter()
-            E = np.empty((k, S, D))
-            idx = np.empty((k, n_sub), dtype=np.int64) if n_sub else None
-            for t in range(k):
-                E[t] = self.sampler._normals(S, D)
-                if n_sub:
-                    idx[t] = np.random.randint(n_total, size=n_sub)
-            draw_s[0] += time.perf_counter() - t0
-            return E, idx
+        draw_s, h = [0.], self.ctx.h
         N.call('bc_vi_optimize_begin', self.ctx.h, data.h, _ptr(core), m, int(model_id), _ptr(params), int(params.shape[0]),
                int(kind), _ptr(sp), S, _ptr(w0), int(opt_itrs), _ptr(steps), n_sub,
                float(n_total) / n_sub if n_sub else 1., 1 if want_trace else 0)
-        try:
-            done = 0
-            nxt = draw(min(chunk, int(opt_itrs)))
-            while done < opt_itrs:
-                E, idx = nxt
-                N.call('bc_vi_optimize_chunk_begin', self.ctx.h, _ptr(E), _ptr(idx) if idx is not None else None, int(E.shape[0]))
-                done += E.shape[0]
-                try:
-                    nxt = draw(min(chunk, int(opt_itrs) - done)) if done < opt_itrs else None      # beside the GPU
-                finally:
-                    status = lib.bc_vi_optimize_chunk_end(self.ctx.h)
-                if status == N.BC_NUMERICAL_PRECISION:
-                    raise np.linalg.LinAlgError(N.last_error())
-                N.check(status)
-            out = np.empty(m)
-            trace = np.empty((int(opt_itrs), m)) if want_trace else None
-            N.call('bc_vi_optimize_end', self.ctx.h, _ptr(out), _ptr(trace) if want_trace else None)
-        except BaseException:
-            lib.bc_vi_optimize_end(self.ctx.h, None, None)      # (closes the run; a no-op status if _end itself has closed it)
-            raise
+        out = np.empty(m)
+        trace = np.empty((int(opt_itrs), m)) if want_trace else None
+
+        def chunk_begin(drawn):
+            E, idx = drawn
+            N.call('bc_vi_optimize_chunk_begin', h, _ptr(E), _ptr(idx) if idx is not None else None, int(E.shape[0]))
+            return E.shape[0]
+
+        def chunk_end():
+            status = lib.bc_vi_optimize_chunk_end(h)
+            if status == N.BC_NUMERICAL_PRECISION:
+                raise np.linalg.LinAlgError(N.last_error())
+            return status
+        run_chunks(opt_itrs, chunk, step_draws(self.sampler, S, D, n_total, n_sub, seconds=draw_s), chunk_begin, chunk_end,
+                   close=lambda: lib.bc_vi_optimize_end(h, None, None),
+                   finish=lambda: N.call('bc_vi_optimize_end', h, _ptr(out), _ptr(trace) if want_trace else None))
         if timings is not None:
-            ms = C.c_double()
-            N.call('bc_vi_optimize_device_ms', self.ctx.h, C.byref(ms))
-            timings['draw_s'], timings['device_ms'] = draw_s[0], ms.value
+            timings['draw_s'], timings['device_ms'] = draw_s[0], device_ms('bc_vi_optimize_device_ms', self.ctx)
         self.vi_optimize_calls += 1
         if kind == 2:
             # the mode the last step ended at: where the sampler's next call -- on the host or in the next run -- starts

@@ -2,6 +2,7 @@
 // sums / norms) and K3 (fused score + argmax sweep).  gfx950 only.
 #include "bc_internal.h"
 #include "bc_layout.h"
+#include "bc_slab.h"
 #include "bc_sweep_plan.h"
 #include "../../include/beta_cores_f32.h"
 #include <cstdarg>
@@ -144,6 +145,51 @@ int bc_ctx_refuse_busy(const bc_ctx* ctx, const char* who, unsigned holders, uns
       bc_set_error("%s: a %s run is %sopen on this context (call %s_end first)", who, r.kind, (own & r.bit) ? "already " : "", r.kind);
       return BC_INVALID_ARGUMENT;
     }
+  return BC_OK;
+}
+
+int bc_run_wait_chunk(bc_ctx* ctx, bc_run* r) {
+  r->chunk_pending = false;
+  BC_HIP(hipSetDevice(ctx->device));
+  BC_HIP(hipStreamSynchronize(ctx->stream));
+  r->clock.collect();
+  return BC_OK;
+}
+
+int bc_run_end(bc_ctx* ctx, bc_run* r, const bc_run_kind& kd, bool* was_pending) {
+  const int rc = bc_run_close(r, kd, was_pending);
+  if (rc) return rc;
+  BC_HIP(hipSetDevice(ctx->device));
+  if (*was_pending) BC_HIP(hipStreamSynchronize(ctx->stream));      // abandoned mid-chunk: nothing may outlive the run's buffers
+  return BC_OK;
+}
+
+int bc_device_ms(const char* who, const bc_ctx* ctx, const bc_run_clock* clock, double* out_ms) {
+  if (!ctx || !out_ms) BC_REFUSE("%s: bad argument", who);
+  *out_ms = clock ? clock->ms : 0.;
+  return BC_OK;
+}
+
+int bc_stage_step_chunk(bc_ctx* ctx, bc_stage* st, const char* who, const double* normals, size_t n_e, const int64_t* sub_idx, size_t k,
+                        size_t n_sub, int64_t first_step, int64_t n_rows, const double** e_dev, const long long** idx_dev) {
+  const size_t n_idx = k * n_sub;
+  for (size_t j = 0; j < n_idx; ++j)
+    if (sub_idx[j] < 0 || sub_idx[j] >= n_rows)
+      BC_REFUSE("%s: index %lld (step %lld, position %lld) out of range [0,%lld)", who, (long long)sub_idx[j],
+                (long long)(first_step + (int64_t)(j / n_sub)), (long long)(j % n_sub), (long long)n_rows);
+  // ---- nothing of this chunk has been enqueued up to here
+  BC_HIP(hipSetDevice(ctx->device));
+  bc_slab sl;
+  sl.take(n_e);
+  const size_t o_idx = sl.take_unpadded(n_idx), need = sl.total;      // (the indices are the last piece: not rounded)
+  const int rc = bc_stage_reserve(ctx, st, need);
+  if (rc) return rc;
+  memcpy(st->pin.p, normals, n_e * sizeof(double));
+  long long* hidx = reinterpret_cast<long long*>(st->pin.p + o_idx);
+  for (size_t j = 0; j < n_idx; ++j) hidx[j] = (long long)sub_idx[j];
+  BC_HIP(hipMemcpyAsync(st->dev.p, st->pin.p, need * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  *e_dev = st->dev.p;
+  *idx_dev = reinterpret_cast<const long long*>(st->dev.p + o_idx);
   return BC_OK;
 }
 

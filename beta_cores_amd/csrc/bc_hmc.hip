@@ -228,20 +228,18 @@ __global__ __launch_bounds__(BC_HMC_BLOCK) void k_hmc_last(HmcState s, const int
 }
 
 // ------------------------------------------------------------------ host side
-struct bc_hmc {
+static const bc_run_kind HMC_RUN = {"bc_hmc", "iterations"};
+struct bc_hmc : bc_run {          // (the run in progress: active, chunk_pending, failed, done of total iterations, the clock)
   bc_scratch dev;                 // the chains' state (HmcState) | inverse mass | flag
   bc_scratch part;                // the rows pass's partials
   bc_stage stage;                 // a chunk's draws: normals [k][c][d] | log-uniforms [k][c]
   bc_scratch out;                 // a chunk's results: samples [k][c][d] | log-joints [k][c] | accept flags [k][c] (ints)
-  bc_run_clock clock;
-  bool active = false, chunk_pending = false, failed = false;
   const bc_data* data = nullptr;
   const bc_data* w = nullptr;
   HmcState st;
   int* d_flag = nullptr;
   int32_t n_leapfrog = 0, pending_k = 0;
   size_t o_l = 0, o_a = 0;        // where the pending chunk's log-joints and accept flags begin in `out` (set by _chunk_begin)
-  int64_t n_iter = 0, done = 0;
 };
 
 bool bc_hmc_active(const bc_ctx* ctx) { return ctx->hmc && ctx->hmc->active; }
@@ -330,19 +328,15 @@ static int rows_pass(bc_ctx* ctx, const bc_data* data, const bc_data* w, const d
 }
 
 static int check_problem(bc_ctx* ctx, const bc_data* data, const bc_data* w, int32_t c, const char* who) {
-  if (data->ctx != ctx || (w && w->ctx != ctx)) { bc_set_error("%s: rows or weights belong to another context", who); return BC_INVALID_ARGUMENT; }
-  if (c < 1 || c > BC_HMC_MAX_CHAINS) { bc_set_error("%s: 1 .. %d chains are served, got %d", who, BC_HMC_MAX_CHAINS, c); return BC_INVALID_ARGUMENT; }
+  if (data->ctx != ctx || (w && w->ctx != ctx)) BC_REFUSE("%s: rows or weights belong to another context", who);
+  if (c < 1 || c > BC_HMC_MAX_CHAINS) BC_REFUSE("%s: 1 .. %d chains are served, got %d", who, BC_HMC_MAX_CHAINS, c);
   const int d = data->dz;
-  if (d < 1 || d > BC_HMC_MAX_DIM) { bc_set_error("%s: rows must have 1 .. %d columns, got %d", who, BC_HMC_MAX_DIM, d); return BC_INVALID_ARGUMENT; }
-  if (w && (w->dz != 1 || w->n_rows != data->n_rows)) {
-    bc_set_error("%s: weights must be %lld x 1, got %lld x %d", who, (long long)data->n_rows, (long long)w->n_rows, w->dz);
-    return BC_INVALID_ARGUMENT;
-  }
+  if (d < 1 || d > BC_HMC_MAX_DIM) BC_REFUSE("%s: rows must have 1 .. %d columns, got %d", who, BC_HMC_MAX_DIM, d);
+  if (w && (w->dz != 1 || w->n_rows != data->n_rows))
+    BC_REFUSE("%s: weights must be %lld x 1, got %lld x %d", who, (long long)data->n_rows, (long long)w->n_rows, w->dz);
   if (w && bc_refuse_f32(w, who)) return BC_INVALID_ARGUMENT;
-  if (lds_of(nkb_of(d)) > (size_t)ctx->max_lds) {
-    bc_set_error("%s: D = %d needs %zu bytes of LDS, the device offers %d", who, d, lds_of(nkb_of(d)), ctx->max_lds);
-    return BC_INVALID_ARGUMENT;
-  }
+  if (lds_of(nkb_of(d)) > (size_t)ctx->max_lds)
+    BC_REFUSE("%s: D = %d needs %zu bytes of LDS, the device offers %d", who, d, lds_of(nkb_of(d)), ctx->max_lds);
   return BC_OK;
 }
 
@@ -385,10 +379,8 @@ static bc_hmc* hmc_of(bc_ctx* ctx) {
 
 extern "C" int bc_logistic_logjoint_batch(bc_ctx* ctx, const bc_data* data, const bc_data* w, const double* theta, int32_t c,
                                           double* out_value, double* out_grad) {
-  if (!ctx || !data || !theta || !out_grad) {
-    bc_set_error("bc_logistic_logjoint_batch: bad argument (context, rows, theta and gradients are required)");
-    return BC_INVALID_ARGUMENT;
-  }
+  if (!ctx || !data || !theta || !out_grad)
+    BC_REFUSE("bc_logistic_logjoint_batch: bad argument (context, rows, theta and gradients are required)");
   int rc = check_problem(ctx, data, w, c, "bc_logistic_logjoint_batch");
   if (rc) return rc;
   rc = bc_ctx_refuse_busy(ctx, "bc_logistic_logjoint_batch", BC_HOLD_HMC | BC_HOLD_HMC_SMALL);
@@ -420,19 +412,15 @@ extern "C" int bc_hmc_auto_chunk(int32_t c, int32_t d) {
 
 extern "C" int bc_hmc_begin(bc_ctx* ctx, const bc_data* data, const bc_data* w, const double* start, int32_t c, const double* inv_mass,
                             int32_t n_leapfrog, int64_t n_iter) {
-  if (!ctx || !data || !start || !inv_mass) { bc_set_error("bc_hmc_begin: bad argument (context, rows, start and inv_mass are required)"); return BC_INVALID_ARGUMENT; }
+  if (!ctx || !data || !start || !inv_mass) BC_REFUSE("bc_hmc_begin: bad argument (context, rows, start and inv_mass are required)");
   int rc = check_problem(ctx, data, w, c, "bc_hmc_begin");
   if (rc) return rc;
-  if (n_leapfrog < 1 || n_iter < 1) {
-    bc_set_error("bc_hmc_begin: needs n_leapfrog >= 1 and n_iter >= 1 (n_leapfrog = %d, n_iter = %lld)", n_leapfrog, (long long)n_iter);
-    return BC_INVALID_ARGUMENT;
-  }
+  if (n_leapfrog < 1 || n_iter < 1)
+    BC_REFUSE("bc_hmc_begin: needs n_leapfrog >= 1 and n_iter >= 1 (n_leapfrog = %d, n_iter = %lld)", n_leapfrog, (long long)n_iter);
   const int d = data->dz;
   for (int k = 0; k < d; ++k)
-    if (!(inv_mass[k] > 0.) || !std::isfinite(inv_mass[k])) {
-      bc_set_error("bc_hmc_begin: inv_mass[%d] = %g is not finite and positive", k, inv_mass[k]);
-      return BC_INVALID_ARGUMENT;
-    }
+    if (!(inv_mass[k] > 0.) || !std::isfinite(inv_mass[k]))
+      BC_REFUSE("bc_hmc_begin: inv_mass[%d] = %g is not finite and positive", k, inv_mass[k]);
   rc = bc_ctx_refuse_busy(ctx, "bc_hmc_begin", BC_HOLD_ALL, BC_HOLD_HMC);
   if (rc) return rc;
   BC_HIP(hipSetDevice(ctx->device));
@@ -452,26 +440,16 @@ extern "C" int bc_hmc_begin(bc_ctx* ctx, const bc_data* data, const bc_data* w, 
   h->data = data;
   h->w = w;
   h->n_leapfrog = n_leapfrog;
-  h->n_iter = n_iter;
-  h->done = 0;
-  h->clock.ms = 0.;
   h->pending_k = 0;
-  h->active = true;
-  h->chunk_pending = false;
-  h->failed = false;
+  bc_run_opened(h, n_iter);
   return BC_OK;
 }
 
 extern "C" int bc_hmc_chunk_begin(bc_ctx* ctx, const double* normals, const double* log_u, int32_t k, double step_size) {
   bc_hmc* h = ctx ? ctx->hmc : nullptr;
-  if (!h || !h->active || !normals || !log_u || k <= 0) { bc_set_error("bc_hmc_chunk_begin: bad argument, or no run is open"); return BC_INVALID_ARGUMENT; }
-  if (h->chunk_pending) { bc_set_error("bc_hmc_chunk_begin: a chunk is pending (call bc_hmc_chunk_end first)"); return BC_INVALID_ARGUMENT; }
-  if (h->failed) { bc_set_error("bc_hmc_chunk_begin: the run has failed (call bc_hmc_end)"); return BC_INVALID_ARGUMENT; }
-  if (h->done + (int64_t)k > h->n_iter) {
-    bc_set_error("bc_hmc_chunk_begin: %d iterations after %lld exceed the run's %lld", k, (long long)h->done, (long long)h->n_iter);
-    return BC_INVALID_ARGUMENT;
-  }
-  if (!(step_size > 0.) || !std::isfinite(step_size)) { bc_set_error("bc_hmc_chunk_begin: the step size must be finite and positive, got %g", step_size); return BC_INVALID_ARGUMENT; }
+  int rc = bc_run_admit(h, HMC_RUN, normals && log_u, k);
+  if (rc) return rc;
+  if (!(step_size > 0.) || !std::isfinite(step_size)) BC_REFUSE("bc_hmc_chunk_begin: the step size must be finite and positive, got %g", step_size);
   // ---- nothing of this chunk has been enqueued up to here
   BC_HIP(hipSetDevice(ctx->device));
   const HmcState& s = h->st;
@@ -482,7 +460,7 @@ extern "C" int bc_hmc_chunk_begin(bc_ctx* ctx, const double* normals, const doub
   out.take(n_e);
   h->o_l = out.take(n_u);
   h->o_a = out.take((n_u + 1) / 2);      // (ints)
-  int rc = bc_stage_reserve(ctx, &h->stage, st.total);
+  rc = bc_stage_reserve(ctx, &h->stage, st.total);
   if (!rc) rc = bc_scratch_grow(ctx, &h->out, out.total);
   if (rc) return rc;
   memcpy(h->stage.pin.p, normals, n_e * sizeof(double));
@@ -519,15 +497,14 @@ extern "C" int bc_hmc_chunk_begin(bc_ctx* ctx, const double* normals, const doub
 
 extern "C" int bc_hmc_chunk_end(bc_ctx* ctx, double* out_samples, double* out_logjoint, int32_t* out_accept) {
   bc_hmc* h = ctx ? ctx->hmc : nullptr;
-  if (!h || !h->active || !h->chunk_pending) { bc_set_error("bc_hmc_chunk_end: no chunk is pending"); return BC_INVALID_ARGUMENT; }
+  int rc = bc_run_pending(h, "bc_hmc_chunk_end");
+  if (rc) return rc;
   // (checked first: the chunk stays pending, a second call with the outputs can still fetch it)
-  if (!out_samples || !out_logjoint || !out_accept) { bc_set_error("bc_hmc_chunk_end: the three outputs are required"); return BC_INVALID_ARGUMENT; }
-  h->chunk_pending = false;
-  BC_HIP(hipSetDevice(ctx->device));
+  if (!out_samples || !out_logjoint || !out_accept) BC_REFUSE("bc_hmc_chunk_end: the three outputs are required");
+  rc = bc_run_wait_chunk(ctx, h);
+  if (rc) return rc;
   int flag = 0;
-  BC_HIP(hipStreamSynchronize(ctx->stream));
   BC_HIP(hipMemcpy(&flag, h->d_flag, sizeof(int), hipMemcpyDeviceToHost));
-  h->clock.collect();
   if (flag != 0) {
     h->failed = true;
     bc_set_error("bc_hmc: the log-joint or its gradient at a chain's start is not finite (a weight or a start point that is not finite)");
@@ -543,27 +520,21 @@ extern "C" int bc_hmc_chunk_end(bc_ctx* ctx, double* out_samples, double* out_lo
 
 extern "C" int bc_hmc_end(bc_ctx* ctx) {
   bc_hmc* h = ctx ? ctx->hmc : nullptr;
-  if (!h || !h->active) { bc_set_error("bc_hmc_end: no run is open"); return BC_INVALID_ARGUMENT; }
-  BC_HIP(hipSetDevice(ctx->device));
-  const bool pending = h->chunk_pending;
-  h->active = false;
-  h->chunk_pending = false;
-  h->data = nullptr;
-  h->w = nullptr;
-  if (pending) BC_HIP(hipStreamSynchronize(ctx->stream));      // abandoned mid-chunk: nothing may outlive the run's buffers
+  bool pending = false;
+  const int rc = bc_run_end(ctx, h, HMC_RUN, &pending);
+  if (rc) return rc;
+  h->data = h->w = nullptr;
   return BC_OK;
 }
 
 extern "C" int bc_hmc_device_ms(bc_ctx* ctx, double* out_ms) {
-  if (!ctx || !out_ms) { bc_set_error("bc_hmc_device_ms: bad argument"); return BC_INVALID_ARGUMENT; }
-  *out_ms = ctx->hmc ? ctx->hmc->clock.ms : 0.;
-  return BC_OK;
+  return bc_device_ms("bc_hmc_device_ms", ctx, ctx && ctx->hmc ? &ctx->hmc->clock : nullptr, out_ms);
 }
 
 extern "C" int bc_hmc_logistic(bc_ctx* ctx, const bc_data* data, const bc_data* w, const double* start, int32_t c, const double* inv_mass,
                                int32_t n_leapfrog, double step_size, int64_t n_iter, const double* normals, const double* log_u,
                                int32_t chunk_steps, double* out_samples, double* out_logjoint, int32_t* out_accept) {
-  if (!normals || !log_u || !out_samples || !out_logjoint || !out_accept || chunk_steps < 0) { bc_set_error("bc_hmc_logistic: bad argument"); return BC_INVALID_ARGUMENT; }
+  if (!normals || !log_u || !out_samples || !out_logjoint || !out_accept || chunk_steps < 0) BC_REFUSE("bc_hmc_logistic: bad argument");
   int rc = bc_hmc_begin(ctx, data, w, start, c, inv_mass, n_leapfrog, n_iter);
   if (rc) return rc;
   const int d = data->dz;

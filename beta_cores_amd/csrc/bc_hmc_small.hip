@@ -30,6 +30,7 @@
 #include "bc_hmc_dev.h"
 #include "bc_hmc_small_dev.h"
 #include "bc_slab.h"
+#include "bc_batch.h"
 #include "../../include/beta_cores_hmc_small.h"
 #include "../../include/beta_cores_score.h"
 #include <cmath>
@@ -147,21 +148,19 @@ __global__ __launch_bounds__(CPB * BC_SM_BLOCK) void k_hmc_small(SmArgs a) {
 }
 
 // ------------------------------------------------------------------ host side
-struct bc_hmc_small {
+static const bc_run_kind HMC_SMALL_RUN = {"bc_hmc_small", "iterations"};
+struct bc_hmc_small : bc_run {    // (the run in progress: active, chunk_pending, done of total iterations, the clock; `failed` is never set)
   bc_scratch prob;                // rows | w | row_ptr (int64)
   bc_scratch state;               // theta | g | lj | inverse masses | flags (ints)
   bc_stage stage;                 // a chunk's draws and steps: normals | log-uniforms | step [P]
   bc_scratch out;                 // a chunk's results: samples | log-joints | accept flags (ints)
   bc_scratch score;               // a chunk's held-out scores (bc_score_chunk): ll [P k C] | correct [P k C] (ints)
-  bc_run_clock clock;
-  bool active = false, chunk_pending = false;
   bool scored = false;            // bc_score_chunk has enqueued the pending chunk's scores
   SmArgs a;
   size_t lds = 0;
   int cpb = 1;                    // chains per block of the run's launches
   int32_t n_problems = 0, pending_k = 0;
   size_t o_l = 0, o_a = 0;        // where the pending chunk's log-joints and accept flags begin in `out` (set by _chunk_begin)
-  int64_t n_iter = 0, done = 0;
 };
 
 bool bc_hmc_small_active(const bc_ctx* ctx) { return ctx->hmc_small && ctx->hmc_small->active; }
@@ -218,8 +217,9 @@ static int chains_per_block(const bc_ctx* ctx, int64_t max_n, int d, int c) {
   return best;
 }
 
+#define BC_SM_MAX_ROWS ((int64_t)1 << 24)
 static bool fits(const bc_ctx* ctx, int64_t n, int32_t d) {
-  if (n < 1 || d < 1 || d > BC_HMC_MAX_DIM || n > (int64_t)1 << 24) return false;
+  if (n < 1 || d < 1 || d > BC_HMC_MAX_DIM || n > BC_SM_MAX_ROWS) return false;
   return lds_doubles(n, d) * sizeof(double) <= (size_t)ctx->max_lds;
 }
 
@@ -232,27 +232,15 @@ static bc_hmc_small* small_of(bc_ctx* ctx) {
 
 // the checks of a batch, before anything is touched; *max_n: the largest problem
 static int check_batch(bc_ctx* ctx, const int64_t* row_ptr, int32_t n_problems, int32_t d, int32_t c, const char* who, int64_t* max_n) {
-  if (n_problems < 1) { bc_set_error("%s: needs at least one problem, got %d", who, n_problems); return BC_INVALID_ARGUMENT; }
-  if (c < 1 || c > BC_HMC_MAX_CHAINS) { bc_set_error("%s: 1 .. %d chains are served, got %d", who, BC_HMC_MAX_CHAINS, c); return BC_INVALID_ARGUMENT; }
-  if (d < 1 || d > BC_HMC_MAX_DIM) { bc_set_error("%s: rows must have 1 .. %d columns, got %d", who, BC_HMC_MAX_DIM, d); return BC_INVALID_ARGUMENT; }
-  if (row_ptr[0] != 0) { bc_set_error("%s: row_ptr[0] must be 0, got %lld", who, (long long)row_ptr[0]); return BC_INVALID_ARGUMENT; }
-  if ((int64_t)n_problems * c > (int64_t)1 << 30) { bc_set_error("%s: %d problems x %d chains are too many blocks for one launch", who, n_problems, c); return BC_INVALID_ARGUMENT; }
-  int64_t mx = 0;
-  for (int32_t p = 0; p < n_problems; ++p) {
-    const int64_t n = row_ptr[p + 1] - row_ptr[p];
-    if (n < 1) {
-      bc_set_error("%s: row_ptr must increase strictly (every problem has at least one row): row_ptr[%d] = %lld, row_ptr[%d] = %lld", who, p,
-                   (long long)row_ptr[p], p + 1, (long long)row_ptr[p + 1]);
-      return BC_INVALID_ARGUMENT;
-    }
-    if (!fits(ctx, n, d)) {
-      bc_set_error("%s: problem %d (%lld rows x %d) needs %zu bytes of LDS, a block has %d", who, p, (long long)n, d,
-                   lds_doubles(n, d) * sizeof(double), ctx->max_lds);
-      return BC_INVALID_ARGUMENT;
-    }
-    if (n > mx) mx = n;
-  }
-  *max_n = mx;
+  if (n_problems < 1) BC_REFUSE("%s: needs at least one problem, got %d", who, n_problems);
+  if (c < 1 || c > BC_HMC_MAX_CHAINS) BC_REFUSE("%s: 1 .. %d chains are served, got %d", who, BC_HMC_MAX_CHAINS, c);
+  if (d < 1 || d > BC_HMC_MAX_DIM) BC_REFUSE("%s: rows must have 1 .. %d columns, got %d", who, BC_HMC_MAX_DIM, d);
+  if ((int64_t)n_problems * c > (int64_t)1 << 30) BC_REFUSE("%s: %d problems x %d chains are too many blocks for one launch", who, n_problems, c);
+  const int rc = bc_batch_walk(who, row_ptr, n_problems, BC_SM_MAX_ROWS, "rows", max_n);
+  if (rc) return rc;
+  if (!fits(ctx, *max_n, d))      // (this unit's own limit: a problem's rows lie in its block's LDS; the largest problem decides)
+    BC_REFUSE("%s: a problem of %lld rows x %d needs %zu bytes of LDS, a block has %d", who, (long long)*max_n, d,
+              lds_doubles(*max_n, d) * sizeof(double), ctx->max_lds);
   return BC_OK;
 }
 
@@ -311,10 +299,8 @@ static int launch(bc_ctx* ctx, const bc_hmc_small* h, const SmArgs& a) {
 
 extern "C" int bc_hmc_small_logjoint(bc_ctx* ctx, const double* rows, const double* w, const int64_t* row_ptr, int32_t n_problems, int32_t d,
                                      const double* theta, int32_t c, double* out_value, double* out_grad) {
-  if (!ctx || !rows || !w || !row_ptr || !theta || !out_grad) {
-    bc_set_error("bc_hmc_small_logjoint: bad argument (context, rows, weights, row_ptr, theta and gradients are required)");
-    return BC_INVALID_ARGUMENT;
-  }
+  if (!ctx || !rows || !w || !row_ptr || !theta || !out_grad)
+    BC_REFUSE("bc_hmc_small_logjoint: bad argument (context, rows, weights, row_ptr, theta and gradients are required)");
   int64_t max_n = 0;
   int rc = check_batch(ctx, row_ptr, n_problems, d, c, "bc_hmc_small_logjoint", &max_n);
   if (!rc) rc = bc_ctx_refuse_busy(ctx, "bc_hmc_small_logjoint", BC_HOLD_ALL, BC_HOLD_HMC_SMALL);
@@ -337,22 +323,16 @@ extern "C" int bc_hmc_small_logjoint(bc_ctx* ctx, const double* rows, const doub
 
 extern "C" int bc_hmc_small_begin(bc_ctx* ctx, const double* rows, const double* w, const int64_t* row_ptr, int32_t n_problems, int32_t d,
                                   const double* start, int32_t c, const double* inv_mass, int32_t n_leapfrog, int64_t n_iter) {
-  if (!ctx || !rows || !w || !row_ptr || !start || !inv_mass) {
-    bc_set_error("bc_hmc_small_begin: bad argument (context, rows, weights, row_ptr, start and inv_mass are required)");
-    return BC_INVALID_ARGUMENT;
-  }
+  if (!ctx || !rows || !w || !row_ptr || !start || !inv_mass)
+    BC_REFUSE("bc_hmc_small_begin: bad argument (context, rows, weights, row_ptr, start and inv_mass are required)");
   int64_t max_n = 0;
   int rc = check_batch(ctx, row_ptr, n_problems, d, c, "bc_hmc_small_begin", &max_n);
   if (rc) return rc;
-  if (n_leapfrog < 1 || n_iter < 1) {
-    bc_set_error("bc_hmc_small_begin: needs n_leapfrog >= 1 and n_iter >= 1 (n_leapfrog = %d, n_iter = %lld)", n_leapfrog, (long long)n_iter);
-    return BC_INVALID_ARGUMENT;
-  }
+  if (n_leapfrog < 1 || n_iter < 1)
+    BC_REFUSE("bc_hmc_small_begin: needs n_leapfrog >= 1 and n_iter >= 1 (n_leapfrog = %d, n_iter = %lld)", n_leapfrog, (long long)n_iter);
   for (size_t k = 0; k < (size_t)n_problems * d; ++k)
-    if (!(inv_mass[k] > 0.) || !std::isfinite(inv_mass[k])) {
-      bc_set_error("bc_hmc_small_begin: inv_mass[%zu][%zu] = %g is not finite and positive", k / d, k % d, inv_mass[k]);
-      return BC_INVALID_ARGUMENT;
-    }
+    if (!(inv_mass[k] > 0.) || !std::isfinite(inv_mass[k]))
+      BC_REFUSE("bc_hmc_small_begin: inv_mass[%zu][%zu] = %g is not finite and positive", k / d, k % d, inv_mass[k]);
   rc = bc_ctx_refuse_busy(ctx, "bc_hmc_small_begin", BC_HOLD_ALL, BC_HOLD_HMC_SMALL);
   if (rc) return rc;
   BC_HIP(hipSetDevice(ctx->device));
@@ -366,35 +346,23 @@ extern "C" int bc_hmc_small_begin(bc_ctx* ctx, const double* rows, const double*
   rc = launch(ctx, h, a);
   if (rc) return rc;
   h->a.n_leapfrog = n_leapfrog;
-  h->n_iter = n_iter;
-  h->done = 0;
-  h->clock.ms = 0.;
   h->pending_k = 0;
-  h->active = true;
-  h->chunk_pending = false;
+  bc_run_opened(h, n_iter);
   return BC_OK;
 }
 
 extern "C" int bc_hmc_small_chunk_begin(bc_ctx* ctx, const double* normals, const double* log_u, int64_t problem_stride, int32_t k,
                                         const double* step) {
   bc_hmc_small* h = ctx ? ctx->hmc_small : nullptr;
-  if (!h || !h->active || !normals || !log_u || !step || k <= 0) { bc_set_error("bc_hmc_small_chunk_begin: bad argument, or no run is open"); return BC_INVALID_ARGUMENT; }
-  if (h->chunk_pending) { bc_set_error("bc_hmc_small_chunk_begin: a chunk is pending (call bc_hmc_small_chunk_end first)"); return BC_INVALID_ARGUMENT; }
-  if (h->done + (int64_t)k > h->n_iter) {
-    bc_set_error("bc_hmc_small_chunk_begin: %d iterations after %lld exceed the run's %lld", k, (long long)h->done, (long long)h->n_iter);
-    return BC_INVALID_ARGUMENT;
-  }
+  int rc = bc_run_admit(h, HMC_SMALL_RUN, normals && log_u && step, k);
+  if (rc) return rc;
   const size_t P = (size_t)h->n_problems, c = (size_t)h->a.c, d = (size_t)h->a.d;
   const size_t kcd = (size_t)k * c * d, kc = (size_t)k * c;
-  if (problem_stride != 0 && (problem_stride < 0 || (size_t)problem_stride < kcd)) {
-    bc_set_error("bc_hmc_small_chunk_begin: problem_stride must be 0 or at least k C D = %zu, got %lld", kcd, (long long)problem_stride);
-    return BC_INVALID_ARGUMENT;
-  }
+  if (problem_stride != 0 && (problem_stride < 0 || (size_t)problem_stride < kcd))
+    BC_REFUSE("bc_hmc_small_chunk_begin: problem_stride must be 0 or at least k C D = %zu, got %lld", kcd, (long long)problem_stride);
   for (size_t p = 0; p < P; ++p)
-    if (!(step[p] > 0.) || !std::isfinite(step[p])) {
-      bc_set_error("bc_hmc_small_chunk_begin: step[%zu] = %g is not finite and positive", p, step[p]);
-      return BC_INVALID_ARGUMENT;
-    }
+    if (!(step[p] > 0.) || !std::isfinite(step[p]))
+      BC_REFUSE("bc_hmc_small_chunk_begin: step[%zu] = %g is not finite and positive", p, step[p]);
   // ---- nothing of this chunk has been enqueued up to here
   BC_HIP(hipSetDevice(ctx->device));
   const bool shared = problem_stride == 0;
@@ -405,7 +373,7 @@ extern "C" int bc_hmc_small_chunk_begin(bc_ctx* ctx, const double* normals, cons
   out.take(P * kcd);
   h->o_l = out.take(P * kc);
   h->o_a = out.take((P * kc + 1) / 2);      // (ints)
-  int rc = bc_stage_reserve(ctx, &h->stage, need);
+  rc = bc_stage_reserve(ctx, &h->stage, need);
   if (!rc) rc = bc_scratch_grow(ctx, &h->out, out.total);
   if (rc) return rc;
   double* pin = h->stage.pin.p;
@@ -441,26 +409,16 @@ extern "C" int bc_hmc_small_chunk_begin(bc_ctx* ctx, const double* normals, cons
 // the chunk end behind both headers.  out_samples may be null only for `who` = bc_score_chunk_end; out_correct / out_ll: both or neither
 static int chunk_end(bc_ctx* ctx, bc_hmc_small* h, double* out_samples, double* out_logjoint, int32_t* out_accept, int32_t* out_status,
                      int32_t* out_correct, double* out_ll) {
-  h->chunk_pending = false;
   h->scored = false;
-  BC_HIP(hipSetDevice(ctx->device));
-  BC_HIP(hipStreamSynchronize(ctx->stream));
+  const int rc = bc_run_wait_chunk(ctx, h);
+  if (rc) return rc;
   const size_t P = (size_t)h->n_problems, c = (size_t)h->a.c, d = (size_t)h->a.d;
   std::vector<int> flag(P);
   BC_HIP(hipMemcpy(flag.data(), h->a.flag, P * sizeof(int), hipMemcpyDeviceToHost));
-  h->clock.collect();
   const size_t kc = (size_t)h->pending_k * c, kcd = kc * d;
   const int* acc_dev = reinterpret_cast<const int*>(h->out.p + h->o_a);
   const int* cor_dev = out_ll ? reinterpret_cast<const int*>(h->score.p + bc_even(P * kc)) : nullptr;
-  // runs of consecutive unmarked problems are copied together (one run of all P when nothing is marked)
-  size_t p = 0;
-  while (p < P) {
-    if (flag[p] != 0) {
-      out_status[p++] = BC_NUMERICAL_PRECISION;
-      continue;
-    }
-    size_t q = p;
-    while (q < P && flag[q] == 0) out_status[q++] = BC_OK;
+  return bc_batch_unmarked_runs(flag.data(), P, out_status, [&](size_t p, size_t q) {
     if (out_samples) BC_HIP(hipMemcpy(out_samples + p * kcd, h->out.p + p * kcd, (q - p) * kcd * sizeof(double), hipMemcpyDeviceToHost));
     BC_HIP(hipMemcpy(out_logjoint + p * kc, h->out.p + h->o_l + p * kc, (q - p) * kc * sizeof(double), hipMemcpyDeviceToHost));
     BC_HIP(hipMemcpy(out_accept + p * kc, acc_dev + p * kc, (q - p) * kc * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -468,23 +426,23 @@ static int chunk_end(bc_ctx* ctx, bc_hmc_small* h, double* out_samples, double* 
       BC_HIP(hipMemcpy(out_ll + p * kc, h->score.p + p * kc, (q - p) * kc * sizeof(double), hipMemcpyDeviceToHost));
       BC_HIP(hipMemcpy(out_correct + p * kc, cor_dev + p * kc, (q - p) * kc * sizeof(int32_t), hipMemcpyDeviceToHost));
     }
-    p = q;
-  }
-  return BC_OK;
+    return BC_OK;
+  });
 }
 
 extern "C" int bc_hmc_small_chunk_end(bc_ctx* ctx, double* out_samples, double* out_logjoint, int32_t* out_accept, int32_t* out_status) {
   bc_hmc_small* h = ctx ? ctx->hmc_small : nullptr;
-  if (!h || !h->active || !h->chunk_pending) { bc_set_error("bc_hmc_small_chunk_end: no chunk is pending"); return BC_INVALID_ARGUMENT; }
+  const int rc = bc_run_pending(h, "bc_hmc_small_chunk_end");
+  if (rc) return rc;
   // (checked first: the chunk stays pending, a second call with the outputs can still fetch it)
-  if (!out_samples || !out_logjoint || !out_accept || !out_status) { bc_set_error("bc_hmc_small_chunk_end: the four outputs are required"); return BC_INVALID_ARGUMENT; }
+  if (!out_samples || !out_logjoint || !out_accept || !out_status) BC_REFUSE("bc_hmc_small_chunk_end: the four outputs are required");
   return chunk_end(ctx, h, out_samples, out_logjoint, out_accept, out_status, nullptr, nullptr);
 }
 
 // ---- include/beta_cores_score.h: the held-out scores of the pending chunk, computed where its samples lie (k_lr_score, bc_score.hip)
 extern "C" int bc_score_chunk(bc_ctx* ctx, const bc_data* zt, const bc_data* yt) {
   bc_hmc_small* h = ctx ? ctx->hmc_small : nullptr;
-  if (!h || !h->active || !h->chunk_pending) { bc_set_error("bc_score_chunk: no chunk of a batched small-problem run is pending"); return BC_INVALID_ARGUMENT; }
+  if (!h || !h->active || !h->chunk_pending) BC_REFUSE("bc_score_chunk: no chunk of a batched small-problem run is pending");
   const int64_t t = (int64_t)h->n_problems * h->pending_k * h->a.c;
   int rc = bc_score_check(ctx, zt, yt, t, h->a.d, "bc_score_chunk");
   if (rc) return rc;
@@ -501,28 +459,23 @@ extern "C" int bc_score_chunk(bc_ctx* ctx, const bc_data* zt, const bc_data* yt)
 extern "C" int bc_score_chunk_end(bc_ctx* ctx, double* out_samples, double* out_logjoint, int32_t* out_accept, int32_t* out_status,
                                   int32_t* out_correct, double* out_ll) {
   bc_hmc_small* h = ctx ? ctx->hmc_small : nullptr;
-  if (!h || !h->active || !h->chunk_pending) { bc_set_error("bc_score_chunk_end: no chunk is pending"); return BC_INVALID_ARGUMENT; }
+  const int rc = bc_run_pending(h, "bc_score_chunk_end");
+  if (rc) return rc;
   // (checked first: the chunk stays pending, a second call -- of either chunk end -- can still fetch it)
-  if (!out_logjoint || !out_accept || !out_status) { bc_set_error("bc_score_chunk_end: log-joints, accept flags and status are required"); return BC_INVALID_ARGUMENT; }
-  if ((out_correct == nullptr) != (out_ll == nullptr)) { bc_set_error("bc_score_chunk_end: out_correct and out_ll are given together or not at all"); return BC_INVALID_ARGUMENT; }
-  if (out_ll && !h->scored) { bc_set_error("bc_score_chunk_end: no score was enqueued for this chunk (call bc_score_chunk first)"); return BC_INVALID_ARGUMENT; }
+  if (!out_logjoint || !out_accept || !out_status) BC_REFUSE("bc_score_chunk_end: log-joints, accept flags and status are required");
+  if ((out_correct == nullptr) != (out_ll == nullptr)) BC_REFUSE("bc_score_chunk_end: out_correct and out_ll are given together or not at all");
+  if (out_ll && !h->scored) BC_REFUSE("bc_score_chunk_end: no score was enqueued for this chunk (call bc_score_chunk first)");
   return chunk_end(ctx, h, out_samples, out_logjoint, out_accept, out_status, out_correct, out_ll);
 }
 
 extern "C" int bc_hmc_small_end(bc_ctx* ctx) {
   bc_hmc_small* h = ctx ? ctx->hmc_small : nullptr;
-  if (!h || !h->active) { bc_set_error("bc_hmc_small_end: no run is open"); return BC_INVALID_ARGUMENT; }
-  BC_HIP(hipSetDevice(ctx->device));
-  const bool pending = h->chunk_pending;
-  h->active = false;
-  h->chunk_pending = false;
-  h->scored = false;
-  if (pending) BC_HIP(hipStreamSynchronize(ctx->stream));      // abandoned mid-chunk: nothing may outlive the run's buffers
-  return BC_OK;
+  bool pending = false;
+  const int rc = bc_run_end(ctx, h, HMC_SMALL_RUN, &pending);
+  if (!rc) h->scored = false;
+  return rc;
 }
 
 extern "C" int bc_hmc_small_device_ms(bc_ctx* ctx, double* out_ms) {
-  if (!ctx || !out_ms) { bc_set_error("bc_hmc_small_device_ms: bad argument"); return BC_INVALID_ARGUMENT; }
-  *out_ms = ctx->hmc_small ? ctx->hmc_small->clock.ms : 0.;
-  return BC_OK;
+  return bc_device_ms("bc_hmc_small_device_ms", ctx, ctx && ctx->hmc_small ? &ctx->hmc_small->clock : nullptr, out_ms);
 }

@@ -8,6 +8,7 @@
 #include <vector>
 #include "../../include/beta_cores.h"
 #include "bc_layout.h"
+#include "bc_run.h"
 
 #define BC_WAVE 64
 #define BC_TILE BC_LAY_TILE           // rows per Phi tile: bc_layout.h's value, which the public header states to callers
@@ -22,6 +23,8 @@ int bc_hip_fail(hipError_t e, const char* what, const char* file, int line);
     hipError_t _e = (call);                                                 \
     if (_e != hipSuccess) return bc_hip_fail(_e, #call, __FILE__, __LINE__); \
   } while (0)
+// a refusal before anything is touched: the message (printf style), then BC_INVALID_ARGUMENT
+#define BC_REFUSE(...) do { bc_set_error(__VA_ARGS__); return BC_INVALID_ARGUMENT; } while (0)
 
 struct bc_timer {
   std::vector<hipEvent_t> start, stop;
@@ -39,7 +42,7 @@ struct bc_scratch {
   size_t cap = 0;                // doubles
 };
 
-// ---- what the chunked device runs share (bc_viopt.hip, bc_hmc.hip, bc_hmc_small.hip; the functions are in bc_core.hip)
+// ---- what the chunked device runs share (bc_viopt.hip, bc_hmc.hip, bc_hmc_small.hip, bc_psvi_many.hip; the functions are in bc_core.hip)
 // the pinned twin of bc_scratch: grow-only host memory, contents not kept when it grows
 struct bc_pinned {
   double* p = nullptr;
@@ -61,6 +64,18 @@ struct bc_run_clock {
   void collect();                // after the stream has been synchronised; an elapsed time that cannot be read is left out
   void free();
 };
+// a chunked run as its unit's state embeds it: the protocol's state (bc_run.h) and the clock of its chunks
+struct bc_run : bc_run_state {
+  bc_run_clock clock;
+};
+// the tail of every _begin: a fresh run of `total`, its clock at 0
+inline void bc_run_opened(bc_run* r, int64_t total) { bc_run_open(r, total); r->clock.ms = 0.; }
+// _chunk_end, after bc_run_pending: the chunk is no longer pending; sets the device, waits for the stream, collects the clock
+int bc_run_wait_chunk(struct bc_ctx* ctx, bc_run* r);
+// _end: refuses where no run is open; otherwise closes it (bc_run_close) and waits for a chunk that was abandoned
+int bc_run_end(struct bc_ctx* ctx, bc_run* r, const bc_run_kind& kd, bool* was_pending);
+// the body of every *_device_ms (`clock`: null where the unit has no state on the context yet)
+int bc_device_ms(const char* who, const struct bc_ctx* ctx, const bc_run_clock* clock, double* out_ms);
 
 // phases of bc_vi_gradient, timed with HIP events when the context's timing is on (bc_ctx_phase_times)
 #define BC_VI_PHASES 5           // upload (Theta, coreset rows, w) | K1 of the coreset rows | K1 over the data rows (store-free) |
@@ -175,6 +190,11 @@ int bc_stage_reserve(bc_ctx* ctx, bc_stage* st, size_t doubles);   // both halve
 void bc_scratch_free(bc_scratch* s);
 void bc_pinned_free(bc_pinned* s);
 void bc_stage_free(bc_stage* st);
+// A step chunk's draws into `st`, one transfer: n_e normals ([k][S][D]), then, where n_sub > 0, the int64 row numbers
+// [k][n_sub] of the steps first_step .. first_step + k - 1, each checked against [0, n_rows).  An index out of range is
+// BC_INVALID_ARGUMENT with nothing enqueued.  *e_dev / *idx_dev: where they lie on the device.
+int bc_stage_step_chunk(bc_ctx* ctx, bc_stage* st, const char* who, const double* normals, size_t n_e, const int64_t* sub_idx, size_t k,
+                        size_t n_sub, int64_t first_step, int64_t n_rows, const double** e_dev, const long long** idx_dev);
 
 int bc_timer_begin(bc_ctx* ctx, int which);
 int bc_gram_no_y(bc_ctx* ctx, const bc_data* data, const double* w_dev, double** out_dev);   // bc_gram.hip

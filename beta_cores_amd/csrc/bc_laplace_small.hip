@@ -18,6 +18,7 @@
 #include "bc_internal.h"
 #include "bc_vi_laplace_dev.h"
 #include "bc_slab.h"
+#include "bc_batch.h"
 #include "../../include/beta_cores_laplace_small.h"
 #include <cstring>
 #include <vector>
@@ -120,8 +121,6 @@ void bc_laplace_small_free(bc_ctx* ctx) {
   ctx->laplace_small = nullptr;
 }
 
-#define LM_REFUSE(...) do { bc_set_error(__VA_ARGS__); return BC_INVALID_ARGUMENT; } while (0)
-
 extern "C" int bc_laplace_small(bc_ctx* ctx, const double* rows, const double* w, const int64_t* row_ptr, int32_t n_problems, int32_t d,
                                 const double* start, int32_t diag, const double* normals, int64_t problem_stride, int32_t s,
                                 const bc_data* zt, const bc_data* yt, double* out_mu, double* out_hdiag, double* out_value,
@@ -129,37 +128,32 @@ extern "C" int bc_laplace_small(bc_ctx* ctx, const double* rows, const double* w
                                 int32_t* out_correct, double* out_ll) {
   const char* who = "bc_laplace_small";
   if (!ctx || !rows || !w || !row_ptr || !out_mu || !out_hdiag || !out_value || !out_counts || !out_status)
-    LM_REFUSE("%s: bad argument (context, rows, weights, row_ptr, out_mu, out_hdiag, out_value, out_counts and out_status are required)", who);
-  if (n_problems < 1) LM_REFUSE("%s: needs at least one problem, got %d", who, n_problems);
-  if (d < 1 || d > BC_LAPLACE_SMALL_MAX_DIM) LM_REFUSE("%s: rows must have 1 .. %d columns, got %d", who, BC_LAPLACE_SMALL_MAX_DIM, d);
-  if (s < 0 || s > BC_LAPLACE_SMALL_MAX_DRAWS) LM_REFUSE("%s: 0 .. %d draws per problem are served, got %d", who, BC_LAPLACE_SMALL_MAX_DRAWS, s);
-  if (diag != 0 && diag != 1) LM_REFUSE("%s: diag must be 0 or 1, got %d", who, diag);
-  if ((normals == nullptr) != (s == 0)) LM_REFUSE("%s: normals are given exactly when s >= 1 (s = %d)", who, s);
+    BC_REFUSE("%s: bad argument (context, rows, weights, row_ptr, out_mu, out_hdiag, out_value, out_counts and out_status are required)", who);
+  if (n_problems < 1) BC_REFUSE("%s: needs at least one problem, got %d", who, n_problems);
+  if (d < 1 || d > BC_LAPLACE_SMALL_MAX_DIM) BC_REFUSE("%s: rows must have 1 .. %d columns, got %d", who, BC_LAPLACE_SMALL_MAX_DIM, d);
+  if (s < 0 || s > BC_LAPLACE_SMALL_MAX_DRAWS) BC_REFUSE("%s: 0 .. %d draws per problem are served, got %d", who, BC_LAPLACE_SMALL_MAX_DRAWS, s);
+  if (diag != 0 && diag != 1) BC_REFUSE("%s: diag must be 0 or 1, got %d", who, diag);
+  if ((normals == nullptr) != (s == 0)) BC_REFUSE("%s: normals are given exactly when s >= 1 (s = %d)", who, s);
   const size_t sd = (size_t)s * d;
   if (problem_stride != 0 && (problem_stride < 0 || (size_t)problem_stride < sd))
-    LM_REFUSE("%s: problem_stride must be 0 or at least s D = %zu, got %lld", who, sd, (long long)problem_stride);
-  if ((out_chol == nullptr) != (out_inv == nullptr)) LM_REFUSE("%s: out_chol and out_inv are given together or not at all", who);
-  if (diag && out_chol) LM_REFUSE("%s: the diagonal form has no factors (out_chol and out_inv must be NULL with diag)", who);
-  if ((zt == nullptr) != (yt == nullptr)) LM_REFUSE("%s: the held-out rows and labels are given together or not at all", who);
+    BC_REFUSE("%s: problem_stride must be 0 or at least s D = %zu, got %lld", who, sd, (long long)problem_stride);
+  if ((out_chol == nullptr) != (out_inv == nullptr)) BC_REFUSE("%s: out_chol and out_inv are given together or not at all", who);
+  if (diag && out_chol) BC_REFUSE("%s: the diagonal form has no factors (out_chol and out_inv must be NULL with diag)", who);
+  if ((zt == nullptr) != (yt == nullptr)) BC_REFUSE("%s: the held-out rows and labels are given together or not at all", who);
   if ((out_correct == nullptr) != (out_ll == nullptr) || (out_ll != nullptr) != (zt != nullptr))
-    LM_REFUSE("%s: out_correct and out_ll are given exactly when the held-out rows and labels are", who);
-  if (row_ptr[0] != 0) LM_REFUSE("%s: row_ptr[0] must be 0, got %lld", who, (long long)row_ptr[0]);
-  for (int32_t p = 0; p < n_problems; ++p) {
-    const int64_t n = row_ptr[p + 1] - row_ptr[p];
-    if (n < 1)
-      LM_REFUSE("%s: row_ptr must increase strictly (every problem has at least one row): row_ptr[%d] = %lld, row_ptr[%d] = %lld", who, p,
-                (long long)row_ptr[p], p + 1, (long long)row_ptr[p + 1]);
-    if (n > (int64_t)1 << 24) LM_REFUSE("%s: problem %d has %lld rows, at most 2^24 are served", who, p, (long long)n);
-  }
+    BC_REFUSE("%s: out_correct and out_ll are given exactly when the held-out rows and labels are", who);
+  int64_t max_n = 0;
+  int rc = bc_batch_walk(who, row_ptr, n_problems, (int64_t)1 << 24, "rows", &max_n);
+  if (rc) return rc;
   const size_t P = (size_t)n_problems, n_all = (size_t)row_ptr[P], t = P * (size_t)s;
   if (zt) {
-    if (s < 1) LM_REFUSE("%s: scoring needs at least one draw per problem (s = 0)", who);
-    const int rc = bc_score_check(ctx, zt, yt, (int64_t)t, d, who);
+    if (s < 1) BC_REFUSE("%s: scoring needs at least one draw per problem (s = 0)", who);
+    rc = bc_score_check(ctx, zt, yt, (int64_t)t, d, who);
     if (rc) return rc;
   }
   const size_t lds = (size_t)BC_VIL_WS_DOUBLES(d) * sizeof(double);
-  if (lds > (size_t)ctx->max_lds) LM_REFUSE("%s: D = %d needs %zu bytes of LDS, a block has %d", who, d, lds, ctx->max_lds);
-  int rc = bc_ctx_refuse_busy(ctx, who, BC_HOLD_ALL);
+  if (lds > (size_t)ctx->max_lds) BC_REFUSE("%s: D = %d needs %zu bytes of LDS, a block has %d", who, d, lds, ctx->max_lds);
+  rc = bc_ctx_refuse_busy(ctx, who, BC_HOLD_ALL);
   if (rc) return rc;
   // ---- nothing has been enqueued, allocated or written up to here
   BC_HIP(hipSetDevice(ctx->device));
@@ -228,16 +222,8 @@ extern "C" int bc_laplace_small(bc_ctx* ctx, const double* rows, const double* w
   h->clock.collect();
   std::vector<int> flag(P);
   BC_HIP(hipMemcpy(flag.data(), a.flag, P * sizeof(int), hipMemcpyDeviceToHost));
-  // runs of consecutive unmarked problems are copied together (one run of all P when nothing is marked)
   const size_t dd = (size_t)d * d;
-  size_t p = 0;
-  while (p < P) {
-    if (flag[p] != 0) {
-      out_status[p++] = BC_NUMERICAL_PRECISION;
-      continue;
-    }
-    size_t q = p;
-    while (q < P && flag[q] == 0) out_status[q++] = BC_OK;
+  return bc_batch_unmarked_runs(flag.data(), P, out_status, [&](size_t p, size_t q) {
     const size_t k = q - p;
     BC_HIP(hipMemcpy(out_mu + p * d, a.mu + p * d, k * d * sizeof(double), hipMemcpyDeviceToHost));
     BC_HIP(hipMemcpy(out_hdiag + p * d, a.hdiag + p * d, k * d * sizeof(double), hipMemcpyDeviceToHost));
@@ -252,13 +238,10 @@ extern "C" int bc_laplace_small(bc_ctx* ctx, const double* rows, const double* w
       BC_HIP(hipMemcpy(out_ll + p * s, h->score.p + p * s, k * s * sizeof(double), hipMemcpyDeviceToHost));
       BC_HIP(hipMemcpy(out_correct + p * s, cor_dev + p * s, k * s * sizeof(int32_t), hipMemcpyDeviceToHost));
     }
-    p = q;
-  }
-  return BC_OK;
+    return BC_OK;
+  });
 }
 
 extern "C" int bc_laplace_small_device_ms(bc_ctx* ctx, double* out_ms) {
-  if (!ctx || !out_ms) { bc_set_error("bc_laplace_small_device_ms: bad argument"); return BC_INVALID_ARGUMENT; }
-  *out_ms = ctx->laplace_small ? ctx->laplace_small->clock.ms : 0.;
-  return BC_OK;
+  return bc_device_ms("bc_laplace_small_device_ms", ctx, ctx && ctx->laplace_small ? &ctx->laplace_small->clock : nullptr, out_ms);
 }

@@ -24,6 +24,7 @@
 #include "bc_psvi_dev.h"
 #include "bc_psvi_many_dev.h"
 #include "bc_slab.h"
+#include "bc_batch.h"
 #include "../../include/beta_cores_psvi_many.h"
 #include "../../include/beta_cores_psvi_curve.h"
 #include <cmath>
@@ -305,19 +306,19 @@ static PmLayout pm_layout(size_t R, size_t P, size_t d, size_t s, size_t tiles, 
   return l;
 }
 
-struct bc_psvi_many {
+static const bc_run_kind PSVI_MANY_RUN = {"bc_psvi_many", "steps"};
+struct bc_psvi_many : bc_run {    // (the run in progress: active, chunk_pending, failed, done of total steps, the clock)
   bc_scratch dev;                 // the slab of pm_layout
   bc_pinned pin;                  // the mirror of the uploaded head; later the landing area of _end
   bc_stage stage;                 // a chunk's draws: normals [k][S][D], then indices [k][n_sub]
   bc_scratch sub;                 // the step's gathered rows
   bc_scratch par;                 // Gaussian kind: Sig0inv | b0 | Siginv (constant over the run; not part of the work space)
-  bc_run_clock clock;
-  bool active = false, chunk_pending = false, failed = false, lds_set = false, laid_out = false;
+  bool lds_set = false, laid_out = false;
   const bc_data* data = nullptr;
   PmRun run;
   PmLayout lay;
   size_t R = 0, P = 0;
-  int max_m = 0, done = 0;
+  int max_m = 0;
   std::vector<int64_t> row_ptr;
   std::vector<int> flag;          // the marks as the last _chunk_end saw them
 };
@@ -337,8 +338,6 @@ void bc_psvi_many_free(bc_ctx* ctx) {
   ctx->psvi_many = nullptr;
 }
 
-#define PM_REFUSE(...) do { bc_set_error(__VA_ARGS__); return BC_INVALID_ARGUMENT; } while (0)
-
 extern "C" int64_t bc_psvi_curve_work_doubles(int64_t total_points, int32_t n_problems, int32_t d, int32_t s, int64_t n_sub,
                                                   int32_t opt_itrs, int sampler_kind) {
   if (sampler_kind != BC_VI_SAMPLER_LOGISTIC && sampler_kind != BC_VI_SAMPLER_GAUSS) return -1;
@@ -356,10 +355,7 @@ extern "C" int64_t bc_psvi_many_work_doubles(int64_t total_points, int32_t n_pro
 }
 
 extern "C" int bc_psvi_many_auto_chunk(int32_t s, int32_t d, int64_t n_sub) {
-  if (s <= 0 || d <= 0 || n_sub < 0) return 1;
-  const double per_step = 8. * ((double)s * (double)d + (double)n_sub);
-  const double k = floor((double)BC_VI_STAGE_BYTES / per_step);
-  return k < 1. ? 1 : k > 1048576. ? 1048576 : (int)k;
+  return bc_vi_optimize_auto_chunk(s, d, n_sub);      // (the same staged draws per step: normals [S][D] and n_sub row numbers)
 }
 
 static int pm_begin(const char* who, bc_ctx* ctx, const bc_data* data, int model, int sampler_kind, int32_t diag, const double* pts,
@@ -367,67 +363,62 @@ static int pm_begin(const char* who, bc_ctx* ctx, const bc_data* data, int model
                     const double* steps, const double* moments, int64_t n_sub, double sum_scaling, const double* model_params,
                     int32_t n_model_params, const double* sampler_params, int32_t n_sampler_params) {
   if (!ctx || !data || !pts || !w0 || !row_ptr || !steps || !moments)
-    PM_REFUSE("%s: bad argument (context, data, pts, w0, row_ptr, steps and moments are required)", who);
+    BC_REFUSE("%s: bad argument (context, data, pts, w0, row_ptr, steps and moments are required)", who);
   const bool gauss = model == BC_MODEL_GAUSS_LL && sampler_kind == BC_VI_SAMPLER_GAUSS;
   if (!gauss) {
     if (model == BC_MODEL_GAUSS_LL)
-      PM_REFUSE("%s: the Gaussian location model (BC_MODEL_GAUSS_LL) goes with the Gaussian posterior sampler (BC_VI_SAMPLER_GAUSS), "
+      BC_REFUSE("%s: the Gaussian location model (BC_MODEL_GAUSS_LL) goes with the Gaussian posterior sampler (BC_VI_SAMPLER_GAUSS), "
                 "got kind %d", who, sampler_kind);
     if (model != BC_MODEL_LOGISTIC_LL)
-      PM_REFUSE("%s: only the logistic log-likelihood (BC_MODEL_LOGISTIC_LL) is served, got model %d: the linear-regression and "
+      BC_REFUSE("%s: only the logistic log-likelihood (BC_MODEL_LOGISTIC_LL) is served, got model %d: the linear-regression and "
                 "Gaussian-location kinds take the loop of single builds", who, model);
     if (sampler_kind != BC_VI_SAMPLER_LOGISTIC)
-      PM_REFUSE("%s: only the logistic Laplace sampler (BC_VI_SAMPLER_LOGISTIC, Newton search) is served, got kind %d", who, sampler_kind);
-    if (diag != 0 && diag != 1) PM_REFUSE("%s: diag must be 0 or 1, got %d", who, diag);
+      BC_REFUSE("%s: only the logistic Laplace sampler (BC_VI_SAMPLER_LOGISTIC, Newton search) is served, got kind %d", who, sampler_kind);
+    if (diag != 0 && diag != 1) BC_REFUSE("%s: diag must be 0 or 1, got %d", who, diag);
     if (n_model_params != 0 || n_sampler_params != 0)
-      PM_REFUSE("%s: the logistic kind takes no model or sampler parameters (start and diag are arguments), got %d and %d", who,
+      BC_REFUSE("%s: the logistic kind takes no model or sampler parameters (start and diag are arguments), got %d and %d", who,
                 n_model_params, n_sampler_params);
   } else {
-    if (diag != 0) PM_REFUSE("%s: the Gaussian kind draws with the full covariance only: diag must be 0, got %d", who, diag);
-    if (start) PM_REFUSE("%s: the Gaussian kind's posterior is a closed form: start must be NULL", who);
+    if (diag != 0) BC_REFUSE("%s: the Gaussian kind draws with the full covariance only: diag must be 0, got %d", who, diag);
+    if (start) BC_REFUSE("%s: the Gaussian kind's posterior is a closed form: start must be NULL", who);
     if (!model_params || !sampler_params || n_model_params < 2 || n_sampler_params < 3)
-      PM_REFUSE("%s: the Gaussian kind needs model_params {logdetSig, Siginv} and sampler_params mu0 | Sig0inv | Siginv", who);
+      BC_REFUSE("%s: the Gaussian kind needs model_params {logdetSig, Siginv} and sampler_params mu0 | Sig0inv | Siginv", who);
   }
-  if (n_sub == 0) PM_REFUSE("%s: n_sub = 0 (all rows every step) is not served: every problem has its own Theta", who);
-  if (s < 1 || s > BC_PSVI_MANY_MAX_SAMPLES) PM_REFUSE("%s: S = %d is outside 1..%d", who, s, BC_PSVI_MANY_MAX_SAMPLES);
-  if (n_sub < 1 || n_sub > BC_PSVI_MANY_MAX_SUB) PM_REFUSE("%s: n_sub = %lld is outside 1..%d", who, (long long)n_sub, BC_PSVI_MANY_MAX_SUB);
-  if (opt_itrs < 1) PM_REFUSE("%s: opt_itrs must be at least 1, got %d", who, opt_itrs);
+  if (n_sub == 0) BC_REFUSE("%s: n_sub = 0 (all rows every step) is not served: every problem has its own Theta", who);
+  if (s < 1 || s > BC_PSVI_MANY_MAX_SAMPLES) BC_REFUSE("%s: S = %d is outside 1..%d", who, s, BC_PSVI_MANY_MAX_SAMPLES);
+  if (n_sub < 1 || n_sub > BC_PSVI_MANY_MAX_SUB) BC_REFUSE("%s: n_sub = %lld is outside 1..%d", who, (long long)n_sub, BC_PSVI_MANY_MAX_SUB);
+  if (opt_itrs < 1) BC_REFUSE("%s: opt_itrs must be at least 1, got %d", who, opt_itrs);
   if (n_problems < 1 || n_problems > BC_PSVI_MANY_MAX_PROBLEMS)
-    PM_REFUSE("%s: the number of problems %d is outside 1..%d", who, n_problems, BC_PSVI_MANY_MAX_PROBLEMS);
-  if (row_ptr[0] != 0) PM_REFUSE("%s: row_ptr[0] must be 0, got %lld", who, (long long)row_ptr[0]);
-  int max_m = 0;
-  for (int32_t p = 0; p < n_problems; ++p) {
-    const int64_t n = row_ptr[p + 1] - row_ptr[p];
-    if (n < 1 || n > BC_PSVI_MANY_MAX_POINTS)
-      PM_REFUSE("%s: problem %d has %lld points, 1..%d are served (row_ptr must increase strictly)", who, p, (long long)n, BC_PSVI_MANY_MAX_POINTS);
-    if ((int)n > max_m) max_m = (int)n;
-  }
-  if (!(sum_scaling - sum_scaling == 0.)) PM_REFUSE("%s: sum_scaling is not finite", who);
+    BC_REFUSE("%s: the number of problems %d is outside 1..%d", who, n_problems, BC_PSVI_MANY_MAX_PROBLEMS);
+  int64_t max_m = 0;
+  int rc = bc_batch_walk(who, row_ptr, n_problems, BC_PSVI_MANY_MAX_POINTS, "points", &max_m);
+  if (rc) return rc;
+  if (!(sum_scaling - sum_scaling == 0.)) BC_REFUSE("%s: sum_scaling is not finite", who);
   // (what follows reads the data handle; everything above is decided from the arguments alone)
-  if (data->ctx != ctx) PM_REFUSE("%s: data belongs to another context", who);
+  if (data->ctx != ctx) BC_REFUSE("%s: data belongs to another context", who);
   const int d = data->dz;
-  if (d < 1 || d > BC_VI_MAX_DIM) PM_REFUSE("%s: D = %d is outside 1..%d", who, d, BC_VI_MAX_DIM);
+  if (d < 1 || d > BC_VI_MAX_DIM) BC_REFUSE("%s: D = %d is outside 1..%d", who, d, BC_VI_MAX_DIM);
   const size_t P = (size_t)n_problems, R = (size_t)row_ptr[P], tiles = ((size_t)n_sub + BC_PM_TILE - 1) / BC_PM_TILE;
   const size_t dd = (size_t)d * d;
   double c_model[8] = {0.};
   if (gauss) {
     if ((size_t)n_model_params != 1 + dd || (size_t)n_sampler_params != (size_t)d + 2 * dd)
-      PM_REFUSE("%s: D = %d takes %zu model parameters {logdetSig, Siginv} and %zu sampler parameters mu0 | Sig0inv | Siginv, got %d and %d",
+      BC_REFUSE("%s: D = %d takes %zu model parameters {logdetSig, Siginv} and %zu sampler parameters mu0 | Sig0inv | Siginv, got %d and %d",
                 who, d, 1 + dd, (size_t)d + 2 * dd, n_model_params, n_sampler_params);
     if (memcmp(model_params + 1, sampler_params + d + dd, dd * sizeof(double)) != 0)
-      PM_REFUSE("%s: the sampler's Siginv is not the model's (the doubles must be the same): the draw's Theta' and the tile's "
+      BC_REFUSE("%s: the sampler's Siginv is not the model's (the doubles must be the same): the draw's Theta' and the tile's "
                 "row terms take one matrix", who);
     const double* unused = nullptr;
     if (bc_proj_model_constants(model, model_params, n_model_params, d, c_model, &unused) != BC_OK)
-      PM_REFUSE("%s: bad model parameters", who);
+      BC_REFUSE("%s: bad model parameters", who);
   }
   const PmLayout l = pm_layout(R, P, (size_t)d, (size_t)s, tiles, (size_t)opt_itrs, gauss ? BC_PM_GAUSS : BC_PM_LOGISTIC, (size_t)n_sub);
   if (l.total > (size_t)BC_PSVI_MANY_MAX_WORK_DOUBLES)
-    PM_REFUSE("%s: the run needs %zu doubles of device work space, at most %lld are served (fewer or smaller problems per run)", who,
+    BC_REFUSE("%s: the run needs %zu doubles of device work space, at most %lld are served (fewer or smaller problems per run)", who,
               l.total, (long long)BC_PSVI_MANY_MAX_WORK_DOUBLES);
   const size_t lds_fit = (size_t)(gauss ? BC_VIS_WS_DOUBLES(d) : BC_VIL_WS_DOUBLES(d)) * sizeof(double);
-  if (lds_fit > (size_t)ctx->max_lds) PM_REFUSE("%s: D = %d needs %zu bytes of LDS, the device offers %d", who, d, lds_fit, ctx->max_lds);
-  int rc = bc_ctx_refuse_busy(ctx, who, BC_HOLD_ALL, BC_HOLD_PSVI_MANY);
+  if (lds_fit > (size_t)ctx->max_lds) BC_REFUSE("%s: D = %d needs %zu bytes of LDS, the device offers %d", who, d, lds_fit, ctx->max_lds);
+  rc = bc_ctx_refuse_busy(ctx, who, BC_HOLD_ALL, BC_HOLD_PSVI_MANY);
   if (rc) return rc;
   // ---- nothing has been enqueued, allocated or written up to here
   bc_psvi_many* v = ctx->psvi_many;
@@ -523,27 +514,21 @@ static int pm_begin(const char* who, bc_ctx* ctx, const bc_data* data, int model
   v->lay = l;
   v->R = R;
   v->P = P;
-  v->max_m = max_m;
-  v->done = 0;
+  v->max_m = (int)max_m;
   v->data = data;
   v->row_ptr.assign(row_ptr, row_ptr + P + 1);
   v->flag.assign(P, 0);
-  v->clock.ms = 0.;
   v->laid_out = true;
-  v->active = true;
-  v->chunk_pending = false;
-  v->failed = false;
+  bc_run_opened(v, opt_itrs);
   return BC_OK;
 }
 
 extern "C" int bc_psvi_many_begin(bc_ctx* ctx, const bc_data* data, int model, int sampler_kind, int32_t diag, const double* pts,
                                   const double* w0, const int64_t* row_ptr, int32_t n_problems, const double* start, int32_t s,
                                   int32_t opt_itrs, const double* steps, const double* moments, int64_t n_sub, double sum_scaling) {
-  if (model == BC_MODEL_GAUSS_LL) {      // (this entry has no parameters to give that kind)
-    bc_set_error("bc_psvi_many_begin: only the logistic log-likelihood (BC_MODEL_LOGISTIC_LL) is served, got model %d: the "
-                 "Gaussian-location kind takes bc_psvi_curve_begin", model);
-    return BC_INVALID_ARGUMENT;
-  }
+  if (model == BC_MODEL_GAUSS_LL)      // (this entry has no parameters to give that kind)
+    BC_REFUSE("bc_psvi_many_begin: only the logistic log-likelihood (BC_MODEL_LOGISTIC_LL) is served, got model %d: the "
+              "Gaussian-location kind takes bc_psvi_curve_begin", model);
   return pm_begin("bc_psvi_many_begin", ctx, data, model, sampler_kind, diag, pts, w0, row_ptr, n_problems, start, s, opt_itrs, steps,
                   moments, n_sub, sum_scaling, nullptr, 0, nullptr, 0);
 }
@@ -558,34 +543,17 @@ extern "C" int bc_psvi_curve_begin(bc_ctx* ctx, const bc_data* data, int model, 
 }
 
 extern "C" int bc_psvi_many_chunk_begin(bc_ctx* ctx, const double* normals, const int64_t* sub_idx, int32_t k) {
-  const char* who = "bc_psvi_many_chunk_begin";
   bc_psvi_many* v = ctx ? ctx->psvi_many : nullptr;
-  if (!v || !v->active || !normals || !sub_idx || k <= 0) PM_REFUSE("%s: bad argument, or no run is open", who);
-  if (v->chunk_pending) PM_REFUSE("%s: a chunk is pending (call bc_psvi_many_chunk_end first)", who);
-  if (v->failed) PM_REFUSE("%s: the run has failed (call bc_psvi_many_end)", who);
-  const PmRun& g = v->run;
-  if (v->done + (int64_t)k > g.itrs) PM_REFUSE("%s: %d steps after %d exceed the run's %d", who, k, v->done, g.itrs);
-  const size_t n_sub = (size_t)g.n_sub, n_idx = (size_t)k * n_sub, n_e = (size_t)k * (size_t)g.s * (size_t)g.d;
-  for (size_t j = 0; j < n_idx; ++j)
-    if (sub_idx[j] < 0 || sub_idx[j] >= v->data->n_rows) {
-      v->failed = true;
-      PM_REFUSE("%s: index %lld (step %lld, position %lld) out of range [0,%lld)", who, (long long)sub_idx[j],
-                (long long)(v->done + (int64_t)(j / n_sub)), (long long)(j % n_sub), (long long)v->data->n_rows);
-    }
-  // ---- nothing of this chunk has been enqueued up to here
-  BC_HIP(hipSetDevice(ctx->device));
-  bc_slab sl;
-  sl.take(n_e);
-  const size_t o_idx = sl.take_unpadded(n_idx), need = sl.total;
-  int rc = bc_stage_reserve(ctx, &v->stage, need);
+  int rc = bc_run_admit(v, PSVI_MANY_RUN, normals && sub_idx, k);
   if (rc) return rc;
-  double* pin = v->stage.pin.p;
-  const double* stage_dev = v->stage.dev.p;
-  memcpy(pin, normals, n_e * sizeof(double));
-  long long* hidx = reinterpret_cast<long long*>(pin + o_idx);
-  for (size_t j = 0; j < n_idx; ++j) hidx[j] = (long long)sub_idx[j];
-  BC_HIP(hipMemcpyAsync(v->stage.dev.p, pin, need * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  const long long* didx = reinterpret_cast<const long long*>(stage_dev + o_idx);
+  const PmRun& g = v->run;
+  const size_t n_sub = (size_t)g.n_sub;
+  const double* stage_dev = nullptr;
+  const long long* didx = nullptr;
+  rc = bc_stage_step_chunk(ctx, &v->stage, "bc_psvi_many_chunk_begin", normals, (size_t)k * (size_t)g.s * (size_t)g.d, sub_idx, (size_t)k,
+                           n_sub, v->done, v->data->n_rows, &stage_dev, &didx);
+  if (rc == BC_INVALID_ARGUMENT) v->failed = true;      // (an index out of range spoils this run: only _end is left)
+  if (rc) return rc;
   rc = v->clock.start(ctx->stream);
   if (rc) return rc;
   v->chunk_pending = true;      // from here on something is enqueued: _chunk_end must wait even if a launch below fails
@@ -597,7 +565,7 @@ extern "C" int bc_psvi_many_chunk_begin(bc_ctx* ctx, const double* normals, cons
   const unsigned ra_tiles = (unsigned)g.tiles + (unsigned)((v->R + BC_PM_TILE - 1) / BC_PM_TILE);
   const size_t lds_ra = BC_PM_ROWAUX_DOUBLES(g.d) * sizeof(double);
   for (int t = 0; t < k; ++t) {
-    const int i = v->done + t;
+    const int i = (int)v->done + t;
     rc = bc_take_rows_dev(ctx, v->data, didx + (size_t)t * n_sub, (int64_t)n_sub, v->sub.p);
     if (rc) { v->failed = true; return rc; }
     const double* E = stage_dev + (size_t)t * g.s * g.d;
@@ -622,11 +590,9 @@ extern "C" int bc_psvi_many_chunk_begin(bc_ctx* ctx, const double* normals, cons
 
 extern "C" int bc_psvi_many_chunk_end(bc_ctx* ctx, int32_t* out_marked) {
   bc_psvi_many* v = ctx ? ctx->psvi_many : nullptr;
-  if (!v || !v->active || !v->chunk_pending) PM_REFUSE("bc_psvi_many_chunk_end: no chunk is pending");
-  v->chunk_pending = false;
-  BC_HIP(hipSetDevice(ctx->device));
-  BC_HIP(hipStreamSynchronize(ctx->stream));
-  v->clock.collect();
+  int rc = bc_run_pending(v, "bc_psvi_many_chunk_end");
+  if (!rc) rc = bc_run_wait_chunk(ctx, v);
+  if (rc) return rc;
   BC_HIP(hipMemcpy(v->flag.data(), v->run.flag, v->P * sizeof(int), hipMemcpyDeviceToHost));
   if (out_marked) {
     int32_t n = 0;
@@ -637,19 +603,15 @@ extern "C" int bc_psvi_many_chunk_end(bc_ctx* ctx, int32_t* out_marked) {
 }
 
 extern "C" int bc_psvi_many_end(bc_ctx* ctx, double* out_w, double* out_pts, double* out_modes, int32_t* out_status) {
-  const char* who = "bc_psvi_many_end";
   bc_psvi_many* v = ctx ? ctx->psvi_many : nullptr;
-  if (!v || !v->active) PM_REFUSE("%s: no run is open", who);
-  BC_HIP(hipSetDevice(ctx->device));
-  const bool pending = v->chunk_pending;
-  v->active = false;
-  v->chunk_pending = false;
+  bool pending = false;
+  int rc = bc_run_end(ctx, v, PSVI_MANY_RUN, &pending);
+  if (rc) return rc;
   v->data = nullptr;
-  if (pending) BC_HIP(hipStreamSynchronize(ctx->stream));      // abandoned mid-chunk: nothing may outlive the run's buffers
   if (!out_w && !out_pts && !out_modes && !out_status) return BC_OK;
-  if (!out_w || !out_pts || !out_modes || !out_status) PM_REFUSE("%s: the four outputs are given together or not at all", who);
-  if (v->failed || pending || v->done != v->run.itrs)
-    PM_REFUSE("%s: the run is not complete (%d of %d steps%s): no results", who, v->done, v->run.itrs, v->failed ? ", failed" : "");
+  if (!out_w || !out_pts || !out_modes || !out_status) BC_REFUSE("bc_psvi_many_end: the four outputs are given together or not at all");
+  rc = bc_run_complete(v, PSVI_MANY_RUN, pending, "no results");
+  if (rc) return rc;
   const size_t R = v->R, P = v->P, d = (size_t)v->run.d;
   double* down = v->pin.p;      // w | pts | modes, as _begin sized it
   double *dw = down, *dp = down + bc_even(R), *dm = dp + bc_even(R * d);
@@ -657,21 +619,17 @@ extern "C" int bc_psvi_many_end(bc_ctx* ctx, double* out_w, double* out_pts, dou
   BC_HIP(hipMemcpyAsync(dp, v->run.pts, R * d * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   BC_HIP(hipMemcpyAsync(dm, v->run.mode, P * d * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   BC_HIP(hipStreamSynchronize(ctx->stream));
-  for (size_t p = 0; p < P; ++p) {
-    if (v->flag[p] != 0) { out_status[p] = BC_NUMERICAL_PRECISION; continue; }
-    const size_t r0 = (size_t)v->row_ptr[p], m = (size_t)(v->row_ptr[p + 1] - v->row_ptr[p]);
-    out_status[p] = BC_OK;
+  return bc_batch_unmarked_runs(v->flag.data(), P, out_status, [&](size_t p, size_t q) {
+    const size_t r0 = (size_t)v->row_ptr[p], m = (size_t)v->row_ptr[q] - r0;
     memcpy(out_w + r0, dw + r0, m * sizeof(double));
     memcpy(out_pts + r0 * d, dp + r0 * d, m * d * sizeof(double));
-    memcpy(out_modes + p * d, dm + p * d, d * sizeof(double));
-  }
-  return BC_OK;
+    memcpy(out_modes + p * d, dm + p * d, (q - p) * d * sizeof(double));
+    return BC_OK;
+  });
 }
 
 extern "C" int bc_psvi_many_device_ms(bc_ctx* ctx, double* out_ms) {
-  if (!ctx || !out_ms) PM_REFUSE("bc_psvi_many_device_ms: bad argument");
-  *out_ms = ctx->psvi_many ? ctx->psvi_many->clock.ms : 0.;
-  return BC_OK;
+  return bc_device_ms("bc_psvi_many_device_ms", ctx, ctx && ctx->psvi_many ? &ctx->psvi_many->clock : nullptr, out_ms);
 }
 
 extern "C" int bc_psvi_many_last_step(bc_ctx* ctx, int64_t total_points, int32_t n_problems, int32_t d, int32_t s, double* out_w_before,
@@ -679,13 +637,13 @@ extern "C" int bc_psvi_many_last_step(bc_ctx* ctx, int64_t total_points, int32_t
                                       double* out_gw, double* out_gp, double* out_w, double* out_pts, double* out_mom1_w,
                                       double* out_mom1_p, double* out_mom2_w, double* out_mom2_p, int32_t* out_newton, int32_t* out_flag) {
   const char* who = "bc_psvi_many_last_step";
-  if (!ctx) PM_REFUSE("%s: bad argument", who);
+  if (!ctx) BC_REFUSE("%s: bad argument", who);
   bc_psvi_many* v = ctx->psvi_many;
-  if (!v || !v->laid_out) PM_REFUSE("%s: no run has been begun on this context", who);
-  if (v->chunk_pending) PM_REFUSE("%s: a chunk is pending (call bc_psvi_many_chunk_end first)", who);
+  if (!v || !v->laid_out) BC_REFUSE("%s: no run has been begun on this context", who);
+  if (v->chunk_pending) BC_REFUSE("%s: a chunk is pending (call bc_psvi_many_chunk_end first)", who);
   const PmRun& g = v->run;
   if ((size_t)total_points != v->R || (size_t)n_problems != v->P || d != g.d || s != g.s)
-    PM_REFUSE("%s: the last run had %zu points in %zu problems, D = %d, S = %d, not %lld in %d, D = %d, S = %d", who, v->R, v->P, g.d, g.s,
+    BC_REFUSE("%s: the last run had %zu points in %zu problems, D = %d, S = %d, not %lld in %d, D = %d, S = %d", who, v->R, v->P, g.d, g.s,
               (long long)total_points, n_problems, d, s);
   BC_HIP(hipSetDevice(ctx->device));
   BC_HIP(hipStreamSynchronize(ctx->stream));

@@ -48,15 +48,14 @@ __global__ __launch_bounds__(256) void k_vi_adam(const int* __restrict__ flag, c
   if (trace) trace[(size_t)i * m + j] = x;
 }
 
-struct bc_viopt {
+static const bc_run_kind VIOPT_RUN = {"bc_vi_optimize", "steps"};
+struct bc_viopt : bc_run {        // (the run in progress: active, chunk_pending, failed, done of total steps, the clock)
   bc_scratch dev;                 // one slab: what _begin uploads, then the run's device-only state
   bc_pinned pin;                  // pinned mirror of the uploaded head; later the landing area of w | trace | flag
   bc_stage stage;                 // a chunk's draws: normals [k][S][D], then indices [k][n_sub] (an index takes one double)
   bc_scratch sub;                 // the step's sub-sample of the data rows (their bytes rounded up to whole doubles)
-  bc_run_clock clock;
   bc_vi_plan* plan = nullptr;
-  // the run in progress
-  bool active = false, chunk_pending = false, failed = false, lds_set = false;
+  bool lds_set = false;
   bool laid_out = false;          // va / nrsel describe the slab as the last _begin left it (bc_vi_optimize_last_draw)
   int nrsel = 0;                  // rows of the zero-padded Theta block K1 reads
   const bc_data* data = nullptr;
@@ -65,7 +64,7 @@ struct bc_viopt {
   VilArgs la;                     // (logistic kind; va then only names the Theta block for bc_vi_optimize_last_draw)
   int kind = 0;                   // BC_VI_SAMPLER_* of the run
   int64_t m = 0, n_sub = 0;
-  int32_t s = 0, itrs = 0, done = 0;
+  int32_t s = 0;
   int d = 0, dz = 0;
   double scale = 1.;
   double *d_w = nullptr, *d_mom1 = nullptr, *d_mom2 = nullptr, *d_grad = nullptr, *d_resid = nullptr, *d_step = nullptr, *d_trace = nullptr;
@@ -97,44 +96,30 @@ extern "C" int bc_vi_optimize_auto_chunk(int32_t s, int32_t d, int64_t n_sub) {
 extern "C" int bc_vi_optimize_begin(bc_ctx* ctx, const bc_data* data, const double* core_rows, int64_t m, int model, const double* params,
                                     int32_t n_params, int sampler_kind, const double* sampler_params, int32_t s, const double* w0,
                                     int32_t opt_itrs, const double* step, int64_t n_sub, double sum_scaling, int want_trace) {
-  if (!ctx || !data || !core_rows || !w0 || !step || !sampler_params || (n_params > 0 && !params) || n_params < 0) {
-    bc_set_error("bc_vi_optimize_begin: bad argument");
-    return BC_INVALID_ARGUMENT;
-  }
-  if (data->ctx != ctx) { bc_set_error("bc_vi_optimize_begin: data belongs to another context"); return BC_INVALID_ARGUMENT; }
-  if (m <= 0 || opt_itrs <= 0 || n_sub < 0 || s <= 0 || s > 256) {
-    bc_set_error("bc_vi_optimize_begin: needs m > 0 coreset rows, opt_itrs > 0, n_sub >= 0 and 1 <= S <= 256 (m = %lld, opt_itrs = %d, n_sub = %lld, S = %d)",
-                 (long long)m, opt_itrs, (long long)n_sub, s);
-    return BC_INVALID_ARGUMENT;
-  }
-  if (sampler_kind != BC_VI_SAMPLER_LINREG && sampler_kind != BC_VI_SAMPLER_GAUSS && sampler_kind != BC_VI_SAMPLER_LOGISTIC) {
-    bc_set_error("bc_vi_optimize_begin: unknown sampler kind %d", sampler_kind);
-    return BC_INVALID_ARGUMENT;
-  }
+  if (!ctx || !data || !core_rows || !w0 || !step || !sampler_params || (n_params > 0 && !params) || n_params < 0)
+    BC_REFUSE("bc_vi_optimize_begin: bad argument");
+  if (data->ctx != ctx) BC_REFUSE("bc_vi_optimize_begin: data belongs to another context");
+  if (m <= 0 || opt_itrs <= 0 || n_sub < 0 || s <= 0 || s > 256)
+    BC_REFUSE("bc_vi_optimize_begin: needs m > 0 coreset rows, opt_itrs > 0, n_sub >= 0 and 1 <= S <= 256 (m = %lld, opt_itrs = %d, n_sub = %lld, S = %d)",
+              (long long)m, opt_itrs, (long long)n_sub, s);
+  if (sampler_kind != BC_VI_SAMPLER_LINREG && sampler_kind != BC_VI_SAMPLER_GAUSS && sampler_kind != BC_VI_SAMPLER_LOGISTIC)
+    BC_REFUSE("bc_vi_optimize_begin: unknown sampler kind %d", sampler_kind);
   const bool gauss = sampler_kind == BC_VI_SAMPLER_GAUSS, logistic = sampler_kind == BC_VI_SAMPLER_LOGISTIC;
   const bool model_ok = gauss      ? (model == BC_MODEL_GAUSS_LL || model == BC_MODEL_GAUSS_BETA)
                         : logistic ? (model == BC_MODEL_LOGISTIC_LL || model == BC_MODEL_LOGISTIC_BETA)
                                    : (model == BC_MODEL_LINREG_LL || model == BC_MODEL_LINREG_BETA);
-  if (!model_ok) { bc_set_error("bc_vi_optimize_begin: model %d does not go with sampler kind %d", model, sampler_kind); return BC_INVALID_ARGUMENT; }
+  if (!model_ok) BC_REFUSE("bc_vi_optimize_begin: model %d does not go with sampler kind %d", model, sampler_kind);
   const int dz = data->dz;
   int d = 0, dk = 0, nrsel = 0, ntsel = 0;
-  if (bc_vi_plan_layout(model, s, dz, &d, &dk, &nrsel, &ntsel) != BC_OK || d > BC_VI_MAX_DIM) {
-    bc_set_error("bc_vi_optimize_begin: D = %d is outside 1..%d", d, BC_VI_MAX_DIM);
-    return BC_INVALID_ARGUMENT;
-  }
-  if ((size_t)m * (size_t)(dz + 1) > 60000) {
-    bc_set_error("bc_vi_optimize_begin: coreset of %lld rows x %d exceeds the staging area", (long long)m, dz);
-    return BC_INVALID_ARGUMENT;
-  }
-  if (logistic && !(sampler_params[d] == 0. || sampler_params[d] == 1.)) {
-    bc_set_error("bc_vi_optimize_begin: the diag flag of the logistic sampler must be 0.0 or 1.0");
-    return BC_INVALID_ARGUMENT;
-  }
+  if (bc_vi_plan_layout(model, s, dz, &d, &dk, &nrsel, &ntsel) != BC_OK || d > BC_VI_MAX_DIM)
+    BC_REFUSE("bc_vi_optimize_begin: D = %d is outside 1..%d", d, BC_VI_MAX_DIM);
+  if ((size_t)m * (size_t)(dz + 1) > 60000)
+    BC_REFUSE("bc_vi_optimize_begin: coreset of %lld rows x %d exceeds the staging area", (long long)m, dz);
+  if (logistic && !(sampler_params[d] == 0. || sampler_params[d] == 1.))
+    BC_REFUSE("bc_vi_optimize_begin: the diag flag of the logistic sampler must be 0.0 or 1.0");
   const size_t lds = (size_t)(logistic ? BC_VIL_WS_DOUBLES(d) : BC_VIS_WS_DOUBLES(d)) * sizeof(double);
-  if (lds > (size_t)ctx->max_lds) {
-    bc_set_error("bc_vi_optimize_begin: D = %d needs %zu bytes of LDS, the device offers %d", d, lds, ctx->max_lds);
-    return BC_INVALID_ARGUMENT;
-  }
+  if (lds > (size_t)ctx->max_lds)
+    BC_REFUSE("bc_vi_optimize_begin: D = %d needs %zu bytes of LDS, the device offers %d", d, lds, ctx->max_lds);
   int rc = bc_ctx_refuse_busy(ctx, "bc_vi_optimize_begin", BC_HOLD_ALL, BC_HOLD_VIOPT);
   if (rc) return rc;
   bc_viopt* v = ctx->viopt;
@@ -244,14 +229,11 @@ extern "C" int bc_vi_optimize_begin(bc_ctx* ctx, const bc_data* data, const doub
   v->m = m;
   v->n_sub = n_sub;
   v->s = s;
-  v->itrs = opt_itrs;
-  v->done = 0;
   v->d = d;
   v->dz = dz;
   v->nrsel = nrsel;
   v->laid_out = true;
   v->scale = sum_scaling;
-  v->clock.ms = 0.;
   v->d_w = dev + o_w;
   v->d_step = dev + o_step;
   v->d_mom1 = dev + o_m1;
@@ -260,44 +242,22 @@ extern "C" int bc_vi_optimize_begin(bc_ctx* ctx, const bc_data* data, const doub
   v->d_resid = dev + o_r;
   v->d_trace = want_trace ? dev + o_tr : nullptr;
   v->d_flag = reinterpret_cast<int*>(dev + o_flag);
-  v->active = true;
-  v->chunk_pending = false;
-  v->failed = false;
+  bc_run_opened(v, opt_itrs);
   return BC_OK;
 }
 
 extern "C" int bc_vi_optimize_chunk_begin(bc_ctx* ctx, const double* normals, const int64_t* sub_idx, int32_t k) {
   bc_viopt* v = ctx ? ctx->viopt : nullptr;
-  if (!v || !v->active || !normals || k <= 0) { bc_set_error("bc_vi_optimize_chunk_begin: bad argument, or no run is open"); return BC_INVALID_ARGUMENT; }
-  if (v->chunk_pending) { bc_set_error("bc_vi_optimize_chunk_begin: a chunk is pending (call bc_vi_optimize_chunk_end first)"); return BC_INVALID_ARGUMENT; }
-  if (v->failed) { bc_set_error("bc_vi_optimize_chunk_begin: the run has failed (call bc_vi_optimize_end)"); return BC_INVALID_ARGUMENT; }
-  if (v->done + (int64_t)k > v->itrs) {
-    bc_set_error("bc_vi_optimize_chunk_begin: %d steps after %d exceed the run's %d", k, v->done, v->itrs);
-    return BC_INVALID_ARGUMENT;
-  }
-  const int64_t n_sub = v->n_sub;
-  if ((n_sub > 0) != (sub_idx != nullptr)) { bc_set_error("bc_vi_optimize_chunk_begin: sub_idx must be given exactly when n_sub > 0"); return BC_INVALID_ARGUMENT; }
-  const size_t n_idx = (size_t)k * (size_t)n_sub, n_e = (size_t)k * (size_t)v->s * (size_t)v->d;
-  for (size_t j = 0; j < n_idx; ++j)
-    if (sub_idx[j] < 0 || sub_idx[j] >= v->data->n_rows) {
-      bc_set_error("bc_vi_optimize_chunk_begin: index %lld (step %lld, position %lld) out of range [0,%lld)", (long long)sub_idx[j],
-                   (long long)(v->done + (int64_t)(j / (size_t)n_sub)), (long long)(j % (size_t)n_sub), (long long)v->data->n_rows);
-      return BC_INVALID_ARGUMENT;
-    }
-  // ---- nothing of this chunk has been enqueued up to here
-  BC_HIP(hipSetDevice(ctx->device));
-  bc_slab sl;
-  sl.take(n_e);
-  const size_t o_idx = sl.take_unpadded(n_idx), need = sl.total;      // (the indices are the last piece: not rounded)
-  int rc = bc_stage_reserve(ctx, &v->stage, need);
+  int rc = bc_run_admit(v, VIOPT_RUN, normals != nullptr, k);
   if (rc) return rc;
-  double* pin = v->stage.pin.p;
-  const double* stage_dev = v->stage.dev.p;
-  memcpy(pin, normals, n_e * sizeof(double));
-  long long* hidx = reinterpret_cast<long long*>(pin + o_idx);
-  for (size_t j = 0; j < n_idx; ++j) hidx[j] = (long long)sub_idx[j];
-  BC_HIP(hipMemcpyAsync(v->stage.dev.p, pin, need * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  const long long* didx = reinterpret_cast<const long long*>(stage_dev + o_idx);
+  const int64_t n_sub = v->n_sub;
+  if ((n_sub > 0) != (sub_idx != nullptr)) BC_REFUSE("bc_vi_optimize_chunk_begin: sub_idx must be given exactly when n_sub > 0");
+  const double* stage_dev = nullptr;
+  const long long* didx = nullptr;
+  // (nothing of this chunk is enqueued by a refusal; an index out of range does not fail the run: the next chunk may be given)
+  rc = bc_stage_step_chunk(ctx, &v->stage, "bc_vi_optimize_chunk_begin", normals, (size_t)k * (size_t)v->s * (size_t)v->d, sub_idx, (size_t)k,
+                           (size_t)n_sub, v->done, v->data->n_rows, &stage_dev, &didx);
+  if (rc) return rc;
   rc = v->clock.start(ctx->stream);
   if (rc) return rc;
   v->chunk_pending = true;      // from here on something is enqueued: _chunk_end must wait even if a launch below fails
@@ -306,7 +266,7 @@ extern "C" int bc_vi_optimize_chunk_begin(bc_ctx* ctx, const double* normals, co
   const size_t lds = (size_t)(logistic ? BC_VIL_WS_DOUBLES(v->d) : BC_VIS_WS_DOUBLES(v->d)) * sizeof(double);
   const int m = (int)v->m;
   for (int t = 0; t < k; ++t) {
-    const int i = v->done + t;
+    const int i = (int)v->done + t;
     if (logistic) {
       VilArgs a = v->la;
       a.E = stage_dev + (size_t)t * v->s * v->d;
@@ -326,7 +286,7 @@ extern "C" int bc_vi_optimize_chunk_begin(bc_ctx* ctx, const double* normals, co
     rc = bc_vi_plan_step(ctx, v->plan, &v->core_view, rows, v->d_w, v->scale, v->d_resid, v->d_grad);
     if (rc) return rc;
     hipLaunchKernelGGL(k_vi_adam, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, v->d_flag, v->d_grad, v->d_w, v->d_mom1,
-                       v->d_mom2, m, v->d_step, (int)v->itrs, i, b1, 1. - b1, b2, 1. - b2, eps, v->d_trace);
+                       v->d_mom2, m, v->d_step, (int)v->total, i, b1, 1. - b1, b2, 1. - b2, eps, v->d_trace);
     BC_HIP(hipGetLastError());
   }
   rc = v->clock.stop(ctx->stream);
@@ -337,13 +297,13 @@ extern "C" int bc_vi_optimize_chunk_begin(bc_ctx* ctx, const double* normals, co
 
 extern "C" int bc_vi_optimize_chunk_end(bc_ctx* ctx) {
   bc_viopt* v = ctx ? ctx->viopt : nullptr;
-  if (!v || !v->active || !v->chunk_pending) { bc_set_error("bc_vi_optimize_chunk_end: no chunk is pending"); return BC_INVALID_ARGUMENT; }
-  v->chunk_pending = false;
+  int rc = bc_run_pending(v, "bc_vi_optimize_chunk_end");
+  if (rc) return rc;
   BC_HIP(hipSetDevice(ctx->device));
   int* hflag = reinterpret_cast<int*>(v->pin.p + v->pin.cap - 2);
-  BC_HIP(hipMemcpyAsync(hflag, v->d_flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  BC_HIP(hipStreamSynchronize(ctx->stream));
-  v->clock.collect();
+  BC_HIP(hipMemcpyAsync(hflag, v->d_flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));      // (rides in front of the wait)
+  rc = bc_run_wait_chunk(ctx, v);
+  if (rc) return rc;
   if (*hflag != 0) {
     v->failed = true;
     if (v->kind == BC_VI_SAMPLER_LOGISTIC)
@@ -359,39 +319,32 @@ extern "C" int bc_vi_optimize_chunk_end(bc_ctx* ctx) {
 
 extern "C" int bc_vi_optimize_end(bc_ctx* ctx, double* out_w, double* out_trace) {
   bc_viopt* v = ctx ? ctx->viopt : nullptr;
-  if (!v || !v->active) { bc_set_error("bc_vi_optimize_end: no run is open"); return BC_INVALID_ARGUMENT; }
-  BC_HIP(hipSetDevice(ctx->device));
-  const bool pending = v->chunk_pending;
-  v->active = false;
-  v->chunk_pending = false;
+  bool pending = false;
+  int rc = bc_run_end(ctx, v, VIOPT_RUN, &pending);
+  if (rc) return rc;
   v->data = nullptr;
-  if (pending) BC_HIP(hipStreamSynchronize(ctx->stream));      // abandoned mid-chunk: nothing may outlive the run's buffers
   if (!out_w) return BC_OK;
-  if (v->failed || pending || v->done != v->itrs) {
-    bc_set_error("bc_vi_optimize_end: the run is not complete (%d of %d steps%s): no weights", v->done, v->itrs, v->failed ? ", failed" : "");
-    return BC_INVALID_ARGUMENT;
-  }
-  if (out_trace && !v->d_trace) { bc_set_error("bc_vi_optimize_end: the run was begun without a trace"); return BC_INVALID_ARGUMENT; }
+  rc = bc_run_complete(v, VIOPT_RUN, pending, "no weights");
+  if (rc) return rc;
+  if (out_trace && !v->d_trace) BC_REFUSE("bc_vi_optimize_end: the run was begun without a trace");
   const size_t m = (size_t)v->m;
   double* down = v->pin.p;      // w | trace, as _begin sized it
   BC_HIP(hipMemcpyAsync(down, v->d_w, m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (out_trace) BC_HIP(hipMemcpyAsync(down + bc_even(m), v->d_trace, (size_t)v->itrs * m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (out_trace) BC_HIP(hipMemcpyAsync(down + bc_even(m), v->d_trace, (size_t)v->total * m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   BC_HIP(hipStreamSynchronize(ctx->stream));
   memcpy(out_w, down, m * sizeof(double));
-  if (out_trace) memcpy(out_trace, down + bc_even(m), (size_t)v->itrs * m * sizeof(double));
+  if (out_trace) memcpy(out_trace, down + bc_even(m), (size_t)v->total * m * sizeof(double));
   return BC_OK;
 }
 
 extern "C" int bc_vi_optimize_last_draw(bc_ctx* ctx, int32_t s, int32_t d, double* out_theta, double* out_saux, double* out_raw,
                                         double* out_pad_max) {
-  if (!ctx || !out_theta || !out_pad_max) { bc_set_error("bc_vi_optimize_last_draw: bad argument"); return BC_INVALID_ARGUMENT; }
+  if (!ctx || !out_theta || !out_pad_max) BC_REFUSE("bc_vi_optimize_last_draw: bad argument");
   bc_viopt* v = ctx->viopt;
-  if (!v || !v->laid_out) { bc_set_error("bc_vi_optimize_last_draw: no run has been begun on this context"); return BC_INVALID_ARGUMENT; }
-  if (v->chunk_pending) { bc_set_error("bc_vi_optimize_last_draw: a chunk is pending (call bc_vi_optimize_chunk_end first)"); return BC_INVALID_ARGUMENT; }
-  if (s != v->s || d != v->d) {
-    bc_set_error("bc_vi_optimize_last_draw: the last run had S = %d, D = %d, not S = %d, D = %d", v->s, v->d, s, d);
-    return BC_INVALID_ARGUMENT;
-  }
+  if (!v || !v->laid_out) BC_REFUSE("bc_vi_optimize_last_draw: no run has been begun on this context");
+  if (v->chunk_pending) BC_REFUSE("bc_vi_optimize_last_draw: a chunk is pending (call bc_vi_optimize_chunk_end first)");
+  if (s != v->s || d != v->d)
+    BC_REFUSE("bc_vi_optimize_last_draw: the last run had S = %d, D = %d, not S = %d, D = %d", v->s, v->d, s, d);
   BC_HIP(hipSetDevice(ctx->device));
   const size_t dk = (size_t)v->va.dk, nr = (size_t)v->nrsel, n_th = nr * dk + nr, n_raw = (size_t)s * d;
   std::vector<double> h(n_th + n_raw);      // Theta [nrsel][dk] | saux [nrsel] (contiguous in the slab), then raw [s][d]
@@ -418,12 +371,12 @@ extern "C" int bc_vi_optimize_last_draw(bc_ctx* ctx, int32_t s, int32_t d, doubl
 }
 
 extern "C" int bc_vi_laplace_last_mode(bc_ctx* ctx, int32_t d, double* out_mu, int32_t* out_counts) {
-  if (!ctx || !out_mu || !out_counts) { bc_set_error("bc_vi_laplace_last_mode: bad argument"); return BC_INVALID_ARGUMENT; }
+  if (!ctx || !out_mu || !out_counts) BC_REFUSE("bc_vi_laplace_last_mode: bad argument");
   bc_viopt* v = ctx->viopt;
-  if (!v || !v->laid_out) { bc_set_error("bc_vi_laplace_last_mode: no run has been begun on this context"); return BC_INVALID_ARGUMENT; }
-  if (v->chunk_pending) { bc_set_error("bc_vi_laplace_last_mode: a chunk is pending (call the run's chunk_end first)"); return BC_INVALID_ARGUMENT; }
-  if (v->kind != BC_VI_SAMPLER_LOGISTIC) { bc_set_error("bc_vi_laplace_last_mode: the last run had sampler kind %d, not the logistic one", v->kind); return BC_INVALID_ARGUMENT; }
-  if (d != v->d) { bc_set_error("bc_vi_laplace_last_mode: the last run had D = %d, not D = %d", v->d, d); return BC_INVALID_ARGUMENT; }
+  if (!v || !v->laid_out) BC_REFUSE("bc_vi_laplace_last_mode: no run has been begun on this context");
+  if (v->chunk_pending) BC_REFUSE("bc_vi_laplace_last_mode: a chunk is pending (call the run's chunk_end first)");
+  if (v->kind != BC_VI_SAMPLER_LOGISTIC) BC_REFUSE("bc_vi_laplace_last_mode: the last run had sampler kind %d, not the logistic one", v->kind);
+  if (d != v->d) BC_REFUSE("bc_vi_laplace_last_mode: the last run had D = %d, not D = %d", v->d, d);
   BC_HIP(hipSetDevice(ctx->device));
   int cnt[4] = {0, 0, 0, 0};
   BC_HIP(hipStreamSynchronize(ctx->stream));
@@ -436,24 +389,20 @@ extern "C" int bc_vi_laplace_last_mode(bc_ctx* ctx, int32_t d, double* out_mu, i
 }
 
 extern "C" int bc_vi_optimize_device_ms(bc_ctx* ctx, double* out_ms) {
-  if (!ctx || !out_ms) { bc_set_error("bc_vi_optimize_device_ms: bad argument"); return BC_INVALID_ARGUMENT; }
-  *out_ms = ctx->viopt ? ctx->viopt->clock.ms : 0.;
-  return BC_OK;
+  return bc_device_ms("bc_vi_optimize_device_ms", ctx, ctx && ctx->viopt ? &ctx->viopt->clock : nullptr, out_ms);
 }
 
 extern "C" int bc_vi_optimize(bc_ctx* ctx, const bc_data* data, const double* core_rows, int64_t m, int model, const double* params,
                               int32_t n_params, int sampler_kind, const double* sampler_params, int32_t s, const double* w0,
                               int32_t opt_itrs, const double* step, const double* normals, const int64_t* sub_idx, int64_t n_sub,
                               double sum_scaling, int32_t chunk_steps, double* out_w, double* out_trace) {
-  if (!out_w || !normals || chunk_steps < 0) { bc_set_error("bc_vi_optimize: bad argument"); return BC_INVALID_ARGUMENT; }
-  if (!ctx || !data || n_sub < 0 || (n_sub > 0) != (sub_idx != nullptr)) { bc_set_error("bc_vi_optimize: bad argument"); return BC_INVALID_ARGUMENT; }
+  if (!out_w || !normals || chunk_steps < 0) BC_REFUSE("bc_vi_optimize: bad argument");
+  if (!ctx || !data || n_sub < 0 || (n_sub > 0) != (sub_idx != nullptr)) BC_REFUSE("bc_vi_optimize: bad argument");
   // every index is checked before anything is enqueued (the chunks check theirs again, which costs nothing next to a step)
   for (size_t j = 0; j < (size_t)(opt_itrs > 0 ? opt_itrs : 0) * (size_t)n_sub; ++j)
-    if (sub_idx[j] < 0 || sub_idx[j] >= data->n_rows) {
-      bc_set_error("bc_vi_optimize: index %lld (step %lld, position %lld) out of range [0,%lld)", (long long)sub_idx[j],
-                   (long long)(j / (size_t)n_sub), (long long)(j % (size_t)n_sub), (long long)data->n_rows);
-      return BC_INVALID_ARGUMENT;
-    }
+    if (sub_idx[j] < 0 || sub_idx[j] >= data->n_rows)
+      BC_REFUSE("bc_vi_optimize: index %lld (step %lld, position %lld) out of range [0,%lld)", (long long)sub_idx[j],
+                (long long)(j / (size_t)n_sub), (long long)(j % (size_t)n_sub), (long long)data->n_rows);
   int rc = bc_vi_optimize_begin(ctx, data, core_rows, m, model, params, n_params, sampler_kind, sampler_params, s, w0, opt_itrs, step,
                                 n_sub, sum_scaling, out_trace != nullptr);
   if (rc) return rc;

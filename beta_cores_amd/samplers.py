@@ -13,7 +13,6 @@ enqueueing a gradient on the GPU and waiting for it -- the ~60-120 us of `randn(
 two launches.  The draws come from the same stream in the same order, and a prefetched matrix is always consumed by the very
 next call, so the results and the RNG position after a build are the reference's (tests/test_gpu_storefree.py).
 """
-import ctypes
 
 import numpy as np
 
@@ -21,6 +20,7 @@ import scipy.linalg as sl
 from scipy.optimize import minimize
 
 from . import _native as N
+from ._runs import device_ms, pack_problems
 from .device import DeviceData, _ptr
 from .posterior import HMC_MAX_DIM, check_hmc_problem, gaussian_weighted_post, logistic_newton_pass, small_lapack_scope, weighted_post, _weights_on_device
 
@@ -420,9 +420,7 @@ class _DeviceHMC:
 
     def end(self):
         N.load().bc_hmc_end(self.Z.ctx.h)      # (status ignored: also called to close a failed run)
-        ms = ctypes.c_double()
-        N.call('bc_hmc_device_ms', self.Z.ctx.h, ctypes.byref(ms))
-        return ms.value
+        return device_ms('bc_hmc_device_ms', self.Z.ctx)
 
 
 def hmc_warmup_step(step, accept_fraction, rate=1.0, target=0.8):
@@ -704,9 +702,7 @@ class _DeviceHMCMany:
 
     def __init__(self, ctx, probs):
         self.ctx = ctx
-        self.rows = np.ascontiguousarray(np.concatenate([z for z, _ in probs], axis=0))
-        self.w = np.ascontiguousarray(np.concatenate([w for _, w in probs]))
-        self.row_ptr = np.concatenate(([0], np.cumsum([z.shape[0] for z, _ in probs]))).astype(np.int64)
+        self.rows, self.w, self.row_ptr = pack_problems(probs)
         self.P, self.d = len(probs), probs[0][0].shape[1]
 
     def begin(self, starts, inv_mass, n_leapfrog, n_iter):
@@ -748,9 +744,7 @@ class _DeviceHMCMany:
 
     def end(self):
         N.load().bc_hmc_small_end(self.ctx.h)      # (status ignored: also called to close a failed run)
-        ms = ctypes.c_double()
-        N.call('bc_hmc_small_device_ms', self.ctx.h, ctypes.byref(ms))
-        return ms.value
+        return device_ms('bc_hmc_small_device_ms', self.ctx)
 
 
 class _ManyDraws:
@@ -938,9 +932,7 @@ def logistic_laplace_many(problems, mu0=None, diag=False, n_draws=0, rng=None, d
     if score is not None and (score.ctx is not ctx or score.shape[1] != d):
         raise ValueError('score must hold rows of %d columns on the context of the call' % d)
     diag = bool(diag)
-    rows = np.ascontiguousarray(np.concatenate([z for z, _ in probs], axis=0))
-    w = np.ascontiguousarray(np.concatenate([ww for _, ww in probs]))
-    row_ptr = np.concatenate(([0], np.cumsum([z.shape[0] for z, _ in probs]))).astype(np.int64)
+    rows, w, row_ptr = pack_problems(probs)
     randn = np.random.randn if rng is None else rng.randn
     E, stride = None, 0
     if s > 0 and draws == 'shared':
@@ -964,8 +956,7 @@ def logistic_laplace_many(problems, mu0=None, diag=False, n_draws=0, rng=None, d
     N.call('bc_laplace_small', ctx.h, _ptr(rows), _ptr(w), _ptr(row_ptr), P, d, opt(start), int(diag), opt(E), stride, s,
            None if score is None else score.Z.h, None if score is None else score.Y.h, _ptr(mu), _ptr(hd), _ptr(val), _ptr(cnt),
            _ptr(status), opt(chol), opt(inv), opt(theta), opt(cor), opt(tll))
-    ms = ctypes.c_double()
-    N.call('bc_laplace_small_device_ms', ctx.h, ctypes.byref(ms))
+    ms = device_ms('bc_laplace_small_device_ms', ctx)
     fits, marked = [], []
     for p in range(P):
         if status[p] != 0:
@@ -984,7 +975,7 @@ def logistic_laplace_many(problems, mu0=None, diag=False, n_draws=0, rng=None, d
     if marked and strict:
         raise N.NumericalPrecisionError('logistic_laplace_many: problem(s) %s could not be fitted (a weight, start, value, decrement or '
                                         'pivot that is not finite)' % ', '.join(str(p) for p in marked))
-    return LaplaceManyResult(fits, marked, ms.value)
+    return LaplaceManyResult(fits, marked, ms)
 
 
 def logistic_hmc_many(problems, n_samples=1000, n_chains=16, step_size=0.1, n_leapfrog=8, inv_mass=None, start=None, warmup=0, rng=None,

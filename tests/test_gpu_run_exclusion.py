@@ -1,8 +1,8 @@
 """What may be open on a context at once, and the buffers the chunked device runs keep between runs, through the C ABI
-(bc_vi_optimize_*, bc_hmc_*, bc_hmc_small_*, the fused gradients' _begin / _end).
+(bc_vi_optimize_*, bc_hmc_*, bc_hmc_small_*, bc_psvi_many_*, the fused gradients' _begin / _end).
 
-1. The table of csrc/bc_core.hip (bc_ctx_refuse_busy): with a holder open -- G a pending gradient (csrc/bc_vigrad.hip), V / H / S an open
-   bc_vi_optimize / bc_hmc / bc_hmc_small run -- every entrant is refused with the holder named, or allowed and closed at once;
+1. The table of csrc/bc_core.hip (bc_ctx_refuse_busy): with a holder open -- G a pending gradient (csrc/bc_vigrad.hip), V / H / S / B an open
+   bc_vi_optimize / bc_hmc / bc_hmc_small / bc_psvi_many run -- every entrant is refused with the holder named, or allowed and closed at once;
    the holder then finishes with the bits of the same run on an undisturbed context.
 2. Buffers that grow and are reused at a smaller size: small run, larger run in two chunks, small run again, on one context.
 3. A chunk that is abandoned (_chunk_begin, then _end) leaves the context fit for the next run, and the run's clock running.
@@ -116,6 +116,50 @@ def _opt_run(site, a, chunks=None):
     return _opt_finish(site, a, chunks)
 
 
+def _psvi_case(site, d, s, n_sub, itrs, sizes, seed=171):
+    """A batched BatchPSVI run (logistic kind) on 40 rows of width d resident on the site's context: problem p starts at the first
+    sizes[p] rows with weights 40 / sizes[p]; all problems share each step's normals and row numbers."""
+    rng = np.random.RandomState(seed + d + s + itrs)
+    Z = rng.randn(40, d)
+    i = np.arange(itrs)
+    row_ptr = np.concatenate(([0], np.cumsum(sizes))).astype(np.int64)
+    return dict(Z=Z, dd=site.bc.DeviceData(Z, ctx=site.ctx), pts=np.ascontiguousarray(np.vstack([Z[:m] for m in sizes])),
+                w0=np.concatenate([np.full(m, 40. / m) for m in sizes]), row_ptr=row_ptr, P=len(sizes), d=d, s=s, n_sub=n_sub, itrs=itrs,
+                steps=np.ascontiguousarray(np.tile(0.05 / (1. + i), (len(sizes), 1))),
+                moments=np.ascontiguousarray(np.vstack((1. - 0.9 ** (i + 1), 1. - 0.999 ** (i + 1)))),
+                E=rng.randn(itrs, s, d), idx=rng.randint(40, size=(itrs, n_sub)).astype(np.int64))
+
+
+def _psvi_on(site, a):
+    """The case with its rows resident on another site's context."""
+    return dict(a, dd=site.bc.DeviceData(a['Z'], ctx=site.ctx))
+
+
+def _psvi_begin(site, a):
+    _, lib = _lib()
+    return lib.bc_psvi_many_begin(site.h, a['dd'].h, LOGISTIC_LL, SAMPLER_LOGISTIC, 0, _p(a['pts']), _p(a['w0']), _p(a['row_ptr']), a['P'], None,
+                                  a['s'], a['itrs'], _p(a['steps']), _p(a['moments']), a['n_sub'], 40. / a['n_sub'])
+
+
+def _psvi_finish(site, a, chunks=None):
+    N, lib = _lib()
+    i0 = 0
+    for k in (chunks or [a['itrs']]):
+        assert lib.bc_psvi_many_chunk_begin(site.h, _p(a['E'][i0:i0 + k]), _p(a['idx'][i0:i0 + k]), k) == N.BC_OK, N.last_error()
+        assert lib.bc_psvi_many_chunk_end(site.h, None) == N.BC_OK, N.last_error()
+        i0 += k
+    R = int(a['row_ptr'][-1])
+    w, pts, modes, status = np.full(R, 7.), np.full((R, a['d']), 7.), np.full((a['P'], a['d']), 7.), np.full(a['P'], 7, dtype=np.int32)
+    assert lib.bc_psvi_many_end(site.h, _p(w), _p(pts), _p(modes), _p(status)) == N.BC_OK and not status.any(), (N.last_error(), status)
+    return w, pts, modes
+
+
+def _psvi_run(site, a, chunks=None):
+    N, _ = _lib()
+    assert _psvi_begin(site, a) == N.BC_OK, N.last_error()
+    return _psvi_finish(site, a, chunks)
+
+
 def _same(a, b):
     return len(a) == len(b) and all(np.array_equal(x, y) for x, y in zip(a, b))
 
@@ -123,11 +167,11 @@ def _same(a, b):
 # ------------------------------------------------------------------ 1. the table
 # holder: (the substring every refusal by it carries, the entrants' own wording when they are of its kind)
 HOLDERS = {'G': ('pending', 'already pending'), 'V': ('optimi', 'already open'), 'H': ('bc_hmc_end', 'already open'),
-           'S': ('bc_hmc_small_end', 'already open')}
+           'S': ('bc_hmc_small_end', 'already open'), 'B': ('bc_psvi_many_end', 'already open')}
 # entrant: (its own kind or None, the holders that let it in)
 ENTRANTS = {'bc_vi_gradient_begin': ('G', 'V'), 'bc_vi_beta_gradient_begin': ('G', 'V'), 'bc_psvi_gradient_begin': ('G', 'V'),
-            'bc_vi_optimize_begin': ('V', ''), 'bc_hmc_begin': ('H', ''), 'bc_logistic_logjoint_batch': (None, 'GV'),
-            'bc_hmc_small_begin': ('S', ''), 'bc_hmc_small_logjoint': ('S', '')}
+            'bc_vi_optimize_begin': ('V', ''), 'bc_hmc_begin': ('H', ''), 'bc_logistic_logjoint_batch': (None, 'GVB'),
+            'bc_hmc_small_begin': ('S', ''), 'bc_hmc_small_logjoint': ('S', ''), 'bc_psvi_many_begin': ('B', '')}
 
 
 def _entrants(site, small):
@@ -145,7 +189,8 @@ def _entrants(site, small):
     rows, w, row_ptr, sstart, sim, _ = mc.pack(small)
     P, sc, sd = sstart.shape
     sval, sgrad = np.empty((P, sc)), np.empty((P, sc, sd))
-    keep += [beta, g, r, gp, opt, start, im, val, grad, rows, w, row_ptr, sstart, sim, sval, sgrad]
+    psvi = _psvi_case(site, 3, 2, 5, 1, (1, 2))
+    keep += [beta, g, r, gp, opt, start, im, val, grad, rows, w, row_ptr, sstart, sim, sval, sgrad, psvi]
 
     def closing(st, end):
         if st == N.BC_OK:
@@ -165,6 +210,7 @@ def _entrants(site, small):
         'bc_hmc_small_begin': lambda: closing(
             lib.bc_hmc_small_begin(h, _p(rows), _p(w), _p(row_ptr), P, sd, _p(sstart), sc, _p(sim), 4, 6), lambda: lib.bc_hmc_small_end(h)),
         'bc_hmc_small_logjoint': lambda: lib.bc_hmc_small_logjoint(h, _p(rows), _p(w), _p(row_ptr), P, sd, _p(sstart), sc, _p(sval), _p(sgrad)),
+        'bc_psvi_many_begin': lambda: closing(_psvi_begin(site, psvi), lambda: lib.bc_psvi_many_end(h, None, None, None, None)),
     }
     return calls, keep
 
@@ -174,7 +220,7 @@ def shared_site(bc):
     return _Site(bc)
 
 
-@pytest.mark.parametrize('holder', ['G', 'V', 'H', 'S'])
+@pytest.mark.parametrize('holder', ['G', 'V', 'H', 'S', 'B'])
 def test_the_table(bc, shared_site, holder):
     N, lib = _lib()
     site, fresh = shared_site, _Site(bc)
@@ -210,6 +256,11 @@ def test_the_table(bc, shared_site, holder):
             assert lib.bc_hmc_chunk_begin(site.h, _p(E), _p(U), T, case['eps']) == N.BC_OK, N.last_error()
             assert lib.bc_hmc_chunk_end(site.h, _p(s), _p(lj), _p(acc)) == N.BC_OK and lib.bc_hmc_end(site.h) == N.BC_OK
             return s, lj, acc
+    elif holder == 'B':
+        held = _psvi_case(site, 5, 8, 33, 2, (1, 16, 17))
+        want = _psvi_run(fresh, _psvi_on(fresh, held))
+        assert _psvi_begin(site, held) == N.BC_OK, N.last_error()
+        finish = lambda: _psvi_finish(site, held)
     else:
         want = sum(_small_run(fresh, small), ())
         rows, w, row_ptr, sstart, sim, eps = mc.pack(small)
@@ -250,11 +301,15 @@ def _runs(kind, site):
         a = mc.build_batch('regrow1', 5, (7,), 3, 4, 1, 0.25, 51)['problems']
         b = mc.build_batch('regrow3', 5, (1, 64, 65), 3, 4, 4, 0.25, 52)['problems']
         return (lambda st: sum(_small_run(st, a, [1]), ())), (lambda st: sum(_small_run(st, b, [3, 1]), ()))
+    if kind == 'psvi_many':
+        # the large run: two full 16-row tiles of gathered rows and one row; problems of one tile, one tile exactly, one row over
+        a, b = _psvi_case(site, 3, 2, 5, 1, (1, 2)), _psvi_case(site, 5, 8, 33, 4, (1, 16, 17))
+        return (lambda st: _psvi_run(st, _psvi_on(st, a), [1])), (lambda st: _psvi_run(st, _psvi_on(st, b), [3, 1]))
     a, b = _opt_problem(site, m=3, s=4, itrs=1), _opt_problem(site, m=6, s=8, itrs=4)
     return (lambda st: _opt_run(st, a, [1])), (lambda st: _opt_run(st, b, [3, 1]))
 
 
-@pytest.mark.parametrize('kind', ['hmc', 'hmc_small', 'vi_optimize'])
+@pytest.mark.parametrize('kind', ['hmc', 'hmc_small', 'vi_optimize', 'psvi_many'])
 def test_buffers_that_regrow(bc, kind):
     site = _Site(bc)
     small, large = _runs(kind, site)
@@ -264,7 +319,7 @@ def test_buffers_that_regrow(bc, kind):
 
 
 # ------------------------------------------------------------------ 3. an abandoned chunk
-@pytest.mark.parametrize('kind', ['hmc', 'hmc_small', 'vi_optimize'])
+@pytest.mark.parametrize('kind', ['hmc', 'hmc_small', 'vi_optimize', 'psvi_many'])
 def test_an_abandoned_chunk(bc, kind):
     N, lib = _lib()
     site = _Site(bc)
@@ -286,6 +341,12 @@ def test_an_abandoned_chunk(bc, kind):
         assert lib.bc_hmc_small_begin(h, _p(rows), _p(w), _p(row_ptr), P, d, _p(start), c, _p(im), small[0]['L'], T) == N.BC_OK, N.last_error()
         assert lib.bc_hmc_small_chunk_begin(h, _p(E), _p(U), 0, T, _p(eps)) == N.BC_OK and lib.bc_hmc_small_end(h) == N.BC_OK
         run, clock = (lambda st: sum(_small_run(st, small), ())), lib.bc_hmc_small_device_ms
+    elif kind == 'psvi_many':
+        a = _psvi_case(site, 5, 8, 33, 2, (1, 16, 17))
+        assert _psvi_begin(site, a) == N.BC_OK, N.last_error()
+        assert lib.bc_psvi_many_chunk_begin(h, _p(a['E']), _p(a['idx']), a['itrs']) == N.BC_OK and \
+            lib.bc_psvi_many_end(h, None, None, None, None) == N.BC_OK
+        run, clock = (lambda st: _psvi_run(st, _psvi_on(st, a))), lib.bc_psvi_many_device_ms
     else:
         opt = _opt_problem(site)
         assert _opt_begin(site, opt) == N.BC_OK, N.last_error()
