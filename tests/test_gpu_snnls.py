@@ -216,29 +216,47 @@ PLAIN, ONE_ROUND, ONE_ROUND_RESCORE = 1, 2, 3       # include/beta_cores.h: BC_F
 KNOBS = (None, 'BC_FINISH_NOFUSE', 'BC_FINISH_NOPF')
 
 
-def _build_in_every_form(bc, monkeypatch, alg, phi, steps):
+def _build_in_every_form(bc, monkeypatch, alg, phi, steps, b=None, A=None, state=None, forms=None, run=None):
     """build(steps) under every (BC_PREFILTER, knob) setting -- the environment is read when a solver is created -- and once
-    through the step-wise protocol: [(label, finish form, pre-filter precision, solver)]."""
+    through the step-wise protocol: [(label, finish form, pre-filter precision, solver)].
+    b: the right-hand side (default: the sum of the rows); A: what the solver is given (default phi.T; a resident DevicePhi.T
+    saves the uploads); state = (idx, val): planted with set_sparse_weights() before anything runs, the columns coming from the
+    shard; forms: [(BC_PREFILTER, knob or None, BC_I8_BB)] in place of the full matrix; run(label, solver): in place of
+    build(steps) / build_stepwise(steps) -- the environment is still the form's while it runs, so it may create siblings."""
     s_ = phi.shape[1]
-    b = phi.sum(axis=0)
-    monkeypatch.delenv('BC_I8_BB', raising=False)
-    runs = []
-    for pref in (0, 8) + ((4,) if s_ <= 256 else ()):
-        for knob in KNOBS:
-            monkeypatch.setenv('BC_PREFILTER', str(pref))
-            for k in KNOBS[1:]:
-                monkeypatch.delenv(k, raising=False)
-            if knob:
-                monkeypatch.setenv(knob, '1')
-            sv = _algs(bc)[alg](phi.T, b)
+    b = phi.sum(axis=0) if b is None else b
+    A = phi.T if A is None else A
+    if forms is None:
+        forms = [(pref, knob, False) for pref in (0, 8) + ((4,) if s_ <= 256 else ()) for knob in KNOBS]
+
+    def make(label):
+        sv = _algs(bc)[alg](A, b)
+        if state is not None:
+            sv._eng.set_sparse_weights(state[0], state[1])
+        if run is not None:
+            run(label, sv)
+        elif label == 'step-wise':
+            sv.build_stepwise(steps)
+        else:
             sv.build(steps)
-            runs.append(('BC_PREFILTER=%d %s' % (pref, knob or 'default'), sv._eng.finish_form(), sv._eng.prefilter, sv))
-    for k in KNOBS[1:]:
+        return sv
+
+    runs = []
+    for pref, knob, bb in forms:
+        monkeypatch.setenv('BC_PREFILTER', str(pref))
+        for k in KNOBS[1:] + ('BC_I8_BB',):
+            monkeypatch.delenv(k, raising=False)
+        if knob:
+            monkeypatch.setenv(knob, '1')
+        if bb:
+            monkeypatch.setenv('BC_I8_BB', '1')
+        label = 'BC_PREFILTER=%d %s%s' % (pref, knob or 'default', ' BC_I8_BB=1' if bb else '')
+        sv = make(label)
+        runs.append((label, sv._eng.finish_form(), sv._eng.prefilter, sv))
+    for k in KNOBS[1:] + ('BC_I8_BB',):
         monkeypatch.delenv(k, raising=False)
     monkeypatch.setenv('BC_PREFILTER', '0')
-    sv = _algs(bc)[alg](phi.T, b)
-    sv.build_stepwise(steps)
-    runs.append(('step-wise', 0, 0, sv))
+    runs.append(('step-wise', 0, 0, make('step-wise')))
     return runs
 
 
