@@ -263,6 +263,16 @@ _PSVI_CURVE_SIGNATURES = {
 }
 PSVI_CURVE_EXPORTS = sorted(_PSVI_CURVE_SIGNATURES)
 
+# entry points of the extension header include/beta_cores_diag.h (posterior moments, split-R-hat and ESS of HMC chains on the device)
+_DIAG_SIGNATURES = {
+    'bc_diag_work_doubles': [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64],      # returns an int64 count, not a status
+    'bc_chain_summary': [vp, vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp],
+    'bc_diag_attach': [vp, C.c_int64, C.c_int64],
+    'bc_diag_chunk': [vp],
+    'bc_diag_end': [vp, vp, vp, vp, vp, vp, vp, vp, vp],
+}
+DIAG_EXPORTS = sorted(_DIAG_SIGNATURES)
+
 _lib = None
 
 
@@ -299,10 +309,11 @@ def load():
             + list(_VIOPT_SIGNATURES.items()) + list(_PSVI_SIGNATURES.items()) + list(_VILAPLACE_SIGNATURES.items()) \
             + list(_HMC_SIGNATURES.items()) + list(_HMC_SMALL_SIGNATURES.items()) + list(_SCORE_SIGNATURES.items()) \
             + list(_PREFDIAG_SIGNATURES.items()) + list(_PREDICT_SIGNATURES.items()) + list(_LAPLACE_SMALL_SIGNATURES.items()) \
-            + list(_PSVI_MANY_SIGNATURES.items()) + list(_PSVI_CURVE_SIGNATURES.items()):
+            + list(_PSVI_MANY_SIGNATURES.items()) + list(_PSVI_CURVE_SIGNATURES.items()) + list(_DIAG_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int
+    lib.bc_diag_work_doubles.restype = C.c_int64
     lib.bc_psvi_many_work_doubles.restype = C.c_int64
     lib.bc_psvi_curve_work_doubles.restype = C.c_int64
     lib.bc_version.restype = C.c_int

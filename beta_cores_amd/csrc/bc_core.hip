@@ -126,6 +126,11 @@ void bc_run_clock::free() {
 //   bc_linreg_predict                                                        allow    allow    refuse   refuse   allow
 //   bc_laplace_small (synchronous: holds nothing after it returns)           refuse   refuse   refuse   refuse   refuse
 //   bc_psvi_many_begin                                                       refuse   refuse   refuse   refuse   refuse
+//   bc_chain_summary (synchronous: holds nothing after it returns)           refuse   refuse   refuse   refuse   refuse
+//   bc_diag_end, once its run has been ended (before that the run is its own) refuse   refuse   refuse   -        refuse
+//
+// bc_diag_attach and bc_diag_chunk are calls of an open bc_hmc_small run, like bc_score_chunk: refused unless such a run is open
+// (bc_diag_chunk: unless a chunk of it is pending), whatever else holds the context.
 //
 // An entrant passes the holders of its row that refuse it; they are looked at in the order G, V, H, S, B, and the first one found
 // is named.  Nothing is enqueued, allocated or changed by a refusal.
@@ -221,6 +226,7 @@ extern "C" int bc_ctx_destroy(bc_ctx* ctx) {
   bc_laplace_small_free(ctx);
   bc_psvi_many_free(ctx);
   bc_scratch_free(&ctx->score);
+  bc_scratch_free(&ctx->diag);
   bc_scratch_free(&ctx->predict);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;

@@ -31,6 +31,7 @@
 #include "bc_hmc_small_dev.h"
 #include "bc_slab.h"
 #include "bc_batch.h"
+#include "bc_diag.h"
 #include "../../include/beta_cores_hmc_small.h"
 #include "../../include/beta_cores_score.h"
 #include <cmath>
@@ -156,6 +157,7 @@ struct bc_hmc_small : bc_run {    // (the run in progress: active, chunk_pending
   bc_scratch out;                 // a chunk's results: samples | log-joints | accept flags (ints)
   bc_scratch score;               // a chunk's held-out scores (bc_score_chunk): ll [P k C] | correct [P k C] (ints)
   bool scored = false;            // bc_score_chunk has enqueued the pending chunk's scores
+  bc_diag_attached diag;          // the chain summary attached to the run (bc_diag_attach), and its buffers
   SmArgs a;
   size_t lds = 0;
   int cpb = 1;                    // chains per block of the run's launches
@@ -173,6 +175,8 @@ void bc_hmc_small_free(bc_ctx* ctx) {
   bc_stage_free(&h->stage);
   bc_scratch_free(&h->out);
   bc_scratch_free(&h->score);
+  bc_scratch_free(&h->diag.keep);
+  bc_scratch_free(&h->diag.work);
   h->clock.free();
   delete h;
   ctx->hmc_small = nullptr;
@@ -347,6 +351,7 @@ extern "C" int bc_hmc_small_begin(bc_ctx* ctx, const double* rows, const double*
   if (rc) return rc;
   h->a.n_leapfrog = n_leapfrog;
   h->pending_k = 0;
+  h->diag.on = false;             // (a summary left attached to an earlier run is dropped)
   bc_run_opened(h, n_iter);
   return BC_OK;
 }
@@ -386,6 +391,7 @@ extern "C" int bc_hmc_small_chunk_begin(bc_ctx* ctx, const double* normals, cons
   BC_HIP(hipMemcpyAsync(h->stage.dev.p, pin, need * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   h->chunk_pending = true;      // from here on something is enqueued: _chunk_end must wait even if the launch below fails
   h->scored = false;
+  h->diag.folded = false;
   h->pending_k = k;
   SmArgs a = h->a;
   a.mode = BC_SM_CHUNK;
@@ -466,6 +472,73 @@ extern "C" int bc_score_chunk_end(bc_ctx* ctx, double* out_samples, double* out_
   if ((out_correct == nullptr) != (out_ll == nullptr)) BC_REFUSE("bc_score_chunk_end: out_correct and out_ll are given together or not at all");
   if (out_ll && !h->scored) BC_REFUSE("bc_score_chunk_end: no score was enqueued for this chunk (call bc_score_chunk first)");
   return chunk_end(ctx, h, out_samples, out_logjoint, out_accept, out_status, out_correct, out_ll);
+}
+
+// ---- include/beta_cores_diag.h: the chain summary of the run's kept chunks, retained where they lie (the kernels: bc_diag.hip)
+static bc_diag_shape diag_shape(const bc_hmc_small* h) {
+  bc_diag_shape s;
+  s.p = h->n_problems, s.n = h->diag.n_keep, s.c = h->a.c, s.d = h->a.d, s.max_lag = h->diag.max_lag;
+  return s;
+}
+
+extern "C" int bc_diag_attach(bc_ctx* ctx, int64_t n_keep, int64_t max_lag) {
+  bc_hmc_small* h = ctx ? ctx->hmc_small : nullptr;
+  if (!h || !h->active) BC_REFUSE("bc_diag_attach: no batched small-problem run is open");
+  if (h->diag.on) BC_REFUSE("bc_diag_attach: a summary is already attached to this run");
+  bc_diag_attached& g = h->diag;
+  const int64_t keep0 = g.n_keep, lag0 = g.max_lag;
+  g.n_keep = n_keep, g.max_lag = max_lag;
+  const bc_diag_shape s = diag_shape(h);
+  int rc = bc_diag_check("bc_diag_attach", s);
+  if (!rc) {
+    BC_HIP(hipSetDevice(ctx->device));
+    rc = bc_scratch_grow(ctx, &g.keep, bc_diag_keep_doubles(s));
+  }
+  if (rc) {
+    g.n_keep = keep0, g.max_lag = lag0;
+    return rc;
+  }
+  g.kept = 0;
+  g.folded = false;
+  g.on = true;
+  return BC_OK;
+}
+
+extern "C" int bc_diag_chunk(bc_ctx* ctx) {
+  bc_hmc_small* h = ctx ? ctx->hmc_small : nullptr;
+  if (!h || !h->active || !h->chunk_pending) BC_REFUSE("bc_diag_chunk: no chunk of a batched small-problem run is pending");
+  bc_diag_attached& g = h->diag;
+  if (!g.on) BC_REFUSE("bc_diag_chunk: no summary is attached to this run (call bc_diag_attach first)");
+  if (g.folded) BC_REFUSE("bc_diag_chunk: this chunk has been folded in already");
+  if (g.kept + h->pending_k > g.n_keep)
+    BC_REFUSE("bc_diag_chunk: %d iterations after %lld exceed the summary's %lld", h->pending_k, (long long)g.kept, (long long)g.n_keep);
+  BC_HIP(hipSetDevice(ctx->device));
+  // (the stream orders this behind the chunk's launch and in front of the next chunk's; a marked problem's slice holds no samples:
+  // its summary is never copied)
+  const int rc = bc_diag_keep_launch(ctx, h->out.p, diag_shape(h), h->pending_k, g.kept, g.keep.p);
+  if (rc) return rc;
+  g.kept += h->pending_k;
+  g.folded = true;
+  return BC_OK;
+}
+
+extern "C" int bc_diag_end(bc_ctx* ctx, double* out_mean, double* out_cov, double* out_rhat, double* out_ess, int32_t* out_ess_truncated,
+                           int32_t* out_status, double* out_rho, double* out_moments) {
+  bc_hmc_small* h = ctx ? ctx->hmc_small : nullptr;
+  if (!h || !h->diag.on) BC_REFUSE("bc_diag_end: no summary is attached (call bc_diag_attach on an open batched small-problem run first)");
+  const bc_diag_out out = {out_mean, out_cov, out_rhat, out_ess, out_ess_truncated, out_status, out_rho, out_moments};
+  if (!bc_diag_out_ok(out)) BC_REFUSE("bc_diag_end: mean, cov, rhat, ess, ess_truncated and status are required");
+  bc_diag_attached& g = h->diag;
+  if (h->active && h->chunk_pending) BC_REFUSE("bc_diag_end: a chunk is pending (end it first)");
+  if (g.kept != g.n_keep) BC_REFUSE("bc_diag_end: %lld of %lld iterations have been folded in", (long long)g.kept, (long long)g.n_keep);
+  int rc = bc_ctx_refuse_busy(ctx, "bc_diag_end", BC_HOLD_ALL & ~BC_HOLD_HMC_SMALL);
+  if (rc) return rc;
+  BC_HIP(hipSetDevice(ctx->device));
+  const bc_diag_shape s = diag_shape(h);
+  rc = bc_scratch_grow(ctx, &g.work, bc_diag_run_doubles(s));
+  if (rc) return rc;
+  g.on = false;
+  return bc_diag_run(ctx, g.keep.p, g.work.p, s, h->a.flag, out);
 }
 
 extern "C" int bc_hmc_small_end(bc_ctx* ctx) {

@@ -126,6 +126,7 @@ struct bc_ctx {
   struct bc_lap_small* laplace_small = nullptr;   // bc_laplace_small (bc_laplace_small.hip): the buffers of the batched Laplace fit
   struct bc_psvi_many* psvi_many = nullptr;   // bc_psvi_many_* (bc_psvi_many.hip): the buffers and the state of the batched BatchPSVI run
   bc_scratch score;              // bc_lr_score (bc_score.hip): theta | ll | correct (ints)
+  bc_scratch diag;               // bc_chain_summary (bc_diag.hip): the uploaded samples | the retained layout | the run's work space
   bc_scratch predict;            // bc_linreg_predict (bc_predict.hip): mu | factor | packed factor | noise | scale | partials | ll | sse | mean | var
 };
 

@@ -383,9 +383,10 @@ class HMCResult:
     start, inv_mass: what the run began with; device_ms: GPU milliseconds of the run's chunks (None from a stand-in engine).
     From logistic_hmc_many(score=held) also: correct (n_samples x n_chains: held-out rows predicted correctly by every kept
     position), test_ll (n_samples x n_chains: its summed held-out log-likelihood) and accuracy (held.accuracy(correct)); None
-    otherwise.  samples is None from a run with keep_samples=False."""
+    otherwise.  samples is None from a run with keep_samples=False.  From a run with summary=True also: summary, the
+    ChainSummary of the kept iterations (chain_summary has the definitions); None otherwise."""
 
-    correct = test_ll = accuracy = None
+    correct = test_ll = accuracy = summary = None
 
     def __init__(self, samples, logjoint, accept, step_size, warmup_steps, start, inv_mass, device_ms):
         self.samples, self.logjoint, self.accept = samples, logjoint, accept
@@ -429,7 +430,8 @@ def hmc_warmup_step(step, accept_fraction, rate=1.0, target=0.8):
 
 
 def logistic_hmc(Z, wts=None, n_samples=1000, n_chains=16, step_size=0.1, n_leapfrog=8, inv_mass=None, start=None, warmup=0, rng=None,
-                 ctx=None, comm=None, adapt_every=25, adapt_rate=1.0, chunk=None, engine=None):
+                 ctx=None, comm=None, adapt_every=25, adapt_rate=1.0, chunk=None, engine=None, summary=False, max_lag=None,
+                 summarizer=None):
     """Samples of the logistic posterior of the rows Z = y*x with weights wts under the N(0, I) prior -- the reference's weighted
     log-joint (model_lr.py:88-93; the Stan programs of zellner_logreg/main.py:24-62 with the intercept as a column) -- by plain
     HMC: `n_chains` chains in lock-step, a diagonal inverse mass, a fixed step and `n_leapfrog` leapfrog steps.  Not NUTS, no
@@ -449,6 +451,9 @@ def logistic_hmc(Z, wts=None, n_samples=1000, n_chains=16, step_size=0.1, n_leap
     Draws (NumPy's stream `rng`, or the global one), in this order: the start's normals (start=None only); then per chunk of k
     iterations randn(k, n_chains, D) followed by log(rand(k, n_chains)).  Kept iterations are chunked by `chunk` (None = as many
     as keep the staged draws under 32 MB).
+    summary=True: the result carries `.summary` = chain_summary(result.samples, max_lag) (n_samples >= 4): the samples reach the
+      host anyway.  summarizer: a stand-in `summarizer(samples, max_lag) -> summary` for chain_summary (CPU tests).  Off by
+      default; it changes no draw and no other output.
     Limits: 1 <= n_chains <= 64, D <= 256, one device (comm.world > 1 raises NotImplementedError).
     Returns an HMCResult."""
     if engine is None and not isinstance(Z, DeviceData):
@@ -495,7 +500,10 @@ def logistic_hmc(Z, wts=None, n_samples=1000, n_chains=16, step_size=0.1, n_leap
                                 _ManyDraws(rng, True, 1, c, d, keep=False), c, d, int(n_samples), n_leapfrog, warmup, adapt_every,
                                 adapt_rate, chunk)
     out_s, out_l, out_a, step, warm_steps = res[0]
-    return HMCResult(out_s, out_l, out_a, step, warm_steps, start, inv_mass, ms)
+    result = HMCResult(out_s, out_l, out_a, step, warm_steps, start, inv_mass, ms)
+    if summary:
+        result.summary = summarizer(out_s, max_lag) if summarizer is not None else chain_summary(out_s, max_lag, ctx=getattr(Z, 'ctx', None))
+    return result
 
 
 # ---- held-out scores of many thetas at once (include/beta_cores_score.h)
@@ -657,6 +665,93 @@ def linreg_predictive(held, mu, factor, noise, scale=1.0, per_row=False):
     return PredictiveScores(ll, sse, nt, mean, var)
 
 
+# ---- posterior moments, split-R-hat and ESS of chains on the device (include/beta_cores_diag.h)
+DIAG_MIN_KEPT = 4
+
+
+class ChainSummary:
+    """What chain_summary returns, per problem (a leading axis P where the samples had one): mean [D], cov [D x D] (ddof = 1, over
+    all kept draws of all chains), rhat [D] (split-R-hat: every chain cut into its first and last n // 2 draws), ess [D] (Geyer's
+    initial monotone sequence over the split chains' autocorrelations up to max_lag), ess_truncated [D] (bool: the sum ran into
+    max_lag before a pair of autocorrelations turned non-positive: ess is then an over-estimate) and status (0, or
+    BC_NUMERICAL_PRECISION for a problem with a draw that is not finite or one the sampler had marked: its entries are NaN).
+    rhat and ess are NaN for a coordinate that does not vary; ess is NaN where the first pair is not positive (an antithetic
+    chain).  rho [D x (L + 1)] and moments [D x 2: W, varplus] are test seams (None unless asked for)."""
+
+    def __init__(self, mean, cov, rhat, ess, ess_truncated, status, rho=None, moments=None):
+        self.mean, self.cov, self.rhat, self.ess, self.ess_truncated, self.status = mean, cov, rhat, ess, ess_truncated, status
+        self.rho, self.moments = rho, moments
+
+    def problem(self, j):
+        """Problem j's entry of a batched summary."""
+        opt = [None if a is None else a[j] for a in (self.rho, self.moments)]
+        return ChainSummary(self.mean[j], self.cov[j], self.rhat[j], self.ess[j], self.ess_truncated[j], int(self.status[j]), *opt)
+
+    def worst_rhat(self):
+        """The largest R-hat over the coordinates that vary (NaN if none does)."""
+        r = np.asarray(self.rhat)
+        return float(np.nanmax(r)) if np.any(np.isfinite(r)) else float('nan')
+
+    def least_ess(self):
+        """The smallest ESS over the coordinates that have one (NaN if none has)."""
+        e = np.asarray(self.ess)
+        return float(np.nanmin(e)) if np.any(np.isfinite(e)) else float('nan')
+
+
+def _summary_lag(n, max_lag):
+    """(the max_lag handed to the library, L = the lag it clips to) for n kept iterations; None = every lag, n // 2 - 1"""
+    if n < DIAG_MIN_KEPT:
+        raise ValueError('a summary needs at least %d kept iterations (two per half), got %d' % (DIAG_MIN_KEPT, n))
+    top = n // 2 - 1
+    lag = top if max_lag is None else int(max_lag)
+    if lag < 1:
+        raise ValueError('max_lag must be >= 1, got %r' % (max_lag,))
+    return lag, min(lag, top)
+
+
+class _SummaryArrays:
+    """The host arrays of one summary call (NaN where the library leaves a marked problem's slices alone) and their pointers."""
+
+    def __init__(self, P, d, L, seams):
+        self.mean, self.cov = np.full((P, d), np.nan), np.full((P, d, d), np.nan)
+        self.rhat, self.ess = np.full((P, d), np.nan), np.full((P, d), np.nan)
+        self.trunc, self.status = np.zeros((P, d), dtype=np.int32), np.zeros(P, dtype=np.int32)
+        self.rho = np.full((P, d, L + 1), np.nan) if seams else None
+        self.moments = np.full((P, d, 2), np.nan) if seams else None
+
+    def pointers(self):
+        return [_ptr(a) if a is not None else None
+                for a in (self.mean, self.cov, self.rhat, self.ess, self.trunc, self.status, self.rho, self.moments)]
+
+    def result(self):
+        return ChainSummary(self.mean, self.cov, self.rhat, self.ess, self.trunc != 0, self.status, self.rho, self.moments)
+
+
+def chain_summary(samples, max_lag=None, ctx=None, seams=False):
+    """Posterior mean and covariance, split-R-hat and effective sample size of HMC chains, computed on the device
+    (include/beta_cores_diag.h states the definitions; kernels k_diag_keep, k_diag_seq, k_diag_cov: the covariance on the fp64
+    matrix cores).  samples: n x C x D (kept iterations x chains x coordinates, as HMCResult.samples) or P x n x C x D for P
+    problems at once; n >= 4, C <= 64, D <= 256.  max_lag: the largest autocorrelation lag looked at (None = n // 2 - 1, every
+    lag a half chain has; a larger request is clipped).  A problem's bits do not depend on the others in the batch.
+    seams=True also returns rho and moments (tests).  No CPU fallback.  Returns a ChainSummary."""
+    x = np.asarray(samples, dtype=np.float64)
+    if x.ndim not in (3, 4):
+        raise ValueError('samples must be n x C x D or P x n x C x D, got shape %r' % (x.shape,))
+    one = x.ndim == 3
+    x = np.ascontiguousarray(x[None] if one else x)
+    P, n, c, d = x.shape
+    if P < 1:
+        raise ValueError('needs at least one problem')
+    lag, L = _summary_lag(n, max_lag)
+    if ctx is None:
+        from .device import default_context
+        ctx = default_context()
+    out = _SummaryArrays(P, d, L, seams)
+    N.call('bc_chain_summary', ctx.h, _ptr(x), int(P), int(n), int(c), int(d), int(lag), *out.pointers())
+    res = out.result()
+    return res.problem(0) if one else res
+
+
 # ---- the same for MANY small problems at once: the weighted coresets of an evaluation curve (include/beta_cores_hmc_small.h)
 class HMCManyResult(list):
     """What logistic_hmc_many returns: a list with one HMCResult per problem (None for a marked problem under strict=False).
@@ -722,17 +817,32 @@ class _DeviceHMCMany:
         acc, status = np.zeros((self.P, k, self.c), dtype=np.int32), np.empty(self.P, dtype=np.int32)
         return k, lj, acc, status
 
-    def chunk(self, normals, log_u, steps, shared):
+    def attach_summary(self, n_keep, max_lag):
+        """A chain summary of the run's n_keep kept iterations (include/beta_cores_diag.h): chunks run with fold=True are
+        retained on the device, summary_end() reduces them."""
+        self._lag = _summary_lag(int(n_keep), max_lag)
+        N.call('bc_diag_attach', self.ctx.h, int(n_keep), self._lag[0])
+
+    def summary_end(self, seams=False):
+        out = _SummaryArrays(self.P, self.d, self._lag[1], seams)
+        N.call('bc_diag_end', self.ctx.h, *out.pointers())
+        return out.result()
+
+    def chunk(self, normals, log_u, steps, shared, fold=False):
         k, lj, acc, status = self._begin_chunk(normals, log_u, steps, shared)
+        if fold:
+            N.call('bc_diag_chunk', self.ctx.h)
         s = np.empty((self.P, k, self.c, self.d))
         N.call('bc_hmc_small_chunk_end', self.ctx.h, _ptr(s), _ptr(lj), _ptr(acc), _ptr(status))
         return s, lj, acc, status
 
-    def chunk_scored(self, normals, log_u, steps, shared, held, keep_samples):
+    def chunk_scored(self, normals, log_u, steps, shared, held, keep_samples, fold=False):
         """chunk() with the held-out scores of every position, computed on the device where the chunk's samples lie (k_lr_score):
         (samples or None, logjoint, accept, status, correct, test_ll).  held=None: a warm-up chunk -- nothing is scored and no
-        samples are copied (None for samples, correct and test_ll)."""
+        samples are copied (None for samples, correct and test_ll).  fold: the chunk is retained for the attached summary."""
         k, lj, acc, status = self._begin_chunk(normals, log_u, steps, shared)
+        if fold:
+            N.call('bc_diag_chunk', self.ctx.h)
         s = np.empty((self.P, k, self.c, self.d)) if keep_samples and held is not None else None
         cor = tll = None
         if held is not None:
@@ -774,21 +884,28 @@ class _ManyDraws:
 
 
 def _run_hmc_group(eng, idx, starts, ims, steps0, draws, c, d, n_samples, n_leapfrog, warmup, adapt_every, adapt_rate, chunk, held=None,
-                   keep_samples=True):
+                   keep_samples=True, summaries=None, max_lag=None):
     """The loop of logistic_hmc and logistic_hmc_many -- warm-up chunks with hmc_warmup_step per problem, then the kept chunks at
     frozen steps -- for the problems `idx` of one engine.  Returns ({p: (samples, logjoint, accept, step, warm_steps)}, marked indices, device ms).
     held (with an engine that has chunk_scored): the kept chunks are scored on the device, warm-up chunks are neither scored nor
-    copied, keep_samples=False copies no samples at all (samples is None); the result tuples end with (correct, test_ll)."""
+    copied, keep_samples=False copies no samples at all (samples is None); the result tuples end with (correct, test_ll).
+    summaries (a dict, with an engine that has attach_summary): the kept chunks -- and only those -- are retained on the device in
+    order, and after the last one summaries[p] is problem p's ChainSummary (max_lag as chain_summary's); such a run too can do
+    without the sample copies.  None: exactly the calls of a run without a summary."""
     G = len(idx)
     step = [float(steps0[p]) for p in idx]
     warm = [[] for _ in idx]
     in_run = held is not None and hasattr(eng, 'chunk_scored')
-    keep = keep_samples or not in_run
+    on_dev = summaries is not None and hasattr(eng, 'attach_summary')
+    fold = dict(fold=True) if on_dev else {}
+    keep = keep_samples or not (in_run or on_dev)
     out = [(np.empty((n_samples, c, d)) if keep else None, np.empty((n_samples, c)), np.empty((n_samples, c), dtype=bool)) for _ in idx]
     sc = [(np.empty((n_samples, c), dtype=np.int64), np.empty((n_samples, c))) for _ in idx] if in_run else None
     bad = np.zeros(G, dtype=bool)
     eng.begin(np.ascontiguousarray(starts[idx]), np.ascontiguousarray(ims[idx]), int(n_leapfrog), int(warmup) + int(n_samples))
     try:
+        if on_dev:
+            eng.attach_summary(int(n_samples), max_lag)
         ci, left = 0, int(warmup)
         while left > 0 and not bad.all():
             k = min(left, int(adapt_every))
@@ -809,9 +926,11 @@ def _run_hmc_group(eng, idx, starts, ims, steps0, draws, c, d, n_samples, n_leap
             k = min(n_samples - i0, int(chunk))
             e, u = draws.get(ci, k, idx)
             if in_run:
-                s, lj, acc, status, cor, tll = eng.chunk_scored(e, u, np.array(step), draws.shared, held, keep)
+                s, lj, acc, status, cor, tll = eng.chunk_scored(e, u, np.array(step), draws.shared, held, keep, **fold)
+            elif not keep:      # (a summarised run that keeps no samples and scores nothing: no sample copy, nothing scored)
+                s, lj, acc, status = eng.chunk_scored(e, u, np.array(step), draws.shared, None, False, **fold)[:4]
             else:
-                s, lj, acc, status = eng.chunk(e, u, np.array(step), draws.shared)
+                s, lj, acc, status = eng.chunk(e, u, np.array(step), draws.shared, **fold)
             bad |= status != 0
             for j in range(G):
                 if not bad[j]:
@@ -822,6 +941,9 @@ def _run_hmc_group(eng, idx, starts, ims, steps0, draws, c, d, n_samples, n_leap
                         sc[j][0][i0:i0 + k], sc[j][1][i0:i0 + k] = cor[j], tll[j]
             i0 += k
             ci += 1
+        if on_dev and i0 == n_samples:
+            every = eng.summary_end()
+            summaries.update((p, every.problem(j)) for j, p in enumerate(idx) if not bad[j] and every.status[j] == 0)
     finally:
         ms = eng.end()
     res = {p: out[j] + (step[j], np.array(warm[j])) + (sc[j] if in_run else ()) for j, p in enumerate(idx) if not bad[j]}
@@ -980,7 +1102,7 @@ def logistic_laplace_many(problems, mu0=None, diag=False, n_draws=0, rng=None, d
 
 def logistic_hmc_many(problems, n_samples=1000, n_chains=16, step_size=0.1, n_leapfrog=8, inv_mass=None, start=None, warmup=0, rng=None,
                       draws='shared', adapt_every=25, adapt_rate=1.0, chunk=None, strict=True, ctx=None, engine=None, score=None,
-                      keep_samples=True, scorer=None, laplace='each'):
+                      keep_samples=True, scorer=None, laplace='each', summary=False, summarizer=None, max_lag=None):
     """logistic_hmc for MANY small problems in one batched run: the posteriors of the weighted coresets of an evaluation curve
     (`for m in range(M + 1): sample the coreset of size m` in the logistic drivers).  One thread block per problem and group of
     up to four chains holds the problem's rows in LDS and runs whole chunks of iterations there (k_hmc_small); a chunk is one
@@ -1014,12 +1136,21 @@ def logistic_hmc_many(problems, n_samples=1000, n_chains=16, step_size=0.1, n_le
       samples lie, before anything is copied; warm-up chunks are neither scored nor copied.  A problem on the 'single' route is
       scored by logistic_score on its returned samples after the run.  Both give the bits of
       logistic_score(score, result.pooled()).  None: nothing changes.
-    keep_samples=False (with score): `samples` is None and no chunk's samples are copied -- the largest transfer of a chunk.
+    keep_samples=False (with score or summary): `samples` is None and no chunk's samples are copied -- the largest transfer of a
+      chunk.
+    summary=True: every HMCResult carries `.summary`, the ChainSummary of its kept iterations (posterior mean and covariance,
+      split-R-hat, ESS: chain_summary has the definitions; n_samples >= 4; max_lag as chain_summary's).  On the 'small' route
+      the kept chunks -- never a warm-up chunk -- are retained on the device as they are produced and reduced there after the
+      last one, so it needs no sample on the host; on the 'single' route it is chain_summary of the returned samples.  Both
+      give the bits of chain_summary(result.samples, max_lag).  Off by default: no draw, output or bit of a run changes with it.
     engine: a stand-in `engine(Z_p, wts_p)` per problem with logistic_hmc's engine protocol (CPU tests); scorer: a stand-in
-      `scorer(held, thetas) -> (correct, ll)` for logistic_score (CPU tests).
+      `scorer(held, thetas) -> (correct, ll)` for logistic_score (CPU tests); summarizer: a stand-in
+      `summarizer(samples, max_lag) -> summary` for chain_summary (CPU tests).
     Limits: 1 <= n_chains <= 64, D <= 256, one device.  Returns an HMCManyResult."""
-    if not keep_samples and score is None:
+    if not keep_samples and score is None and not summary:
         raise ValueError('keep_samples=False needs score: nothing would be returned')
+    if summary:
+        _summary_lag(int(n_samples), max_lag)
     if scorer is None:
         scorer = logistic_score
     if draws not in ('shared', 'independent'):
@@ -1091,12 +1222,21 @@ def logistic_hmc_many(problems, n_samples=1000, n_chains=16, step_size=0.1, n_le
     stream = _ManyDraws(rng, shared, P, c, d, keep=len(groups) > 1)
     done, marked, ms_small = {}, [], None
     for eng, idx in groups:
+        sums = {} if summary else None
+        extra = dict(summaries=sums, max_lag=max_lag) if summary else {}
         res, bad, ms = _run_hmc_group(eng, idx, starts, ims, steps0, stream, c, d, int(n_samples), n_leapfrog, warmup, adapt_every,
-                                      adapt_rate, chunk, held=score, keep_samples=keep_samples)
+                                      adapt_rate, chunk, held=score, keep_samples=keep_samples, **extra)
         for p, r in res.items():
             s, lj, acc, step, warm = r[:5]
             done[p] = HMCResult(s, lj, acc, step, warm, starts[p], ims[p], ms)
             done[p].route = 'small' if fits[p] else 'single'
+            if summary:
+                if p in sums:
+                    done[p].summary = sums[p]
+                else:      # (the route that returns its samples anyway)
+                    done[p].summary = summarizer(s, max_lag) if summarizer is not None else chain_summary(s, max_lag, ctx=ctx)
+                    if not keep_samples and score is None:
+                        done[p].samples = None
             if score is not None:
                 if len(r) > 5:
                     cor, tll = r[5:]

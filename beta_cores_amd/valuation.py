@@ -18,7 +18,11 @@ class ShapleyResult:
     """What tmc_shapley returns.  phi: G values (sum of marginals / occurrences; 0 for a group that never occurred);
     occurrences: G counts; values: T x (max_groups + 1), values[t, 0] = 0.5 and values[t, j + 1] the held-out accuracy of the
     first j + 1 groups of permutation t; perms: T x G; n_fallback: how many of the T * max_groups problems did not fit one
-    block's LDS and took logistic_hmc_many's 'single' route."""
+    block's LDS and took logistic_hmc_many's 'single' route.  From tmc_shapley(summary=True) also max_rhat and min_ess, both
+    T x max_groups: the worst split-R-hat and the smallest effective sample size over the coordinates of the posterior behind
+    values[t, j + 1] (samplers.chain_summary has the definitions); None otherwise."""
+
+    max_rhat = min_ess = None
 
     def __init__(self, phi, occurrences, values, perms, n_fallback):
         self.phi, self.occurrences, self.values, self.perms, self.n_fallback = phi, occurrences, values, perms, n_fallback
@@ -32,7 +36,7 @@ def default_perms_per_batch(groups, d, max_groups, group_cap=None):
 
 
 def tmc_shapley(Z, groups, held, n_perms, max_groups, group_cap=None, rng=None, n_samples=64, n_chains=16, warmup=100, start=None,
-                perms_per_batch=None, engine=None, scorer=None, **hmc_kwargs):
+                perms_per_batch=None, engine=None, scorer=None, summary=False, summarizer=None, **hmc_kwargs):
     """Truncated Monte-Carlo Shapley values of the G groups `groups` (sequences of row indices into Z) for the held-out accuracy
     of the logistic posterior (group_selection.py:145-164 -- `update_per_t` and `dshapley` -- not the slice of tmcshapley.py:84,
     which scores the wrong prefix).
@@ -54,7 +58,10 @@ def tmc_shapley(Z, groups, held, n_perms, max_groups, group_cap=None, rng=None, 
       rows under 256 MB (default_perms_per_batch).
     start: C x D for all problems, None = zeros.  n_samples, n_chains, warmup and **hmc_kwargs (step_size, n_leapfrog, inv_mass,
       adapt_every, chunk, ctx, ...) go to logistic_hmc_many.
-    engine, scorer: stand-ins for the HMC engine and the device scorer, as logistic_hmc_many takes them (CPU tests).
+    summary=True: every posterior's chains are summarised on the device where they lie (logistic_hmc_many(summary=True): still
+      no sample is copied) and the result carries max_rhat and min_ess; no value of phi changes with it.
+    engine, scorer, summarizer: stand-ins for the HMC engine, the device scorer and the device summary, as logistic_hmc_many takes
+      them (CPU tests).
     Returns a ShapleyResult."""
     Z = np.ascontiguousarray(np.asarray(Z, dtype=np.float64))
     if Z.ndim != 2:
@@ -89,6 +96,8 @@ def tmc_shapley(Z, groups, held, n_perms, max_groups, group_cap=None, rng=None, 
     values[:, 0] = 0.5
     perms = np.zeros((n_perms, G), dtype=np.int64)
     n_fallback = 0
+    max_rhat, min_ess = (np.full((n_perms, max_groups), np.nan), np.full((n_perms, max_groups), np.nan)) if summary else (None, None)
+    extra = dict(summary=True, summarizer=summarizer) if summary else {}
     for t0 in range(0, n_perms, perms_per_batch):
         t1 = min(n_perms, t0 + perms_per_batch)
         problems = []
@@ -101,12 +110,17 @@ def tmc_shapley(Z, groups, held, n_perms, max_groups, group_cap=None, rng=None, 
                 problems.append((Z[np.concatenate(rows)], None))
         res = samplers.logistic_hmc_many(problems, n_samples=n_samples, n_chains=c, warmup=warmup, start=start,
                                          rng=np.random.RandomState(seed), draws='shared', score=held, keep_samples=False, engine=engine,
-                                         scorer=scorer, **hmc_kwargs)
+                                         scorer=scorer, **extra, **hmc_kwargs)
         n_fallback += len(res.fallback)
         values[t0:t1, 1:] = np.array([r.accuracy for r in res]).reshape(t1 - t0, max_groups)
+        if summary:
+            max_rhat[t0:t1] = np.array([r.summary.worst_rhat() for r in res]).reshape(t1 - t0, max_groups)
+            min_ess[t0:t1] = np.array([r.summary.least_ess() for r in res]).reshape(t1 - t0, max_groups)
     for t in range(n_perms):
         for j in range(max_groups):
             phi[perms[t, j]] += values[t, j + 1] - values[t, j]
             occ[perms[t, j]] += 1
     phi = np.divide(phi, occ, out=np.zeros_like(phi), where=occ != 0)
-    return ShapleyResult(phi, occ, values, perms, n_fallback)
+    out = ShapleyResult(phi, occ, values, perms, n_fallback)
+    out.max_rhat, out.min_ess = max_rhat, min_ess
+    return out

@@ -35,6 +35,7 @@ def main():
     ap.add_argument('--flip', type=float, default=0.3)
     ap.add_argument('--rand-trials', type=int, default=20)
     ap.add_argument('--seed', type=int, default=1)
+    ap.add_argument('--summary', action='store_true', help="the worst split-R-hat and the smallest ESS over all the run's posteriors, reduced on the device")
     a = ap.parse_args()
     rng = np.random.RandomState(a.seed)
     sizes = rng.randint(10, 51, size=a.groups)
@@ -54,11 +55,14 @@ def main():
     hmc = dict(n_samples=64, n_chains=16, warmup=100, step_size=0.1, n_leapfrog=8)
 
     t0 = time.perf_counter()
-    val = bc.valuation.tmc_shapley(Z, groups, held, a.perms, min(a.max_groups, a.groups), group_cap=50, rng=rng, **hmc)
+    val = bc.valuation.tmc_shapley(Z, groups, held, a.perms, min(a.max_groups, a.groups), group_cap=50, rng=rng, summary=a.summary, **hmc)
     t_val = time.perf_counter() - t0
     print('%d groups (%d rows, D = %d), %d flipped; %d permutations x %d prefixes = %d posteriors valued in %.2f s (%d through the '
           'single-problem engine)' % (a.groups, n, a.d, len(flipped), a.perms, val.values.shape[1] - 1, a.perms * (val.values.shape[1] - 1),
                                       t_val, val.n_fallback))
+    if a.summary:
+        print('chains: worst R-hat %.4f, smallest ESS %.0f of %d draws, over all %d posteriors' %
+              (np.nanmax(val.max_rhat), np.nanmin(val.min_ess), hmc['n_samples'] * hmc['n_chains'], val.max_rhat.size))
     order = np.argsort(-val.phi)
     print('Shapley values: flipped groups mean %+.4f, the others mean %+.4f' % (val.phi[flipped].mean(), np.delete(val.phi, flipped).mean()))
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The logistic drivers' evaluation with exact-posterior samples drawn on the GPU.
 
-    python examples/logistic_mcmc_eval.py [--n 200000] [--d 10] [--m 200] [--samples 250] [--chains 16] [--seed 1] [--curve K [--laplace]] [--bpsvi M]
+    python examples/logistic_mcmc_eval.py [--n 200000] [--d 10] [--m 200] [--samples 250] [--chains 16] [--seed 1] [--curve K [--laplace] [--summary]] [--bpsvi M]
 
 The reference's logistic drivers end by drawing ~1 000 posterior samples with MCMC -- of the full data as ground truth
 (examples/common/mcmc.py:21), of the weighted coreset as the thing to judge (zellner_logreg/main.py:225-230) -- and scoring them
@@ -71,6 +71,7 @@ def main():
     ap.add_argument('--proj-dim', type=int, default=200)
     ap.add_argument('--seed', type=int, default=1)
     ap.add_argument('--curve', type=int, default=0, help='score this many nested coreset sizes 0 .. m from one batched call (0: off)')
+    ap.add_argument('--summary', action='store_true', help='with --curve: the worst split-R-hat and the smallest ESS of every coreset size, reduced on the device')
     ap.add_argument('--laplace', action='store_true', help='with --curve: the Laplace posteriors of the same coresets, fitted, drawn and scored on the device')
     ap.add_argument('--bpsvi', type=int, default=0, help='the BatchPSVI pseudo-coresets of sizes 1 .. M from one build_many, Laplace-fitted and sampled in one call each (0: off)')
     ap.add_argument('--bpsvi-itrs', type=int, default=100, help='with --bpsvi: joint ADAM steps on weights and points')
@@ -121,7 +122,7 @@ def main():
               (name, compute_accuracy(Xt, Yt, th), log_likelihood(Zt, th).sum(axis=0).mean(), np.abs((th.mean(axis=0) - mu_t) / sd_t).max()))
     if nested:
         t0 = time.perf_counter()
-        curve = bc.samplers.logistic_hmc_many(nested, rng=rng, **hmc)
+        curve = bc.samplers.logistic_hmc_many(nested, rng=rng, summary=a.summary, **hmc)
         t_curve = time.perf_counter() - t0
         print('curve: %d coreset sizes in one batched call, %.2f s (%.1f ms on the GPU); through the single-problem engine: %s' %
               (len(nested), t_curve, curve.device_ms or 0., curve.fallback or 'none'))
@@ -143,6 +144,9 @@ def main():
             print('m = %-4d points %-4d accuracy %.4f   test log-likelihood %.3f   |mean - truth| / sd: max %.3f   step %.4g' %
                   (m, len(w_m), compute_accuracy(Xt, Yt, th), log_likelihood(Zt, th).sum(axis=0).mean(),
                    np.abs((th.mean(axis=0) - mu_t) / sd_t).max(), res.step_size))
+            if a.summary:      # (can these chains be trusted?  R-hat near 1 and an ESS of hundreds say yes)
+                print('         chains      worst R-hat %.4f   smallest ESS %.0f of %d draws%s' %
+                      (res.summary.worst_rhat(), res.summary.least_ess(), th.shape[0], '   (ESS sum cut at max_lag)' if res.summary.ess_truncated.any() else ''))
             if lap_curve:
                 acc, tll, mu_l, newton = lap_curve[k]
                 print('         laplace     accuracy %.4f   test log-likelihood %.3f   |mode - truth| / sd: max %.3f   Newton steps %d' %
