@@ -273,6 +273,17 @@ _DIAG_SIGNATURES = {
 }
 DIAG_EXPORTS = sorted(_DIAG_SIGNATURES)
 
+# entry points of the extension header include/beta_cores_hmc_adapt.h (the per-chain warm-up of an open batched small-problem run)
+_HMC_ADAPT_SIGNATURES = {
+    'bc_hmc_adapt_plan': [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, vp, vp],
+    'bc_hmc_adapt_begin': [vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32],
+    'bc_hmc_adapt_chunk_begin': [vp, vp, vp, C.c_int64, C.c_int32],
+    'bc_hmc_adapt_chunk_end': [vp, vp, vp, vp, vp, vp, vp],
+    'bc_hmc_adapted_chunk_begin': [vp, vp, vp, C.c_int64, C.c_int32],
+    'bc_hmc_adapt_state': [vp, vp, vp],
+}
+HMC_ADAPT_EXPORTS = sorted(_HMC_ADAPT_SIGNATURES)
+
 _lib = None
 
 
@@ -309,7 +320,8 @@ def load():
             + list(_VIOPT_SIGNATURES.items()) + list(_PSVI_SIGNATURES.items()) + list(_VILAPLACE_SIGNATURES.items()) \
             + list(_HMC_SIGNATURES.items()) + list(_HMC_SMALL_SIGNATURES.items()) + list(_SCORE_SIGNATURES.items()) \
             + list(_PREFDIAG_SIGNATURES.items()) + list(_PREDICT_SIGNATURES.items()) + list(_LAPLACE_SMALL_SIGNATURES.items()) \
-            + list(_PSVI_MANY_SIGNATURES.items()) + list(_PSVI_CURVE_SIGNATURES.items()) + list(_DIAG_SIGNATURES.items()):
+            + list(_PSVI_MANY_SIGNATURES.items()) + list(_PSVI_CURVE_SIGNATURES.items()) + list(_DIAG_SIGNATURES.items()) \
+            + list(_HMC_ADAPT_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int

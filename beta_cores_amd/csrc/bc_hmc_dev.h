@@ -99,6 +99,7 @@ BC_HMC_FN inline void bc_hmc_inner_chain(const double* red, double eps, const do
 
 // The trajectory's end: the last half step of the momentum, H1 and the decision.  Returns 1 (block-uniform) when the proposal
 // is accepted (th, lj, g then hold the proposal's), 0 when it is rejected (they are not written at all).  gp [d], ljp [1]: scratch.
+// ws[2 d + 1] holds H0 - H1 on return (not finite where H1 is not).
 BC_HMC_FN inline int bc_hmc_last_chain(const double* red, double eps, const double* im, int d, double half_d_log_2pi, const double* h0,
                                        double logu, const double* r, const double* thp, double* gp, double* ljp, double* th,
                                        double* lj, double* g, double* ws) {
@@ -116,6 +117,7 @@ BC_HMC_FN inline int bc_hmc_last_chain(const double* red, double eps, const doub
     for (int k = 0; k < d; ++k) kin = fma(ws[k], ws[d + k], kin);
     const double h1 = -*ljp + 0.5 * kin;
     ws[2 * d] = (bc_hmc_finite(h1) && logu < *h0 - h1) ? 1. : 0.;
+    ws[2 * d + 1] = *h0 - h1;      // (handed out in addition, for the warm-up of bc_hmc_adapt_dev.h; thread 0 reads it back)
   }
   BC_HMC_SYNC();
   const int acc = ws[2 * d] != 0.;

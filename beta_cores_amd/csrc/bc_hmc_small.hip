@@ -21,6 +21,14 @@
 //
 // The same kernel serves the start pass (mode BC_SM_INIT: log-joint and gradient at the start, marks a problem whose are not
 // finite) and the pass on its own (BC_SM_PASS: bc_hmc_small_logjoint, the test seam).
+//
+// The per-chain warm-up (include/beta_cores_hmc_adapt.h) is the instantiation AD = 1 of the same kernel; the instantiations
+// AD = 0 are the text they were.  There a chain reads its OWN inverse mass and step: the scalars of bc_hmc_adapt_dev.h stay in
+// registers of thread 0 of the slot, the step of the next iteration is handed to the slot through the fourth scalar of the
+// chain's LDS state (unused otherwise), and the running mean and M2 of the window live in global memory, element k touched by
+// thread k alone, once per iteration.  The flags and coefficients of an iteration come from the plan, the same for every chain,
+// so the one barrier the stage adds per iteration is block-uniform; the LDS layout and the capacity rule are unchanged.  With
+// a.plan = null the launch is a chunk of kept iterations at the chains' frozen steps and masses.
 #define BC_SM_BLOCK 256
 #define BC_HMC_FN __device__
 #define BC_HMC_TID ((int)(threadIdx.x & (BC_SM_BLOCK - 1)))
@@ -29,11 +37,14 @@
 #include "bc_internal.h"
 #include "bc_hmc_dev.h"
 #include "bc_hmc_small_dev.h"
+#include "bc_hmc_adapt_dev.h"
+#include "bc_hmc_adapt_plan.h"
 #include "bc_slab.h"
 #include "bc_batch.h"
 #include "bc_diag.h"
 #include "../../include/beta_cores_hmc_small.h"
 #include "../../include/beta_cores_score.h"
+#include "../../include/beta_cores_hmc_adapt.h"
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -61,9 +72,16 @@ struct SmArgs {
   int* out_a;                   // [P][k][C]
   double half_d_log_2pi;
   int d, c, k, n_leapfrog, mode, value;
+  // ---- the per-chain warm-up (AD = 1 only)
+  double* ad_st;                // [P * C][BC_HMC_ADAPT_STATE]
+  double* ad_im;                // [P * C][d]: the chains' own inverse masses
+  double *ad_mean, *ad_m2;      // [P * C][d]: the window's running mean and M2
+  const double* plan;           // the chunk's [k][4] = eta | sg | zeta | flags, or null: kept iterations at the frozen state
+  double *out_step, *out_alpha; // [P][k][C]
+  double delta, log10;
 };
 
-template <int CPB>
+template <int CPB, int AD = 0>
 __global__ __launch_bounds__(CPB * BC_SM_BLOCK) void k_hmc_small(SmArgs a) {
   extern __shared__ double sm_lds[];
   const int tid = BC_HMC_TID, nt = BC_HMC_NT, slot = threadIdx.x / BC_SM_BLOCK;
@@ -101,12 +119,18 @@ __global__ __launch_bounds__(CPB * BC_SM_BLOCK) void k_hmc_small(SmArgs a) {
     th[k] = a.theta[o + k];
     if (a.mode == BC_SM_CHUNK) {
       g[k] = a.g[o + k];
-      im[k] = a.im[(size_t)p * d + k];
+      im[k] = AD ? a.ad_im[o + k] : a.im[(size_t)p * d + k];
     }
   }
   if (tid == 0) {
     red[0] = 0.;
     sc[0] = a.mode == BC_SM_CHUNK ? a.lj[bid] : 0.;
+  }
+  bc_hmc_adapt_scalars st = {0., 0., 0., 0., 0., 0.};      // thread 0's; t and nw, which follow the plan, in every thread
+  if (AD) {
+    const double* sg = a.ad_st + (size_t)bid * BC_HMC_ADAPT_STATE;
+    st.x = sg[0], st.xbar = sg[1], st.hbar = sg[2], st.mu = sg[3], st.t = sg[4], st.nw = sg[5];
+    if (tid == 0) sc[3] = bc_hmc_adapt_exp(a.plan ? st.x : bc_hmc_adapt_frozen_log_step(st.x, st.xbar, st.t));
   }
   BC_HMC_SYNC();
   if (a.mode != BC_SM_CHUNK) {
@@ -119,7 +143,7 @@ __global__ __launch_bounds__(CPB * BC_SM_BLOCK) void k_hmc_small(SmArgs a) {
     }
     return;
   }
-  const double eps = a.step[p];
+  double eps = AD ? sc[3] : a.step[p];
   const double* __restrict__ en = a.e + (size_t)p * a.e_stride;
   const double* __restrict__ un = a.logu + (size_t)p * a.u_stride;
   const size_t ob = (size_t)p * a.k * a.c;
@@ -140,12 +164,42 @@ __global__ __launch_bounds__(CPB * BC_SM_BLOCK) void k_hmc_small(SmArgs a) {
       a.out_l[ob + tc] = sc[0];
       a.out_a[ob + tc] = acc;
     }
+    if (AD && a.plan) {      // the adaptation stage (block-uniform: the plan and the chunk decide)
+      const double* pl = a.plan + 4 * (size_t)t;
+      const int fl = (int)pl[3];
+      st.t += 1.;
+      if (tid == 0) {
+        const double alpha = bc_hmc_adapt_alpha(ws[2 * d + 1]);
+        a.out_step[ob + tc] = eps;
+        a.out_alpha[ob + tc] = alpha;
+        bc_hmc_adapt_step_size(alpha, a.delta, pl[0], pl[1], pl[2], &st);
+      }
+      if (fl & BC_HMC_ADAPT_FOLD) {
+        st.nw += 1.;
+        bc_hmc_adapt_fold(th, d, st.nw, a.ad_mean + o, a.ad_m2 + o);
+      }
+      if (fl & BC_HMC_ADAPT_WEND) {
+        bc_hmc_adapt_window_end(d, st.nw, a.ad_mean + o, a.ad_m2 + o, im);
+        st.t = st.nw = 0.;
+        if (tid == 0) bc_hmc_adapt_restart(a.log10, &st);
+      }
+      if (tid == 0) sc[3] = bc_hmc_adapt_exp(st.x);
+      BC_HMC_SYNC();      // (the next step and a new inverse mass are read by the whole slot)
+      eps = sc[3];
+    }
   }
   for (int k = tid; k < d; k += nt) {
     a.theta[o + k] = th[k];
     a.g[o + k] = g[k];
+    if (AD && a.plan) a.ad_im[o + k] = im[k];
   }
-  if (tid == 0) a.lj[bid] = sc[0];
+  if (tid == 0) {
+    a.lj[bid] = sc[0];
+    if (AD && a.plan) {
+      double* sg = a.ad_st + (size_t)bid * BC_HMC_ADAPT_STATE;
+      sg[0] = st.x, sg[1] = st.xbar, sg[2] = st.hbar, sg[3] = st.mu, sg[4] = st.t, sg[5] = st.nw;
+    }
+  }
 }
 
 // ------------------------------------------------------------------ host side
@@ -163,6 +217,13 @@ struct bc_hmc_small : bc_run {    // (the run in progress: active, chunk_pending
   int cpb = 1;                    // chains per block of the run's launches
   int32_t n_problems = 0, pending_k = 0;
   size_t o_l = 0, o_a = 0;        // where the pending chunk's log-joints and accept flags begin in `out` (set by _chunk_begin)
+  // ---- the per-chain warm-up (include/beta_cores_hmc_adapt.h)
+  bc_scratch adapt;               // per chain: scalars [BC_HMC_ADAPT_STATE] | inverse mass [d] | mean [d] | M2 [d]
+  std::vector<double> plan;       // [warm_total][4] = eta | sg | zeta | flags
+  bool adapt_on = false;          // bc_hmc_adapt_begin has been called on this run
+  bool pending_adapt = false;     // the pending chunk is a warm-up chunk: its steps and alphas lie behind the accept flags
+  int32_t warm_total = 0, warm_done = 0;
+  size_t o_st = 0, o_al = 0;      // where they begin in `out`
 };
 
 bool bc_hmc_small_active(const bc_ctx* ctx) { return ctx->hmc_small && ctx->hmc_small->active; }
@@ -177,6 +238,7 @@ void bc_hmc_small_free(bc_ctx* ctx) {
   bc_scratch_free(&h->score);
   bc_scratch_free(&h->diag.keep);
   bc_scratch_free(&h->diag.work);
+  bc_scratch_free(&h->adapt);
   h->clock.free();
   delete h;
   ctx->hmc_small = nullptr;
@@ -190,6 +252,11 @@ static size_t lds_doubles(int64_t n, int d, int cpb = 1) {
 static const void* kernel_of(int cpb) {
   return cpb == 4 ? reinterpret_cast<const void*>(&k_hmc_small<4>)
                   : cpb == 2 ? reinterpret_cast<const void*>(&k_hmc_small<2>) : reinterpret_cast<const void*>(&k_hmc_small<1>);
+}
+
+static const void* adapt_kernel_of(int cpb) {
+  return cpb == 4 ? reinterpret_cast<const void*>(&k_hmc_small<4, 1>)
+                  : cpb == 2 ? reinterpret_cast<const void*>(&k_hmc_small<2, 1>) : reinterpret_cast<const void*>(&k_hmc_small<1, 1>);
 }
 
 // Chains per block: of 1, 2, 4 (divisors of c whose block fits the LDS for the largest problem) the smallest that keeps the most
@@ -292,9 +359,13 @@ static int stage_batch(bc_ctx* ctx, bc_hmc_small* h, const double* rows, const d
   return BC_OK;
 }
 
-static int launch(bc_ctx* ctx, const bc_hmc_small* h, const SmArgs& a) {
+static int launch(bc_ctx* ctx, const bc_hmc_small* h, const SmArgs& a, bool adapt = false) {
   const dim3 grid((unsigned)((size_t)h->n_problems * (a.c / h->cpb))), block(h->cpb * BC_SM_BLOCK);
-  if (h->cpb == 4) hipLaunchKernelGGL(k_hmc_small<4>, grid, block, h->lds, ctx->stream, a);
+  if (adapt) {
+    if (h->cpb == 4) hipLaunchKernelGGL((k_hmc_small<4, 1>), grid, block, h->lds, ctx->stream, a);
+    else if (h->cpb == 2) hipLaunchKernelGGL((k_hmc_small<2, 1>), grid, block, h->lds, ctx->stream, a);
+    else hipLaunchKernelGGL((k_hmc_small<1, 1>), grid, block, h->lds, ctx->stream, a);
+  } else if (h->cpb == 4) hipLaunchKernelGGL(k_hmc_small<4>, grid, block, h->lds, ctx->stream, a);
   else if (h->cpb == 2) hipLaunchKernelGGL(k_hmc_small<2>, grid, block, h->lds, ctx->stream, a);
   else hipLaunchKernelGGL(k_hmc_small<1>, grid, block, h->lds, ctx->stream, a);
   BC_HIP(hipGetLastError());
@@ -352,32 +423,47 @@ extern "C" int bc_hmc_small_begin(bc_ctx* ctx, const double* rows, const double*
   h->a.n_leapfrog = n_leapfrog;
   h->pending_k = 0;
   h->diag.on = false;             // (a summary left attached to an earlier run is dropped)
+  h->adapt_on = h->pending_adapt = false;
   bc_run_opened(h, n_iter);
   return BC_OK;
 }
 
-extern "C" int bc_hmc_small_chunk_begin(bc_ctx* ctx, const double* normals, const double* log_u, int64_t problem_stride, int32_t k,
-                                        const double* step) {
+// The chunk begin behind bc_hmc_small_chunk_begin (`step`: P steps, one per problem) and the two of beta_cores_hmc_adapt.h
+// (step = null; warm: a warm-up chunk, whose plan rows travel where the steps do, else kept iterations at the frozen state).
+static const bc_run_kind HMC_ADAPT_RUN = {"bc_hmc_adapt", "iterations"}, HMC_ADAPTED_RUN = {"bc_hmc_adapted", "iterations"};
+static int chunk_begin(bc_ctx* ctx, const bc_run_kind& kd, const double* normals, const double* log_u, int64_t problem_stride, int32_t k,
+                       const double* step, bool warm) {
   bc_hmc_small* h = ctx ? ctx->hmc_small : nullptr;
-  int rc = bc_run_admit(h, HMC_SMALL_RUN, normals && log_u && step, k);
+  const bool adapt = step == nullptr;
+  // (said here for the two of beta_cores_hmc_adapt.h: which call ends the pending chunk depends on what it is, not on this one)
+  if (adapt && h && h->active && h->chunk_pending) BC_REFUSE("%s_chunk_begin: a chunk is pending (end it first)", kd.name);
+  int rc = bc_run_admit(h, kd, normals && log_u, k);
   if (rc) return rc;
+  if (adapt && !h->adapt_on) BC_REFUSE("%s_chunk_begin: the run has no per-chain warm-up (call bc_hmc_adapt_begin first)", kd.name);
+  if (adapt && warm && (int64_t)h->warm_done + k > h->warm_total)
+    BC_REFUSE("%s_chunk_begin: %d warm-up iterations after %d exceed the plan's %d", kd.name, k, h->warm_done, h->warm_total);
   const size_t P = (size_t)h->n_problems, c = (size_t)h->a.c, d = (size_t)h->a.d;
   const size_t kcd = (size_t)k * c * d, kc = (size_t)k * c;
   if (problem_stride != 0 && (problem_stride < 0 || (size_t)problem_stride < kcd))
-    BC_REFUSE("bc_hmc_small_chunk_begin: problem_stride must be 0 or at least k C D = %zu, got %lld", kcd, (long long)problem_stride);
-  for (size_t p = 0; p < P; ++p)
+    BC_REFUSE("%s_chunk_begin: problem_stride must be 0 or at least k C D = %zu, got %lld", kd.name, kcd, (long long)problem_stride);
+  for (size_t p = 0; !adapt && p < P; ++p)
     if (!(step[p] > 0.) || !std::isfinite(step[p]))
-      BC_REFUSE("bc_hmc_small_chunk_begin: step[%zu] = %g is not finite and positive", p, step[p]);
+      BC_REFUSE("%s_chunk_begin: step[%zu] = %g is not finite and positive", kd.name, p, step[p]);
   // ---- nothing of this chunk has been enqueued up to here
   BC_HIP(hipSetDevice(ctx->device));
   const bool shared = problem_stride == 0;
   const size_t n_e = shared ? kcd : P * kcd, n_u = shared ? kc : P * kc;
+  const size_t n_st = adapt ? (warm ? 4 * (size_t)k : 0) : P;      // the steps, or the chunk's rows of the plan
   bc_slab st, out;
   st.take(n_e);
-  const size_t o_u = st.take(n_u), o_st = st.take(P), need = st.total;
+  const size_t o_u = st.take(n_u), o_st = st.take(n_st), need = st.total;
   out.take(P * kcd);
   h->o_l = out.take(P * kc);
   h->o_a = out.take((P * kc + 1) / 2);      // (ints)
+  if (adapt && warm) {
+    h->o_st = out.take(P * kc);
+    h->o_al = out.take(P * kc);
+  }
   rc = bc_stage_reserve(ctx, &h->stage, need);
   if (!rc) rc = bc_scratch_grow(ctx, &h->out, out.total);
   if (rc) return rc;
@@ -387,32 +473,45 @@ extern "C" int bc_hmc_small_chunk_begin(bc_ctx* ctx, const double* normals, cons
   else
     for (size_t p = 0; p < P; ++p) memcpy(pin + p * kcd, normals + p * (size_t)problem_stride, kcd * sizeof(double));
   memcpy(pin + o_u, log_u, n_u * sizeof(double));
-  memcpy(pin + o_st, step, P * sizeof(double));
+  if (!adapt) memcpy(pin + o_st, step, P * sizeof(double));
+  else if (warm) memcpy(pin + o_st, h->plan.data() + 4 * (size_t)h->warm_done, n_st * sizeof(double));
   BC_HIP(hipMemcpyAsync(h->stage.dev.p, pin, need * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   h->chunk_pending = true;      // from here on something is enqueued: _chunk_end must wait even if the launch below fails
   h->scored = false;
   h->diag.folded = false;
   h->pending_k = k;
+  h->pending_adapt = adapt && warm;
   SmArgs a = h->a;
   a.mode = BC_SM_CHUNK;
   a.k = k;
   a.e = dev;
   a.logu = dev + o_u;
-  a.step = dev + o_st;
+  a.step = adapt ? nullptr : dev + o_st;
+  a.plan = adapt && warm ? dev + o_st : nullptr;
+  a.out_step = adapt && warm ? h->out.p + h->o_st : nullptr;
+  a.out_alpha = adapt && warm ? h->out.p + h->o_al : nullptr;
   a.e_stride = shared ? 0 : (long long)kcd;
   a.u_stride = shared ? 0 : (long long)kc;
   a.out_s = h->out.p;
   a.out_l = h->out.p + h->o_l;
   a.out_a = reinterpret_cast<int*>(h->out.p + h->o_a);
   rc = h->clock.start(ctx->stream);
-  if (!rc) rc = launch(ctx, h, a);
+  if (!rc) rc = launch(ctx, h, a, adapt);
   if (!rc) rc = h->clock.stop(ctx->stream);
   if (rc) return rc;
   h->done += k;
+  if (adapt && warm) h->warm_done += k;
   return BC_OK;
 }
 
-// the chunk end behind both headers.  out_samples may be null only for `who` = bc_score_chunk_end; out_correct / out_ll: both or neither
+extern "C" int bc_hmc_small_chunk_begin(bc_ctx* ctx, const double* normals, const double* log_u, int64_t problem_stride, int32_t k,
+                                        const double* step) {
+  if (!step) BC_REFUSE("bc_hmc_small_chunk_begin: bad argument, or no run is open");
+  return chunk_begin(ctx, HMC_SMALL_RUN, normals, log_u, problem_stride, k, step, false);
+}
+
+// the chunk end behind the three headers.  out_samples may be null for bc_score_chunk_end and bc_hmc_adapt_chunk_end (their callers
+// check); out_correct / out_ll: both or neither
 static int chunk_end(bc_ctx* ctx, bc_hmc_small* h, double* out_samples, double* out_logjoint, int32_t* out_accept, int32_t* out_status,
                      int32_t* out_correct, double* out_ll) {
   h->scored = false;
@@ -541,11 +640,123 @@ extern "C" int bc_diag_end(bc_ctx* ctx, double* out_mean, double* out_cov, doubl
   return bc_diag_run(ctx, g.keep.p, g.work.p, s, h->a.flag, out);
 }
 
+// ---- include/beta_cores_hmc_adapt.h: the per-chain warm-up of the open run (the stage: k_hmc_small<CPB, 1>)
+extern "C" int bc_hmc_adapt_plan(int32_t n_warmup, int32_t init_buffer, int32_t term_buffer, int32_t base_window, double gamma, double t0,
+                                 double kappa, int32_t* out_flags, double* out_coef) {
+  if (n_warmup > 0 && (!out_flags || !out_coef)) BC_REFUSE("bc_hmc_adapt_plan: the flags and the coefficients are required");
+  if (bc_hmc_adapt_plan_fill(n_warmup, init_buffer, term_buffer, base_window, gamma, t0, kappa, out_flags, out_coef))
+    BC_REFUSE("bc_hmc_adapt_plan: needs n_warmup >= 0, buffers >= 0, base_window >= 1, gamma > 0, t0 >= 0 and kappa > 0, all finite "
+              "(n_warmup = %d, buffers %d / %d, base_window = %d, gamma = %g, t0 = %g, kappa = %g)", n_warmup, init_buffer, term_buffer,
+              base_window, gamma, t0, kappa);
+  return BC_OK;
+}
+
+extern "C" int bc_hmc_adapt_begin(bc_ctx* ctx, const double* log_step, double delta, double gamma, double t0, double kappa, int32_t n_warmup,
+                                  int32_t init_buffer, int32_t term_buffer, int32_t base_window) {
+  bc_hmc_small* h = ctx ? ctx->hmc_small : nullptr;
+  if (!h || !h->active || !log_step) BC_REFUSE("bc_hmc_adapt_begin: bad argument, or no batched small-problem run is open");
+  if (h->adapt_on) BC_REFUSE("bc_hmc_adapt_begin: the run's warm-up has been begun already");
+  if (h->chunk_pending || h->done != 0) BC_REFUSE("bc_hmc_adapt_begin: must be called before the run's first chunk");
+  if (!(delta > 0.) || !(delta < 1.)) BC_REFUSE("bc_hmc_adapt_begin: delta must lie in (0, 1), got %g", delta);
+  if (n_warmup < 1 || (int64_t)n_warmup > h->total)
+    BC_REFUSE("bc_hmc_adapt_begin: n_warmup must be 1 .. the run's %lld iterations, got %d", (long long)h->total, n_warmup);
+  const size_t P = (size_t)h->n_problems, c = (size_t)h->a.c, d = (size_t)h->a.d, pc = P * c;
+  for (size_t p = 0; p < P; ++p)
+    if (!std::isfinite(log_step[p])) BC_REFUSE("bc_hmc_adapt_begin: log_step[%zu] = %g is not finite", p, log_step[p]);
+  std::vector<int32_t> flags((size_t)n_warmup);
+  std::vector<double> coef(3 * (size_t)n_warmup);
+  const int rc_plan = bc_hmc_adapt_plan(n_warmup, init_buffer, term_buffer, base_window, gamma, t0, kappa, flags.data(), coef.data());
+  if (rc_plan) return rc_plan;
+  // ---- the arguments are good
+  BC_HIP(hipSetDevice(ctx->device));
+  h->plan.resize(4 * (size_t)n_warmup);
+  for (size_t i = 0; i < (size_t)n_warmup; ++i) {
+    for (int j = 0; j < 3; ++j) h->plan[4 * i + j] = coef[3 * i + j];
+    h->plan[4 * i + 3] = (double)flags[i];
+  }
+  bc_slab sl;
+  const size_t o_sc = sl.take(pc * BC_HMC_ADAPT_STATE), o_im = sl.take(pc * d), o_mean = sl.take(pc * d), o_m2 = sl.take(pc * d);
+  int rc = bc_scratch_grow(ctx, &h->adapt, sl.total);
+  if (rc) return rc;
+  for (int cpb = 1; cpb <= 4; cpb <<= 1)
+    BC_HIP(hipFuncSetAttribute(adapt_kernel_of(cpb), hipFuncAttributeMaxDynamicSharedMemorySize, ctx->max_lds));
+  // every chain starts from its problem's step and inverse mass (the masses are read back: the run keeps them on the device only)
+  std::vector<double> host(sl.total, 0.), im(P * d);
+  BC_HIP(hipMemcpyAsync(im.data(), h->a.im, P * d * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  BC_HIP(hipStreamSynchronize(ctx->stream));
+  const double log10 = log(10.);
+  for (size_t b = 0; b < pc; ++b) {
+    double* st = host.data() + o_sc + b * BC_HMC_ADAPT_STATE;
+    st[0] = log_step[b / c];
+    st[3] = log10 + st[0];
+    memcpy(host.data() + o_im + b * d, im.data() + (b / c) * d, d * sizeof(double));
+  }
+  BC_HIP(hipMemcpyAsync(h->adapt.p, host.data(), sl.total * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  BC_HIP(hipStreamSynchronize(ctx->stream));      // (a pageable source)
+  h->a.ad_st = h->adapt.p + o_sc;
+  h->a.ad_im = h->adapt.p + o_im;
+  h->a.ad_mean = h->adapt.p + o_mean;
+  h->a.ad_m2 = h->adapt.p + o_m2;
+  h->a.delta = delta;
+  h->a.log10 = log10;
+  h->warm_total = n_warmup;
+  h->warm_done = 0;
+  h->adapt_on = true;
+  return BC_OK;
+}
+
+extern "C" int bc_hmc_adapt_chunk_begin(bc_ctx* ctx, const double* normals, const double* log_u, int64_t problem_stride, int32_t k) {
+  return chunk_begin(ctx, HMC_ADAPT_RUN, normals, log_u, problem_stride, k, nullptr, true);
+}
+
+extern "C" int bc_hmc_adapted_chunk_begin(bc_ctx* ctx, const double* normals, const double* log_u, int64_t problem_stride, int32_t k) {
+  return chunk_begin(ctx, HMC_ADAPTED_RUN, normals, log_u, problem_stride, k, nullptr, false);
+}
+
+extern "C" int bc_hmc_adapt_chunk_end(bc_ctx* ctx, double* out_samples, double* out_logjoint, int32_t* out_accept, int32_t* out_status,
+                                      double* out_step, double* out_alpha) {
+  bc_hmc_small* h = ctx ? ctx->hmc_small : nullptr;
+  int rc = bc_run_pending(h, "bc_hmc_adapt_chunk_end");
+  if (rc) return rc;
+  // (checked first: the chunk stays pending, a second call can still fetch it)
+  if (!h->pending_adapt) BC_REFUSE("bc_hmc_adapt_chunk_end: the pending chunk is not a warm-up chunk of bc_hmc_adapt_chunk_begin");
+  if (!out_logjoint || !out_accept || !out_status || !out_step || !out_alpha)
+    BC_REFUSE("bc_hmc_adapt_chunk_end: log-joints, accept flags, status, steps and alphas are required");
+  rc = chunk_end(ctx, h, out_samples, out_logjoint, out_accept, out_status, nullptr, nullptr);
+  if (rc) return rc;
+  const size_t P = (size_t)h->n_problems, kc = (size_t)h->pending_k * h->a.c;
+  for (size_t p = 0; p < P; ++p) {
+    if (out_status[p] != BC_OK) continue;      // (a marked problem: nothing is copied)
+    BC_HIP(hipMemcpy(out_step + p * kc, h->out.p + h->o_st + p * kc, kc * sizeof(double), hipMemcpyDeviceToHost));
+    BC_HIP(hipMemcpy(out_alpha + p * kc, h->out.p + h->o_al + p * kc, kc * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  return BC_OK;
+}
+
+extern "C" int bc_hmc_adapt_state(bc_ctx* ctx, double* out_step, double* out_inv_mass) {
+  bc_hmc_small* h = ctx ? ctx->hmc_small : nullptr;
+  if (!h || !h->active || !out_step || !out_inv_mass) BC_REFUSE("bc_hmc_adapt_state: bad argument, or no batched small-problem run is open");
+  if (!h->adapt_on) BC_REFUSE("bc_hmc_adapt_state: the run has no per-chain warm-up (call bc_hmc_adapt_begin first)");
+  if (h->chunk_pending) BC_REFUSE("bc_hmc_adapt_state: a chunk is pending (end it first)");
+  BC_HIP(hipSetDevice(ctx->device));
+  const size_t pc = (size_t)h->n_problems * h->a.c, d = (size_t)h->a.d;
+  std::vector<double> st(pc * BC_HMC_ADAPT_STATE);
+  BC_HIP(hipMemcpyAsync(st.data(), h->a.ad_st, st.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  BC_HIP(hipMemcpyAsync(out_inv_mass, h->a.ad_im, pc * d * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  BC_HIP(hipStreamSynchronize(ctx->stream));
+  // (the text the kernel evaluates at the start of a kept chunk, on the host: the same operations, the same bits)
+  for (size_t b = 0; b < pc; ++b) {
+    const double* sb = st.data() + b * BC_HMC_ADAPT_STATE;
+    out_step[b] = bc_hmc_adapt_exp(bc_hmc_adapt_frozen_log_step(sb[0], sb[1], sb[4]));
+  }
+  return BC_OK;
+}
+
 extern "C" int bc_hmc_small_end(bc_ctx* ctx) {
   bc_hmc_small* h = ctx ? ctx->hmc_small : nullptr;
   bool pending = false;
   const int rc = bc_run_end(ctx, h, HMC_SMALL_RUN, &pending);
-  if (!rc) h->scored = false;
+  if (!rc) h->scored = h->pending_adapt = false;
   return rc;
 }
 

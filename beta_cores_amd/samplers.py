@@ -384,9 +384,11 @@ class HMCResult:
     From logistic_hmc_many(score=held) also: correct (n_samples x n_chains: held-out rows predicted correctly by every kept
     position), test_ll (n_samples x n_chains: its summed held-out log-likelihood) and accuracy (held.accuracy(correct)); None
     otherwise.  samples is None from a run with keep_samples=False.  From a run with summary=True also: summary, the
-    ChainSummary of the kept iterations (chain_summary has the definitions); None otherwise."""
+    ChainSummary of the kept iterations (chain_summary has the definitions); None otherwise.  From
+    logistic_hmc_many(adapt='stan'): step_size is (n_chains,), inv_mass (n_chains, D), warmup_steps (warmup, n_chains) and
+    warmup_accept_stat (warmup, n_chains) holds the acceptance statistic of every warm-up iteration; None otherwise."""
 
-    correct = test_ll = accuracy = summary = None
+    correct = test_ll = accuracy = summary = warmup_accept_stat = None
 
     def __init__(self, samples, logjoint, accept, step_size, warmup_steps, start, inv_mass, device_ms):
         self.samples, self.logjoint, self.accept = samples, logjoint, accept
@@ -435,7 +437,8 @@ def logistic_hmc(Z, wts=None, n_samples=1000, n_chains=16, step_size=0.1, n_leap
     """Samples of the logistic posterior of the rows Z = y*x with weights wts under the N(0, I) prior -- the reference's weighted
     log-joint (model_lr.py:88-93; the Stan programs of zellner_logreg/main.py:24-62 with the intercept as a column) -- by plain
     HMC: `n_chains` chains in lock-step, a diagonal inverse mass, a fixed step and `n_leapfrog` leapfrog steps.  Not NUTS, no
-    dual averaging.  Every pass over the rows serves all chains at once on the device (k_lr_rows_mc); a chunk of iterations is
+    dual averaging here: logistic_hmc_many(adapt='stan') adapts step and mass per chain as Stan's warm-up does, for problems
+    that fit one block's LDS.  Every pass over the rows serves all chains at once on the device (k_lr_rows_mc); a chunk of iterations is
     enqueued whole and waited for once.  No CPU fallback.
 
     Z: a DeviceData (the full data, resident), or an ndarray, which is uploaded -- a weighted coreset of a few hundred points goes
@@ -778,10 +781,27 @@ class _SingleAsBatch:
     def auto_chunk(self, c, d):
         return self.eng.auto_chunk(c, d)
 
+    adapted = False      # set by _run_hmc_group after a per-chain warm-up: the kept chunks run at the engine's frozen state
+
+    def adapt_begin(self, log_steps, target_accept, warmup):
+        self.eng.adapt_begin(float(log_steps[0]), target_accept, warmup)
+
+    def adapt_chunk(self, normals, log_u, shared):
+        e, u = (normals, log_u) if shared else (normals[0], log_u[0])
+        lj, acc, stp, alpha = self.eng.adapt_chunk(np.ascontiguousarray(e), np.ascontiguousarray(u))
+        return lj[None], acc[None], np.zeros(1, dtype=np.int32), stp[None], alpha[None]
+
+    def adapt_state(self):
+        stp, im = self.eng.adapt_state()
+        return stp[None], im[None]
+
     def chunk(self, normals, log_u, steps, shared):
         e, u = (normals, log_u) if shared else (normals[0], log_u[0])
         try:
-            s, lj, acc = self.eng.chunk(np.ascontiguousarray(e), np.ascontiguousarray(u), float(steps[0]))
+            if self.adapted:
+                s, lj, acc = self.eng.adapted_chunk(np.ascontiguousarray(e), np.ascontiguousarray(u))
+            else:
+                s, lj, acc = self.eng.chunk(np.ascontiguousarray(e), np.ascontiguousarray(u), float(steps[0]))
         except N.NumericalPrecisionError:
             if not self.swallow:
                 raise
@@ -808,11 +828,36 @@ class _DeviceHMCMany:
     def auto_chunk(self, c, d):
         return int(N.load().bc_hmc_auto_chunk(int(c), int(d)))
 
+    adapted = False      # set by _run_hmc_group after a per-chain warm-up: the kept chunks run at the chains' frozen state
+
+    def adapt_begin(self, log_steps, target_accept, warmup):
+        """The per-chain warm-up of include/beta_cores_hmc_adapt.h on the open run, with Stan's constants and windows."""
+        log_steps = np.ascontiguousarray(log_steps, dtype=np.float64)
+        N.call('bc_hmc_adapt_begin', self.ctx.h, _ptr(log_steps), float(target_accept), 0.05, 10., 0.75, int(warmup), 75, 50, 25)
+
+    def adapt_chunk(self, normals, log_u, shared):
+        """One warm-up chunk, one launch: (logjoint, accept, status, step, alpha), each P x k x C; no sample is copied."""
+        k = normals.shape[0] if shared else normals.shape[1]
+        normals, log_u = np.ascontiguousarray(normals), np.ascontiguousarray(log_u)
+        N.call('bc_hmc_adapt_chunk_begin', self.ctx.h, _ptr(normals), _ptr(log_u), 0 if shared else k * self.c * self.d, int(k))
+        lj, stp, alpha = np.zeros((self.P, k, self.c)), np.zeros((self.P, k, self.c)), np.zeros((self.P, k, self.c))
+        acc, status = np.zeros((self.P, k, self.c), dtype=np.int32), np.empty(self.P, dtype=np.int32)
+        N.call('bc_hmc_adapt_chunk_end', self.ctx.h, None, _ptr(lj), _ptr(acc), _ptr(status), _ptr(stp), _ptr(alpha))
+        return lj, acc, status, stp, alpha
+
+    def adapt_state(self):
+        stp, im = np.empty((self.P, self.c)), np.empty((self.P, self.c, self.d))
+        N.call('bc_hmc_adapt_state', self.ctx.h, _ptr(stp), _ptr(im))
+        return stp, im
+
     def _begin_chunk(self, normals, log_u, steps, shared):
         k = normals.shape[0] if shared else normals.shape[1]
         normals, log_u = np.ascontiguousarray(normals), np.ascontiguousarray(log_u)
-        steps = np.ascontiguousarray(steps, dtype=np.float64)
-        N.call('bc_hmc_small_chunk_begin', self.ctx.h, _ptr(normals), _ptr(log_u), 0 if shared else k * self.c * self.d, int(k), _ptr(steps))
+        if self.adapted:
+            N.call('bc_hmc_adapted_chunk_begin', self.ctx.h, _ptr(normals), _ptr(log_u), 0 if shared else k * self.c * self.d, int(k))
+        else:
+            steps = np.ascontiguousarray(steps, dtype=np.float64)
+            N.call('bc_hmc_small_chunk_begin', self.ctx.h, _ptr(normals), _ptr(log_u), 0 if shared else k * self.c * self.d, int(k), _ptr(steps))
         lj = np.empty((self.P, k, self.c))
         acc, status = np.zeros((self.P, k, self.c), dtype=np.int32), np.empty(self.P, dtype=np.int32)
         return k, lj, acc, status
@@ -884,14 +929,17 @@ class _ManyDraws:
 
 
 def _run_hmc_group(eng, idx, starts, ims, steps0, draws, c, d, n_samples, n_leapfrog, warmup, adapt_every, adapt_rate, chunk, held=None,
-                   keep_samples=True, summaries=None, max_lag=None):
+                   keep_samples=True, summaries=None, max_lag=None, stan=None, adapted=None):
     """The loop of logistic_hmc and logistic_hmc_many -- warm-up chunks with hmc_warmup_step per problem, then the kept chunks at
     frozen steps -- for the problems `idx` of one engine.  Returns ({p: (samples, logjoint, accept, step, warm_steps)}, marked indices, device ms).
     held (with an engine that has chunk_scored): the kept chunks are scored on the device, warm-up chunks are neither scored nor
     copied, keep_samples=False copies no samples at all (samples is None); the result tuples end with (correct, test_ll).
     summaries (a dict, with an engine that has attach_summary): the kept chunks -- and only those -- are retained on the device in
     order, and after the last one summaries[p] is problem p's ChainSummary (max_lag as chain_summary's); such a run too can do
-    without the sample copies.  None: exactly the calls of a run without a summary."""
+    without the sample copies.  None: exactly the calls of a run without a summary.
+    stan (a target acceptance, with an engine that has adapt_begin): the warm-up is the engine's per-chain one, in chunks of `chunk`
+    iterations; the kept chunks run at every chain's frozen step and mass.  step is then (C,) and warm_steps (warmup, C), and
+    adapted[p] = (inv_mass (C, D), alpha (warmup, C)).  None: exactly the calls of a run without it."""
     G = len(idx)
     step = [float(steps0[p]) for p in idx]
     warm = [[] for _ in idx]
@@ -907,6 +955,24 @@ def _run_hmc_group(eng, idx, starts, ims, steps0, draws, c, d, n_samples, n_leap
         if on_dev:
             eng.attach_summary(int(n_samples), max_lag)
         ci, left = 0, int(warmup)
+        if stan is not None:
+            eng.adapt_begin(np.log(np.array(step)), float(stan), int(warmup))
+            traces = []
+            while left > 0 and not bad.all():
+                k = min(left, int(chunk))
+                e, u = draws.get(ci, k, idx)
+                status, stp, alpha = eng.adapt_chunk(e, u, draws.shared)[2:]
+                bad |= status != 0
+                traces.append((stp, alpha))
+                left -= k
+                ci += 1
+            if not bad.all():
+                step_c, im_c = eng.adapt_state()
+                for j, p in enumerate(idx):
+                    if not bad[j]:
+                        step[j], warm[j] = step_c[j].copy(), np.concatenate([t[0][j] for t in traces])
+                        adapted[p] = (im_c[j].copy(), np.concatenate([t[1][j] for t in traces]))
+            eng.adapted = True
         while left > 0 and not bad.all():
             k = min(left, int(adapt_every))
             e, u = draws.get(ci, k, idx)
@@ -921,16 +987,19 @@ def _run_hmc_group(eng, idx, starts, ims, steps0, draws, c, d, n_samples, n_leap
                     step[j] = hmc_warmup_step(step[j], float(np.mean(acc[j] != 0)), adapt_rate)
             left -= k
             ci += 1
+        # (after a per-chain warm-up the engine runs at its chains' own frozen steps: none is passed, and a marked problem's entry,
+        # which stays the start's number beside the others' arrays, is never packed)
+        kept_steps = None if stan is not None else np.array(step)
         i0 = 0
         while i0 < n_samples and not bad.all():
             k = min(n_samples - i0, int(chunk))
             e, u = draws.get(ci, k, idx)
             if in_run:
-                s, lj, acc, status, cor, tll = eng.chunk_scored(e, u, np.array(step), draws.shared, held, keep, **fold)
+                s, lj, acc, status, cor, tll = eng.chunk_scored(e, u, kept_steps, draws.shared, held, keep, **fold)
             elif not keep:      # (a summarised run that keeps no samples and scores nothing: no sample copy, nothing scored)
-                s, lj, acc, status = eng.chunk_scored(e, u, np.array(step), draws.shared, None, False, **fold)[:4]
+                s, lj, acc, status = eng.chunk_scored(e, u, kept_steps, draws.shared, None, False, **fold)[:4]
             else:
-                s, lj, acc, status = eng.chunk(e, u, np.array(step), draws.shared, **fold)
+                s, lj, acc, status = eng.chunk(e, u, kept_steps, draws.shared, **fold)
             bad |= status != 0
             for j in range(G):
                 if not bad[j]:
@@ -1102,7 +1171,8 @@ def logistic_laplace_many(problems, mu0=None, diag=False, n_draws=0, rng=None, d
 
 def logistic_hmc_many(problems, n_samples=1000, n_chains=16, step_size=0.1, n_leapfrog=8, inv_mass=None, start=None, warmup=0, rng=None,
                       draws='shared', adapt_every=25, adapt_rate=1.0, chunk=None, strict=True, ctx=None, engine=None, score=None,
-                      keep_samples=True, scorer=None, laplace='each', summary=False, summarizer=None, max_lag=None):
+                      keep_samples=True, scorer=None, laplace='each', summary=False, summarizer=None, max_lag=None, adapt='chunks',
+                      target_accept=0.8):
     """logistic_hmc for MANY small problems in one batched run: the posteriors of the weighted coresets of an evaluation curve
     (`for m in range(M + 1): sample the coreset of size m` in the logistic drivers).  One thread block per problem and group of
     up to four chains holds the problem's rows in LDS and runs whole chunks of iterations there (k_hmc_small); a chunk is one
@@ -1143,6 +1213,16 @@ def logistic_hmc_many(problems, n_samples=1000, n_chains=16, step_size=0.1, n_le
       the kept chunks -- never a warm-up chunk -- are retained on the device as they are produced and reduced there after the
       last one, so it needs no sample on the host; on the 'single' route it is chain_summary of the returned samples.  Both
       give the bits of chain_summary(result.samples, max_lag).  Off by default: no draw, output or bit of a run changes with it.
+    adapt='chunks' (default): the warm-up above.  'stan': every CHAIN adapts its own step and its own diagonal inverse mass on the
+      device, as Stan's warm-up does (include/beta_cores_hmc_adapt.h): dual averaging of log(step) towards a mean acceptance
+      statistic of `target_accept` (gamma 0.05, t0 10, kappa 0.75), the variances of the positions estimated in doubling windows
+      (75 / 50 / 25; none with warmup < 20) and regularised as Stan does.  No NUTS, no step-size search, no step jitter.  The
+      warm-up runs in chunks of `chunk` iterations, one launch each, with today's draws per chunk; adapt_every and adapt_rate
+      are ignored; step_size and inv_mass are where every chain of a problem starts.  The kept iterations run at each chain's
+      averaged step and adapted mass.  Every HMCResult then has step_size (C,), inv_mass (C, D), warmup_steps (warmup, C: the
+      step of every warm-up iteration) and warmup_accept_stat (warmup, C: its acceptance statistic min(1, exp(H0 - H1))).
+      Needs warmup >= 1; a problem that does not fit one block's LDS is refused with a ValueError before anything is launched.
+      score, keep_samples, summary and laplace combine with it unchanged.
     engine: a stand-in `engine(Z_p, wts_p)` per problem with logistic_hmc's engine protocol (CPU tests); scorer: a stand-in
       `scorer(held, thetas) -> (correct, ll)` for logistic_score (CPU tests); summarizer: a stand-in
       `summarizer(samples, max_lag) -> summary` for chain_summary (CPU tests).
@@ -1157,6 +1237,11 @@ def logistic_hmc_many(problems, n_samples=1000, n_chains=16, step_size=0.1, n_le
         raise ValueError("draws must be 'shared' or 'independent'")
     if laplace not in ('each', 'batched'):
         raise ValueError("laplace must be 'each' or 'batched'")
+    if adapt not in ('chunks', 'stan'):
+        raise ValueError("adapt must be 'chunks' or 'stan'")
+    stan = adapt == 'stan'
+    if stan and (warmup < 1 or not 0. < float(target_accept) < 1.):
+        raise ValueError("adapt='stan' needs warmup >= 1 and 0 < target_accept < 1")
     probs, d = _small_problems(problems)
     P = len(probs)
     c = int(n_chains)
@@ -1177,6 +1262,10 @@ def logistic_hmc_many(problems, n_samples=1000, n_chains=16, step_size=0.1, n_le
         if score is not None and (score.ctx is not ctx or score.shape[1] != d):
             raise ValueError('score must hold rows of %d columns on the context of the run' % d)
     fits = [True] * P if engine is not None else [bool(N.load().bc_hmc_small_fits(ctx.h, int(z.shape[0]), int(d))) for z, _ in probs]
+    if stan and not all(fits):
+        p = fits.index(False)
+        raise ValueError("adapt='stan': problem %d (%d rows x %d) does not fit one block's LDS; the per-chain warm-up serves the "
+                         "batched route only" % (p, probs[p][0].shape[0], d))
     resident = {}
 
     def on_device(p):      # (the rows of p on the device: the Laplace fit and the single-problem route share them)
@@ -1224,11 +1313,16 @@ def logistic_hmc_many(problems, n_samples=1000, n_chains=16, step_size=0.1, n_le
     for eng, idx in groups:
         sums = {} if summary else None
         extra = dict(summaries=sums, max_lag=max_lag) if summary else {}
+        own = {}
+        if stan:
+            extra.update(stan=float(target_accept), adapted=own)
         res, bad, ms = _run_hmc_group(eng, idx, starts, ims, steps0, stream, c, d, int(n_samples), n_leapfrog, warmup, adapt_every,
                                       adapt_rate, chunk, held=score, keep_samples=keep_samples, **extra)
         for p, r in res.items():
             s, lj, acc, step, warm = r[:5]
-            done[p] = HMCResult(s, lj, acc, step, warm, starts[p], ims[p], ms)
+            done[p] = HMCResult(s, lj, acc, step, warm, starts[p], own[p][0] if stan else ims[p], ms)
+            if stan:
+                done[p].warmup_accept_stat = own[p][1]
             done[p].route = 'small' if fits[p] else 'single'
             if summary:
                 if p in sums:

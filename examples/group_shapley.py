@@ -35,6 +35,7 @@ def main():
     ap.add_argument('--flip', type=float, default=0.3)
     ap.add_argument('--rand-trials', type=int, default=20)
     ap.add_argument('--seed', type=int, default=1)
+    ap.add_argument('--adapt', default='chunks', choices=['chunks', 'stan'], help="the samplers' warm-up: 'stan' adapts step and mass per chain on the device")
     ap.add_argument('--summary', action='store_true', help="the worst split-R-hat and the smallest ESS over all the run's posteriors, reduced on the device")
     a = ap.parse_args()
     rng = np.random.RandomState(a.seed)
@@ -52,7 +53,7 @@ def main():
         Y[groups[g]] *= -1.
     Z = Y[:, None] * X
     held = bc.samplers.HeldOut(Xt, Yt)
-    hmc = dict(n_samples=64, n_chains=16, warmup=100, step_size=0.1, n_leapfrog=8)
+    hmc = dict(n_samples=64, n_chains=16, warmup=100, step_size=0.1, n_leapfrog=8, adapt=a.adapt)
 
     t0 = time.perf_counter()
     val = bc.valuation.tmc_shapley(Z, groups, held, a.perms, min(a.max_groups, a.groups), group_cap=50, rng=rng, summary=a.summary, **hmc)

@@ -73,6 +73,8 @@ def main():
     ap.add_argument('--curve', type=int, default=0, help='score this many nested coreset sizes 0 .. m from one batched call (0: off)')
     ap.add_argument('--summary', action='store_true', help='with --curve: the worst split-R-hat and the smallest ESS of every coreset size, reduced on the device')
     ap.add_argument('--laplace', action='store_true', help='with --curve: the Laplace posteriors of the same coresets, fitted, drawn and scored on the device')
+    ap.add_argument('--adapt', default='chunks', choices=['chunks', 'stan'],
+                    help="the warm-up of the batched calls: 'stan' adapts step and mass per chain on the device (logistic_hmc_many)")
     ap.add_argument('--bpsvi', type=int, default=0, help='the BatchPSVI pseudo-coresets of sizes 1 .. M from one build_many, Laplace-fitted and sampled in one call each (0: off)')
     ap.add_argument('--bpsvi-itrs', type=int, default=100, help='with --bpsvi: joint ADAM steps on weights and points')
     a = ap.parse_args()
@@ -122,7 +124,7 @@ def main():
               (name, compute_accuracy(Xt, Yt, th), log_likelihood(Zt, th).sum(axis=0).mean(), np.abs((th.mean(axis=0) - mu_t) / sd_t).max()))
     if nested:
         t0 = time.perf_counter()
-        curve = bc.samplers.logistic_hmc_many(nested, rng=rng, summary=a.summary, **hmc)
+        curve = bc.samplers.logistic_hmc_many(nested, rng=rng, summary=a.summary, adapt=a.adapt, **hmc)
         t_curve = time.perf_counter() - t0
         print('curve: %d coreset sizes in one batched call, %.2f s (%.1f ms on the GPU); through the single-problem engine: %s' %
               (len(nested), t_curve, curve.device_ms or 0., curve.fallback or 'none'))
@@ -166,7 +168,7 @@ def main():
         probs = [(np.asarray(p, dtype=np.float64), np.asarray(w, dtype=np.float64)) for _, (w, p, _) in kept]
         held = bc.samplers.HeldOut(Xt, Yt)
         laps = bc.samplers.logistic_laplace_many(probs, n_draws=min(a.samples, bc.samplers.LAPLACE_SMALL_MAX_DRAWS), rng=rng, score=held, keep_draws=False)
-        many = bc.samplers.logistic_hmc_many(probs, rng=rng, score=held, keep_samples=False, **hmc)
+        many = bc.samplers.logistic_hmc_many(probs, rng=rng, score=held, keep_samples=False, adapt=a.adapt, **hmc)
         for (m, (w, _, _)), fit, res in zip(kept, laps, many):
             print('m = %-4d points %-4d laplace: accuracy %.4f  test log-likelihood %.3f   hmc: accuracy %.4f  test log-likelihood %.3f' %
                   (m, len(w), held.accuracy(fit.correct), fit.test_ll.mean(), held.accuracy(res.correct.ravel()), res.test_ll.mean()))
